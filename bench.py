@@ -2,6 +2,8 @@
 """Headline benchmark: MuDPT ViT-B/16 forward+backward(+SGD step) images/s, batch 256 per MI355X, bf16.
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full                     # + roofline, HBM kernels, parity modes, CPU baselines
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR         # + the last timed step's outputs as DIR/*.npy
     python bench.py --gpus N --steps K --warmup W          # N > 1 with WORLD_SIZE unset: starts N fresh child processes itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -10,6 +12,10 @@ One "step" = BASELINE.json configs[1]: forward + cross-entropy + backward throug
 for 256 synthetic 224x224 images and 11 class prompts (n_ctx 4, depth 12), the RCCL all-reduce of the 10
 trainable tensors when N > 1, and the SGD update.  Inputs, weights and parameters are resident in HBM before
 the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line; every other figure (the HIP-event roofline of
+the GEMMs and HBM-bound kernels, the parity-mode timings, the CPU baselines, the all-reduce timing at N > 1) is measured
+only with --full.
 """
 from __future__ import annotations
 
@@ -195,6 +201,36 @@ def stub_worker(args, rank: int, world: int):
         dist.destroy_process_group()
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: budget of all files together
+
+
+def last_step_outputs(model, loss):
+    """What a caller of the timed step holds after it: the loss (this rank's), the gradients of the trainable tensors (summed over the
+    ranks at N > 1) and the tensors' values after the SGD update; host float32 copies, by name."""
+    out = {"loss": loss.detach().float().reshape(1).cpu()}
+    for k, p in model.named_parameters():
+        out[f"grad.{k}"] = p.grad.detach().float().cpu().clone()
+        out[f"param.{k}"] = p.detach().float().cpu().clone()
+    return out
+
+
+def dump_outputs(path: str, outputs) -> None:
+    """DIR/<name>.npy per array, at most DUMP_BYTES in all.  Beyond that budget every array above 4096 elements keeps its share of it as
+    a fixed sample: the flat elements at the sorted first indices of torch.randperm(numel, generator seeded 0) -- the same positions
+    on every run and every build."""
+    import math
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in outputs.values()) * 4
+    frac = min(1.0, (DUMP_BYTES - (1 << 20)) / total)
+    for name, t in outputs.items():
+        if frac < 1.0 and t.numel() > 4096:
+            keep = math.ceil(t.numel() * frac)
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), t.numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -222,7 +258,14 @@ def main():
     ap.add_argument("--fp32-streams", action="store_true", help="keep the gradient stream (and in bf16 mode the update stream) in fp32 (A/B of the T streams)")
     ap.add_argument("--graph", action="store_true", help="replay forward+backward from a captured hipGraph (implies --no-profile)")
     ap.add_argument("--no-parity-mode", action="store_true", help="skip the short fp16 (parity configuration) timing appended to the bf16 line")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline and HBM-kernel figures (HIP "
+                    "events), parity-mode timings, CPU baselines, the all-reduce alone at N > 1 (--no-profile / --no-parity-mode / "
+                    "--no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed -- loss, the gradients and the updated "
+                    "values of the trainable tensors -- as DIR/<name>.npy (float32; at most 64 MB, a seeded sample of each array beyond that)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_profile = args.no_parity_mode = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args.gpus))  # the bare command: this process only starts and reaps the ranks
@@ -324,6 +367,7 @@ def main():
     elapsed = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2]
+    outputs = last_step_outputs(model, loss) if args.dump_outputs and rank == 0 else None  # before any further step moves them
     classes, exec_flop = model.profile_read_classes() if not args.no_profile else ({}, 0.0)
     gemm_ms, gemm_flop, gemm_n = classes.get("gemm_pp", (0.0, 0.0, 0))  # of the SAMPLED launches (every stride-th)
     model.profile(False)
@@ -345,6 +389,9 @@ def main():
         t = torch.tensor([elapsed], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+        collective = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "op": "all_reduce(sum) of the flat gradient bucket, one per step",
+                      "bucket_bytes": model.flat_grads.numel() * 4}
+    if dist is not None and args.full:
         # what the one collective of a step costs on its own: the 4.97 MB bucket, timed by events around dist.all_reduce (untimed extra calls)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
         dist.barrier()
@@ -354,11 +401,12 @@ def main():
             e1.record()
         torch.cuda.synchronize()
         us = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in evs)
-        collective = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "op": "all_reduce(sum) of the flat gradient bucket, one per step",
-                      "bucket_bytes": model.flat_grads.numel() * 4, "allreduce_us_median": round(us[len(us) // 2], 1), "allreduce_us_min": round(us[0], 1)}
+        collective.update(allreduce_us_median=round(us[len(us) // 2], 1), allreduce_us_min=round(us[0], 1))
     loss_v = float(loss.item())
     if not (loss_v == loss_v) or abs(loss_v) == float("inf"):
         raise SystemExit(f"non-finite loss {loss_v}")
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     model.close()
     del model
 

@@ -293,10 +293,55 @@ def run_tokenizer():
     print(f"wrote {path}: {len(cases)} strings")
 
 
+def run_tokenizer_merges():
+    """tokenizer_merges.json: the rows of CLIP's merge table that tests/test_tokenizer_cpu.py needs, under their ranks, so that the test runs
+    without the 1.3 MB table.  Kept: every merge BPE applies to the strings of tokenizer_cases.json, the benchmark prompts and the
+    too-long prompt, plus every merge that spells the same token as one of them (the vocabulary maps a token to its LAST merge).  Greedy
+    BPE picks the lowest-ranked pair present, and all applied merges keep their ranks, so any such subset merges exactly as the full
+    table does; the test fills the other ranks with pairs no byte string can form."""
+    import json
+    from mudpt_amd import synth, tokenizer
+    tok = tokenizer.BPETokenizer(tokenizer.find_vocab(os.path.join(REFERENCE, "clip", tokenizer.VOCAB_FILE)))
+    spec = json.load(open(os.path.join(ROOT, "tests", "golden", "tokenizer_cases.json"), encoding="utf-8"))
+    texts = [c["text"] for c in spec["cases"]] + [f"a photo of a {n}." for n in synth.BENCH_CLASSNAMES] + ["word " * 100]
+    by_rank = {r: m for m, r in tok.rank.items()}
+    used = set()
+    orig = tok._merge
+
+    def recording_merge(symbols):  # the greedy loop of BPETokenizer._merge, noting the rank of every pair it fuses
+        out = list(symbols)
+        while len(out) > 1:
+            ranked = [tok.rank[p] for p in zip(out, out[1:]) if p in tok.rank]
+            if not ranked:
+                break
+            used.add(min(ranked))
+            (a, b), nxt, i = by_rank[min(ranked)], [], 0
+            while i < len(out):
+                if i + 1 < len(out) and out[i] == a and out[i + 1] == b:
+                    nxt.append(a + b)
+                    i += 2
+                else:
+                    nxt.append(out[i])
+                    i += 1
+            out = nxt
+        assert out == orig(symbols)
+        return out
+    tok._merge = recording_merge
+    for t in texts:
+        tok.encode(t)
+    spelled = {"".join(by_rank[r]) for r in used}
+    keep = sorted(r for r, m in by_rank.items() if "".join(m) in spelled)
+    path = os.path.join(ROOT, "tests", "golden", "tokenizer_merges.json")
+    with open(path, "w") as f:
+        json.dump({"n_merges": tokenizer.N_MERGES, "merges": {str(r): " ".join(by_rank[r]) for r in keep}}, f, ensure_ascii=False, indent=0)
+    print(f"wrote {path}: {len(keep)} of {tokenizer.N_MERGES} merges")
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     if "--tokenizer-only" in sys.argv:
         run_tokenizer()
+        run_tokenizer_merges()
         sys.exit(0)
     if "--scale100-only" in sys.argv:
         # the same recipes with the logit scale pretrained CLIP checkpoints carry (exp(logit_scale) = 100 instead of the init value
