@@ -20,6 +20,13 @@
  *   mudpt_param_*                        trainers/cocoop.py:96-107,222-226  ctx + meta_net.linear1/2 (5 tensors)
  *   mudpt_forward                        trainers/cocoop.py:178-198 CustomCLIP.forward in eval mode (logits [B, C])
  *   mudpt_forward_backward               trainers/cocoop.py:196-197,258-261 cross-entropy inside forward + backward
+ * With MUDPT_VARIANT_COOP / MUDPT_VARIANT_COOP_CSC they run the CoOp path (trainers/coop.py):
+ *   mudpt_create / mudpt_set_weight      trainers/coop.py:20-37    load_clip_to_cpu: vanilla CLIP, vision tower forward only
+ *   mudpt_set_class_token_position       trainers/coop.py:78-97    name_lens, CLASS_TOKEN_POSITION
+ *   mudpt_set_class_prompts              trainers/coop.py:85-93,99-164  token_prefix / token_suffix, construct_prompts' row order
+ *   mudpt_param_*                        trainers/coop.py:60-76    ctx [n_ctx, d_t] (shared) or [n_cls, n_ctx, d_t] (CSC): 1 tensor
+ *   mudpt_forward / _ex                  trainers/coop.py:212-226  CustomCLIP.forward (logits [B, C])
+ *   mudpt_forward_backward               trainers/coop.py:281-296  forward, F.cross_entropy, backward w.r.t. ctx
  *
  * Conventions: every function returns 0 on success or a MUDPT_ERR_* code; mudpt_last_error() gives
  * the message of the calling thread's last failure.  No exceptions cross the ABI.  A model handle is
@@ -36,7 +43,7 @@
 extern "C" {
 #endif
 
-#define MUDPT_ABI_VERSION 6
+#define MUDPT_ABI_VERSION 7
 
 #define MUDPT_OK 0
 #define MUDPT_ERR_ARG 1   /* bad argument / shape (the reference raises AssertionError, mudpt.py:52,55,190) */
@@ -61,6 +68,13 @@ extern "C" {
 
 #define MUDPT_VARIANT_MUDPT 0  /* trainers/mudpt.py: deep multi-modal prompts, 10 trainables */
 #define MUDPT_VARIANT_COCOOP 1 /* trainers/cocoop.py: instance-conditioned text prompts, 5 trainables; depth is ignored */
+#define MUDPT_VARIANT_COOP 2     /* trainers/coop.py: one shared context [n_ctx, t_width], the trainable "prompt_learner.ctx"; depth is ignored */
+#define MUDPT_VARIANT_COOP_CSC 3 /* trainers/coop.py with CSC: one context per class, [n_cls, n_ctx, t_width]; depth is ignored */
+
+/* CoOp's TRAINER.COOP.CLASS_TOKEN_POSITION (trainers/coop.py:99-164): where the class-name tokens sit relative to the context rows */
+#define MUDPT_CLASS_TOKEN_END 0    /* [SOS, ctx, name, ".", EOT]                        (default) */
+#define MUDPT_CLASS_TOKEN_MIDDLE 1 /* [SOS, ctx[:n/2], name, ctx[n/2:], ".", EOT]        (n/2 rounds down) */
+#define MUDPT_CLASS_TOKEN_FRONT 2  /* [SOS, name, ctx, ".", EOT] */
 
 /* Model shape.  ViT-B/16 MuDPT: {224,16,768,12,12, 512,12,8,77, 512, 4,12, n_cls, max_batch, dtype, 0}. */
 typedef struct mudpt_config {
@@ -92,13 +106,18 @@ int mudpt_set_weight(mudpt_model* m, const char* key, const float* host_data, si
  * positions 0..max(eot_index) only: under the causal mask (clip/model.py:407-413) later positions reach neither the EOT
  * feature (trainers/mudpt.py:154) nor any gradient. */
 int mudpt_set_class_prompts(mudpt_model* m, const float* embedding, const int32_t* eot_index);
+/* CoOp handles only (any other handle: MUDPT_ERR_ARG), before mudpt_set_class_prompts.  position = MUDPT_CLASS_TOKEN_*; name_lens [n_cls]
+ * HOST = len(_tokenizer.encode(name)) of every class (trainers/coop.py:80), may be NULL for MUDPT_CLASS_TOKEN_END.  mudpt_set_class_prompts
+ * still receives token_embedding("<X ... X> <name>.") in tokenized order and reorders the rows itself; it refuses a class unless
+ * 0 <= name_lens[c] and 1 + n_ctx + name_lens[c] <= eot_index[c]. */
+int mudpt_set_class_token_position(mudpt_model* m, int32_t position, const int32_t* name_lens);
 /* What the text tower runs per pass after mudpt_set_class_prompts: token rows, length buckets, longest kept length.  With many classes
  * (>= 2048 rows) the prompts are sorted by length and run in up to "txt_buckets" (mudpt_model_set, default 3) groups, each to its own
  * longest EOT, instead of all to the overall longest: the kept rows are bit-identical, the padding rows are not computed. */
 int mudpt_text_layout(const mudpt_model* m, int32_t* rows, int32_t* buckets, int32_t* max_len);
 
 /* The 10 trainable tensors live in ONE flat fp32 bucket (= the data-parallel all-reduce payload). */
-int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT) or 5 (CoCoOp) */
+int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT), 5 (CoCoOp) or 1 (CoOp) */
 size_t mudpt_param_numel(const mudpt_model* m); /* elements of the flat bucket */
 /* name = the reference's CustomCLIP state-dict key; shape has ndim entries (ndim <= 3). */
 int mudpt_param_info(const mudpt_model* m, int index, const char** name, size_t* offset, size_t* numel,
@@ -293,6 +312,11 @@ int mudpt_reduce_rows(int32_t dtype, float* src_f32, void* src_lp, int32_t B, in
  * 1..n of every L-row sequence) of the text-input gradient dx [B * C, L, d] (fp32, or its T copy dx_lp); fixed order: reproducible. */
 int mudpt_cocoop_dbias(int32_t dtype, const float* dx_f32, const void* dx_lp, float* dbias, int32_t B, int32_t C, int32_t L, int32_t d,
                        int32_t n, float scale, void* stream);
+/* CoOp (trainers/coop.py): the gradient of the context from the text-input gradient dx (fp32, or its T copy dx_lp).  rows [C * n]: token row
+ * of context row j of class c.  csc = 0: dctx[j, :] = scale * sum_c dx[rows[c n + j], :] in a fixed order (reproducible bit for bit);
+ * csc = 1: dctx[c, j, :] = scale * dx[rows[c n + j], :].  d % 64 == 0. */
+int mudpt_coop_dctx(int32_t dtype, const float* dx_f32, const void* dx_lp, const int32_t* rows, float* dctx, int32_t C, int32_t n, int32_t d,
+                    int32_t csc, float scale, void* stream);
 /* fp32 C[M,N] = alpha * op(A) . op(B) (+ bias[N]) (+ beta * C): the prompt projections (trainers/mudpt.py:127-128, clip/model.py:539). */
 int mudpt_sgemm(int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda,
                 const float* B, int32_t ldb, float beta, float* C, int32_t ldc, const float* bias, void* stream);

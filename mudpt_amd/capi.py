@@ -10,8 +10,9 @@ LIB_PATH = os.environ.get("MUDPT_LIB") or os.path.join(HERE, "lib", "libmudpt_hi
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "mudpt.h")
 
 BF16, F16, F32 = 0, 1, 2  # F32: the parity mode (include/mudpt.h MUDPT_F32)
-VARIANT_MUDPT, VARIANT_COCOOP = 0, 1
-ABI_VERSION = 6
+VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC = 0, 1, 2, 3
+CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = 0, 1, 2  # TRAINER.COOP.CLASS_TOKEN_POSITION "end" / "middle" / "front"
+ABI_VERSION = 7
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = range(6)
 
 
@@ -35,6 +36,7 @@ SIGNATURES = {
     "mudpt_destroy": (_i32, [_vp]),
     "mudpt_set_weight": (_i32, [_vp, C.c_char_p, _vp, _sz]),
     "mudpt_set_class_prompts": (_i32, [_vp, _vp, _vp]),
+    "mudpt_set_class_token_position": (_i32, [_vp, _i32, _vp]),
     "mudpt_param_count": (_i32, [_vp]),
     "mudpt_param_numel": (_sz, [_vp]),
     "mudpt_param_info": (_i32, [_vp, _i32, C.POINTER(C.c_char_p), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i32),
@@ -77,6 +79,7 @@ SIGNATURES = {
     "mudpt_head": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mudpt_reduce_rows": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _vp]),
     "mudpt_cocoop_dbias": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "mudpt_coop_dctx": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "mudpt_sgemm": (_i32, [_i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i32, _f32, _vp, _i32, _vp, _vp]),
 }
 

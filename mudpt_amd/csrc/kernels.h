@@ -207,6 +207,11 @@ int launch_mean(const float* v, int n, float* out, hipStream_t s);  // out[0] = 
 int launch_cocoop_prompts(float* x0, const float* emb_pos, const float* ctx, const float* bias, const float* pos, int B, int C, int L, int d, int n, hipStream_t s);
 // d bias[i] = scale * sum over the classes and the n context rows of the text-input gradient (fp32 dx or its T copy)
 int launch_cocoop_dbias(int dtype, const float* dx, const void* dx_lp, float* dbias, int B, int C, int L, int d, int n, float scale, hipStream_t s);
+// CoOp (trainers/coop.py, coop.hip): rows / pos [C * n] = token row and prompt position of context row j of class c (caller's class order)
+// x[rows[c n + j]] = ctx[csc ? c : 0][j] + tpos[pos[c n + j]]
+int launch_coop_splice(float* x, const float* ctx, const float* tpos, const int* rows, const int* pos, int C, int n, int d, bool csc, hipStream_t s);
+// shared: dctx[j] = scale * sum_c dx[rows[c n + j]] (fixed order, coop.hip); CSC: dctx[c][j] = scale * dx[rows[c n + j]]  (fp32 dx or its T copy)
+int launch_coop_dctx(int dtype, const float* dx, const void* dx_lp, const int* rows, float* dctx, int C, int n, int d, bool csc, float scale, hipStream_t s);
 // y = x / ||x|| per row, inv = 1 / ||x||
 int launch_l2norm(const float* x, float* y, float* inv, int rows, int e, hipStream_t s);
 int launch_relu(float* y, size_t n, hipStream_t s);

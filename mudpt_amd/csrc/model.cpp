@@ -131,6 +131,7 @@ struct Tower {
     // other rows of the tower input have no trainable ancestor), so its in_proj dX GEMM and ln_1 backward run on those rows.
     const int* head_rows = nullptr;  // [nseq * n_ctx] token rows of the prompt tokens
     int head_n = 0;                  // rows per sequence
+    int head_span = 0;               // rows prompt_row0 .. prompt_row0 + head_span - 1 hold every head row (0 = head_n; CoOp middle / front: wider)
     void *hd_dqkv = nullptr, *hd_h = nullptr;  // T [max_seq * n_ctx, 3 d], [max_seq * n_ctx, d]
     std::vector<void*> act_allocs;  // activation / scratch buffers (sized for max_seq sequences of L rows): re-made when L changes
     // Length buckets (text tower with many classes): the sequences are sorted by length and packed bucket after bucket, each bucket with
@@ -205,6 +206,13 @@ struct mudpt_model {
     float cp_unscale = 0.f;  // of the step in flight between mudpt_cp_head and mudpt_cp_backward
     int cp_B = 0, cp_stage = 0;  // 1 = towers forward done, 2 = head (training) done
     int hid = 0;  // meta_net hidden width = embed_dim / 16 (trainers/cocoop.py:104)
+    // CoOp variant (trainers/coop.py): 1 trainable (ctx, shared or one per class with CSC), vanilla vision tower (forward only), C text
+    // sequences as MuDPT.  The context rows of class c sit at prompt positions coop_pos[c * n ..] (CLASS_TOKEN_POSITION); tprompt_rows
+    // then holds their token rows in the CALLER's class order (coop.hip)
+    bool coop = false, csc = false;
+    int class_token_position = MUDPT_CLASS_TOKEN_END;
+    std::vector<int> name_lens;  // [n_cls] (trainers/coop.py:80); empty = all 0 (END without lengths)
+    int* coop_pos = nullptr;     // [n_cls * n_ctx] device
     float *mn_hid = nullptr, *mn_bias = nullptr, *mn_dbias = nullptr, *mn_dhid = nullptr;  // [B, hid], [B, dt], [B, dt], [B, hid]
     float loss_scale = 128.f;  // static, power of two; see mudpt_forward_backward
     // bf16 mode keeps the gradient of the residual stream in T only (the fp32 copy costs 237 MB of HBM traffic per LayerNorm
@@ -360,6 +368,8 @@ static const char* kCocoopNames[5] = {
     "prompt_learner.meta_net.linear2.bias",
 };
 enum { Q_CTX = 0, Q_W1, Q_B1, Q_W2, Q_B2 };
+// CoOp: the one trainable under CustomCLIP (trainers/coop.py:74,206; only prompt_learner is registered, :255-259)
+static const char* kCoopName = "prompt_learner.ctx";
 
 
 static int dev_alloc(mudpt_model* m, void** out, size_t bytes) {
@@ -461,9 +471,11 @@ extern "C" const char* mudpt_last_error(void) { return get_error(); }
 extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
     ARG_CHECK(c && out, "create: null argument");
     ARG_CHECK(c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F16 || c->dtype == MUDPT_F32, "create: dtype must be MUDPT_BF16, MUDPT_F16 or MUDPT_F32");
-    ARG_CHECK(c->variant == MUDPT_VARIANT_MUDPT || c->variant == MUDPT_VARIANT_COCOOP, "create: unknown variant %d", c->variant);
+    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_COOP_CSC, "create: unknown variant %d", c->variant);
     const bool cocoop = c->variant == MUDPT_VARIANT_COCOOP;
-    ARG_CHECK(cocoop || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
+    const bool coop = c->variant == MUDPT_VARIANT_COOP || c->variant == MUDPT_VARIANT_COOP_CSC;
+    const bool vanilla = cocoop || coop;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
+    ARG_CHECK(vanilla || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
     ARG_CHECK(c->n_ctx > 0 && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
     ARG_CHECK(c->patch > 0 && c->image_size % c->patch == 0, "create: image_size %d / patch %d unsupported", c->image_size, c->patch);
     ARG_CHECK(c->v_width == c->v_heads * 64 && c->t_width == c->t_heads * 64, "create: head dim must be 64");
@@ -471,7 +483,7 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
     ARG_CHECK(c->embed_dim == c->t_width, "create: embed_dim must equal t_width (visual_ctx_deep_projections output is added to text prompts)");
     ARG_CHECK(1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
     const int P = (c->image_size / c->patch) * (c->image_size / c->patch);
-    const int Lv = 1 + P + (cocoop ? 0 : c->n_ctx);  // CoCoOp's image encoder is the vanilla ViT (trainers/cocoop.py:38, clip/model.py:443-496)
+    const int Lv = 1 + P + (vanilla ? 0 : c->n_ctx);  // CoCoOp's / CoOp's image encoder is the vanilla ViT (trainers/cocoop.py:38, coop.py:37, clip/model.py:443-496)
     ARG_CHECK(Lv <= 4096 && c->ctx_len <= 4096, "create: sequence length %d/%d exceeds the attention limit (4096)", Lv, c->ctx_len);
 
     mudpt_model* m = new mudpt_model();
@@ -494,12 +506,14 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
     m->lp_upd = (c->dtype == MUDPT_BF16);
     m->gelu_q8 = (c->dtype == MUDPT_BF16);
     m->cocoop = cocoop;
+    m->coop = coop;
+    m->csc = c->variant == MUDPT_VARIANT_COOP_CSC;
     m->ct = c->n_cls;
-    if (cocoop) m->cfg.depth = 1;  // no deep prompts
+    if (vanilla) m->cfg.depth = 1;  // no deep prompts
     const int dv = c->v_width, dt = c->t_width, e = c->embed_dim, n = c->n_ctx, D1 = m->cfg.depth - 1, B = c->max_batch, C = c->n_cls;
     const int TS = cocoop ? B * C : C;  // text sequences per step: one per (image, class) pair in CoCoOp (trainers/cocoop.py:187-194)
     auto fail = [&](int code) { mudpt_destroy(m); return code; };
-    if (int r = alloc_tower_weights(m, m->vis, dv, c->v_layers, c->v_heads, false, cocoop ? Lv : Lv - n, m->exact)) return fail(r);  // e4m3 weight copies: vision tower of the parity mode
+    if (int r = alloc_tower_weights(m, m->vis, dv, c->v_layers, c->v_heads, false, vanilla ? Lv : Lv - n, m->exact)) return fail(r);  // e4m3 weight copies: vision tower of the parity mode
     if (int r = alloc_tower_acts(m, m->vis, Lv, B)) return fail(r);
     // the text tower's activations are sized by mudpt_set_class_prompts: its trimmed length (max(eot) + 1 of ctx_len positions) and, for
     // CoCoOp, the number of images whose B * C prompts fit the memory budget at once are only known there
@@ -535,6 +549,7 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
             ALLOC(m->mn_hid, (size_t)B * m->hid * 4); ALLOC(m->mn_dhid, (size_t)B * m->hid * 4);
             ALLOC(m->mn_bias, (size_t)B * dt * 4); ALLOC(m->mn_dbias, (size_t)B * dt * 4);
         }
+        if (coop) ALLOC(m->coop_pos, (size_t)C * n * 4);
         ALLOC(m->gemm_scratch, mudpt_model::kScratchElems * 4); ALLOC(m->gemm_scratch2, mudpt_model::kScratchElems * 4);
         HIP_TRY(hipStreamCreateWithFlags(&m->s2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&m->ev_fork, &m->ev_join, &m->ev_fork_b, &m->ev_join_b}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -546,7 +561,7 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
         }
         HIP_TRY(hipMemcpy(m->cls_rows, cr.data(), cr.size() * 4, hipMemcpyHostToDevice));
         m->vis.tail_rows = m->cls_rows;
-        m->vis.head_rows = cocoop ? nullptr : m->vprompt_rows;
+        m->vis.head_rows = vanilla ? nullptr : m->vprompt_rows;
         ALLOC(m->tprompt_rows, (size_t)TS * n * 4);
         m->txt.head_rows = m->tprompt_rows;  // ctx rows of every prompt; this table and the next are filled by mudpt_set_class_prompts
         m->txt.tail_rows = m->eot_rows;
@@ -560,9 +575,11 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
                                (size_t)n * dv, (size_t)D1 * n * dv, (size_t)e * dv, (size_t)e};
     // CoCoOp: ctx [n, dt], meta_net.linear1 [e/16, e] + [e/16], meta_net.linear2 [dt, e/16] + [dt]  (trainers/cocoop.py:96-107)
     const size_t cshapes[5] = {(size_t)n * dt, (size_t)(e / 16) * e, (size_t)(e / 16), (size_t)dt * (e / 16), (size_t)dt};
-    m->nparams = cocoop ? 5 : 10;
+    // CoOp: ctx [n, dt], or [n_cls, n, dt] with CSC (trainers/coop.py:60-76)
+    const size_t coop_numel = (size_t)(m->csc ? C : 1) * n * dt;
+    m->nparams = cocoop ? 5 : coop ? 1 : 10;
     size_t o = 0;
-    for (int i = 0; i < m->nparams; ++i) { m->off[i] = o; m->numel[i] = cocoop ? cshapes[i] : shapes[i]; o += m->numel[i]; }
+    for (int i = 0; i < m->nparams; ++i) { m->off[i] = o; m->numel[i] = cocoop ? cshapes[i] : coop ? coop_numel : shapes[i]; o += m->numel[i]; }
     m->total = o;
     if (int r = dev_alloc(m, (void**)&m->momentum, o * 4)) return fail(r);
 
@@ -700,6 +717,35 @@ extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* da
     return MUDPT_OK;
 }
 
+// CoOp's construct_prompts (trainers/coop.py:99-164), row by row: position of context row j, and the row of the TOKENIZED prompt
+// "<X x n> <name>." that lands at prompt row t (context rows: t itself; their content is the spliced context).  suffix = rows 1 + n ..,
+// h = n / 2 (rounded down, :122).  Rows from 1 + n + name_len on (".", EOT, padding) keep their place, so the EOT row does not move.
+static int coop_ctx_row(int position, int n, int nl, int j) {
+    if (position == MUDPT_CLASS_TOKEN_MIDDLE) return j < n / 2 ? 1 + j : 1 + nl + j;  // [SOS, ctx[:h], name, ctx[h:], suffix[nl:]]
+    if (position == MUDPT_CLASS_TOKEN_FRONT) return 1 + nl + j;                          // [SOS, name, ctx, suffix[nl:]]
+    return 1 + j;                                                                        // [SOS, ctx, suffix]
+}
+static int coop_src_row(int position, int n, int nl, int t) {
+    const int h = n / 2;
+    if (position == MUDPT_CLASS_TOKEN_MIDDLE && t >= 1 + h && t < 1 + h + nl) return 1 + n + (t - 1 - h);
+    if (position == MUDPT_CLASS_TOKEN_FRONT && t >= 1 && t < 1 + nl) return 1 + n + (t - 1);
+    return t;
+}
+
+extern "C" int mudpt_set_class_token_position(mudpt_model* m, int32_t position, const int32_t* name_lens) {
+    ARG_CHECK(m, "set_class_token_position: null model");
+    ARG_CHECK(m->coop, "set_class_token_position: not a CoOp model (MUDPT_VARIANT_COOP / MUDPT_VARIANT_COOP_CSC)");
+    ARG_CHECK(position == MUDPT_CLASS_TOKEN_END || position == MUDPT_CLASS_TOKEN_MIDDLE || position == MUDPT_CLASS_TOKEN_FRONT,
+              "set_class_token_position: position %d is not MUDPT_CLASS_TOKEN_END / _MIDDLE / _FRONT", position);
+    ARG_CHECK(name_lens || position == MUDPT_CLASS_TOKEN_END, "set_class_token_position: middle / front need name_lens");
+    m->class_token_position = position;
+    m->name_lens.clear();
+    if (name_lens) m->name_lens.assign(name_lens, name_lens + m->cfg.n_cls);
+    m->prompts_set = false;  // the row tables are built by the next mudpt_set_class_prompts
+    m->text_valid = false;
+    return MUDPT_OK;
+}
+
 extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const int32_t* eot) {
     ARG_CHECK(m && emb && eot, "set_class_prompts: null argument");
     for (const std::string& k : m->missing)
@@ -710,6 +756,13 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     for (int cc = 0; cc < c.n_cls; ++cc) ARG_CHECK(eot[cc] >= 0 && eot[cc] < (int)L, "set_class_prompts: eot index %d out of range", eot[cc]);
     emb += c0 * L * d;
     eot += c0;
+    const int n = c.n_ctx, ctp = m->class_token_position;
+    auto name_len = [&](size_t cc) { return m->name_lens.empty() ? 0 : m->name_lens[cc]; };
+    if (m->coop) {  // every context row lies before the EOT row, which construct_prompts does not move
+        for (size_t cc = 0; cc < C; ++cc)
+            ARG_CHECK(name_len(cc) >= 0 && 1 + n + name_len(cc) <= eot[cc], "set_class_prompts: class %zu: name_lens %d with n_ctx %d does not fit before its EOT row %d",
+                      cc, name_len(cc), n, eot[cc]);
+    }
     // The text tower is causal (clip/model.py:407-413 build_attention_mask) and only the EOT row of each prompt is used
     // (trainers/mudpt.py:154): positions behind the last EOT of the class set influence neither a used output nor a gradient,
     // so the tower runs on the first Le = max(eot) + 1 positions of every prompt ("a photo of a <name>." ends at position 7-9
@@ -804,7 +857,8 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     const std::vector<Tower::Seg> segs = tower_segs(X, (int)C);
     const size_t packed_rows = X.segs.empty() ? C * Le : (size_t)X.rows;
     std::vector<float> ep(packed_rows * d);
-    std::vector<int> rows(C * reps), rows_local(C * reps), tr(C * reps * c.n_ctx), perm(C);
+    std::vector<int> rows(C * reps), rows_local(C * reps), tr(C * reps * c.n_ctx), perm(C), cpos(m->coop ? C * n : 0);
+    int span = n;
     for (const Tower::Seg& g : segs)
         for (int j = 0; j < g.nseq; ++j) {
             const int sq = g.seq0 + j, cc = order[sq];
@@ -813,7 +867,23 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
             for (size_t i = 0; i < reps; ++i) {  // reps > 1 (CoCoOp) only with one bucket: image i's prompts follow image i - 1's
                 rows[i * C + sq] = (int)(i * C * Le + r0) + eot[cc];
                 rows_local[i * C + sq] = (int)(i * C * Le + r0 - g.row0) + eot[cc];
-                for (int k = 0; k < c.n_ctx; ++k) tr[(i * C + sq) * c.n_ctx + k] = (int)(i * C * Le + r0) + 1 + k;  // ctx rows 1..n (trainers/mudpt.py:97-115)
+                if (!m->coop)
+                    for (int k = 0; k < c.n_ctx; ++k) tr[(i * C + sq) * c.n_ctx + k] = (int)(i * C * Le + r0) + 1 + k;  // ctx rows 1..n (trainers/mudpt.py:97-115)
+            }
+            if (m->coop) {
+                // CoOp: the prompt rows in construct_prompts' order, THEN the positional embedding (trainers/coop.py:187-188); the context
+                // rows' table in the caller's class order, token rows of the packed layout (coop.hip)
+                const int nl = name_len(cc);
+                for (int k = 0; k < n; ++k) {
+                    cpos[(size_t)cc * n + k] = coop_ctx_row(ctp, n, nl, k);
+                    tr[(size_t)cc * n + k] = (int)r0 + cpos[(size_t)cc * n + k];
+                }
+                span = std::max(span, coop_ctx_row(ctp, n, nl, n - 1));
+                for (int t = 0; t < g.L; ++t) {
+                    const float* src = emb + ((size_t)cc * L + coop_src_row(ctp, n, nl, t)) * d;
+                    for (size_t k = 0; k < d; ++k) ep[(r0 + t) * d + k] = src[k] + pos[(size_t)t * d + k];
+                }
+                continue;
             }
             for (size_t i = 0; i < (size_t)g.L * d; ++i) ep[r0 * d + i] = emb[(size_t)cc * L * d + i] + pos[i];  // trainers/mudpt.py:143
         }
@@ -822,6 +892,8 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     HIP_TRY(hipMemcpy(m->eot_local, rows_local.data(), rows_local.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->tprompt_rows, tr.data(), tr.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->class_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
+    if (m->coop) HIP_TRY(hipMemcpy(m->coop_pos, cpos.data(), cpos.size() * 4, hipMemcpyHostToDevice));
+    X.head_span = span;  // block 0's backward computes the attention rows 1 .. span, which hold every context row (CoOp middle / front: > n)
     X.tail_local = m->eot_local;
     m->prompts_set = true;
     m->text_valid = false;
@@ -843,6 +915,17 @@ extern "C" int mudpt_param_info(const mudpt_model* m, int i, const char** name, 
     ARG_CHECK(m && i >= 0 && i < m->nparams, "param_info: bad index %d", i);
     const mudpt_config& c = m->cfg;
     const int64_t n = c.n_ctx, D1 = c.depth - 1, dt = c.t_width, dv = c.v_width, e = c.embed_dim;
+    if (m->coop) {  // trainers/coop.py:60-76
+        if (name) *name = kCoopName;
+        if (offset) *offset = m->off[0];
+        if (numel) *numel = m->numel[0];
+        if (ndim) *ndim = m->csc ? 3 : 2;
+        if (shape) {
+            const int64_t s3[3] = {(int64_t)c.n_cls, n, dt}, s2[3] = {n, dt, 0};
+            for (int k = 0; k < 3; ++k) shape[k] = m->csc ? s3[k] : s2[k];
+        }
+        return MUDPT_OK;
+    }
     if (m->cocoop) {
         const int64_t hd = e / 16;
         const int64_t cshp[5][3] = {{n, dt, 0}, {hd, e, 0}, {hd, 0, 0}, {dt, hd, 0}, {dt, 0, 0}};
@@ -1121,7 +1204,10 @@ static int block_bwd(mudpt_model* m, Tower& t, int i, int nseq, hipStream_t s, f
         at.dout = (const char*)t.dattn + (size_t)g.row0 * d * esz; at.dqkv = (char*)t.dqkv + (size_t)g.row0 * 3 * d * esz; at.delta = t.delta + g.lse0;
         at.B = g.nseq; at.L = g.L; at.H = t.heads; at.causal = t.causal;
         // block 0: only the prompt rows of dqkv are read below (Tower::head_rows)
-        if (i == 0 && t.head_rows && t.layers > 1 && m->attn_window) { at.win_row0 = t.prompt_row0; at.win_n = t.head_n; }
+        if (i == 0 && t.head_rows && t.layers > 1 && m->attn_window) {
+            at.win_row0 = t.prompt_row0;
+            at.win_n = std::min(t.head_span > 0 ? t.head_span : t.head_n, g.L - t.prompt_row0);  // a bucket's head rows lie before its EOT rows
+        }
         TRY(attn_call(m, t, at, true, s));
     }
     if (i == 0 && t.head_rows && t.layers > 1) {
@@ -1163,7 +1249,7 @@ static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_
     pe.patches = P; pe.seq_len = Lv; pe.pos = m->vpos;
     TRY(gemm_call(m, EPI_PATCH, pe, s));
     TRY(launch_set_rows(m->xpre, B, Lv, dv, 0, 1, m->cls, m->vpos, s));
-    if (!m->cocoop) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, Pm + m->off[P_VCTX], m->shared, s));
+    if (!m->cocoop && !m->coop) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, Pm + m->off[P_VCTX], m->shared, s));
     LnFwdArgs lp; lp.x = m->xpre; lp.ldx = dv; lp.gamma = m->ln_pre_g; lp.beta = m->ln_pre_b; lp.out = m->vis.a[0].x_in; lp.ldo = dv; lp.out_f32 = true;
     lp.mean = m->pre_mean; lp.rstd = m->pre_rstd; lp.rows = B * Lv; lp.d = dv;
     TRY(launch_ln_fwd(m->dtype, lp, s));
@@ -1276,6 +1362,7 @@ static int cocoop_forward_backward(mudpt_model* m, const float* images, const in
 // ---- the MuDPT step in pieces (the monolithic entry points and the class-parallel phases share them) ------------------------------
 // prompt learner, trainers/mudpt.py:117-130 + clip/model.py:534-539
 static int prompt_learner_forward(mudpt_model* m, hipStream_t s) {
+    if (m->coop) return MUDPT_OK;  // CoOp: the context goes into the prompts as it is (trainers/coop.py:166-175)
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, dt = c.t_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1;
     float* Pm = m->params;
@@ -1297,8 +1384,11 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
     const std::vector<Tower::Seg> segs = tower_segs(m->txt, Ct);
     const bool packed = segs.size() > 1;
     HIP_TRY(hipMemcpyAsync(m->txt.a[0].x_in, m->emb_pos, (size_t)tower_rows(m->txt, Ct) * dt * 4, hipMemcpyDeviceToDevice, s2));
-    for (const Tower::Seg& g : segs)
-        TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, Pm + m->off[P_CTX], m->tpos + dt, s2));
+    if (m->coop)  // trainers/coop.py:166-175,187-188: the context rows at every class's own positions, all buckets in one launch
+        TRY(launch_coop_splice(m->txt.a[0].x_in, Pm + m->off[0], m->tpos, m->tprompt_rows, m->coop_pos, Ct, n, dt, m->csc, s2));
+    else
+        for (const Tower::Seg& g : segs)
+            TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, Pm + m->off[P_CTX], m->tpos + dt, s2));
     for (int i = 0; i < m->txt.layers; ++i) {
         TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? m->txt_deep + (size_t)(i - 1) * n * dt : nullptr, s2));
     }
@@ -1421,6 +1511,9 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
                 TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, (char*)X.dx_lp + (size_t)g.row0 * dt * 2, g.nseq, g.L, dt, 1, n,
                                        m->d_txt_deep + (size_t)(i - 1) * n * dt, true, g.seq0 > 0, unscale, s2));
     }
+    // CoOp: d ctx from the context rows of every class (shared: summed over the classes in a fixed order; CSC: per class), coop.hip
+    if (m->coop)
+        return launch_coop_dctx(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, m->tprompt_rows, G + m->off[0], Ct, n, dt, m->csc, unscale, s2);
     // d ctx (text side): rows 1..n of the first block's input, summed over the class prompts
     for (const Tower::Seg& g : segs)
         TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, m->lp_grad ? (char*)X.dx_lp + (size_t)g.row0 * dt * 2 : nullptr, g.nseq, g.L, dt, 1, n,
@@ -1523,6 +1616,9 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
     TRY(towers_forward(m, images, B, s, false));
     HIP_TRY(hipMemsetAsync(m->grads, 0, m->total * 4, s));
     TRY(head_train(m, labels, B, grad_scale, loss, logits, s));
+    // CoOp (trainers/coop.py:281-296): only the context is trainable, and it feeds the text tower alone -- no vision backward, no
+    // prompt-learner GEMMs: the text tower's backward and the context gradient, on the main stream
+    if (m->coop) return text_backward(m, m->cp_unscale, s);
     // text tower backward on the side stream (enqueued first; joins before the prompt-learner backward)
     HIP_TRY(hipEventRecord(m->ev_fork_b, s));
     HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork_b, 0));
@@ -1545,6 +1641,7 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
 extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
     ARG_CHECK(m, "set_class_shard: null model");
     if (m->cocoop) { set_error("set_class_shard: CoCoOp's text features depend on the image; shard the batch instead"); return MUDPT_ERR_ARG; }
+    if (m->coop) { set_error("set_class_shard: class-parallel CoOp is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
     ARG_CHECK(c0 >= 0 && c1 > c0 && c1 <= m->cfg.n_cls, "set_class_shard: [%d, %d) is not a non-empty range of the %d classes", c0, c1, m->cfg.n_cls);
     m->c0 = c0; m->ct = c1 - c0;
     m->sharded = !(c0 == 0 && c1 == m->cfg.n_cls);
@@ -1555,6 +1652,7 @@ extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
 }
 extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, size_t* numel) {
     ARG_CHECK(m && !m->cocoop, "cp_buffers: not a MuDPT model");
+    ARG_CHECK(!m->coop, "cp_buffers: not a MuDPT model (the class-parallel phases run MuDPT only)");
     if (feat) *feat = m->txt_f;
     if (dfeat) *dfeat = m->dtxt;
     if (numel) *numel = (size_t)m->cfg.n_cls * m->cfg.embed_dim;
@@ -1562,6 +1660,7 @@ extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, siz
 }
 extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, int32_t flags, void* stream) {
     TRY(ready(m, B, false));
+    ARG_CHECK(!m->coop, "cp_forward: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(images && !m->cocoop, "cp_forward: null images / not a MuDPT model");
     const bool reuse = (flags & MUDPT_FWD_REUSE_TEXT) != 0;
     if (reuse && !m->text_valid) { set_error("cp_forward: MUDPT_FWD_REUSE_TEXT before any text-tower pass"); return MUDPT_ERR_STATE; }
@@ -1572,6 +1671,7 @@ extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, 
 }
 extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, float grad_scale, float* loss, float* logits, int32_t flags, void* stream) {
     TRY(ready(m, B, labels != nullptr));
+    ARG_CHECK(!m->coop, "cp_head: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(!m->cocoop && (labels ? loss != nullptr : logits != nullptr), "cp_head: training needs labels and loss, inference needs logits");
     if (m->cp_stage < 1 || m->cp_B != B) { set_error("cp_head: call mudpt_cp_forward with the same batch first"); return MUDPT_ERR_STATE; }
     hipStream_t s = (hipStream_t)stream;
@@ -1587,6 +1687,7 @@ extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, f
     return MUDPT_OK;
 }
 extern "C" int mudpt_cp_backward(mudpt_model* m, int32_t part, void* stream) {
+    ARG_CHECK(!(m && m->coop), "cp_backward: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(m && !m->cocoop && (part == MUDPT_CP_VISION || part == MUDPT_CP_TEXT), "cp_backward: part must be MUDPT_CP_VISION or MUDPT_CP_TEXT");
     hipStream_t s = (hipStream_t)stream;
     if (part == MUDPT_CP_VISION) {
@@ -1851,6 +1952,10 @@ extern "C" int mudpt_reduce_rows(int32_t dtype, float* src, void* src_lp, int32_
 extern "C" int mudpt_cocoop_dbias(int32_t dtype, const float* dx_f32, const void* dx_lp, float* dbias, int32_t B, int32_t C, int32_t L, int32_t d, int32_t n,
                                   float scale, void* stream) {
     return launch_cocoop_dbias(dtype, dx_f32, dx_lp, dbias, B, C, L, d, n, scale, (hipStream_t)stream);
+}
+extern "C" int mudpt_coop_dctx(int32_t dtype, const float* dx_f32, const void* dx_lp, const int32_t* rows, float* dctx, int32_t C, int32_t n, int32_t d,
+                               int32_t csc, float scale, void* stream) {
+    return launch_coop_dctx(dtype, dx_f32, dx_lp, rows, dctx, C, n, d, csc != 0, scale, (hipStream_t)stream);
 }
 extern "C" int mudpt_sgemm(int32_t tA, int32_t tB, int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda, const float* B, int32_t ldb,
                            float beta, float* C, int32_t ldc, const float* bias, void* stream) {

@@ -42,7 +42,8 @@ def default_cfg() -> CfgNode:
                 WARMUP_CONS_LR=1e-5, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, SGD_DAMPNING=0.0, SGD_NESTEROV=False),
         TRAIN=C(PRINT_FREQ=5),
         TRAINER=C(NAME="MuDPT", MUDPT=C(N_CTX=2, CTX_INIT="a photo of a", DEEP_PROMPT_DEPTH=8, PREC="fp16"),
-                  COCOOP=C(N_CTX=4, CTX_INIT="a photo of a", PREC="fp16")),  # train.py:92-95 + configs/trainers/CoCoOp/*.yaml
+                  COCOOP=C(N_CTX=4, CTX_INIT="a photo of a", PREC="fp16"),  # train.py:92-95 + configs/trainers/CoCoOp/*.yaml
+                  COOP=C(N_CTX=16, CTX_INIT="", PREC="fp16", CSC=False, CLASS_TOKEN_POSITION="end")),  # train.py:83-88
     )
 
 

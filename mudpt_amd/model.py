@@ -58,7 +58,8 @@ class CustomCLIP(nn.Module):
     def __init__(self, shape: ModelShape, clip_state: Dict[str, torch.Tensor], tokenized_prompts: torch.Tensor,
                  ctx_token_ids: Optional[Sequence[int]] = None, max_batch: int = 256, dtype: str = "bf16",
                  device: str = "cuda:0", seed: Optional[int] = None, variant: str = "mudpt", knobs: Optional[Dict[str, int]] = None,
-                 class_shard: Optional[Sequence[int]] = None, group=None):
+                 class_shard: Optional[Sequence[int]] = None, group=None, class_token_position: str = "end",
+                 name_lens: Optional[Sequence[int]] = None):
         super().__init__()
         if not torch.cuda.is_available():
             raise capi.MudptError("mudpt_amd needs an MI355X (HIP device); there is no CPU path in the product")
@@ -71,11 +72,17 @@ class CustomCLIP(nn.Module):
         self.tokenized_prompts = tokenized_prompts.clone()
         # "cocoop": the same library runs trainers/cocoop.py's CustomCLIP (vanilla vision tower, meta_net, one text-tower pass
         # per (image, class) pair); the module then owns ctx + meta_net under the reference's names (prompt_learner.*)
+        # "coop" / "coop_csc": trainers/coop.py's CustomCLIP (vanilla vision tower, forward only; one trainable, prompt_learner.ctx, shared
+        # [n_ctx, d_t] or one per class [n_cls, n_ctx, d_t]); class_token_position / name_lens: TRAINER.COOP.CLASS_TOKEN_POSITION and
+        # len(_tokenizer.encode(name)) per class (coop.py:80), needed for "middle" / "front"
+        if variant == "coop_csc" and ctx_token_ids is not None:
+            variant = "coop"  # trainers/coop.py:52-61: the CTX_INIT path builds one shared context whatever CSC says
         self.variant = variant
         cfg = capi.Config(shape.image_size, shape.patch, shape.v_width, shape.v_layers, shape.v_heads, shape.t_width,
                           shape.t_layers, shape.t_heads, shape.ctx_len, shape.embed_dim, shape.n_ctx, shape.depth,
                           self.n_cls, self.max_batch, {"bf16": capi.BF16, "fp16": capi.F16, "fp32": capi.F32}[dtype],
-                          {"mudpt": capi.VARIANT_MUDPT, "cocoop": capi.VARIANT_COCOOP}[variant])
+                          {"mudpt": capi.VARIANT_MUDPT, "cocoop": capi.VARIANT_COCOOP, "coop": capi.VARIANT_COOP,
+                           "coop_csc": capi.VARIANT_COOP_CSC}[variant])
         torch.cuda.set_device(self.device)
         h = C.c_void_p()
         capi.check(self.lib.mudpt_create(C.byref(cfg), C.byref(h)), "create")
@@ -92,9 +99,18 @@ class CustomCLIP(nn.Module):
         # of the two exchanges (None = the default group)
         self.class_shard, self.group = None, group
         if class_shard is not None and tuple(class_shard) != (0, self.n_cls):
-            assert variant == "mudpt", "CoCoOp's text features depend on the image: shard the batch, not the classes"
+            assert variant != "cocoop", "CoCoOp's text features depend on the image: shard the batch, not the classes"
+            assert variant == "mudpt", "class-parallel CoOp is not implemented: shard the batch, not the classes"
             self.class_shard = (int(class_shard[0]), int(class_shard[1]))
             capi.check(self.lib.mudpt_set_class_shard(h, *self.class_shard), "set_class_shard")
+        self.class_token_position = class_token_position
+        if variant in ("coop", "coop_csc"):  # before the class prompts: they are reordered by it (trainers/coop.py:99-164)
+            pos = {"end": capi.CLASS_TOKEN_END, "middle": capi.CLASS_TOKEN_MIDDLE, "front": capi.CLASS_TOKEN_FRONT}[class_token_position]
+            lens = None if name_lens is None else torch.tensor([int(v) for v in name_lens], dtype=torch.int32)
+            assert lens is None or lens.numel() == self.n_cls, f"name_lens has {lens.numel()} entries for {self.n_cls} classes"
+            capi.check(self.lib.mudpt_set_class_token_position(h, pos, capi.ptr(lens)), "set_class_token_position")
+        else:
+            assert class_token_position == "end" and name_lens is None, "class_token_position / name_lens are CoOp settings"
         # class prompts: token_embedding(tokenized) and the EOT position (trainers/mudpt.py:85-90,154)
         emb_w = clip_state["token_embedding.weight"].detach().to("cpu", torch.float32)
         tok = tokenized_prompts.to("cpu").long()
@@ -201,7 +217,7 @@ class CustomCLIP(nn.Module):
         # eval mode: the text features only depend on the parameters; recompute them only when the flat bucket's version
         # counter moved (the reference re-runs the text tower for every test batch)
         version = self.flat_params._version
-        reuse = (not self.training) and self._text_version == version and self.variant == "mudpt"  # CoCoOp's text features depend on the image
+        reuse = (not self.training) and self._text_version == version and self.variant != "cocoop"  # CoCoOp's text features depend on the image
         if self.class_shard is not None:
             capi.check(self.lib.mudpt_cp_forward(self._h, capi.ptr(image), B, 1 if reuse else 0, self._stream()), "cp_forward")
             if not reuse:

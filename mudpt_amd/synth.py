@@ -29,6 +29,19 @@ def bench_tokenized_prompts(ctx_len: int = 77) -> torch.Tensor:
     return tok
 
 
+X_TOKEN = 343  # "X", the placeholder context word of CoOp's prompts (trainers/coop.py:72); recorded in tests/golden/coop_*.npz
+
+
+def bench_coop_prompts(n_ctx: int, ctx_len: int = 77):
+    """clip.tokenize("X X .. X <name>.") for the benchmark names (trainers/coop.py:72,82-84) and len(_tokenizer.encode(name)) (:80), without
+    the BPE vocabulary: the CoOp plugin's stand-in on synthetic data."""
+    tok = torch.zeros(len(_BENCH_NAME_TOKENS), ctx_len, dtype=torch.int32)
+    for i, name in enumerate(_BENCH_NAME_TOKENS):
+        ids = [49406] + [X_TOKEN] * n_ctx + name + [269, 49407]
+        tok[i, :len(ids)] = torch.tensor(ids, dtype=torch.int32)
+    return tok, [len(n) for n in _BENCH_NAME_TOKENS]
+
+
 def synthetic_tokenized_prompts(n_cls: int, n_ctx: int = 4, ctx_len: int = 77, seed: int = 7) -> torch.Tensor:
     """Prompts shaped like "<ctx words> <name tokens> ." for synthetic class lists (e.g. 1000 ImageNet-sized).  Name lengths
     follow a long-tailed mix like BPE-tokenised ImageNet names: 70 % 1-3 tokens, 25 % 4-6, 5 % 7-12 (the longest name sets

@@ -68,7 +68,7 @@ def tokenize_prompts(prompts, ctx_len=77, near=None):
 LOSS_SCALE_INIT, LOSS_SCALE_MIN, LOSS_SCALE_GROWTH_INTERVAL = 128.0, 1.0, 2000
 
 
-def data_parallel_step(trainer, batch):
+def data_parallel_step(trainer, batch, with_acc: bool = False):
     """One training step of either plugin (trainers/mudpt.py:235-261, trainers/cocoop.py:246-276) in data-parallel form:
     forward + cross-entropy + backward in ONE library call on this rank's images (gradient of loss / world), ONE all-reduce of the
     flat bucket, the consensus on what every rank sees (parallel.step_consensus), then the optimizer step -- so replicas stay bitwise
@@ -78,10 +78,20 @@ def data_parallel_step(trainer, batch):
     Loss scaling follows torch.cuda.amp.GradScaler (the reference's amp path, trainers/mudpt.py:228,239-246): the backward runs on
     per-sample gradients times a power-of-two scale inside the library; gradients that come back non-finite (an fp16 copy of a token
     gradient overflowed) make every rank SKIP the optimizer step and halve the scale; LOSS_SCALE_GROWTH_INTERVAL clean steps in a row
-    double it again, up to the initial value.  A non-finite LOSS is an error, as in Dassl's model_backward_and_update."""
+    double it again, up to the initial value.  A non-finite LOSS is an error, as in Dassl's model_backward_and_update.
+
+    with_acc (the CoOp plugin, trainers/coop.py:297-300): the summary also has "acc", the top-1 accuracy of the GLOBAL batch in percent
+    (dassl.metrics.compute_accuracy of the gathered logits): correct and total counts are summed over the ranks."""
     image, label = trainer.parse_batch_train(batch)
     model = trainer.model
-    loss = model.forward_backward(image, label, grad_scale=parallel.grad_scale())
+    if with_acc:
+        loss, logits = model.forward_backward(image, label, grad_scale=parallel.grad_scale(), return_logits=True)
+        counts = torch.stack([(logits.argmax(dim=1) == label.to(logits.device)).sum().float(),
+                              torch.tensor(float(label.shape[0]), device=logits.device)])
+        if parallel.world_size() > 1:
+            torch.distributed.all_reduce(counts, op=torch.distributed.ReduceOp.SUM)
+    else:
+        loss = model.forward_backward(image, label, grad_scale=parallel.grad_scale())
     parallel.allreduce_grads(model.flat_grads)
     loss_ok, grads_ok, global_loss = parallel.step_consensus(loss, model.flat_grads)
     if not loss_ok:
@@ -101,6 +111,8 @@ def data_parallel_step(trainer, batch):
         model.set_loss_scale(state["scale"])
         print(f"Gradient overflow: step skipped, loss scale halved to {state['scale']:g}")
     loss_summary = {"loss": global_loss}
+    if with_acc:
+        loss_summary["acc"] = (counts[0] * 100.0 / counts[1]).item()
     if (trainer.batch_idx + 1) == trainer.num_batches:
         trainer.update_lr()
     return loss_summary
