@@ -27,6 +27,14 @@
  *   mudpt_param_*                        trainers/coop.py:60-76    ctx [n_ctx, d_t] (shared) or [n_cls, n_ctx, d_t] (CSC): 1 tensor
  *   mudpt_forward / _ex                  trainers/coop.py:212-226  CustomCLIP.forward (logits [B, C])
  *   mudpt_forward_backward               trainers/coop.py:281-296  forward, F.cross_entropy, backward w.r.t. ctx
+ * With MUDPT_VARIANT_VPT / MUDPT_VARIANT_MPT (created by mudpt_create_ex) they run the deep-prompt baselines (trainers/vpt.py, mpt.py):
+ *   mudpt_create_ex                      clip/model.py:404-416,443-470,752-770  per-tower prompt counts and depths (mudpt_prompt_shape)
+ *   mudpt_set_class_prompts              trainers/vpt.py:43-70, mpt.py:43-125  "<TEXT_CTX_INIT> <name>." (MPT: rows 1..n_t replaced)
+ *   mudpt_param_*                        clip/model.py:202-251,459-465, mpt.py:86  every "visual_ctx" [n, width], in named_parameters() order
+ *   mudpt_forward / _ex                  trainers/vpt.py:94-111, mpt.py:156-172    CustomCLIP.forward (logits [B, C])
+ *   mudpt_forward_backward               trainers/vpt.py:168-200, mpt.py:224-256   forward, F.cross_entropy, backward w.r.t. the prompts
+ *   (VPT: the text tower has nothing to learn; its features are computed once per handle and reused until mudpt_set_weight /
+ *    mudpt_set_class_prompts.  mudpt_set_class_shard, mudpt_cp_* and mudpt_set_class_token_position refuse both variants.)
  *
  * Conventions: every function returns 0 on success or a MUDPT_ERR_* code; mudpt_last_error() gives
  * the message of the calling thread's last failure.  No exceptions cross the ABI.  A model handle is
@@ -70,6 +78,8 @@ extern "C" {
 #define MUDPT_VARIANT_COCOOP 1 /* trainers/cocoop.py: instance-conditioned text prompts, 5 trainables; depth is ignored */
 #define MUDPT_VARIANT_COOP 2     /* trainers/coop.py: one shared context [n_ctx, t_width], the trainable "prompt_learner.ctx"; depth is ignored */
 #define MUDPT_VARIANT_COOP_CSC 3 /* trainers/coop.py with CSC: one context per class, [n_cls, n_ctx, t_width]; depth is ignored */
+#define MUDPT_VARIANT_VPT 4      /* trainers/vpt.py: deep vision prompts only; mudpt_create_ex, n_ctx / depth are ignored */
+#define MUDPT_VARIANT_MPT 5      /* trainers/mpt.py: independent deep prompts in each tower; mudpt_create_ex, n_ctx / depth are ignored */
 
 /* CoOp's TRAINER.COOP.CLASS_TOKEN_POSITION (trainers/coop.py:99-164): where the class-name tokens sit relative to the context rows */
 #define MUDPT_CLASS_TOKEN_END 0    /* [SOS, ctx, name, ".", EOT]                        (default) */
@@ -93,7 +103,21 @@ typedef struct mudpt_model mudpt_model;
 int mudpt_abi_version(void);
 const char* mudpt_last_error(void);
 
-int mudpt_create(const mudpt_config* cfg, mudpt_model** out);
+int mudpt_create(const mudpt_config* cfg, mudpt_model** out);  /* VPT / MPT: MUDPT_ERR_ARG, use mudpt_create_ex */
+
+/* VPT / MPT prompt shape, TRAINER.<NAME>.* (train.py:98-113).  Vision: visual_ctx [v_n_ctx, v_width] appended after the positional
+ * embedding and before ln_pre, and blocks 1 <= i < v_depth replace the last v_n_ctx rows with their own visual_ctx -- only if
+ * 0 < v_depth <= 12 (clip/model.py:459); any other depth is the vanilla ViT, which then runs forward only.  Text (MPT): the
+ * text_prompt_learner's visual_ctx [t_n_ctx, t_width] takes rows 1..t_n_ctx of every class prompt (with the positional embedding,
+ * trainers/mpt.py:108-125), and blocks 1 <= i < min(t_depth, t_layers) replace those rows with their own visual_ctx (no cap).
+ * Refused (MUDPT_ERR_ARG, before any GPU call): VPT without a vision prompt (nothing to train), VPT with text deep prompts
+ * (t_n_ctx > 0 and t_depth > 1), MPT with t_n_ctx < 1. */
+typedef struct mudpt_prompt_shape {
+    int32_t t_n_ctx, t_depth; /* TRAINER.<NAME>.DEEP_TEXT_N_CTX / TEXT_PROMPT_DEPTH */
+    int32_t v_n_ctx, v_depth; /* TRAINER.<NAME>.DEEP_VISUAL_N_CTX / VISUAL_PROMPT_DEPTH */
+} mudpt_prompt_shape;
+/* mudpt_create for every variant: prompts = NULL for MuDPT / CoCoOp / CoOp (then identical to mudpt_create), required for VPT / MPT. */
+int mudpt_create_ex(const mudpt_config* cfg, const mudpt_prompt_shape* prompts, mudpt_model** out);
 int mudpt_destroy(mudpt_model* m);
 
 /* Frozen weight by OpenAI CLIP state-dict key ("visual.transformer.resblocks.0.attn.in_proj_weight", ...),
@@ -117,7 +141,7 @@ int mudpt_set_class_token_position(mudpt_model* m, int32_t position, const int32
 int mudpt_text_layout(const mudpt_model* m, int32_t* rows, int32_t* buckets, int32_t* max_len);
 
 /* The 10 trainable tensors live in ONE flat fp32 bucket (= the data-parallel all-reduce payload). */
-int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT), 5 (CoCoOp) or 1 (CoOp) */
+int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT), 5 (CoCoOp), 1 (CoOp), 1 + vision blocks (VPT) or that + 1 + text blocks (MPT) */
 size_t mudpt_param_numel(const mudpt_model* m); /* elements of the flat bucket */
 /* name = the reference's CustomCLIP state-dict key; shape has ndim entries (ndim <= 3). */
 int mudpt_param_info(const mudpt_model* m, int index, const char** name, size_t* offset, size_t* numel,
@@ -190,7 +214,8 @@ int mudpt_sgd_reset(mudpt_model* m);
 /* Test hook: copy an internal fp32 activation of the last call to HOST memory (synchronises the device).
  * name: "vis.x_in.<i>" / "txt.x_in.<i>" (input of block i, after the prompt splice; [seq, L, d], text L = max(eot) + 1), "vis.x_out" / "txt.x_out"
  * (output of the last block on the ONE row per sequence the model uses -- CLS / EOT token -- [seq, d]: the tail of the last
- * block runs on those rows only), "image_features", "text_features".  host_out may be NULL to query *numel. */
+ * block runs on those rows only), "image_features", "text_features", "text_launches" (1 value: text-tower passes plus text-side head
+ * launches -- normalisation of the text features, their gradient -- since the handle was created).  host_out may be NULL to query *numel. */
 int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch, float* host_out, size_t capacity, size_t* numel);
 
 /* Debug knobs of ONE handle, for A/B measurements in one process and for tests (tools/gemm_bench.py, bench.py flags, tests/).  Nothing is

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("MUDPT_LIB") or os.path.join(HERE, "lib", "libmudpt_hi
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "mudpt.h")
 
 BF16, F16, F32 = 0, 1, 2  # F32: the parity mode (include/mudpt.h MUDPT_F32)
-VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC = 0, 1, 2, 3
+VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARIANT_MPT = 0, 1, 2, 3, 4, 5
 CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = 0, 1, 2  # TRAINER.COOP.CLASS_TOKEN_POSITION "end" / "middle" / "front"
 ABI_VERSION = 7
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = range(6)
@@ -26,6 +26,11 @@ class Config(C.Structure):
         "embed_dim", "n_ctx", "depth", "n_cls", "max_batch", "dtype", "variant")]
 
 
+class PromptShape(C.Structure):
+    """mudpt_prompt_shape: TRAINER.VPT.* / TRAINER.MPT.* DEEP_TEXT_N_CTX, TEXT_PROMPT_DEPTH, DEEP_VISUAL_N_CTX, VISUAL_PROMPT_DEPTH."""
+    _fields_ = [(n, C.c_int32) for n in ("t_n_ctx", "t_depth", "v_n_ctx", "v_depth")]
+
+
 _vp, _i32, _f32, _sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); must list every function include/mudpt.h declares (tests check that)
@@ -33,6 +38,7 @@ SIGNATURES = {
     "mudpt_abi_version": (_i32, []),
     "mudpt_last_error": (C.c_char_p, []),
     "mudpt_create": (_i32, [C.POINTER(Config), C.POINTER(_vp)]),
+    "mudpt_create_ex": (_i32, [C.POINTER(Config), C.POINTER(PromptShape), C.POINTER(_vp)]),
     "mudpt_destroy": (_i32, [_vp]),
     "mudpt_set_weight": (_i32, [_vp, C.c_char_p, _vp, _sz]),
     "mudpt_set_class_prompts": (_i32, [_vp, _vp, _vp]),

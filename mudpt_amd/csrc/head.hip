@@ -238,7 +238,7 @@ int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s) {
 
 // forward + mean cross-entropy + backward to the RAW features in one pass over the logit rows (logits are written too)
 int launch_head_fused_train(const HeadArgs& a, hipStream_t s) {
-    ARG_CHECK(a.img && a.logits && a.txt_n && a.txt_inv && a.img_n && a.img_inv && a.labels && a.loss && a.dlogits && a.row_loss && a.dimg && a.dtxt,
+    ARG_CHECK(a.img && a.logits && a.txt_n && a.txt_inv && a.img_n && a.img_inv && a.labels && a.loss && a.dlogits && a.row_loss && a.dimg,
               "head: null operand");
     ARG_CHECK(a.B > 0 && a.C > 0 && a.e > 0 && a.e <= 1024, "head: bad shape B=%d C=%d e=%d", a.B, a.C, a.e);
     if (a.txt)
@@ -256,6 +256,7 @@ int launch_head_fused_train(const HeadArgs& a, hipStream_t s) {
     HIP_TRY(hipGetLastError());
     if (a.B_total <= 0)
         if (int rc = launch_mean(a.row_loss, a.B, a.loss, s)) return rc;
+    if (!a.dtxt) return MUDPT_OK;  // the text features have nothing to learn (VPT): no text half
     hipLaunchKernelGGL(head_dtxt_kernel, dim3((a.C + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), HEAD_ROWS * a.e * 4, s, a);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;

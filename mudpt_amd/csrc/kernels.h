@@ -198,7 +198,7 @@ int launch_head_bwd(const HeadArgs& a, hipStream_t s);
 // in the workgroup that made the logit rows.  a.txt == null: keep the normalised text features of the previous call.
 bool head_fused_fits(const HeadArgs& a, bool train);
 int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s);
-int launch_head_fused_train(const HeadArgs& a, hipStream_t s);  // logits + loss + dimg + dtxt (gradients of the raw features)
+int launch_head_fused_train(const HeadArgs& a, hipStream_t s);  // logits + loss + dimg + dtxt (gradients of the raw features; dtxt null: skipped)
 // CoCoOp (trainers/cocoop.py): per-image text features.  txt / txt_n / txt_inv / dtxt have B * C rows (row i * C + c).
 int launch_pair_head_fwd(const HeadArgs& a, hipStream_t s);
 int launch_pair_head_bwd(const HeadArgs& a, hipStream_t s);  // loss, dlogits, dtxt (gradient of the raw text features)

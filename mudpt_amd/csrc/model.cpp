@@ -104,6 +104,9 @@ struct Tower {
     void *h_lo = nullptr, *g_lo = nullptr, *attn_lo = nullptr;               // low halves of h, g, the attention output: rows of 2 d / 8 d / 2 d bytes
     void *h_sel_lo = nullptr, *g_sel_lo = nullptr, *attn_sel_lo = nullptr;   // ... of the last block's tail
     int prompt_row0 = 0;  // first prompt row inside a sequence (vision: L - n, text: 1)
+    // Prompt rows per sequence and deep-prompt layers of THIS tower: blocks 1 .. D1 splice n rows.  MuDPT / CoCoOp / CoOp: both towers
+    // from mudpt_config (n_ctx, depth - 1; the vanilla vision tower of CoCoOp / CoOp has none); VPT / MPT: mudpt_prompt_shape, per tower
+    int n = 0, D1 = 0;
     std::vector<BlockW> w;
     std::vector<BlockAct> a;  // layers entries; the last block's output exists on the tail rows only (xout_sel)
     // scratch shared by all blocks
@@ -193,8 +196,7 @@ struct mudpt_model {
     // parameters
     float *params = nullptr, *grads = nullptr, *momentum = nullptr;
     bool sgd_first = true;
-    size_t off[10];
-    size_t numel[10];
+    std::vector<size_t> off, numel;  // per trainable tensor, elements (nparams entries)
     size_t total = 0;
     // CoCoOp variant (trainers/cocoop.py): 5 trainables, vanilla vision tower (forward only), B * C text sequences
     bool cocoop = false;
@@ -213,6 +215,14 @@ struct mudpt_model {
     int class_token_position = MUDPT_CLASS_TOKEN_END;
     std::vector<int> name_lens;  // [n_cls] (trainers/coop.py:80); empty = all 0 (END without lengths)
     int* coop_pos = nullptr;     // [n_cls * n_ctx] device
+    // VPT / MPT variants (trainers/vpt.py, mpt.py): every spliced prompt is a trainable of its own, so block i's rows come straight from
+    // the bound bucket and their gradients go straight into the gradient bucket; no prompt-learner GEMMs.  Bucket offsets (elements) of the
+    // text ctx (MPT: text_prompt_learner.visual_ctx), the text blocks' [D1][n][dt], the vision visual_ctx and the vision blocks' [D1][n][dv]
+    bool vpt = false, mpt = false, indep = false;  // indep = vpt || mpt: independent prompts per tower
+    size_t t_ctx_off = 0, t_deep_off = 0, v_ctx_off = 0, v_deep_off = 0;
+    std::vector<std::string> pnames;  // the reference's keys (named_parameters() order)
+    std::vector<int64_t> prows, pcols;
+    long text_launches = 0;  // text-tower passes + text-side head launches (mudpt_debug_read "text_launches")
     float *mn_hid = nullptr, *mn_bias = nullptr, *mn_dbias = nullptr, *mn_dhid = nullptr;  // [B, hid], [B, dt], [B, dt], [B, hid]
     float loss_scale = 128.f;  // static, power of two; see mudpt_forward_backward
     // bf16 mode keeps the gradient of the residual stream in T only (the fp32 copy costs 237 MB of HBM traffic per LayerNorm
@@ -451,7 +461,7 @@ static int alloc_tower_acts(mudpt_model* m, Tower& t, int L, int max_seq) {
     if (t.may_split) { ALLOC_T(t.attn_sel_lo, S * d * 2); ALLOC_T(t.h_sel_lo, S * d * 2); ALLOC_T(t.g_sel_lo, S * 4 * d * 2); }
     ALLOC_T(t.dsel, S * d * 4); ALLOC_T(t.dsel_lp, S * d * 2);
     ALLOC_T(t.q_sel, S * d * 2); ALLOC_T(t.dq_sel, S * d * 2); ALLOC_T(t.dqx_sel, S * d * 2); ALLOC_T(t.lse_sel, S * heads * 4);
-    t.head_n = m->cfg.n_ctx;
+    t.head_n = t.n;
     ALLOC_T(t.hd_dqkv, S * t.head_n * 3 * d * 2); ALLOC_T(t.hd_h, S * t.head_n * d * 2);
 #undef ALLOC_T
     return MUDPT_OK;
@@ -468,22 +478,43 @@ static void expect_block_keys(mudpt_model* m, const std::string& prefix, int lay
 extern "C" int mudpt_abi_version(void) { return MUDPT_ABI_VERSION; }
 extern "C" const char* mudpt_last_error(void) { return get_error(); }
 
-extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
-    ARG_CHECK(c && out, "create: null argument");
+static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out) {
     ARG_CHECK(c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F16 || c->dtype == MUDPT_F32, "create: dtype must be MUDPT_BF16, MUDPT_F16 or MUDPT_F32");
-    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_COOP_CSC, "create: unknown variant %d", c->variant);
+    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_MPT, "create: unknown variant %d", c->variant);
     const bool cocoop = c->variant == MUDPT_VARIANT_COCOOP;
     const bool coop = c->variant == MUDPT_VARIANT_COOP || c->variant == MUDPT_VARIANT_COOP_CSC;
+    const bool vpt = c->variant == MUDPT_VARIANT_VPT, mpt = c->variant == MUDPT_VARIANT_MPT, indep = vpt || mpt;
     const bool vanilla = cocoop || coop;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
-    ARG_CHECK(vanilla || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
-    ARG_CHECK(c->n_ctx > 0 && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
+    ARG_CHECK(vanilla || indep || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
+    ARG_CHECK((indep || c->n_ctx > 0) && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
     ARG_CHECK(c->patch > 0 && c->image_size % c->patch == 0, "create: image_size %d / patch %d unsupported", c->image_size, c->patch);
     ARG_CHECK(c->v_width == c->v_heads * 64 && c->t_width == c->t_heads * 64, "create: head dim must be 64");
     ARG_CHECK(c->v_width % 64 == 0 && c->t_width % 64 == 0 && c->v_width <= 1024 && c->t_width <= 1024, "create: widths must be multiples of 64, <= 1024");
     ARG_CHECK(c->embed_dim == c->t_width, "create: embed_dim must equal t_width (visual_ctx_deep_projections output is added to text prompts)");
-    ARG_CHECK(1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
+    ARG_CHECK(indep || 1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
+    // prompt rows and deep-prompt layers per tower (Tower::n, Tower::D1)
+    int nv = vanilla ? 0 : c->n_ctx, D1v = vanilla ? 0 : c->depth - 1, nt = c->n_ctx, D1t = vanilla ? 0 : c->depth - 1;
+    if (indep) {
+        const char* T = vpt ? "VPT" : "MPT";
+        ARG_CHECK(ps->t_n_ctx >= 0 && ps->v_n_ctx >= 0, "create_ex: TRAINER.%s.DEEP_TEXT_N_CTX %d / DEEP_VISUAL_N_CTX %d must be >= 0", T, ps->t_n_ctx, ps->v_n_ctx);
+        // the vision prompt exists only for 0 < VISUAL_PROMPT_DEPTH <= 12, whatever the layer count (clip/model.py:459)
+        const bool vprompt = ps->v_n_ctx > 0 && ps->v_depth > 0 && ps->v_depth <= 12;
+        if (vpt) {
+            ARG_CHECK(vprompt, "create_ex: VPT without a vision prompt (TRAINER.VPT.DEEP_VISUAL_N_CTX %d, TRAINER.VPT.VISUAL_PROMPT_DEPTH %d: "
+                      "needs > 0 and 1..12) has nothing to train", ps->v_n_ctx, ps->v_depth);
+            ARG_CHECK(!(ps->t_n_ctx > 0 && ps->t_depth > 1), "create_ex: VPT with text deep prompts (TRAINER.VPT.DEEP_TEXT_N_CTX %d, "
+                      "TRAINER.VPT.TEXT_PROMPT_DEPTH %d) is not supported: use MPT", ps->t_n_ctx, ps->t_depth);
+        } else {
+            ARG_CHECK(ps->t_n_ctx >= 1, "create_ex: MPT needs TRAINER.MPT.DEEP_TEXT_N_CTX >= 1 (got %d)", ps->t_n_ctx);
+            ARG_CHECK(1 + ps->t_n_ctx < c->ctx_len, "create_ex: TRAINER.MPT.DEEP_TEXT_N_CTX %d too large for ctx_len %d", ps->t_n_ctx, c->ctx_len);
+        }
+        nv = vprompt ? ps->v_n_ctx : 0;
+        D1v = vprompt ? std::min(ps->v_depth, c->v_layers) - 1 : 0;  // blocks 1 <= i < depth own a visual_ctx (clip/model.py:404-416)
+        nt = mpt ? ps->t_n_ctx : 0;
+        D1t = mpt ? std::max(0, std::min(ps->t_depth, c->t_layers) - 1) : 0;  // no cap on the text depth (clip/model.py:752-770)
+    }
     const int P = (c->image_size / c->patch) * (c->image_size / c->patch);
-    const int Lv = 1 + P + (vanilla ? 0 : c->n_ctx);  // CoCoOp's / CoOp's image encoder is the vanilla ViT (trainers/cocoop.py:38, coop.py:37, clip/model.py:443-496)
+    const int Lv = 1 + P + nv;  // CoCoOp's / CoOp's image encoder is the vanilla ViT (trainers/cocoop.py:38, coop.py:37, clip/model.py:443-496)
     ARG_CHECK(Lv <= 4096 && c->ctx_len <= 4096, "create: sequence length %d/%d exceeds the attention limit (4096)", Lv, c->ctx_len);
 
     mudpt_model* m = new mudpt_model();
@@ -508,12 +539,15 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
     m->cocoop = cocoop;
     m->coop = coop;
     m->csc = c->variant == MUDPT_VARIANT_COOP_CSC;
+    m->vpt = vpt; m->mpt = mpt; m->indep = indep;
     m->ct = c->n_cls;
-    if (vanilla) m->cfg.depth = 1;  // no deep prompts
-    const int dv = c->v_width, dt = c->t_width, e = c->embed_dim, n = c->n_ctx, D1 = m->cfg.depth - 1, B = c->max_batch, C = c->n_cls;
+    if (vanilla || indep) m->cfg.depth = 1;  // no MuDPT deep prompts
+    if (indep) m->cfg.n_ctx = nt;            // the text prompt rows (mudpt_set_class_prompts)
+    m->vis.n = nv; m->vis.D1 = D1v; m->txt.n = nt; m->txt.D1 = D1t;
+    const int dv = c->v_width, dt = c->t_width, e = c->embed_dim, n = m->cfg.n_ctx, D1 = m->cfg.depth - 1, B = c->max_batch, C = c->n_cls;
     const int TS = cocoop ? B * C : C;  // text sequences per step: one per (image, class) pair in CoCoOp (trainers/cocoop.py:187-194)
     auto fail = [&](int code) { mudpt_destroy(m); return code; };
-    if (int r = alloc_tower_weights(m, m->vis, dv, c->v_layers, c->v_heads, false, vanilla ? Lv : Lv - n, m->exact)) return fail(r);  // e4m3 weight copies: vision tower of the parity mode
+    if (int r = alloc_tower_weights(m, m->vis, dv, c->v_layers, c->v_heads, false, Lv - nv, m->exact)) return fail(r);  // e4m3 weight copies: vision tower of the parity mode
     if (int r = alloc_tower_acts(m, m->vis, Lv, B)) return fail(r);
     // the text tower's activations are sized by mudpt_set_class_prompts: its trimmed length (max(eot) + 1 of ctx_len positions) and, for
     // CoCoOp, the number of images whose B * C prompts fit the memory budget at once are only known there
@@ -529,7 +563,7 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
         ALLOC(m->patches, (size_t)B * P * K0 * 2);
         ALLOC(m->xpre, (size_t)B * Lv * dv * 4); ALLOC(m->pre_mean, (size_t)B * Lv * 4); ALLOC(m->pre_rstd, (size_t)B * Lv * 4);
         ALLOC(m->f_ln, (size_t)B * dv * 4); ALLOC(m->post_mean, B * 4); ALLOC(m->post_rstd, B * 4); ALLOC(m->df_ln, (size_t)B * dv * 4);
-        ALLOC(m->cls_rows, B * 4); ALLOC(m->vprompt_rows, (size_t)B * n * 4);
+        ALLOC(m->cls_rows, B * 4); ALLOC(m->vprompt_rows, (size_t)B * nv * 4);
         ALLOC(m->tpos, (size_t)c->ctx_len * dt * 4); ALLOC(m->ln_fin_g, dt * 4); ALLOC(m->ln_fin_b, dt * 4);
         ALLOC(m->tproj, (size_t)dt * e * 4);
         ALLOC(m->emb_pos, (size_t)C * c->ctx_len * dt * 4); ALLOC(m->eot_rows, TS * 4); ALLOC(m->eot_local, TS * 4); ALLOC(m->class_perm, C * 4);
@@ -538,7 +572,7 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
         const size_t dn = (size_t)(D1 > 0 ? D1 : 1) * n;
         ALLOC(m->shared, (size_t)n * dv * 4); ALLOC(m->t2v, dn * dv * 4); ALLOC(m->v2t, dn * e * 4);
         ALLOC(m->vis_deep, dn * dv * 4); ALLOC(m->txt_deep, dn * dt * 4);
-        ALLOC(m->vsplice, (size_t)B * dn * dv * 4);
+        ALLOC(m->vsplice, (size_t)B * (D1v > 0 ? D1v : 1) * nv * dv * 4);
         ALLOC(m->d_vis_deep, dn * dv * 4); ALLOC(m->d_txt_deep, dn * dt * 4); ALLOC(m->d_vprompt0, (size_t)n * dv * 4);
         ALLOC(m->img_f, (size_t)B * e * 4); ALLOC(m->txt_f, (size_t)TS * e * 4); ALLOC(m->img_n, (size_t)B * e * 4); ALLOC(m->txt_n, (size_t)TS * e * 4);
         ALLOC(m->img_inv, B * 4); ALLOC(m->txt_inv, TS * 4);
@@ -554,16 +588,16 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
         HIP_TRY(hipStreamCreateWithFlags(&m->s2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&m->ev_fork, &m->ev_join, &m->ev_fork_b, &m->ev_join_b}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
         // row index tables
-        std::vector<int> cr(B), pr((size_t)B * n);
+        std::vector<int> cr(B), pr((size_t)B * nv);
         for (int b = 0; b < B; ++b) {
             cr[b] = b * Lv;
-            for (int i = 0; i < n; ++i) pr[(size_t)b * n + i] = b * Lv + (Lv - n) + i;
+            for (int i = 0; i < nv; ++i) pr[(size_t)b * nv + i] = b * Lv + (Lv - nv) + i;
         }
         HIP_TRY(hipMemcpy(m->cls_rows, cr.data(), cr.size() * 4, hipMemcpyHostToDevice));
         m->vis.tail_rows = m->cls_rows;
-        m->vis.head_rows = vanilla ? nullptr : m->vprompt_rows;
-        ALLOC(m->tprompt_rows, (size_t)TS * n * 4);
-        m->txt.head_rows = m->tprompt_rows;  // ctx rows of every prompt; this table and the next are filled by mudpt_set_class_prompts
+        m->vis.head_rows = nv > 0 ? m->vprompt_rows : nullptr;
+        ALLOC(m->tprompt_rows, (size_t)TS * nt * 4);
+        m->txt.head_rows = nt > 0 ? m->tprompt_rows : nullptr;  // ctx rows of every prompt; this table and the next are filled by mudpt_set_class_prompts
         m->txt.tail_rows = m->eot_rows;
         HIP_TRY(hipMemcpy(m->vprompt_rows, pr.data(), pr.size() * 4, hipMemcpyHostToDevice));
         return MUDPT_OK;
@@ -577,9 +611,32 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
     const size_t cshapes[5] = {(size_t)n * dt, (size_t)(e / 16) * e, (size_t)(e / 16), (size_t)dt * (e / 16), (size_t)dt};
     // CoOp: ctx [n, dt], or [n_cls, n, dt] with CSC (trainers/coop.py:60-76)
     const size_t coop_numel = (size_t)(m->csc ? C : 1) * n * dt;
-    m->nparams = cocoop ? 5 : coop ? 1 : 10;
+    // VPT / MPT: every visual_ctx [n, width] in the reference's named_parameters() order (text_prompt_learner, text_encoder, image_encoder);
+    // the blocks' tensors follow one another, so they are the [D1][n][width] array the splice and the gradient reductions address
+    if (indep) {
+        auto add = [&](const std::string& k, int64_t rows, int64_t cols) { m->pnames.push_back(k); m->prows.push_back(rows); m->pcols.push_back(cols); };
+        if (mpt) {
+            add("text_prompt_learner.visual_ctx", nt, dt);  // trainers/mpt.py:86
+            for (int i = 1; i <= D1t; ++i) add("text_encoder.transformer.resblocks." + std::to_string(i) + ".visual_ctx", nt, dt);
+        }
+        if (nv > 0) {
+            add("image_encoder.visual_ctx", nv, dv);  // clip/model.py:459-465
+            for (int i = 1; i <= D1v; ++i) add("image_encoder.transformer.resblocks." + std::to_string(i) + ".visual_ctx", nv, dv);
+        }
+        m->t_ctx_off = 0;
+        m->t_deep_off = (size_t)nt * dt;
+        m->v_ctx_off = mpt ? (size_t)(1 + D1t) * nt * dt : 0;
+        m->v_deep_off = m->v_ctx_off + (size_t)nv * dv;
+    }
+    m->nparams = cocoop ? 5 : coop ? 1 : indep ? (int)m->pnames.size() : 10;
+    m->off.assign(std::max(m->nparams, 1), 0);
+    m->numel.assign(std::max(m->nparams, 1), 0);
     size_t o = 0;
-    for (int i = 0; i < m->nparams; ++i) { m->off[i] = o; m->numel[i] = cocoop ? cshapes[i] : coop ? coop_numel : shapes[i]; o += m->numel[i]; }
+    for (int i = 0; i < m->nparams; ++i) {
+        m->off[i] = o;
+        m->numel[i] = cocoop ? cshapes[i] : coop ? coop_numel : indep ? (size_t)(m->prows[i] * m->pcols[i]) : shapes[i];
+        o += m->numel[i];
+    }
     m->total = o;
     if (int r = dev_alloc(m, (void**)&m->momentum, o * 4)) return fail(r);
 
@@ -592,6 +649,21 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
     expect_block_keys(m, "transformer", c->t_layers);
     *out = m;
     return MUDPT_OK;
+}
+
+extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
+    ARG_CHECK(c && out, "create: null argument");
+    ARG_CHECK(c->variant != MUDPT_VARIANT_VPT && c->variant != MUDPT_VARIANT_MPT,
+              "create: variant %d (VPT / MPT) needs the per-tower prompt shape: use mudpt_create_ex", c->variant);
+    return create_impl(c, nullptr, out);
+}
+
+extern "C" int mudpt_create_ex(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out) {
+    ARG_CHECK(c && out, "create_ex: null argument");
+    const bool indep = c->variant == MUDPT_VARIANT_VPT || c->variant == MUDPT_VARIANT_MPT;
+    ARG_CHECK(!indep || ps, "create_ex: variant %d (VPT / MPT) needs a mudpt_prompt_shape", c->variant);
+    ARG_CHECK(indep || !ps, "create_ex: a mudpt_prompt_shape is for VPT / MPT only (variant %d: pass NULL)", c->variant);
+    return create_impl(c, ps, out);
 }
 
 extern "C" int mudpt_destroy(mudpt_model* m) {
@@ -712,6 +784,7 @@ extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* da
 #undef EXPECT
     if (rc) return rc;
     m->any_weight_set = true;
+    if (m->vpt) m->text_valid = false;  // VPT keeps its text features across steps: any frozen weight may change them
     for (size_t i = 0; i < m->missing.size(); ++i)
         if (m->missing[i] == k) { m->missing.erase(m->missing.begin() + i); break; }
     return MUDPT_OK;
@@ -770,7 +843,7 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     // mudpt_model_set("txt_trim", 0) keeps all ctx_len positions (A/B runs, tests).
     int max_eot = 0;
     for (size_t cc = 0; cc < C; ++cc) max_eot = std::max(max_eot, (int)eot[cc]);
-    const size_t Le = m->txt_trim ? (size_t)std::max(max_eot + 1, c.n_ctx + 2) : L;
+    const size_t Le = m->txt_trim ? (size_t)std::max(max_eot + 1, m->txt.n + 2) : L;
     // Sequences per text-tower pass.  MuDPT: the C class prompts.  CoCoOp: every image has its own C prompts (trainers/cocoop.py:187-194
     // loops over the images, C sequences at a time); here a CHUNK of images goes through the tower at once -- as many as fit a
     // memory budget (activations for the backward are ~150 KB per token at width 512) and the kernels' 32-bit offsets -- and
@@ -808,7 +881,7 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     X.segs.clear();
     std::vector<int> order(C);  // packed position -> local class
     for (size_t cc = 0; cc < C; ++cc) order[cc] = (int)cc;
-    auto len_of = [&](int cc) { return std::max(eot[cc] + 1, c.n_ctx + 2); };
+    auto len_of = [&](int cc) { return std::max(eot[cc] + 1, X.n + 2); };
     if (!m->cocoop && m->txt_trim && m->txt_buckets > 1 && C * Le >= 2048) {
         std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return len_of(x) < len_of(y); });
         std::vector<int> dl, cnt;  // distinct lengths ascending, sequences per length
@@ -857,8 +930,8 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     const std::vector<Tower::Seg> segs = tower_segs(X, (int)C);
     const size_t packed_rows = X.segs.empty() ? C * Le : (size_t)X.rows;
     std::vector<float> ep(packed_rows * d);
-    std::vector<int> rows(C * reps), rows_local(C * reps), tr(C * reps * c.n_ctx), perm(C), cpos(m->coop ? C * n : 0);
-    int span = n;
+    std::vector<int> rows(C * reps), rows_local(C * reps), tr(C * reps * X.n), perm(C), cpos(m->coop ? C * n : 0);
+    int span = X.n;
     for (const Tower::Seg& g : segs)
         for (int j = 0; j < g.nseq; ++j) {
             const int sq = g.seq0 + j, cc = order[sq];
@@ -868,7 +941,7 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
                 rows[i * C + sq] = (int)(i * C * Le + r0) + eot[cc];
                 rows_local[i * C + sq] = (int)(i * C * Le + r0 - g.row0) + eot[cc];
                 if (!m->coop)
-                    for (int k = 0; k < c.n_ctx; ++k) tr[(i * C + sq) * c.n_ctx + k] = (int)(i * C * Le + r0) + 1 + k;  // ctx rows 1..n (trainers/mudpt.py:97-115)
+                    for (int k = 0; k < X.n; ++k) tr[(i * C + sq) * X.n + k] = (int)(i * C * Le + r0) + 1 + k;  // ctx rows 1..n (trainers/mudpt.py:97-115)
             }
             if (m->coop) {
                 // CoOp: the prompt rows in construct_prompts' order, THEN the positional embedding (trainers/coop.py:187-188); the context
@@ -915,6 +988,14 @@ extern "C" int mudpt_param_info(const mudpt_model* m, int i, const char** name, 
     ARG_CHECK(m && i >= 0 && i < m->nparams, "param_info: bad index %d", i);
     const mudpt_config& c = m->cfg;
     const int64_t n = c.n_ctx, D1 = c.depth - 1, dt = c.t_width, dv = c.v_width, e = c.embed_dim;
+    if (m->indep) {  // every visual_ctx [n, width] (clip/model.py:202-251,459-465, trainers/mpt.py:86)
+        if (name) *name = m->pnames[i].c_str();
+        if (offset) *offset = m->off[i];
+        if (numel) *numel = m->numel[i];
+        if (ndim) *ndim = 2;
+        if (shape) { shape[0] = m->prows[i]; shape[1] = m->pcols[i]; shape[2] = 0; }
+        return MUDPT_OK;
+    }
     if (m->coop) {  // trainers/coop.py:60-76
         if (name) *name = kCoopName;
         if (offset) *offset = m->off[0];
@@ -1027,7 +1108,7 @@ static int block_fwd_tail(mudpt_model* m, Tower& t, int nseq, hipStream_t s, boo
 // vmcnt retires in order).  So LN1 of block i >= 1 computes x_in[i] = x_mid[i-1] + upd, with the deep-prompt rows
 // spliced in (splice != null), and writes it for the backward; LN2 computes x_mid[i] = x_in[i] + upd.
 static int block_fwd(mudpt_model* m, Tower& t, int i, int nseq, const float* splice, hipStream_t s) {
-    const int M = tower_rows(t, nseq), d = t.d, dt = m->dtype, n = m->cfg.n_ctx;
+    const int M = tower_rows(t, nseq), d = t.d, dt = m->dtype, n = t.n;
     const std::vector<Tower::Seg> segs = tower_segs(t, nseq);
     // bf16 mode: the update stream (out_proj / c_proj results) is kept in T like the gradient stream -- half the store time
     // of those GEMMs and 2 bytes less per element in the LayerNorm that adds it.  The last block's c_proj stays fp32 (launch_add).
@@ -1229,7 +1310,7 @@ static int block_bwd(mudpt_model* m, Tower& t, int i, int nseq, hipStream_t s, f
     LnBwdArgs b1; b1.dy = t.h; b1.lddy = d; b1.x = a.x_in; b1.ldx = d; b1.mean = a.mean1; b1.rstd = a.rstd1; b1.gamma = w.ln1_g; b1.lddres = d;
     if (m->lp_grad) b1.dres_lp = t.dx_lp; else { b1.dres = t.dx; b1.dx = t.dx; }
     b1.lddx = d; b1.dx_lp = t.dx_lp; b1.lddx_lp = d; b1.rows = M; b1.d = d;
-    if (side) { b1.side = side; b1.side_row0 = t.prompt_row0; b1.side_n = m->cfg.n_ctx; b1.side_L = t.L; b1.side_ldb = side_ldb; }
+    if (side) { b1.side = side; b1.side_row0 = t.prompt_row0; b1.side_n = t.n; b1.side_L = t.L; b1.side_ldb = side_ldb; }
     TRY(ln_bwd_call(m, t, b1, s));
     return MUDPT_OK;
 }
@@ -1238,9 +1319,11 @@ static int block_bwd(mudpt_model* m, Tower& t, int i, int nseq, hipStream_t s, f
 // clip/model.py:478-496 (CoCoOp: the vanilla ViT, no prompt rows) -> m->img_f [B, e]
 static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_t s) {
     const mudpt_config& c = m->cfg;
-    const int dv = c.v_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1;
+    const int dv = c.v_width, e = c.embed_dim, n = m->vis.n, D1 = m->vis.D1;
     const int P = (c.image_size / c.patch) * (c.image_size / c.patch), Lv = m->vis.L, K0 = (3 * c.patch * c.patch + 63) / 64 * 64;
     float* Pm = m->params;
+    // VPT / MPT: block i's rows are its own visual_ctx in the bucket; MuDPT: the prompt learner's projections (prompt_learner_forward)
+    const float* deep = m->indep ? Pm + m->v_deep_off : m->vis_deep;
     const int m_patch = site_mode(m->vis, SITE_PATCH, K0);  // parity mode: split pixels (an fp16 pixel alone carries 2.4e-4 of rounding into block 0)
     if (m_patch != LO_NONE) TRY(launch_patchify_split(m->dtype, images, m->patches, m->patches_lo, m_patch, B, c.image_size, c.patch, K0, s));
     else TRY(launch_patchify(m->dtype, images, m->patches, B, c.image_size, c.patch, K0, s));
@@ -1249,12 +1332,13 @@ static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_
     pe.patches = P; pe.seq_len = Lv; pe.pos = m->vpos;
     TRY(gemm_call(m, EPI_PATCH, pe, s));
     TRY(launch_set_rows(m->xpre, B, Lv, dv, 0, 1, m->cls, m->vpos, s));
-    if (!m->cocoop && !m->coop) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, Pm + m->off[P_VCTX], m->shared, s));
+    // prompt rows after the positional embedding, before ln_pre: MuDPT visual_ctx + shared (clip/model.py:534), VPT / MPT visual_ctx (:463-465)
+    if (n > 0) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, Pm + (m->indep ? m->v_ctx_off : m->off[P_VCTX]), m->indep ? nullptr : m->shared, s));
     LnFwdArgs lp; lp.x = m->xpre; lp.ldx = dv; lp.gamma = m->ln_pre_g; lp.beta = m->ln_pre_b; lp.out = m->vis.a[0].x_in; lp.ldo = dv; lp.out_f32 = true;
     lp.mean = m->pre_mean; lp.rstd = m->pre_rstd; lp.rows = B * Lv; lp.d = dv;
     TRY(launch_ln_fwd(m->dtype, lp, s));
     for (int i = 0; i < m->vis.layers; ++i) {
-        TRY(block_fwd(m, m->vis, i, B, (i >= 1 && i - 1 < D1) ? m->vis_deep + (size_t)(i - 1) * n * dv : nullptr, s));
+        TRY(block_fwd(m, m->vis, i, B, (i >= 1 && i - 1 < D1) ? deep + (size_t)(i - 1) * n * dv : nullptr, s));
     }
     LnFwdArgs lq; lq.x = m->vis.xout_sel; lq.ldx = dv; lq.gamma = m->ln_post_g; lq.beta = m->ln_post_b; lq.out = m->f_ln; lq.ldo = dv;
     lq.out_f32 = true; lq.mean = m->post_mean; lq.rstd = m->post_rstd; lq.rows = B; lq.d = dv;
@@ -1362,7 +1446,7 @@ static int cocoop_forward_backward(mudpt_model* m, const float* images, const in
 // ---- the MuDPT step in pieces (the monolithic entry points and the class-parallel phases share them) ------------------------------
 // prompt learner, trainers/mudpt.py:117-130 + clip/model.py:534-539
 static int prompt_learner_forward(mudpt_model* m, hipStream_t s) {
-    if (m->coop) return MUDPT_OK;  // CoOp: the context goes into the prompts as it is (trainers/coop.py:166-175)
+    if (m->coop || m->indep) return MUDPT_OK;  // CoOp / VPT / MPT: the trainables go into the towers as they are (trainers/coop.py:166-175)
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, dt = c.t_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1;
     float* Pm = m->params;
@@ -1379,18 +1463,20 @@ static int prompt_learner_forward(mudpt_model* m, hipStream_t s) {
 // text tower, trainers/mudpt.py:142-156, over this handle's classes [c0, c0 + ct): rows c0.. of the [n_cls, e] feature table
 static int text_forward(mudpt_model* m, hipStream_t s2) {
     const mudpt_config& c = m->cfg;
-    const int dt = c.t_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1, Ct = m->ct;
+    const int dt = c.t_width, e = c.embed_dim, n = m->txt.n, D1 = m->txt.D1, Ct = m->ct;
     float* Pm = m->params;
     const std::vector<Tower::Seg> segs = tower_segs(m->txt, Ct);
     const bool packed = segs.size() > 1;
+    const float* deep = m->indep ? Pm + m->t_deep_off : m->txt_deep;  // MPT: the text blocks' own visual_ctx in the bucket
+    ++m->text_launches;
     HIP_TRY(hipMemcpyAsync(m->txt.a[0].x_in, m->emb_pos, (size_t)tower_rows(m->txt, Ct) * dt * 4, hipMemcpyDeviceToDevice, s2));
     if (m->coop)  // trainers/coop.py:166-175,187-188: the context rows at every class's own positions, all buckets in one launch
         TRY(launch_coop_splice(m->txt.a[0].x_in, Pm + m->off[0], m->tpos, m->tprompt_rows, m->coop_pos, Ct, n, dt, m->csc, s2));
-    else
+    else if (n > 0)  // MuDPT ctx / MPT text_prompt_learner.visual_ctx at rows 1..n, with the positional embedding (trainers/mpt.py:108-125)
         for (const Tower::Seg& g : segs)
-            TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, Pm + m->off[P_CTX], m->tpos + dt, s2));
+            TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, Pm + (m->indep ? m->t_ctx_off : m->off[P_CTX]), m->tpos + dt, s2));
     for (int i = 0; i < m->txt.layers; ++i) {
-        TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? m->txt_deep + (size_t)(i - 1) * n * dt : nullptr, s2));
+        TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? deep + (size_t)(i - 1) * n * dt : nullptr, s2));
     }
     LnFwdArgs lf; lf.x = m->txt.xout_sel; lf.ldx = dt; lf.gamma = m->ln_fin_g; lf.beta = m->ln_fin_b; lf.out = m->t_ln; lf.ldo = dt;
     lf.out_f32 = true; lf.mean = m->fin_mean; lf.rstd = m->fin_rstd; lf.rows = Ct; lf.d = dt;
@@ -1426,6 +1512,7 @@ static int head_forward(mudpt_model* m, int B, bool reuse_text, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     HeadArgs h; h.img = m->img_f; h.txt = m->txt_f; h.scale = m->scale; h.logits = m->logits; h.img_n = m->img_n; h.txt_n = m->txt_n;
     h.img_inv = m->img_inv; h.txt_inv = m->txt_inv; h.B = B; h.C = c.n_cls; h.e = c.embed_dim;
+    if (!reuse_text || !head_fused_fits(h, false)) ++m->text_launches;  // the normalisation of the text features
     if (head_fused_fits(h, false)) {
         if (reuse_text) h.txt = nullptr;  // the normalised text features of the previous call are still in m->txt_n
         TRY(launch_head_fused_fwd(h, s));
@@ -1456,7 +1543,8 @@ extern "C" int mudpt_forward_ex(mudpt_model* m, const float* images, int32_t B, 
     TRY(not_sharded(m, "forward"));
     ARG_CHECK(images && logits, "forward: null argument");
     hipStream_t s = (hipStream_t)stream;
-    const bool reuse = (flags & MUDPT_FWD_REUSE_TEXT) != 0 && !m->cocoop;  // CoCoOp's text features depend on the image
+    // CoCoOp's text features depend on the image; VPT's on nothing trainable: once computed they stay (until mudpt_set_weight / _set_class_prompts)
+    const bool reuse = ((flags & MUDPT_FWD_REUSE_TEXT) != 0 || (m->vpt && m->text_valid)) && !m->cocoop;
     if (reuse && !m->text_valid) { set_error("forward: MUDPT_FWD_REUSE_TEXT before any text-tower pass"); return MUDPT_ERR_STATE; }
     m->train_fwd = false;
     TRY(forward_impl(m, images, B, s, reuse));
@@ -1465,21 +1553,26 @@ extern "C" int mudpt_forward_ex(mudpt_model* m, const float* images, int32_t B, 
 }
 
 // head of the training step: cross-entropy (mean) + cosine logits backward, trainers/mudpt.py:178-182,250 -> loss, dimg, dtxt (all classes)
-static int head_train(mudpt_model* m, const int64_t* labels, int B, float grad_scale, float* loss, float* logits, hipStream_t s) {
+// reuse_text (VPT): m->txt_n / txt_inv still hold the normalised features of the cached text pass; text_grad = false (VPT): no dtxt
+static int head_train(mudpt_model* m, const int64_t* labels, int B, float grad_scale, float* loss, float* logits, hipStream_t s,
+                      bool reuse_text = false, bool text_grad = true) {
     const mudpt_config& c = m->cfg;
     const int e = c.embed_dim, C = c.n_cls;
     HeadArgs h; h.img = m->img_f; h.txt = m->txt_f; h.labels = labels; h.scale = m->scale; h.logits = m->logits; h.loss = m->loss; h.dlogits = m->dlogits;
-    h.row_loss = m->row_loss; h.dimg = m->dimg; h.dtxt = m->dtxt; h.img_n = m->img_n; h.txt_n = m->txt_n; h.img_inv = m->img_inv; h.txt_inv = m->txt_inv;
+    h.row_loss = m->row_loss; h.dimg = m->dimg; h.dtxt = text_grad ? m->dtxt : nullptr; h.img_n = m->img_n; h.txt_n = m->txt_n; h.img_inv = m->img_inv; h.txt_inv = m->txt_inv;
     // Static loss scaling: the backward pass runs on per-sample gradients times loss_scale (dlogits = (softmax -
     // onehot) * loss_scale, independent of B and of the number of ranks), so the T copies of the token gradients
     // stay inside fp16's normal range (unscaled they are ~1e-7 at B = 256: flushed).  The four reductions that leave
     // the towers multiply by `unscale`; everything after them is fp32 and linear.
     m->cp_unscale = grad_scale / ((float)B * m->loss_scale);
     h.grad_scale = m->loss_scale * (float)B; h.B = B; h.C = C; h.e = e;
+    if (text_grad) ++m->text_launches;  // the text half of the backward (head_dtxt_kernel / its unfused form)
     if (head_fused_fits(h, true)) {
+        if (reuse_text) h.txt = nullptr;  // keep the normalised text features
+        else ++m->text_launches;
         TRY(launch_head_fused_train(h, s));
     } else {
-        TRY(head_forward(m, B, false, s));
+        TRY(head_forward(m, B, reuse_text, s));
         TRY(launch_head_bwd(h, s));
     }
     if (logits) HIP_TRY(hipMemcpyAsync(logits, m->logits, (size_t)B * C * 4, hipMemcpyDeviceToDevice, s));
@@ -1491,9 +1584,11 @@ static int head_train(mudpt_model* m, const int64_t* labels, int B, float grad_s
 // d_txt_deep and the ctx slice of the gradient bucket
 static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
     const mudpt_config& c = m->cfg;
-    const int dt = c.t_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1, Ct = m->ct;
+    const int dt = c.t_width, e = c.embed_dim, n = m->txt.n, D1 = m->txt.D1, Ct = m->ct;
     float* G = m->grads;
     Tower& X = m->txt;
+    float* d_deep = m->indep ? G + m->t_deep_off : m->d_txt_deep;  // MPT: straight into the gradient bucket
+    ++m->text_launches;
     const std::vector<Tower::Seg> segs = tower_segs(X, Ct);
     const float* dfeat = m->dtxt + (size_t)m->c0 * e;
     if (segs.size() > 1) {  // length buckets: the tower's sequences are in length-sorted order
@@ -1509,7 +1604,7 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
         if (i >= 1 && i - 1 < D1)
             for (const Tower::Seg& g : segs)  // bucket after bucket in a fixed order: deterministic
                 TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, (char*)X.dx_lp + (size_t)g.row0 * dt * 2, g.nseq, g.L, dt, 1, n,
-                                       m->d_txt_deep + (size_t)(i - 1) * n * dt, true, g.seq0 > 0, unscale, s2));
+                                       d_deep + (size_t)(i - 1) * n * dt, true, g.seq0 > 0, unscale, s2));
     }
     // CoOp: d ctx from the context rows of every class (shared: summed over the classes in a fixed order; CSC: per class), coop.hip
     if (m->coop)
@@ -1517,15 +1612,18 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
     // d ctx (text side): rows 1..n of the first block's input, summed over the class prompts
     for (const Tower::Seg& g : segs)
         TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, m->lp_grad ? (char*)X.dx_lp + (size_t)g.row0 * dt * 2 : nullptr, g.nseq, g.L, dt, 1, n,
-                               G + m->off[P_CTX], false, true, unscale, s2));
+                               G + (m->indep ? m->t_ctx_off : m->off[P_CTX]), false, true, unscale, s2));
     return MUDPT_OK;
 }
 
 static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) {
     const mudpt_config& c = m->cfg;
-    const int dv = c.v_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1;
+    const int dv = c.v_width, e = c.embed_dim, n = m->vis.n, D1 = m->vis.D1;
     const int Lv = m->vis.L;
     Tower& V = m->vis;
+    // VPT / MPT: the blocks' and the input prompt's gradients go straight into the gradient bucket (MuDPT: into the prompt learner's backward)
+    float* d_deep = m->indep ? m->grads + m->v_deep_off : m->d_vis_deep;
+    float* d_p0 = m->indep ? m->grads + m->v_ctx_off : m->d_vprompt0;
     TRY(launch_sgemm(false, true, B, dv, e, 1.f, m->dimg, e, m->vproj, e, 0.f, m->df_ln, dv, nullptr, s));
     LnBwdArgs bq; bq.dy = m->df_ln; bq.lddy = dv; bq.dy_f32 = true; bq.x = V.xout_sel; bq.ldx = dv; bq.mean = m->post_mean; bq.rstd = m->post_rstd;
     bq.gamma = m->ln_post_g; bq.dx = m->lp_grad ? nullptr : V.dsel; bq.lddx = dv; bq.dx_lp = V.dsel_lp; bq.lddx_lp = dv; bq.rows = B; bq.d = dv;
@@ -1540,7 +1638,7 @@ static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) 
         if (i == V.layers - 1) {
             TRY(block_bwd_tail(m, V, B, s));
             if (spliced) {  // the tail's ln_1 backward is not fused: take the rows from the stream
-                TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : V.dx, V.dx_lp, B, Lv, dv, Lv - n, n, m->d_vis_deep + (size_t)(i - 1) * n * dv, true, false, unscale, s));
+                TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : V.dx, V.dx_lp, B, Lv, dv, Lv - n, n, d_deep + (size_t)(i - 1) * n * dv, true, false, unscale, s));
             }
         } else {
             TRY(block_bwd(m, V, i, B, s, spliced ? m->vsplice + (size_t)(i - 1) * n * dv : nullptr, side_ldb));
@@ -1549,13 +1647,13 @@ static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) 
     {
         // blocks 1 .. layers-2 (the fused ones): rows 0 .. n (layers - 2) of every image's side block
         const int fused = (V.layers - 2 < D1 ? V.layers - 2 : D1) * n;
-        if (fused > 0) TRY(launch_reduce_rows(m->dtype, m->vsplice, nullptr, B, used, dv, 0, fused, m->d_vis_deep, false, false, unscale, s));
+        if (fused > 0) TRY(launch_reduce_rows(m->dtype, m->vsplice, nullptr, B, used, dv, 0, fused, d_deep, false, false, unscale, s));
     }
     // ln_pre backward on the prompt rows only (patch / CLS rows have no trainable ancestor), in place
     LnBwdArgs bp; bp.dy = m->lp_grad ? (const void*)V.dx_lp : (const void*)V.dx; bp.lddy = dv; bp.dy_f32 = !m->lp_grad; bp.x = m->xpre; bp.ldx = dv; bp.row_index = m->vprompt_rows; bp.mean = m->pre_mean; bp.rstd = m->pre_rstd;
     bp.gamma = m->ln_pre_g; bp.dx = V.dx; bp.lddx = dv; bp.rows = B * n; bp.d = dv; bp.by_token = true;
     TRY(launch_ln_bwd(m->dtype, bp, s));
-    TRY(launch_reduce_rows(m->dtype, V.dx, nullptr, B, Lv, dv, Lv - n, n, m->d_vprompt0, false, false, unscale, s));
+    TRY(launch_reduce_rows(m->dtype, V.dx, nullptr, B, Lv, dv, Lv - n, n, d_p0, false, false, unscale, s));
     return MUDPT_OK;
 }
 
@@ -1605,6 +1703,27 @@ static int prompt_learner_backward(mudpt_model* m, hipStream_t s) {  // both hal
     return prompt_learner_backward_vision(m, s);
 }
 
+// VPT / MPT (trainers/vpt.py:168-200, mpt.py:224-256): forward, cross-entropy, backward straight into the gradient bucket.  VPT: the text
+// tower runs on the first step only (its features depend on no trainable), the head skips its text half, and the step is vision forward,
+// head and vision backward.  MPT: both towers' backward, concurrently as MuDPT's; with the vanilla vision tower (no vision prompt) the text
+// tower's backward alone.
+static int indep_forward_backward(mudpt_model* m, const float* images, const int64_t* labels, int B, float grad_scale, float* loss, float* logits,
+                                  hipStream_t s) {
+    const bool reuse = m->vpt && m->text_valid;
+    TRY(towers_forward(m, images, B, s, reuse));
+    HIP_TRY(hipMemsetAsync(m->grads, 0, m->total * 4, s));
+    TRY(head_train(m, labels, B, grad_scale, loss, logits, s, reuse, !m->vpt));
+    if (m->vpt) return vision_backward(m, B, m->cp_unscale, s);
+    if (!m->vis.head_rows) return text_backward(m, m->cp_unscale, s);
+    HIP_TRY(hipEventRecord(m->ev_fork_b, s));
+    HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork_b, 0));
+    TRY(text_backward(m, m->cp_unscale, m->s2));
+    HIP_TRY(hipEventRecord(m->ev_join_b, m->s2));
+    TRY(vision_backward(m, B, m->cp_unscale, s));
+    HIP_TRY(hipStreamWaitEvent(s, m->ev_join_b, 0));
+    return MUDPT_OK;
+}
+
 extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const int64_t* labels, int32_t B, float grad_scale,
                                       float* loss, float* logits, void* stream) {
     TRY(ready(m, B, true));
@@ -1613,6 +1732,7 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
     m->train_fwd = true;
     if (m->cocoop) return cocoop_forward_backward(m, images, labels, B, grad_scale, loss, logits, s);
     TRY(not_sharded(m, "forward_backward"));
+    if (m->indep) return indep_forward_backward(m, images, labels, B, grad_scale, loss, logits, s);
     TRY(towers_forward(m, images, B, s, false));
     HIP_TRY(hipMemsetAsync(m->grads, 0, m->total * 4, s));
     TRY(head_train(m, labels, B, grad_scale, loss, logits, s));
@@ -1642,6 +1762,7 @@ extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
     ARG_CHECK(m, "set_class_shard: null model");
     if (m->cocoop) { set_error("set_class_shard: CoCoOp's text features depend on the image; shard the batch instead"); return MUDPT_ERR_ARG; }
     if (m->coop) { set_error("set_class_shard: class-parallel CoOp is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
+    if (m->indep) { set_error("set_class_shard: class-parallel VPT / MPT is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
     ARG_CHECK(c0 >= 0 && c1 > c0 && c1 <= m->cfg.n_cls, "set_class_shard: [%d, %d) is not a non-empty range of the %d classes", c0, c1, m->cfg.n_cls);
     m->c0 = c0; m->ct = c1 - c0;
     m->sharded = !(c0 == 0 && c1 == m->cfg.n_cls);
@@ -1652,7 +1773,7 @@ extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
 }
 extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, size_t* numel) {
     ARG_CHECK(m && !m->cocoop, "cp_buffers: not a MuDPT model");
-    ARG_CHECK(!m->coop, "cp_buffers: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!m->coop && !m->indep, "cp_buffers: not a MuDPT model (the class-parallel phases run MuDPT only)");
     if (feat) *feat = m->txt_f;
     if (dfeat) *dfeat = m->dtxt;
     if (numel) *numel = (size_t)m->cfg.n_cls * m->cfg.embed_dim;
@@ -1660,7 +1781,7 @@ extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, siz
 }
 extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, int32_t flags, void* stream) {
     TRY(ready(m, B, false));
-    ARG_CHECK(!m->coop, "cp_forward: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!m->coop && !m->indep, "cp_forward: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(images && !m->cocoop, "cp_forward: null images / not a MuDPT model");
     const bool reuse = (flags & MUDPT_FWD_REUSE_TEXT) != 0;
     if (reuse && !m->text_valid) { set_error("cp_forward: MUDPT_FWD_REUSE_TEXT before any text-tower pass"); return MUDPT_ERR_STATE; }
@@ -1671,7 +1792,7 @@ extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, 
 }
 extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, float grad_scale, float* loss, float* logits, int32_t flags, void* stream) {
     TRY(ready(m, B, labels != nullptr));
-    ARG_CHECK(!m->coop, "cp_head: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!m->coop && !m->indep, "cp_head: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(!m->cocoop && (labels ? loss != nullptr : logits != nullptr), "cp_head: training needs labels and loss, inference needs logits");
     if (m->cp_stage < 1 || m->cp_B != B) { set_error("cp_head: call mudpt_cp_forward with the same batch first"); return MUDPT_ERR_STATE; }
     hipStream_t s = (hipStream_t)stream;
@@ -1687,7 +1808,7 @@ extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, f
     return MUDPT_OK;
 }
 extern "C" int mudpt_cp_backward(mudpt_model* m, int32_t part, void* stream) {
-    ARG_CHECK(!(m && m->coop), "cp_backward: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!(m && (m->coop || m->indep)), "cp_backward: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(m && !m->cocoop && (part == MUDPT_CP_VISION || part == MUDPT_CP_TEXT), "cp_backward: part must be MUDPT_CP_VISION or MUDPT_CP_TEXT");
     hipStream_t s = (hipStream_t)stream;
     if (part == MUDPT_CP_VISION) {
@@ -1857,6 +1978,11 @@ extern "C" int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch,
     else if (k.rfind("txt.", 0) == 0) tower(m->txt, k.substr(4), m->ct);  // this handle's classes
     else if (k == "image_features") { src = m->img_f; n = (size_t)batch * c.embed_dim; }
     else if (k == "text_features") { src = m->txt_f; n = (size_t)c.n_cls * c.embed_dim; }
+    else if (k == "text_launches") {  // a host counter, not a device tensor
+        *numel = 1;
+        if (host_out) { ARG_CHECK(capacity >= 1, "debug_read: capacity 0"); host_out[0] = (float)m->text_launches; }
+        return MUDPT_OK;
+    }
     ARG_CHECK(src, "debug_read: unknown tensor '%s'", name);
     *numel = n;
     if (!host_out) return MUDPT_OK;

@@ -43,7 +43,11 @@ def default_cfg() -> CfgNode:
         TRAIN=C(PRINT_FREQ=5),
         TRAINER=C(NAME="MuDPT", MUDPT=C(N_CTX=2, CTX_INIT="a photo of a", DEEP_PROMPT_DEPTH=8, PREC="fp16"),
                   COCOOP=C(N_CTX=4, CTX_INIT="a photo of a", PREC="fp16"),  # train.py:92-95 + configs/trainers/CoCoOp/*.yaml
-                  COOP=C(N_CTX=16, CTX_INIT="", PREC="fp16", CSC=False, CLASS_TOKEN_POSITION="end")),  # train.py:83-88
+                  COOP=C(N_CTX=16, CTX_INIT="", PREC="fp16", CSC=False, CLASS_TOKEN_POSITION="end"),  # train.py:83-88
+                  VPT=C(DEEP_TEXT_N_CTX=0, DEEP_VISUAL_N_CTX=0, TEXT_PROMPT_DEPTH=0, VISUAL_PROMPT_DEPTH=0, TEXT_CTX_INIT="a photo of a",
+                        PREC="fp16"),  # train.py:98-104
+                  MPT=C(DEEP_TEXT_N_CTX=0, DEEP_VISUAL_N_CTX=0, TEXT_PROMPT_DEPTH=0, VISUAL_PROMPT_DEPTH=0, TEXT_CTX_INIT="a photo of a",
+                        PREC="fp16")),  # train.py:106-112
     )
 
 

@@ -2,6 +2,7 @@
 
     python -m mudpt_amd.harness --epochs 2 --batch 4 --n-ctx 4 --depth 12 [--prec fp16|amp] [--eval-only --model-dir D]
     python -m mudpt_amd.harness --trainer CoOp --epochs 2 [--csc] [--class-token-position end|middle|front]
+    python -m mudpt_amd.harness --trainer VPT|MPT --epochs 2 [--deep-text-n-ctx N --text-prompt-depth D --deep-visual-n-ctx N --visual-prompt-depth D]
 
 Mirrors what ``train.py`` (reference :153-173) does after config assembly: build_trainer(cfg) -> train() / test()."""
 from __future__ import annotations
@@ -10,12 +11,12 @@ import argparse
 
 import torch
 
-from . import cocoop, coop, dassl_lite, parallel, trainer  # noqa: F401  (importing trainer / cocoop / coop registers MuDPT / CoCoOp / CoOp)
+from . import cocoop, coop, dassl_lite, parallel, trainer, vpt  # noqa: F401  (importing trainer / cocoop / coop / vpt registers MuDPT / CoCoOp / CoOp / VPT, MPT)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--trainer", default="MuDPT", choices=["MuDPT", "CoCoOp", "CoOp"])
+    ap.add_argument("--trainer", default="MuDPT", choices=["MuDPT", "CoCoOp", "CoOp", "VPT", "MPT"])
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--classes", type=int, default=11)
@@ -25,6 +26,9 @@ def main(argv=None):
     ap.add_argument("--prec", default="fp16", choices=["fp16", "fp32", "amp"])
     ap.add_argument("--csc", action="store_true", help="CoOp: class-specific contexts (TRAINER.COOP.CSC)")
     ap.add_argument("--class-token-position", default="end", choices=["end", "middle", "front"], help="CoOp: TRAINER.COOP.CLASS_TOKEN_POSITION")
+    # VPT / MPT: TRAINER.<NAME>.DEEP_TEXT_N_CTX / TEXT_PROMPT_DEPTH / DEEP_VISUAL_N_CTX / VISUAL_PROMPT_DEPTH; default: the shipped yaml's
+    for flag in ("--deep-text-n-ctx", "--text-prompt-depth", "--deep-visual-n-ctx", "--visual-prompt-depth"):
+        ap.add_argument(flag, type=int, default=None, help="VPT / MPT prompt shape (default: configs/trainers/<NAME>/vit_b16_c2_ep5_batch4.yaml)")
     ap.add_argument("--output-dir", default="output/mudpt_amd")
     ap.add_argument("--backbone-path", default="")
     ap.add_argument("--eval-only", action="store_true")
@@ -45,10 +49,16 @@ def main(argv=None):
     cfg.TRAINER.COCOOP.PREC = a.prec
     cfg.TRAINER.COOP.N_CTX, cfg.TRAINER.COOP.PREC, cfg.TRAINER.COOP.CSC = a.n_ctx, a.prec, a.csc
     cfg.TRAINER.COOP.CLASS_TOKEN_POSITION = a.class_token_position
+    for name in ("VPT", "MPT"):
+        node = getattr(cfg.TRAINER, name)
+        node.PREC = a.prec
+        given = (a.deep_text_n_ctx, a.text_prompt_depth, a.deep_visual_n_ctx, a.visual_prompt_depth)
+        shape = [g if g is not None else y for g, y in zip(given, vpt.YAML_PROMPTS[name])]
+        node.DEEP_TEXT_N_CTX, node.TEXT_PROMPT_DEPTH, node.DEEP_VISUAL_N_CTX, node.VISUAL_PROMPT_DEPTH = shape
     torch.manual_seed(cfg.SEED)
     t = trainer.TRAINER_REGISTRY.get(a.trainer)(cfg) if not trainer.HAVE_DASSL else None
     if t is None:
-        raise SystemExit("Dassl is installed: use the reference's train.py --trainer MuDPT / CoCoOp / CoOp (see INTEGRATION.md)")
+        raise SystemExit("Dassl is installed: use the reference's train.py --trainer MuDPT / CoCoOp / CoOp / VPT / MPT (see INTEGRATION.md)")
     if a.eval_only:
         t.load_model(a.model_dir, epoch=a.load_epoch)
         return t.test()

@@ -59,7 +59,7 @@ class CustomCLIP(nn.Module):
                  ctx_token_ids: Optional[Sequence[int]] = None, max_batch: int = 256, dtype: str = "bf16",
                  device: str = "cuda:0", seed: Optional[int] = None, variant: str = "mudpt", knobs: Optional[Dict[str, int]] = None,
                  class_shard: Optional[Sequence[int]] = None, group=None, class_token_position: str = "end",
-                 name_lens: Optional[Sequence[int]] = None):
+                 name_lens: Optional[Sequence[int]] = None, prompt_shape: Optional[Sequence[int]] = None):
         super().__init__()
         if not torch.cuda.is_available():
             raise capi.MudptError("mudpt_amd needs an MI355X (HIP device); there is no CPU path in the product")
@@ -75,6 +75,10 @@ class CustomCLIP(nn.Module):
         # "coop" / "coop_csc": trainers/coop.py's CustomCLIP (vanilla vision tower, forward only; one trainable, prompt_learner.ctx, shared
         # [n_ctx, d_t] or one per class [n_cls, n_ctx, d_t]); class_token_position / name_lens: TRAINER.COOP.CLASS_TOKEN_POSITION and
         # len(_tokenizer.encode(name)) per class (coop.py:80), needed for "middle" / "front"
+        # "vpt" / "mpt": trainers/vpt.py's / mpt.py's CustomCLIP (independent deep prompts per tower, every "visual_ctx" a trainable of its
+        # own under the reference's key); prompt_shape = (DEEP_TEXT_N_CTX, TEXT_PROMPT_DEPTH, DEEP_VISUAL_N_CTX, VISUAL_PROMPT_DEPTH) of
+        # TRAINER.VPT / TRAINER.MPT (include/mudpt.h mudpt_prompt_shape); shape.n_ctx / depth are not used.  MPT's ctx_token_ids: the
+        # TEXT_CTX_INIT tokens that initialise text_prompt_learner.visual_ctx (trainers/mpt.py:55-62)
         if variant == "coop_csc" and ctx_token_ids is not None:
             variant = "coop"  # trainers/coop.py:52-61: the CTX_INIT path builds one shared context whatever CSC says
         self.variant = variant
@@ -82,10 +86,16 @@ class CustomCLIP(nn.Module):
                           shape.t_layers, shape.t_heads, shape.ctx_len, shape.embed_dim, shape.n_ctx, shape.depth,
                           self.n_cls, self.max_batch, {"bf16": capi.BF16, "fp16": capi.F16, "fp32": capi.F32}[dtype],
                           {"mudpt": capi.VARIANT_MUDPT, "cocoop": capi.VARIANT_COCOOP, "coop": capi.VARIANT_COOP,
-                           "coop_csc": capi.VARIANT_COOP_CSC}[variant])
+                           "coop_csc": capi.VARIANT_COOP_CSC, "vpt": capi.VARIANT_VPT, "mpt": capi.VARIANT_MPT}[variant])
+        assert (prompt_shape is not None) == (variant in ("vpt", "mpt")), "prompt_shape is the VPT / MPT setting, and they need it"
+        self.prompt_shape = None if prompt_shape is None else tuple(int(v) for v in prompt_shape)
         torch.cuda.set_device(self.device)
         h = C.c_void_p()
-        capi.check(self.lib.mudpt_create(C.byref(cfg), C.byref(h)), "create")
+        if self.prompt_shape is not None:
+            ps = capi.PromptShape(*self.prompt_shape)
+            capi.check(self.lib.mudpt_create_ex(C.byref(cfg), C.byref(ps), C.byref(h)), "create_ex")
+        else:
+            capi.check(self.lib.mudpt_create(C.byref(cfg), C.byref(h)), "create")
         self._h = h
         for name, value in (knobs or {}).items():  # per-handle tuning knobs (mudpt_model_set): A/B runs and tests
             self.set_knob(name, value)
@@ -165,7 +175,7 @@ class CustomCLIP(nn.Module):
 
     @property
     def ctx_key(self) -> str:
-        return "mudpt_prompt_learner.ctx" if self.variant == "mudpt" else "prompt_learner.ctx"
+        return {"mudpt": "mudpt_prompt_learner.ctx", "mpt": "text_prompt_learner.visual_ctx"}.get(self.variant, "prompt_learner.ctx")
 
     def set_knob(self, name: str, value: int):
         """``mudpt_model_set``: "gemm_variant", "lp_grad" and the split-operand knobs ("vis_lo", "txt_lo", "vis_sites", "txt_sites",
@@ -217,7 +227,8 @@ class CustomCLIP(nn.Module):
         # eval mode: the text features only depend on the parameters; recompute them only when the flat bucket's version
         # counter moved (the reference re-runs the text tower for every test batch)
         version = self.flat_params._version
-        reuse = (not self.training) and self._text_version == version and self.variant != "cocoop"  # CoCoOp's text features depend on the image
+        # CoCoOp's text features depend on the image; VPT's on no trainable: the library keeps them itself (until a frozen weight changes)
+        reuse = (not self.training) and self._text_version == version and self.variant not in ("cocoop", "vpt")
         if self.class_shard is not None:
             capi.check(self.lib.mudpt_cp_forward(self._h, capi.ptr(image), B, 1 if reuse else 0, self._stream()), "cp_forward")
             if not reuse:
