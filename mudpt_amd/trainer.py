@@ -4,10 +4,12 @@ Same class name, registry name, hooks and error behaviour as the reference plugi
 ``check_cfg`` (:189), ``build_model`` (:192), ``forward_backward`` (:235), ``parse_batch_train`` (:263),
 inherited ``model_inference`` (``self.model(input)``) and ``load_model`` (:270).  With Dassl installed it subclasses
 ``dassl.engine.TrainerX`` and registers in Dassl's ``TRAINER_REGISTRY`` so ``train.py --trainer MuDPT`` and
-``scripts/mudpt/*.sh`` run unchanged; without Dassl it falls back to ``dassl_lite``.
+``scripts/mudpt/*.sh`` run unchanged; without Dassl it falls back to ``dassl_lite``.  Its hooks and ``build_model``
+skeleton live in ``PromptTrainer``, which the CoCoOp, CoOp, VPT and MPT plugins (cocoop.py, coop.py, vpt.py) subclass as well.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 import os.path as osp
 
@@ -236,72 +238,86 @@ def warn_if_fp16_misses_the_bound(prec: str, state) -> bool:
     return True
 
 
-@TRAINER_REGISTRY.register()
-class MuDPT(TrainerX):
+def ctx_init_token_ids(text: str, n: int, ctx_len: int, near=None):
+    """clip.tokenize(CTX_INIT)[0, 1:1 + n] (trainers/mudpt.py:60-63, cocoop.py:83-86, coop.py:57-60, mpt.py:59-62): the ids whose token
+    embeddings initialise the context.  The benchmark's "a photo of a" comes from the recorded ids as far as they go, anything else from
+    the BPE tokenizer."""
+    if text == "a photo of a" and n <= len(synth.CTX_INIT_TOKENS):
+        return synth.CTX_INIT_TOKENS[:n]
+    return [int(v) for v in tokenize_prompts([text], ctx_len, near=near)[0, 1:1 + n]]
+
+
+def class_prompts(prefix: str, names, ctx_len: int, near=None):
+    """The tokenized "<prefix> <classname>." prompt of every class (trainers/mudpt.py:84-85, cocoop.py:110, coop.py:81, vpt.py:61, mpt.py:79)."""
+    return tokenize_prompts([prefix + " " + name + "." for name in names], ctx_len, near=near)
+
+
+class PromptTrainer(TrainerX):
+    """The plugin layer every trainer of this package shares; not registered itself.  A plugin names its cfg node, its registered model
+    and the fixed token buffers its load_model drops, and implements ``prompt_setup``; ``build_model`` is the reference plugins' common
+    skeleton: backbone, CustomCLIP, optimizer / scheduler / register_model on the module that owns the trainables."""
+    CFG_NODE = ""                  # cfg.TRAINER.<CFG_NODE>
+    MODEL_NAME = ""                # register_model name: the checkpoint sub-directory
+    DROP_KEYS = ()                 # fixed token buffers a checkpoint may hold; load_model ignores them
+    SKIPPED_NOTE = "Note that load_model() is skipped as no pretrained model is given"
+    WITH_ACC = False               # the step's summary also has "acc" (compute_accuracy of the logits)
+    PROMPT_LEARNER_ONLY = False    # optimise, register and initialise model.prompt_learner, not the whole model
+    FREEZE_NOTE = True             # print the reference's "Turning off gradients ..." line
+
     def check_cfg(self, cfg):
-        assert cfg.TRAINER.MUDPT.PREC in ["fp16", "fp32", "amp"]  # trainers/mudpt.py:190
+        assert getattr(cfg.TRAINER, self.CFG_NODE).PREC in ["fp16", "fp32", "amp"]  # trainers/mudpt.py:190, cocoop.py:204, coop.py:236, ...
+
+    def prompt_setup(self, node, names, ctx_len: int, near):
+        """Print the prompt settings; return (n_ctx, depth) of the ModelShape, the tokenized class prompts and the plugin's own CustomCLIP
+        keyword arguments (ctx_token_ids, variant, ...).  ``names``: the class names with "_" replaced by " "."""
+        raise NotImplementedError
 
     def build_model(self):
         cfg = self.cfg
-        classnames = self.dm.dataset.classnames
-        mc = cfg.TRAINER.MUDPT
-        assert mc.DEEP_PROMPT_DEPTH > 0, "PROMPT_DEPTH should be > 0"  # trainers/mudpt.py:52
-
+        node = getattr(cfg.TRAINER, self.CFG_NODE)
         print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")
         state = load_clip_state_dict(cfg)
         if state is None:
-            shape = ModelShape(n_ctx=mc.N_CTX, depth=mc.DEEP_PROMPT_DEPTH)
-            state = synth.random_clip_state(shape, cfg.MODEL.BACKBONE.SYNTHETIC_SEED)
+            backbone = ModelShape()
+            state = synth.random_clip_state(backbone, cfg.MODEL.BACKBONE.SYNTHETIC_SEED)
         else:
-            shape = ModelShape.from_state_dict(state, mc.N_CTX, mc.DEEP_PROMPT_DEPTH)
+            backbone = ModelShape.from_state_dict(state, 4, 1)  # the prompt's n_ctx / depth come from prompt_setup
         cfg_imsize = cfg.INPUT.SIZE[0]
-        assert cfg_imsize == shape.image_size, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({shape.image_size})"  # :55
-        warn_if_fp16_misses_the_bound(mc.PREC, state)
-
-        # trainers/mudpt.py:57-70,83-85: ctx init words, prompt prefix, "<prefix> <classname>." prompts
-        ctx_init = mc.CTX_INIT
-        if ctx_init:
-            ctx_init = ctx_init.replace("_", " ")
-            prompt_prefix = " ".join(ctx_init.split()[:mc.N_CTX])
-            ctx_ids = [int(v) for v in tokenize_prompts([ctx_init], shape.ctx_len, near=cfg.MODEL.BACKBONE.PATH or None)[0, 1:1 + mc.N_CTX]] \
-                if ctx_init != "a photo of a" else synth.CTX_INIT_TOKENS[:mc.N_CTX]
-        else:
-            print("Initializing A Generic Context")
-            prompt_prefix, ctx_ids = " ".join(["X"] * mc.N_CTX), None
-        print(f'Initial context: "{prompt_prefix}"')
-        print(f"Number of context words (tokens): {mc.N_CTX}")
-        print(f"Depth of deep prompt: {mc.DEEP_PROMPT_DEPTH}")
-        prompts = [prompt_prefix + " " + name.replace("_", " ") + "." for name in classnames]
-        tokenized = tokenize_prompts(prompts, shape.ctx_len, near=cfg.MODEL.BACKBONE.PATH or None)
+        assert cfg_imsize == backbone.image_size, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({backbone.image_size})"  # mudpt.py:55
+        warn_if_fp16_misses_the_bound(node.PREC, state)
+        names = [name.replace("_", " ") for name in self.dm.dataset.classnames]
+        n_ctx, depth, tokenized, kwargs = self.prompt_setup(node, names, backbone.ctx_len, cfg.MODEL.BACKBONE.PATH or None)
 
         print("Building custom CLIP")
         # one process per GPU (the reference: nn.DataParallel in one process): join the process group torch.distributed.run set up
         # BEFORE the model exists, so grad_scale = 1 / world and the parameter broadcast below are in effect from step one
         rank, world, local = parallel.init()
         max_batch = max(-(-cfg.DATALOADER.TRAIN_X.BATCH_SIZE // world), cfg.DATALOADER.TEST.BATCH_SIZE)
-        self.model = CustomCLIP(shape, state, tokenized, ctx_token_ids=ctx_ids, max_batch=max_batch,
-                                dtype=precision_to_dtype(mc.PREC), device=f"cuda:{local}", seed=cfg.SEED,
-                                class_shard=class_parallel_shard(len(classnames), getattr(mc, "CLASS_PARALLEL", None)))
-        if self.model.class_shard is not None:
-            print(f"Class-parallel text tower: this rank encodes classes {self.model.class_shard[0]}..{self.model.class_shard[1] - 1} of {len(classnames)}")
-        # the freeze rule of trainers/mudpt.py:205-218 is structural here: the module only owns the 10 trainables
+        self.model = CustomCLIP(dataclasses.replace(backbone, n_ctx=n_ctx, depth=depth), state, tokenized, max_batch=max_batch,
+                                dtype=precision_to_dtype(node.PREC), device=f"cuda:{local}", seed=cfg.SEED, **kwargs)
+        if self.model.class_shard is not None:  # MuDPT only: CustomCLIP shards no other variant
+            print(f"Class-parallel text tower: this rank encodes classes {self.model.class_shard[0]}..{self.model.class_shard[1] - 1} of {len(names)}")
+        if self.FREEZE_NOTE:
+            print("Turning off gradients in both the image and the text encoder")
+        # the freeze rules (trainers/mudpt.py:205-218, cocoop.py:220-232, ...) are structural here: the module only owns the trainables
         print(f"Parameters to be updated: {set(self.model.param_names)}")
+        # CoCoOp / CoOp give only prompt_learner to the optimizer (cocoop.py:239, coop.py:268).  MuDPT, VPT and MPT initialise
+        # self.model.prompt_learner, an attribute their models do not have (mudpt.py:220-221, vpt.py:152-153, mpt.py:210-211, SURVEY
+        # appendix A.3); the evident intent -- initialise the trainables from a checkpoint -- is applied to the module that owns them
+        trained = self.model.prompt_learner if self.PROMPT_LEARNER_ONLY else self.model
         if cfg.MODEL.INIT_WEIGHTS:
-            # trainers/mudpt.py:220-221 passes self.model.prompt_learner, an attribute that does not exist; the
-            # evident intent -- initialise the trainables from a checkpoint -- is applied to the module that owns them
-            load_pretrained_weights(self.model, cfg.MODEL.INIT_WEIGHTS)
-
-        self.optim = build_optimizer(self.model, cfg.OPTIM)
+            load_pretrained_weights(trained, cfg.MODEL.INIT_WEIGHTS)
+        self.optim = build_optimizer(trained, cfg.OPTIM)
         self.sched = build_lr_scheduler(self.optim, cfg.OPTIM)
-        self.register_model("MultimodalDeepPromptTuning", self.model, self.optim, self.sched)
+        self.register_model(self.MODEL_NAME, trained, self.optim, self.sched)
         self.scaler = None  # loss scaling lives inside the library (mudpt_set_loss_scale)
-        # the reference wraps in nn.DataParallel when device_count > 1 (:230-233); here: one process per GPU
+        # the reference wraps in nn.DataParallel when device_count > 1 (mudpt.py:230-233); here: one process per GPU
         if parallel.world_size() > 1:
             parallel.broadcast_params(self.model.flat_params)
         install_loader(self, local)  # rank-aware (world > 1) and prefetched training loader
 
     def forward_backward(self, batch):
-        return data_parallel_step(self, batch)
+        return data_parallel_step(self, batch, with_acc=self.WITH_ACC)
 
     def parse_batch_train(self, batch):
         return parse_batch(self, batch)
@@ -310,5 +326,31 @@ class MuDPT(TrainerX):
         save_on_main(self, super().save_model, *args, **kwargs)
 
     def load_model(self, directory, epoch=None):
-        load_plugin_checkpoint(self, directory, epoch, ("mudpt_prompt_learner.token_prefix", "mudpt_prompt_learner.token_suffix"),  # trainers/mudpt.py:293-298
-                               "Note that load_model() is skipped as no pretrained model is given")
+        load_plugin_checkpoint(self, directory, epoch, self.DROP_KEYS, self.SKIPPED_NOTE)
+
+
+@TRAINER_REGISTRY.register()
+class MuDPT(PromptTrainer):
+    CFG_NODE, MODEL_NAME = "MUDPT", "MultimodalDeepPromptTuning"  # trainers/mudpt.py:190,227
+    DROP_KEYS = ("mudpt_prompt_learner.token_prefix", "mudpt_prompt_learner.token_suffix")  # trainers/mudpt.py:293-298
+    FREEZE_NOTE = False
+
+    def build_model(self):
+        assert self.cfg.TRAINER.MUDPT.DEEP_PROMPT_DEPTH > 0, "PROMPT_DEPTH should be > 0"  # trainers/mudpt.py:52
+        super().build_model()
+
+    def prompt_setup(self, mc, names, ctx_len, near):
+        # trainers/mudpt.py:57-75,83-85: ctx init words, prompt prefix, "<prefix> <classname>." prompts
+        ctx_init, ctx_ids = mc.CTX_INIT, None
+        if ctx_init:
+            ctx_init = ctx_init.replace("_", " ")
+            prompt_prefix = " ".join(ctx_init.split()[:mc.N_CTX])
+            ctx_ids = ctx_init_token_ids(ctx_init, mc.N_CTX, ctx_len, near)
+        else:
+            print("Initializing A Generic Context")
+            prompt_prefix = " ".join(["X"] * mc.N_CTX)
+        print(f'Initial context: "{prompt_prefix}"')
+        print(f"Number of context words (tokens): {mc.N_CTX}")
+        print(f"Depth of deep prompt: {mc.DEEP_PROMPT_DEPTH}")
+        return mc.N_CTX, mc.DEEP_PROMPT_DEPTH, class_prompts(prompt_prefix, names, ctx_len, near), dict(
+            ctx_token_ids=ctx_ids, variant="mudpt", class_shard=class_parallel_shard(len(names), getattr(mc, "CLASS_PARALLEL", None)))
