@@ -346,6 +346,74 @@ int mudpt_coop_dctx(int32_t dtype, const float* dx_f32, const void* dx_lp, const
 int mudpt_sgemm(int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda,
                 const float* B, int32_t ldb, float beta, float* C, int32_t ldc, const float* bias, void* stream);
 
+/* ---- the launchers' production forms (test surface like the rest of this section: additions here leave MUDPT_ABI_VERSION alone, it
+ * numbers the drop-in boundary above the line) ---- */
+/* mudpt_layernorm_bwd plus what the training step passes: the residual gradient in T (dres_lp, same stride lddres; exclusive with dres),
+ * the fused splice backward -- rows whose position r % side_L lies in [side_row0, side_row0 + side_n) go, in fp32, to
+ * side[(r / side_L) * side_ldb + (pos - side_row0) * d] and ZERO goes to dx / dx_lp (identity row map only; side = NULL: off) -- and the
+ * index mode of a row_index launch: 0 dy / mean / rstd compact (row r), 1 all three by token row (row_index[r]), 2 mean / rstd by token row. */
+int mudpt_layernorm_bwd_ex(int32_t dtype, const void* dy, int32_t lddy, int32_t dy_f32, const float* x, int32_t ldx, const int32_t* row_index,
+                           const float* mean, const float* rstd, const float* gamma, const float* dres, const void* dres_lp, int32_t lddres,
+                           float* dx, int32_t lddx, void* dx_lp, int32_t lddx_lp, float* side, int32_t side_row0, int32_t side_n, int32_t side_L,
+                           size_t side_ldb, int32_t index_mode, int32_t rows, int32_t d, void* stream);
+/* mudpt_layernorm_fwd_fused with the launcher's remaining operands: a row map (row_index, as mudpt_layernorm_fwd: only WITHOUT add / splice /
+ * xout, which the launcher refuses under a row map) and a split output (out_lo in lo_mode 1 / 2, as mudpt_layernorm_fwd_split: T output only). */
+int mudpt_layernorm_fwd_ex(int32_t dtype, const float* x, int32_t ldx, const int32_t* row_index, const float* add, const void* add_lp, int32_t ldadd,
+                           const float* ov_rows, int32_t ov_row0, int32_t ov_n, int32_t ov_L, float* xout, int32_t ldxout, const float* gamma,
+                           const float* beta, void* out, void* out_lo, int32_t lo_mode, int32_t ldo, int32_t out_f32, float* mean, float* rstd,
+                           int32_t rows, int32_t d, void* stream);
+/* mudpt_attention_fwd / _fwd_single writing a split output (the parity mode's vision tower): out = T(O) in rows of ld_out elements (0 = H*64),
+ * out_lo (may be NULL) = the remainder in form lo_mode (1: T; 2: e4m3 bytes of (O - out) * 2^12, the first H*64 bytes of each row) at the same
+ * row stride in bytes. */
+int mudpt_attention_fwd_split(int32_t dtype, const void* qkv, void* out, void* out_lo, int32_t lo_mode, int32_t ld_out, float* lse, int32_t B, int32_t L,
+                              int32_t H, int32_t causal, void* stream);
+int mudpt_attention_fwd_single_split(int32_t dtype, const void* qkv, const void* q_sel, const int32_t* sel_rows, void* out_sel, void* out_lo,
+                                     int32_t lo_mode, int32_t ld_out, float* lse_sel, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream);
+/* mudpt_attention_bwd where dout is zero except on token row sel_rows[b] (= b * L + position) of every sequence (the last block with the
+ * knob last_single = 0, the class-parallel path): query blocks without that row are skipped.  causal: bit 0 only. */
+int mudpt_attention_bwd_sel(int32_t dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                            const int32_t* sel_rows, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream);
+/* mudpt_head with the state the model keeps between calls in the caller's hands: txt_n [C, e] / txt_inv [C] (txt = NULL: reuse them as the
+ * previous call left them -- the fused path only), B_total > 0 (this call is a chunk of a batch of B_total images: gradients are scaled by
+ * 1 / B_total and `loss` is NOT written, the caller takes the mean of the row losses), row_loss [B] (may be NULL).  path 0: the dispatch of
+ * mudpt_head; 1: force the unfused launchers.  *path_taken (HOST, may be NULL) = 0 if the fused kernels ran, 1 if the unfused ones. */
+int mudpt_head_ex(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
+                  int32_t e, float* txt_n, float* txt_inv, float* logits, float* loss, float* row_loss, float* dimg, float* dtxt, int32_t path,
+                  int32_t* path_taken, void* stream);
+/* CoCoOp's head (trainers/cocoop.py:187-197): every image has its own text features txt [B * C, e] (row i * C + c); logits[i, c] = scale *
+ * <normalise(img_i), normalise(txt_{i,c})>, row_loss [B], dtxt [B * C, e] = gradient of (grad_scale * mean CE) w.r.t. the raw text features.
+ * B_total > 0: a chunk of a batch of B_total images (gradients scaled by 1 / B_total, `loss` not written); 0: loss[0] = mean(row_loss).
+ * labels NULL: logits only. */
+int mudpt_pair_head(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
+                    int32_t e, float* logits, float* loss, float* row_loss, float* dtxt, void* stream);
+/* images fp32 [B, 3, S, S] -> patches T [B * (S/p)^2, ldk], inner order (c, py, px), columns 3 p p .. ldk zero (clip/model.py:527-529);
+ * patches_lo not NULL: the split form, the remainder in form lo_mode (1 / 2) in rows of 2 ldk bytes. */
+int mudpt_patchify(int32_t dtype, const float* images, void* patches, void* patches_lo, int32_t lo_mode, int32_t B, int32_t image_size, int32_t patch,
+                   int32_t ldk, void* stream);
+/* The data movers, one launcher each (mudpt_amd/csrc/kernels.h has the definitions):
+ *   set_rows        x[b, row0 + i, :] = rows[i, :] (+ add[i, :]), x fp32 [B, L, d]
+ *   gather_rows     dst[r] = src[rows[r]]   } whole rows of row_bytes (a multiple of 16), strides in bytes
+ *   scatter_rows    dst[rows[r]] = src[r]   }
+ *   add_rows        dst[rows[r], :] += src[r, :] in T (one fp32 add, one rounding; rows distinct)
+ *   colsum          out[n] (+)= sum_m A[m, n], A fp32 [M, N] with row stride lda
+ *   add / cast      y = a + b (fp32) / y = T(x)
+ *   relu / relu_bwd y = max(y, 0) in place / dy = y > 0 ? dy : 0 in place
+ *   cocoop_prompts  x0[(i, c), l, :] = emb_pos[c, l, :], rows 1..n = ctx[l - 1] + bias[i] + pos[l]   (trainers/cocoop.py:148-165)
+ *   coop_splice     x[rows[c n + j], :] = ctx[csc ? c : 0][j] + tpos[pos[c n + j]]                    (trainers/coop.py:99-164) */
+int mudpt_set_rows(float* x, int32_t B, int32_t L, int32_t d, int32_t row0, int32_t n, const float* rows, const float* add, void* stream);
+int mudpt_gather_rows(const void* src, size_t src_stride, const int32_t* rows, void* dst, size_t dst_stride, int32_t nrows, int32_t row_bytes, void* stream);
+int mudpt_scatter_rows(const void* src, size_t src_stride, const int32_t* rows, void* dst, size_t dst_stride, int32_t nrows, int32_t row_bytes, void* stream);
+int mudpt_add_rows(int32_t dtype, const void* src, const int32_t* rows, void* dst, int32_t nrows, int32_t d, void* stream);
+int mudpt_colsum(const float* A, int32_t M, int32_t N, int32_t lda, float* out, int32_t accumulate, void* stream);
+int mudpt_add(const float* a, const float* b, float* y, size_t n, void* stream);
+int mudpt_cast(int32_t dtype, const float* x, void* y, size_t n, void* stream);
+int mudpt_relu(float* y, size_t n, void* stream);
+int mudpt_relu_bwd(float* dy, const float* y, size_t n, void* stream);
+int mudpt_cocoop_prompts(float* x0, const float* emb_pos, const float* ctx, const float* bias, const float* pos, int32_t B, int32_t C, int32_t L,
+                         int32_t d, int32_t n, void* stream);
+int mudpt_coop_splice(float* x, const float* ctx, const float* tpos, const int32_t* rows, const int32_t* pos, int32_t C, int32_t n, int32_t d,
+                      int32_t csc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,27 @@ SIGNATURES = {
     "mudpt_cocoop_dbias": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "mudpt_coop_dctx": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "mudpt_sgemm": (_i32, [_i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i32, _f32, _vp, _i32, _vp, _vp]),
+    "mudpt_layernorm_bwd_ex": (_i32, [_i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
+                                      _vp, _i32, _i32, _i32, _sz, _i32, _i32, _i32, _vp]),
+    "mudpt_layernorm_fwd_ex": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                      _vp, _vp, _i32, _i32, _vp]),
+    "mudpt_attention_fwd_split": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_attention_fwd_single_split": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_attention_bwd_sel": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_head_ex": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_i32), _vp]),
+    "mudpt_pair_head": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mudpt_patchify": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_set_rows": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mudpt_gather_rows": (_i32, [_vp, _sz, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "mudpt_scatter_rows": (_i32, [_vp, _sz, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "mudpt_add_rows": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mudpt_colsum": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "mudpt_add": (_i32, [_vp, _vp, _vp, _sz, _vp]),
+    "mudpt_cast": (_i32, [_i32, _vp, _vp, _sz, _vp]),
+    "mudpt_relu": (_i32, [_vp, _sz, _vp]),
+    "mudpt_relu_bwd": (_i32, [_vp, _vp, _sz, _vp]),
+    "mudpt_cocoop_prompts": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_coop_splice": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -134,6 +134,19 @@ struct Attn {
     __device__ static inline void* lo_ptr(void* base, int lo_mode, size_t row, size_t ldo, int hd) {
         return lo_mode == LO_F8 ? (void*)((char*)base + row * ldo * 2 + hd * 64) : (void*)((elem*)base + row * ldo + hd * 64);
     }
+    // the forward's `out` without a low half: T of the fp32 product (round_to), the value store_t_split calls hi.  store_t's plain cast lets
+    // the compiler fuse the multiply into the conversion (v_fma_mixlo_f16: one rounding of the exact product), and `out` then depended
+    // on whether out_lo was passed: 1 fp16 code on ~4e-5 of the elements (test_attention_fwd_split_output).
+    __device__ static inline void store_t_out(elem* dst_row, const f32x4 (&x)[4], float scale, int lane) {
+        const int g = lane >> 4;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            vec4 v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = round_to<elem>(x[dt][r] * scale);
+            *(vec4*)(dst_row + 16 * dt + 4 * g) = v;
+        }
+    }
     // D^T tile set (4 tiles of 16 d x 16 rows) -> dst[row][16 dt + 4 g + r]
     __device__ static inline void store_t(elem* dst_row, const f32x4 (&x)[4], float scale, int lane) {
         const int g = lane >> 4;
@@ -230,7 +243,7 @@ __device__ inline void fwd_pv_store(const AttnArgs& p, const typename T::elem* V
     if (q < L) {
         const size_t off = ((size_t)b * L + q) * ldo + hd * 64;
         if (p.out_lo) A::store_t_split((elem*)p.out + off, A::lo_ptr(p.out_lo, p.lo_mode, (size_t)b * L + q, ldo, hd), p.lo_mode, O, 1.f / l, lane);
-        else A::store_t((elem*)p.out + off, O, 1.f / l, lane);
+        else A::store_t_out((elem*)p.out + off, O, 1.f / l, lane);
     }
     if (g == 0 && p.lse) p.lse[(size_t)pair * Lp + q] = q < L ? m * 0.125f + __logf(l) : 0.f;
 }
@@ -1034,7 +1047,7 @@ __global__ __launch_bounds__(TW * 64) void attn_fwd_tiled_kernel(AttnArgs p, int
     if (q < L) {
         const size_t off = ((size_t)b * L + q) * ldo + hd * 64;
         if (p.out_lo) A::store_t_split((elem*)p.out + off, A::lo_ptr(p.out_lo, p.lo_mode, (size_t)b * L + q, ldo, hd), p.lo_mode, O, 1.f / l, lane);
-        else A::store_t((elem*)p.out + off, O, 1.f / l, lane);
+        else A::store_t_out((elem*)p.out + off, O, 1.f / l, lane);
     }
     if (g == 0 && p.lse && q < Lp) p.lse[(size_t)pair * Lp + q] = q < L ? m * 0.125f + __logf(l) : 0.f;
 }
@@ -1251,6 +1264,8 @@ static int check(const AttnArgs& a, bool bwd) {
     ARG_CHECK((uintptr_t)a.qkv % 16 == 0, "attention: qkv must be 16-byte aligned");
     ARG_CHECK((size_t)a.B * a.L * 3 * a.H * 64 * 2 < 0x7fffffffull, "attention: qkv larger than 2 GiB");  // 32-bit DMA offsets
     if (!bwd) ARG_CHECK(a.out && (uintptr_t)a.out % 16 == 0, "attention: null/unaligned out");
+    ARG_CHECK(a.ld_out == 0 || (a.ld_out >= a.H * 64 && a.ld_out % 8 == 0), "attention: bad ld_out %d (H*64 = %d)", a.ld_out, a.H * 64);
+    if (!bwd) ARG_CHECK(!a.out_lo || ((uintptr_t)a.out_lo % 16 == 0 && (a.lo_mode == LO_F16 || a.lo_mode == LO_F8)), "attention: out_lo needs 16-byte alignment and lo_mode 1 / 2 (got %d)", a.lo_mode);
     if (bwd) ARG_CHECK(a.out && a.dout && a.dqkv && a.lse && a.delta, "attention bwd: null operand");
     return MUDPT_OK;
 }

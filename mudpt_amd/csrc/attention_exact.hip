@@ -212,6 +212,8 @@ int launch_attn_fwd_exact(const AttnArgs& a, hipStream_t s, const LaunchProf* pr
     ARG_CHECK(a.qkv32 && a.out && a.B > 0 && a.L > 0 && a.H > 0, "attention (exact): bad arguments");
     ARG_CHECK(a.L <= 4096, "attention (exact): L=%d exceeds 4096", a.L);
     const int ld_out = a.ld_out ? a.ld_out : a.H * 64;
+    ARG_CHECK(ld_out >= a.H * 64, "attention (exact): bad ld_out %d (H*64 = %d)", ld_out, a.H * 64);
+    ARG_CHECK(!a.out_lo || a.lo_mode == LO_F16 || a.lo_mode == LO_F8, "attention (exact): out_lo needs lo_mode 1 / 2 (got %d)", a.lo_mode);
     ARG_CHECK(ld_out % 8 == 0 && ((uintptr_t)a.out % 16 == 0) && ((uintptr_t)a.out_lo % 16 == 0) && ((uintptr_t)a.qkv32 % 16 == 0) && ((uintptr_t)a.qkv_lp % 16 == 0),
               "attention (exact): operands must be 16-byte aligned");
     ARG_CHECK((size_t)a.B * a.H < 0x7fffffffull, "attention (exact): too many (sequence, head) pairs");

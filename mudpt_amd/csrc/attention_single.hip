@@ -225,6 +225,7 @@ int launch_attn_fwd_single(int dtype, const AttnArgs& a, const void* q_sel, void
     if (int e = check_single(a)) return e;
     ARG_CHECK(q_sel && out_sel && lse_sel && ld_out >= a.H * 64, "attention (single query) fwd: null operand");
     ARG_CHECK((uintptr_t)q_sel % 16 == 0 && (uintptr_t)out_sel % 16 == 0 && (uintptr_t)out_lo % 16 == 0 && ld_out % 8 == 0, "attention (single query) fwd: operands must be 16-byte aligned");
+    ARG_CHECK(!out_lo || a.lo_mode == LO_F16 || a.lo_mode == LO_F8, "attention (single query) fwd: out_lo needs lo_mode 1 / 2 (got %d)", a.lo_mode);
     const int Lpad = (a.L + 63) & ~63, lds = 4 * Lpad * 4, grid = (a.B * a.H + 3) / 4;
     if (int e = single_attrs()) return e;
     if (dtype == DT_BF16) hipLaunchKernelGGL(attn_fwd_single_kernel<BF16>, dim3(grid), dim3(256), lds, s, a, q_sel, out_sel, out_lo, ld_out, lse_sel, Lpad);

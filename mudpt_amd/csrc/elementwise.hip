@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void set_rows_kernel(float* __restrict__ x, in
 }
 
 int launch_set_rows(float* x, int B, int L, int d, int row0, int n, const float* rows, const float* add, hipStream_t s) {
-    ARG_CHECK(x && rows && B > 0 && n > 0 && row0 >= 0 && row0 + n <= L && d % 4 == 0, "set_rows: bad arguments");
+    ARG_CHECK(x && rows && B > 0 && n > 0 && row0 >= 0 && row0 + n <= L && d > 0 && d % 4 == 0, "set_rows: bad arguments");
     hipLaunchKernelGGL(set_rows_kernel, dim3(B * n), dim3(256), 0, s, x, L, d, row0, n, rows, add);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -144,14 +144,16 @@ __global__ __launch_bounds__(256) void move_rows_kernel(const char* __restrict__
 }
 
 int launch_gather_rows(const void* src, size_t src_stride, const int* rows, void* dst, size_t dst_stride, int nrows, int row_bytes, hipStream_t s) {
-    ARG_CHECK(src && dst && rows && nrows > 0 && row_bytes > 0 && row_bytes % 16 == 0 && src_stride % 16 == 0 && dst_stride % 16 == 0, "gather_rows: bad arguments");
+    ARG_CHECK(src && dst && rows && nrows > 0 && row_bytes > 0 && row_bytes % 16 == 0 && src_stride % 16 == 0 && dst_stride % 16 == 0 &&
+              src_stride >= (size_t)row_bytes && dst_stride >= (size_t)row_bytes, "gather_rows: bad arguments");
     hipLaunchKernelGGL(move_rows_kernel, dim3(nrows), dim3(256), 0, s, (const char*)src, src_stride, rows, (char*)dst, dst_stride, (const int*)nullptr, row_bytes);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }
 
 int launch_scatter_rows(const void* src, size_t src_stride, const int* rows, void* dst, size_t dst_stride, int nrows, int row_bytes, hipStream_t s) {
-    ARG_CHECK(src && dst && rows && nrows > 0 && row_bytes > 0 && row_bytes % 16 == 0 && src_stride % 16 == 0 && dst_stride % 16 == 0, "scatter_rows: bad arguments");
+    ARG_CHECK(src && dst && rows && nrows > 0 && row_bytes > 0 && row_bytes % 16 == 0 && src_stride % 16 == 0 && dst_stride % 16 == 0 &&
+              src_stride >= (size_t)row_bytes && dst_stride >= (size_t)row_bytes, "scatter_rows: bad arguments");
     hipLaunchKernelGGL(move_rows_kernel, dim3(nrows), dim3(256), 0, s, (const char*)src, src_stride, (const int*)nullptr, (char*)dst, dst_stride, rows, row_bytes);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(float* __restrict__ sr
 
 int launch_reduce_rows(int dtype, float* src, void* src_lp, int B, int L, int d, int row0, int n, float* out, bool zero_src,
                        bool accumulate, float scale, hipStream_t s) {
-    ARG_CHECK((src || src_lp) && out && B > 0 && n > 0 && row0 >= 0 && row0 + n <= L, "reduce_rows: bad arguments");
+    ARG_CHECK((src || src_lp) && out && B > 0 && n > 0 && row0 >= 0 && row0 + n <= L && d > 0, "reduce_rows: bad arguments B=%d L=%d d=%d rows %d..%d", B, L, d, row0, row0 + n - 1);
     const int grid = (n * d + 31) / 32;
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(reduce_rows_kernel<BF16>, dim3(grid), dim3(256), 0, s, src, (__bf16*)src_lp, B, L, d, row0, n, out, zero_src, accumulate, scale);
@@ -295,6 +297,9 @@ __global__ __launch_bounds__(SG_WAVES * 64) void sgemm_kernel(bool tA, bool tB, 
 int launch_sgemm(bool tA, bool tB, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb, float beta,
                  float* C, int ldc, const float* bias, hipStream_t s) {
     ARG_CHECK(A && B && C && M > 0 && N > 0 && K > 0, "sgemm: bad arguments M=%d N=%d K=%d", M, N, K);
+    // row-major operands as stored: A is [M, K] (tA: [K, M]), B is [K, N] (tB: [N, K]); a stride shorter than the row makes rows overlap
+    ARG_CHECK(lda >= (tA ? M : K) && ldb >= (tB ? K : N) && ldc >= N, "sgemm: a stride is shorter than its row: lda=%d ldb=%d ldc=%d (M=%d N=%d K=%d tA=%d tB=%d)",
+              lda, ldb, ldc, M, N, K, (int)tA, (int)tB);
     hipLaunchKernelGGL(sgemm_kernel, dim3((N + 15) / 16, (M + 15) / 16), dim3(SG_WAVES * 64), 0, s, tA, tB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -309,7 +314,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ A
 }
 
 int launch_colsum(const float* A, int M, int N, int lda, float* out, bool accumulate, hipStream_t s) {
-    ARG_CHECK(A && out && M > 0 && N > 0, "colsum: bad arguments");
+    ARG_CHECK(A && out && M > 0 && N > 0 && lda >= N, "colsum: bad arguments M=%d N=%d lda=%d", M, N, lda);
     hipLaunchKernelGGL(colsum_kernel, dim3((N + 255) / 256), dim3(256), 0, s, A, M, N, lda, out, accumulate);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -425,8 +430,10 @@ int launch_head_fwd(const HeadArgs& a, hipStream_t s) {
 int launch_head_bwd(const HeadArgs& a, hipStream_t s) {
     if (int e = check_head(a)) return e;
     ARG_CHECK(a.labels && a.loss && a.dlogits && a.row_loss && a.dimg, "head bwd: null operand");
-    hipLaunchKernelGGL(ce_rows_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.logits, a.labels, a.row_loss, a.dlogits, a.B, a.C, a.grad_scale / a.B);
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, a.row_loss, a.B, a.loss);
+    ARG_CHECK(a.B_total <= 0 || a.B_total >= a.B, "head bwd: B_total=%d is smaller than its chunk of B=%d rows", a.B_total, a.B);
+    const int Bt = a.B_total > 0 ? a.B_total : a.B;  // chunked over the images, as in the fused head: the caller then takes the mean (launch_mean)
+    hipLaunchKernelGGL(ce_rows_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.logits, a.labels, a.row_loss, a.dlogits, a.B, a.C, a.grad_scale / Bt);
+    if (a.B_total <= 0) hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, a.row_loss, a.B, a.loss);
     HIP_TRY(hipGetLastError());
     // d img_n = scale * dlogits . txt_n ; d txt_n = scale * dlogits^T . img_n  (dtxt null: the text side has nothing to learn, VPT)
     if (int e = launch_sgemm(false, false, a.B, a.e, a.C, a.scale, a.dlogits, a.C, a.txt_n, a.e, 0.f, a.dimg, a.e, nullptr, s)) return e;
@@ -481,6 +488,7 @@ int launch_pair_head_fwd(const HeadArgs& a, hipStream_t s) {
 int launch_pair_head_bwd(const HeadArgs& a, hipStream_t s) {
     if (int e = check_head(a)) return e;
     ARG_CHECK(a.labels && a.loss && a.dlogits && a.row_loss && a.dtxt, "pair head bwd: null operand");
+    ARG_CHECK(a.B_total <= 0 || a.B_total >= a.B, "pair head bwd: B_total=%d is smaller than its chunk of B=%d rows", a.B_total, a.B);
     const int Bt = a.B_total > 0 ? a.B_total : a.B;  // chunked over the images: the mean is over the whole batch, taken by the caller
     hipLaunchKernelGGL(ce_rows_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.logits, a.labels, a.row_loss, a.dlogits, a.B, a.C, a.grad_scale / Bt);
     if (a.B_total <= 0) hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, a.row_loss, a.B, a.loss);
@@ -506,7 +514,7 @@ __global__ __launch_bounds__(128) void cocoop_prompts_kernel(float* __restrict__
     }
 }
 int launch_cocoop_prompts(float* x0, const float* emb_pos, const float* ctx, const float* bias, const float* pos, int B, int C, int L, int d, int n, hipStream_t s) {
-    ARG_CHECK(x0 && emb_pos && ctx && bias && pos && B > 0 && C > 0 && n > 0 && 1 + n < L && d % 4 == 0, "cocoop_prompts: bad arguments");
+    ARG_CHECK(x0 && emb_pos && ctx && bias && pos && B > 0 && C > 0 && n > 0 && 1 + n < L && d > 0 && d % 4 == 0, "cocoop_prompts: bad arguments");
     hipLaunchKernelGGL(cocoop_prompts_kernel, dim3(B * C * L), dim3(128), 0, s, x0, emb_pos, ctx, bias, pos, C, L, d, n);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -527,7 +535,7 @@ __global__ __launch_bounds__(128) void cocoop_dbias_kernel(const float* __restri
     }
 }
 int launch_cocoop_dbias(int dtype, const float* dx, const void* dx_lp, float* dbias, int B, int C, int L, int d, int n, float scale, hipStream_t s) {
-    ARG_CHECK((dx || dx_lp) && dbias && B > 0 && C > 0 && n > 0 && 1 + n < L, "cocoop_dbias: bad arguments");
+    ARG_CHECK((dx || dx_lp) && dbias && B > 0 && C > 0 && n > 0 && 1 + n < L && d > 0, "cocoop_dbias: bad arguments B=%d C=%d L=%d d=%d n=%d", B, C, L, d, n);
     if (dtype == DT_BF16) hipLaunchKernelGGL(cocoop_dbias_kernel<BF16>, dim3(B), dim3(128), 0, s, dx, (const __bf16*)dx_lp, dbias, C, L, d, n, scale);
     else if (dtype == DT_F16) hipLaunchKernelGGL(cocoop_dbias_kernel<F16>, dim3(B), dim3(128), 0, s, dx, (const _Float16*)dx_lp, dbias, C, L, d, n, scale);
     else { set_error("cocoop_dbias: unknown dtype %d", dtype); return MUDPT_ERR_ARG; }
@@ -544,11 +552,13 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(float* __restrict__ dy, c
     if (i < n) dy[i] = y[i] > 0.f ? dy[i] : 0.f;
 }
 int launch_relu(float* y, size_t n, hipStream_t s) {
+    ARG_CHECK(y && n > 0 && (n + 255) / 256 < 0x7fffffffull, "relu: bad arguments");
     hipLaunchKernelGGL(relu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, n);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }
 int launch_relu_bwd(float* dy, const float* y, size_t n, hipStream_t s) {
+    ARG_CHECK(dy && y && n > 0 && (n + 255) / 256 < 0x7fffffffull, "relu_bwd: bad arguments");
     hipLaunchKernelGGL(relu_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dy, y, n);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;

@@ -17,6 +17,7 @@
 
 namespace mudpt {
 
+constexpr int HEAD_MAX_E_TRAIN = 65536 / (16 * 4);  // head_dtxt_kernel: [16][e] fp32 within the 64 KB it asks for
 constexpr int HEAD_ROWS = 16, HEAD_WAVES = 8, HEAD_RPW = HEAD_ROWS / HEAD_WAVES;  // 16 rows per workgroup, 8 waves, 2 rows per wave in the row-wise phases
 
 // acc[t] += A[16, K] . B[K, 16 tile t]: A from `a_row` (this lane's row, k contiguous: LDS or global), B rows from `b_base + k * ldb`
@@ -215,11 +216,15 @@ static int head_lds_bytes(const HeadArgs& a, bool train) {
     return (HEAD_ROWS * a.e * (train ? 2 : 1) + HEAD_ROWS * Cpad) * 4;
 }
 // true if the fused kernels can hold a 16-row problem in LDS (otherwise the caller keeps the unfused fp32 path of elementwise.hip)
-bool head_fused_fits(const HeadArgs& a, bool train) { return a.e % 16 == 0 && head_lds_bytes(a, train) + 256 <= 163840; }
+// Training: head_dtxt_kernel keeps a [16][e] fp32 tile in its 64 KB LDS allowance, so e <= 1024 there (launch_head_fused_train refuses more).
+bool head_fused_fits(const HeadArgs& a, bool train) {
+    return a.e > 0 && a.e % 16 == 0 && (!train || a.e <= HEAD_MAX_E_TRAIN) && head_lds_bytes(a, train) + 256 <= 163840;
+}
 
 // logits (and the normalised features the backward needs).  txt_n / txt_inv are (re)computed unless a.txt is null (cached text features).
 int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s) {
     ARG_CHECK(a.img && a.logits && a.txt_n && a.txt_inv && a.B > 0 && a.C > 0 && a.e > 0, "head: bad arguments");
+    ARG_CHECK(head_fused_fits(a, false), "head: the fused forward does not take B=%d C=%d e=%d (e %% 16, LDS)", a.B, a.C, a.e);
     if (a.txt)
         if (int rc = launch_l2norm(a.txt, a.txt_n, a.txt_inv, a.C, a.e, s)) return rc;
     const int Cpad = (a.C + 15) / 16 * 16, lds = head_lds_bytes(a, false);
@@ -240,7 +245,9 @@ int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s) {
 int launch_head_fused_train(const HeadArgs& a, hipStream_t s) {
     ARG_CHECK(a.img && a.logits && a.txt_n && a.txt_inv && a.img_n && a.img_inv && a.labels && a.loss && a.dlogits && a.row_loss && a.dimg,
               "head: null operand");
-    ARG_CHECK(a.B > 0 && a.C > 0 && a.e > 0 && a.e <= 1024, "head: bad shape B=%d C=%d e=%d", a.B, a.C, a.e);
+    ARG_CHECK(a.B > 0 && a.C > 0 && a.e > 0 && a.e <= HEAD_MAX_E_TRAIN, "head: bad shape B=%d C=%d e=%d", a.B, a.C, a.e);
+    ARG_CHECK(a.B_total <= 0 || a.B_total >= a.B, "head: B_total=%d is smaller than its chunk of B=%d rows", a.B_total, a.B);
+    ARG_CHECK(head_fused_fits(a, true), "head: the fused training head does not take B=%d C=%d e=%d (e %% 16, LDS)", a.B, a.C, a.e);
     if (a.txt)
         if (int rc = launch_l2norm(a.txt, a.txt_n, a.txt_inv, a.C, a.e, s)) return rc;
     const int Cpad = (a.C + 15) / 16 * 16, lds = head_lds_bytes(a, true);

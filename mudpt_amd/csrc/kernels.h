@@ -190,7 +190,7 @@ struct HeadArgs {
     float* txt_inv = nullptr;     // [C]
     float grad_scale = 1.f;       // dlogits = (softmax - onehot) * grad_scale / B  (the caller folds loss scaling in here)
     int B = 0, C = 0, e = 0;
-    int B_total = 0;              // pair head, chunked over the images: the batch the mean is taken over (0 = B); then the caller computes the loss (launch_mean)
+    int B_total = 0;              // every training head, chunked over the images: the batch the mean is taken over (0 = B); then the caller computes the loss (launch_mean)
 };
 int launch_head_fwd(const HeadArgs& a, hipStream_t s);
 int launch_head_bwd(const HeadArgs& a, hipStream_t s);

@@ -155,6 +155,13 @@ int launch_ln_fwd(int dtype, const LnFwdArgs& a, hipStream_t s, const LaunchProf
     ARG_CHECK(a.x && a.gamma && a.beta && a.out, "ln_fwd: null operand");
     ARG_CHECK(a.rows > 0 && a.d > 0 && a.d % 4 == 0 && a.d <= 256 * LN_MAXV, "ln_fwd: bad shape rows=%d d=%d", a.rows, a.d);
     ARG_CHECK(a.ldx % 4 == 0 && a.ldo % 4 == 0 && a.ldx >= a.d && a.ldo >= a.d, "ln_fwd: bad strides %d/%d", a.ldx, a.ldo);
+    ARG_CHECK(!(a.add || a.add_lp) || (a.ldadd % 4 == 0 && a.ldadd >= a.d), "ln_fwd: bad addend stride %d", a.ldadd);
+    ARG_CHECK(!a.xout || (a.ldxout % 4 == 0 && a.ldxout >= a.d), "ln_fwd: bad xout stride %d", a.ldxout);
+    ARG_CHECK(!a.ov_rows || (a.ov_L > 0 && a.ov_row0 >= 0 && a.ov_n >= 0 && a.ov_row0 + a.ov_n <= a.ov_L),
+              "ln_fwd: bad splice rows %d..+%d of %d", a.ov_row0, a.ov_n, a.ov_L);
+    // out / mean / rstd are indexed by r, x / add / xout by row_index[r] and the splice by r % ov_L: they agree under the identity map only
+    ARG_CHECK(!a.row_index || !(a.add || a.add_lp || a.xout || a.ov_rows), "ln_fwd: the fused add / splice / xout need the identity row map");
+    ARG_CHECK(!a.out_lo || (!a.out_f32 && (a.lo_mode == LO_F16 || a.lo_mode == LO_F8)), "ln_fwd: out_lo needs a T output and lo_mode 1 / 2");
     const dim3 grid((a.rows + 3) / 4), block(256);
     if (dtype == DT_BF16) {
         if (a.out_f32) MUDPT_LAUNCH((ln_fwd_kernel<BF16, true>), grid, block, 0, s, prof, a);
@@ -176,6 +183,11 @@ int launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s, const LaunchProf
     ARG_CHECK(!a.side || (!a.row_index && a.side_L > 0 && a.side_n > 0), "ln_bwd: the fused splice backward needs the identity row map");
     ARG_CHECK(a.rows > 0 && a.d > 0 && a.d % 4 == 0 && a.d <= 256 * LN_MAXV, "ln_bwd: bad shape rows=%d d=%d", a.rows, a.d);
     ARG_CHECK(a.ldx % 4 == 0 && a.lddy % 4 == 0 && a.lddx % 4 == 0, "ln_bwd: strides must be multiples of 4");
+    ARG_CHECK(a.ldx >= a.d && a.lddy >= a.d && (!a.dx || a.lddx >= a.d), "ln_bwd: a row stride is shorter than d=%d (%d/%d/%d)", a.d, a.ldx, a.lddy, a.lddx);
+    ARG_CHECK(!(a.dres || a.dres_lp) || (a.lddres % 4 == 0 && a.lddres >= a.d), "ln_bwd: bad dres stride %d", a.lddres);
+    ARG_CHECK(!a.dx_lp || (a.lddx_lp % 4 == 0 && a.lddx_lp >= a.d), "ln_bwd: bad dx_lp stride %d", a.lddx_lp);
+    ARG_CHECK(!a.side || (a.side_row0 >= 0 && a.side_row0 + a.side_n <= a.side_L && a.side_ldb % 4 == 0 && a.side_ldb >= (size_t)a.side_n * a.d),
+              "ln_bwd: bad splice rows %d..+%d of %d / side stride %zu", a.side_row0, a.side_n, a.side_L, a.side_ldb);
     const dim3 grid((a.rows + 3) / 4), block(256);
     if (dtype == DT_BF16) {
         if (a.dy_f32) MUDPT_LAUNCH((ln_bwd_kernel<BF16, true>), grid, block, 0, s, prof, a);

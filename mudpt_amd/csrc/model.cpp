@@ -2105,7 +2105,6 @@ extern "C" int mudpt_attention_fwd(int32_t dtype, const void* qkv, void* out, fl
 }
 extern "C" int mudpt_attention_fwd_exact(const float* qkv32, void* qkv_lp, void* out_hi, void* out_lo, int32_t lo_mode, int32_t ld_out, float* lse, int32_t B, int32_t L,
                                          int32_t H, int32_t causal, void* stream) {
-    ARG_CHECK(!out_lo || lo_mode == LO_F16 || lo_mode == LO_F8, "attention_fwd_exact: lo_mode must be 1 (fp16) or 2 (e4m3)");
     AttnArgs a; a.qkv32 = qkv32; a.qkv_lp = qkv_lp; a.out = out_hi; a.out_lo = out_lo; a.lo_mode = out_lo ? lo_mode : (int)LO_F16; a.ld_out = ld_out; a.lse = lse; a.B = B; a.L = L; a.H = H; a.causal = causal != 0;
     return launch_attn_fwd_exact(a, (hipStream_t)stream);
 }
@@ -2115,4 +2114,120 @@ extern "C" int mudpt_attention_bwd(int32_t dtype, const void* qkv, const void* o
     a.causal = (causal & 1) != 0; a.two_kernels = (causal & 2) != 0; a.fused_w1 = (causal & 4) != 0; a.force_fused = (causal & 12) != 0; a.sweep = (causal & 16) != 0;
     a.win_n = (causal >> 20) & 0xff; a.win_row0 = (causal >> 8) & 0xfff;  // bits 8-19: first wanted row, bits 20-27: number of wanted rows (0 = all)
     return launch_attn_bwd(dtype, a, (hipStream_t)stream);
+}
+// ---- the launchers' production forms, one thin argument-packing export each (tests/test_kernels_gpu.py, tests/test_movers_gpu.py) ----
+extern "C" int mudpt_layernorm_bwd_ex(int32_t dtype, const void* dy, int32_t lddy, int32_t dy_f32, const float* x, int32_t ldx, const int32_t* row_index,
+                                      const float* mean, const float* rstd, const float* gamma, const float* dres, const void* dres_lp, int32_t lddres,
+                                      float* dx, int32_t lddx, void* dx_lp, int32_t lddx_lp, float* side, int32_t side_row0, int32_t side_n, int32_t side_L,
+                                      size_t side_ldb, int32_t index_mode, int32_t rows, int32_t d, void* stream) {
+    ARG_CHECK(index_mode >= 0 && index_mode <= 2, "layernorm_bwd_ex: index_mode must be 0 (compact), 1 (by_token) or 2 (stats_by_token)");
+    LnBwdArgs a; a.dy = dy; a.lddy = lddy; a.dy_f32 = dy_f32 != 0; a.x = x; a.ldx = ldx; a.row_index = row_index; a.mean = mean; a.rstd = rstd; a.gamma = gamma;
+    a.dres = dres; a.dres_lp = dres_lp; a.lddres = lddres; a.dx = dx; a.lddx = lddx; a.dx_lp = dx_lp; a.lddx_lp = lddx_lp; a.rows = rows; a.d = d;
+    a.by_token = index_mode == 1; a.stats_by_token = index_mode == 2;
+    if (side) { a.side = side; a.side_row0 = side_row0; a.side_n = side_n; a.side_L = side_L; a.side_ldb = side_ldb; }
+    return launch_ln_bwd(dtype, a, (hipStream_t)stream);
+}
+extern "C" int mudpt_layernorm_fwd_ex(int32_t dtype, const float* x, int32_t ldx, const int32_t* row_index, const float* add, const void* add_lp, int32_t ldadd,
+                                      const float* ov_rows, int32_t ov_row0, int32_t ov_n, int32_t ov_L, float* xout, int32_t ldxout, const float* gamma,
+                                      const float* beta, void* out, void* out_lo, int32_t lo_mode, int32_t ldo, int32_t out_f32, float* mean, float* rstd,
+                                      int32_t rows, int32_t d, void* stream) {
+    LnFwdArgs a; a.x = x; a.ldx = ldx; a.row_index = row_index; a.add = add; a.add_lp = add_lp; a.ldadd = ldadd; a.xout = xout; a.ldxout = ldxout;
+    a.gamma = gamma; a.beta = beta; a.out = out; a.out_lo = out_lo; a.lo_mode = lo_mode; a.ldo = ldo; a.out_f32 = out_f32 != 0; a.mean = mean; a.rstd = rstd;
+    a.rows = rows; a.d = d;
+    if (ov_rows) { a.ov_rows = ov_rows; a.ov_row0 = ov_row0; a.ov_n = ov_n; a.ov_L = ov_L; }
+    return launch_ln_fwd(dtype, a, (hipStream_t)stream);
+}
+extern "C" int mudpt_attention_fwd_split(int32_t dtype, const void* qkv, void* out, void* out_lo, int32_t lo_mode, int32_t ld_out, float* lse, int32_t B, int32_t L,
+                                         int32_t H, int32_t causal, void* stream) {
+    AttnArgs a; a.qkv = qkv; a.out = out; a.out_lo = out_lo; a.lo_mode = lo_mode; a.ld_out = ld_out; a.lse = lse; a.B = B; a.L = L; a.H = H;
+    a.causal = (causal & 1) != 0; a.tiled_fwd_16 = (causal & 2) != 0;
+    return launch_attn_fwd(dtype, a, (hipStream_t)stream);
+}
+extern "C" int mudpt_attention_fwd_single_split(int32_t dtype, const void* qkv, const void* q_sel, const int32_t* sel_rows, void* out_sel, void* out_lo,
+                                                int32_t lo_mode, int32_t ld_out, float* lse_sel, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream) {
+    AttnArgs a; a.qkv = qkv; a.sel_rows = sel_rows; a.lo_mode = lo_mode; a.B = B; a.L = L; a.H = H; a.causal = causal != 0;
+    return launch_attn_fwd_single(dtype, a, q_sel, out_sel, out_lo, ld_out, lse_sel, (hipStream_t)stream);
+}
+extern "C" int mudpt_attention_bwd_sel(int32_t dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                       const int32_t* sel_rows, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream) {
+    ARG_CHECK(sel_rows, "attention_bwd_sel: null sel_rows");
+    AttnArgs a; a.qkv = qkv; a.out = (void*)out; a.dout = dout; a.lse = (float*)lse; a.delta = delta; a.dqkv = dqkv; a.sel_rows = sel_rows; a.B = B; a.L = L; a.H = H;
+    a.causal = (causal & 1) != 0;
+    return launch_attn_bwd(dtype, a, (hipStream_t)stream);
+}
+extern "C" int mudpt_head_ex(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
+                             int32_t e, float* txt_n, float* txt_inv, float* logits, float* loss, float* row_loss, float* dimg, float* dtxt, int32_t path,
+                             int32_t* path_taken, void* stream) {
+    ARG_CHECK(img && txt_n && txt_inv && logits && B > 0 && B_total >= 0, "head_ex: bad arguments");  // C, e: the launchers' own checks
+    ARG_CHECK(path == 0 || path == 1, "head_ex: path must be 0 (the dispatch of mudpt_head) or 1 (the unfused launchers)");
+    ARG_CHECK(!labels || (loss && dimg), "head_ex: training needs loss and dimg");
+    hipStream_t s = (hipStream_t)stream;
+    float* scratch = nullptr;
+    const size_t need = (size_t)B * e + B + (size_t)B * C + B;
+    HIP_TRY(hipMalloc((void**)&scratch, need * 4));
+    HeadArgs h; h.img = img; h.txt = txt; h.labels = labels; h.scale = scale; h.logits = logits; h.loss = loss; h.dimg = dimg; h.dtxt = dtxt;
+    h.img_n = scratch; h.img_inv = h.img_n + (size_t)B * e; h.dlogits = h.img_inv + B; h.row_loss = row_loss ? row_loss : h.dlogits + (size_t)B * C;
+    h.txt_n = txt_n; h.txt_inv = txt_inv; h.grad_scale = grad_scale; h.B = B; h.B_total = B_total; h.C = C; h.e = e;
+    const bool fused = path == 0 && head_fused_fits(h, labels != nullptr);
+    if (path_taken) *path_taken = fused ? 0 : 1;
+    int rc;
+    if (fused) rc = labels ? launch_head_fused_train(h, s) : launch_head_fused_fwd(h, s);
+    else {
+        rc = launch_head_fwd(h, s);
+        if (!rc && labels) rc = launch_head_bwd(h, s);
+    }
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    return rc;
+}
+extern "C" int mudpt_pair_head(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
+                               int32_t e, float* logits, float* loss, float* row_loss, float* dtxt, void* stream) {
+    ARG_CHECK(img && txt && logits && B > 0 && e > 0 && B_total >= 0, "pair_head: bad arguments");  // C: the launchers' own check
+    ARG_CHECK(!labels || (loss && row_loss && dtxt), "pair_head: training needs loss, row_loss and dtxt");
+    hipStream_t s = (hipStream_t)stream;
+    float* scratch = nullptr;
+    const size_t BC = (size_t)B * C, need = (size_t)B * e + B + BC * e + BC + BC;
+    HIP_TRY(hipMalloc((void**)&scratch, need * 4));
+    HeadArgs h; h.img = img; h.txt = txt; h.labels = labels; h.scale = scale; h.logits = logits; h.loss = loss; h.dtxt = dtxt; h.row_loss = row_loss;
+    h.img_n = scratch; h.img_inv = h.img_n + (size_t)B * e; h.txt_n = h.img_inv + B; h.txt_inv = h.txt_n + BC * e; h.dlogits = h.txt_inv + BC;
+    h.grad_scale = grad_scale; h.B = B; h.B_total = B_total > 0 ? B_total : B; h.C = C; h.e = e;  // as the CoCoOp step: the mean follows the chunks
+    int rc = launch_l2norm(img, h.img_n, h.img_inv, B, e, s);
+    if (!rc) rc = launch_pair_head_fwd(h, s);
+    if (!rc && labels) rc = launch_pair_head_bwd(h, s);
+    if (!rc && labels && B_total == 0) rc = launch_mean(row_loss, B, loss, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    return rc;
+}
+extern "C" int mudpt_patchify(int32_t dtype, const float* images, void* patches, void* patches_lo, int32_t lo_mode, int32_t B, int32_t image_size, int32_t patch,
+                              int32_t ldk, void* stream) {
+    if (patches_lo) return launch_patchify_split(dtype, images, patches, patches_lo, lo_mode, B, image_size, patch, ldk, (hipStream_t)stream);
+    return launch_patchify(dtype, images, patches, B, image_size, patch, ldk, (hipStream_t)stream);
+}
+extern "C" int mudpt_set_rows(float* x, int32_t B, int32_t L, int32_t d, int32_t row0, int32_t n, const float* rows, const float* add, void* stream) {
+    return launch_set_rows(x, B, L, d, row0, n, rows, add, (hipStream_t)stream);
+}
+extern "C" int mudpt_gather_rows(const void* src, size_t src_stride, const int32_t* rows, void* dst, size_t dst_stride, int32_t nrows, int32_t row_bytes, void* stream) {
+    return launch_gather_rows(src, src_stride, rows, dst, dst_stride, nrows, row_bytes, (hipStream_t)stream);
+}
+extern "C" int mudpt_scatter_rows(const void* src, size_t src_stride, const int32_t* rows, void* dst, size_t dst_stride, int32_t nrows, int32_t row_bytes, void* stream) {
+    return launch_scatter_rows(src, src_stride, rows, dst, dst_stride, nrows, row_bytes, (hipStream_t)stream);
+}
+extern "C" int mudpt_add_rows(int32_t dtype, const void* src, const int32_t* rows, void* dst, int32_t nrows, int32_t d, void* stream) {
+    return launch_add_rows(dtype, src, rows, dst, nrows, d, (hipStream_t)stream);
+}
+extern "C" int mudpt_colsum(const float* A, int32_t M, int32_t N, int32_t lda, float* out, int32_t accumulate, void* stream) {
+    return launch_colsum(A, M, N, lda, out, accumulate != 0, (hipStream_t)stream);
+}
+extern "C" int mudpt_add(const float* a, const float* b, float* y, size_t n, void* stream) { return launch_add(a, b, y, n, (hipStream_t)stream); }
+extern "C" int mudpt_cast(int32_t dtype, const float* x, void* y, size_t n, void* stream) { return launch_cast(dtype, x, y, n, (hipStream_t)stream); }
+extern "C" int mudpt_relu(float* y, size_t n, void* stream) { return launch_relu(y, n, (hipStream_t)stream); }
+extern "C" int mudpt_relu_bwd(float* dy, const float* y, size_t n, void* stream) { return launch_relu_bwd(dy, y, n, (hipStream_t)stream); }
+extern "C" int mudpt_cocoop_prompts(float* x0, const float* emb_pos, const float* ctx, const float* bias, const float* pos, int32_t B, int32_t C, int32_t L,
+                                    int32_t d, int32_t n, void* stream) {
+    return launch_cocoop_prompts(x0, emb_pos, ctx, bias, pos, B, C, L, d, n, (hipStream_t)stream);
+}
+extern "C" int mudpt_coop_splice(float* x, const float* ctx, const float* tpos, const int32_t* rows, const int32_t* pos, int32_t C, int32_t n, int32_t d,
+                                 int32_t csc, void* stream) {
+    return launch_coop_splice(x, ctx, tpos, rows, pos, C, n, d, csc != 0, (hipStream_t)stream);
 }

@@ -1,5 +1,6 @@
 """Shared test helpers: rebuild a golden case (weights from the seeded recipe) for the oracle."""
 import ast
+import ctypes as C
 import os
 
 import numpy as np
@@ -70,3 +71,42 @@ def assert_training_forward_is_the_inference_forward(train_logits, eval_logits, 
         return
     d = (a - b).abs().max().item()
     assert d <= FWD_SPLIT_TOL[dtype], f"training vs inference logits differ by {d:.3e} ({dtype})"
+
+
+# ---- single-kernel tests through the C ABI (test_kernels_gpu.py, test_movers_gpu.py) ------------------------------------------------
+SENT = -1234.5  # destinations are pre-filled with it: exactly representable in fp32, bf16 and fp16
+
+
+def P(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def ok(lib, rc):
+    assert rc == 0, lib.mudpt_last_error().decode()
+    torch.cuda.synchronize()
+
+
+def refused(lib, rc, word):
+    """MUDPT_ERR_ARG with a message that holds `word`; the caller then asserts that its sentinel-filled destinations are untouched."""
+    torch.cuda.synchronize()
+    msg = lib.mudpt_last_error().decode()
+    assert rc == 1 and word in msg, (rc, msg)
+
+
+def e4m3_spacing(s):
+    """Distance between neighbouring OCP e4m3 values at magnitude |s|: 3 mantissa bits, minimum normal 2^-6, below it steps of 2^-9."""
+    a = s.abs().double().clamp_min(2.0 ** -6)
+    return torch.ldexp(torch.ones_like(a), torch.frexp(a).exponent - 1 - 3)
+
+
+PATCH_CASES = [(64, 224, 16, 768), (8, 224, 32, 3072), (16, 336, 14, 640), (5, 32, 8, 192), (3, 28, 14, 640)]  # (B, S, p, ldk) of test_patchify_plain
+PATCH_SPLIT_CASES = [(128, 224, 16, 768), (3, 336, 14, 640), (5, 32, 8, 192), (3, 28, 14, 640), (2, 224, 32, 3072)]
+
+
+def patchify_threads(form, B, S, p, ldk):
+    """Threads the launcher's grid-stride loop has to cover and the most its capped grid holds (elementwise.hip launch_patchify*)."""
+    if form == "vector":
+        return B * 3 * S * (S // 8), 4096 * 256
+    if form == "any":
+        return B * (S // p) ** 2 * ldk, 16384 * 256
+    return B * (S // p) ** 2 * (ldk // 4), 16384 * 256

@@ -78,3 +78,47 @@ def test_host_e4m3_conversion_matches_torch():
     out = torch.zeros(5, dtype=torch.uint8)
     lib.mudpt_e4m3_from_f32(C.c_void_p(big.data_ptr()), C.c_void_p(out.data_ptr()), 5, 0)
     assert out.tolist() == [0x7e, 0x7e, 0x7e, 0xfe, 0x7e]  # saturates, never the NaN code
+
+
+# Launchers that no single-kernel export calls by name, and why that is not a gap.  Keep it short: a launcher belongs here only if a
+# direct float64 test reaches it some other way.
+LAUNCHERS_WITHOUT_AN_EXPORT = {
+    "launch_gemm_pp": "a form launch_gemm dispatches to (gemm_uses_pp); mudpt_gemm reaches it at the large shapes of test_gemm_pingpong_epilogues",
+    "launch_attn_fwd_resident": "a form launch_attn_fwd dispatches to for 224 < L <= 640; mudpt_attention_fwd reaches it (ATTN_CASES, L = 581)",
+    "launch_attn_bwd_resident": "a form launch_attn_bwd dispatches to for 224 < L <= 608; mudpt_attention_bwd reaches it (ATTN_CASES, L = 581)",
+    "launch_sgd": "exported above the single-kernel section as mudpt_sgd_step, which test_model_gpu.py::test_sgd_step_matches_torch holds to torch.optim.SGD",
+}
+
+
+def test_every_launcher_is_called_from_a_test_export():
+    """Every `int launch_*` kernels.h declares must be called from one of the single-kernel exports of model.cpp (the surface the float64 parity
+    tests of tests/test_kernels_gpu.py, test_exact_gpu.py and test_movers_gpu.py drive), or stand in the allowlist above with its reason.  A new
+    launcher that only the whole-model tests reach fails here."""
+    import re
+    csrc = os.path.join(os.path.dirname(capi.HERE), "mudpt_amd", "csrc")
+    header = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "kernels.h")).read())
+    launchers = sorted(set(re.findall(r"^\s*int\s+(launch_[a-z0-9_]+)\s*\(", header, flags=re.M)))
+    assert len(launchers) >= 30, launchers
+    model = open(os.path.join(csrc, "model.cpp")).read()
+    marker = "// ---- single kernels "
+    assert model.count(marker) == 1
+    section = re.sub(r"//[^\n]*", "", model[model.index(marker):])
+    exports = re.findall(r'extern "C" int (mudpt_[a-z0-9_]+)\s*\(', section)
+    assert len(exports) >= 35 and set(exports) <= set(capi.SIGNATURES), exports
+    called = set(re.findall(r"\b(launch_[a-z0-9_]+)\s*\(", section))
+    missing = [f for f in launchers if f not in called and f not in LAUNCHERS_WITHOUT_AN_EXPORT]
+    assert not missing, f"launchers no test export calls (add an export and a float64 test, or an allowlist entry with its reason): {missing}"
+    stale = [f for f in LAUNCHERS_WITHOUT_AN_EXPORT if f not in launchers or f in called]
+    assert not stale, f"allowlist entries that are no longer needed: {stale}"
+    assert all(len(reason) > 20 for reason in LAUNCHERS_WITHOUT_AN_EXPORT.values())
+
+
+def test_patchify_cases_wrap_every_grid_stride_loop():
+    """Arithmetic only, from the launchers' formulas: among the shapes test_movers_gpu.py runs, at least one per patchify kernel has more
+    work than its capped grid holds in one pass (B = 64 vector form, B = 16 at p = 14, B = 128 split form at p = 16)."""
+    from tests.helpers import PATCH_CASES, PATCH_SPLIT_CASES, patchify_threads
+    vector = lambda p, ldk: p % 8 == 0 and ldk == 3 * p * p  # noqa: E731
+    over = lambda form, case: patchify_threads(form, *case)[0] > patchify_threads(form, *case)[1]  # noqa: E731
+    assert any(vector(c[2], c[3]) and over("vector", c) for c in PATCH_CASES)
+    assert any(not vector(c[2], c[3]) and over("any", c) for c in PATCH_CASES)
+    assert any(over("split", c) for c in PATCH_SPLIT_CASES)
