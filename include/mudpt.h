@@ -35,6 +35,17 @@
  *   mudpt_forward_backward               trainers/vpt.py:168-200, mpt.py:224-256   forward, F.cross_entropy, backward w.r.t. the prompts
  *   (VPT: the text tower has nothing to learn; its features are computed once per handle and reused until mudpt_set_weight /
  *    mudpt_set_class_prompts.  mudpt_set_class_shard, mudpt_cp_* and mudpt_set_class_token_position refuse both variants.)
+ * With MUDPT_VARIANT_UMUDPT they run the unified prompt generator's path (trainers/umudpt.py; the towers are MuDPT's, clip/model.py:304-351,556-597):
+ *   mudpt_create                         trainers/umudpt.py:83-92  TRAINER.UMUDPT.N_CTX (1..16) / DEEP_PROMPT_DEPTH (> 0) as n_ctx / depth
+ *   mudpt_set_class_prompts              trainers/umudpt.py:126-133 token_prefix / token_suffix, tokenized_prompts
+ *   mudpt_param_*                        trainers/umudpt.py:110-124,252-255  the 20 "umudpt_prompt_learner.*" tensors: ctx, deep_prompts
+ *                                        ([depth - 1, n_ctx, d_t]: listed with 0 elements at depth 1), ln_pre, self_attn.{attn, ln_1, mlp, ln_2},
+ *                                        ln_post, visual_proj, in named_parameters() order
+ *   mudpt_forward / _ex                  trainers/umudpt.py:161-178,217-230  G = visual_proj(ln_post(Block(ln_pre(cat(ctx, deep_prompts))))) in fp32;
+ *                                        G[0] = the vision tower's input prompt rows, G[1:] its deep prompts; the text tower takes ctx /
+ *                                        deep_prompts as they are.  MUDPT_FWD_REUSE_TEXT keeps G as well as the text features.
+ *   mudpt_forward_backward               trainers/umudpt.py:292-294  forward, F.cross_entropy, backward w.r.t. all 20 tensors
+ *   (mudpt_set_class_shard, mudpt_cp_* and mudpt_set_class_token_position refuse the variant.)
  *
  * Conventions: every function returns 0 on success or a MUDPT_ERR_* code; mudpt_last_error() gives
  * the message of the calling thread's last failure.  No exceptions cross the ABI.  A model handle is
@@ -80,6 +91,7 @@ extern "C" {
 #define MUDPT_VARIANT_COOP_CSC 3 /* trainers/coop.py with CSC: one context per class, [n_cls, n_ctx, t_width]; depth is ignored */
 #define MUDPT_VARIANT_VPT 4      /* trainers/vpt.py: deep vision prompts only; mudpt_create_ex, n_ctx / depth are ignored */
 #define MUDPT_VARIANT_MPT 5      /* trainers/mpt.py: independent deep prompts in each tower; mudpt_create_ex, n_ctx / depth are ignored */
+#define MUDPT_VARIANT_UMUDPT 6   /* trainers/umudpt.py: MuDPT's towers, the vision prompts GENERATED from the text prompts by a trainable block; 20 trainables */
 
 /* CoOp's TRAINER.COOP.CLASS_TOKEN_POSITION (trainers/coop.py:99-164): where the class-name tokens sit relative to the context rows */
 #define MUDPT_CLASS_TOKEN_END 0    /* [SOS, ctx, name, ".", EOT]                        (default) */
@@ -141,7 +153,7 @@ int mudpt_set_class_token_position(mudpt_model* m, int32_t position, const int32
 int mudpt_text_layout(const mudpt_model* m, int32_t* rows, int32_t* buckets, int32_t* max_len);
 
 /* The 10 trainable tensors live in ONE flat fp32 bucket (= the data-parallel all-reduce payload). */
-int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT), 5 (CoCoOp), 1 (CoOp), 1 + vision blocks (VPT) or that + 1 + text blocks (MPT) */
+int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT), 5 (CoCoOp), 1 (CoOp), 1 + vision blocks (VPT) or that + 1 + text blocks (MPT), 20 (UMuDPT) */
 size_t mudpt_param_numel(const mudpt_model* m); /* elements of the flat bucket */
 /* name = the reference's CustomCLIP state-dict key; shape has ndim entries (ndim <= 3). */
 int mudpt_param_info(const mudpt_model* m, int index, const char** name, size_t* offset, size_t* numel,
@@ -215,7 +227,8 @@ int mudpt_sgd_reset(mudpt_model* m);
  * name: "vis.x_in.<i>" / "txt.x_in.<i>" (input of block i, after the prompt splice; [seq, L, d], text L = max(eot) + 1), "vis.x_out" / "txt.x_out"
  * (output of the last block on the ONE row per sequence the model uses -- CLS / EOT token -- [seq, d]: the tail of the last
  * block runs on those rows only), "image_features", "text_features", "text_launches" (1 value: text-tower passes plus text-side head
- * launches -- normalisation of the text features, their gradient -- since the handle was created).  host_out may be NULL to query *numel. */
+ * launches -- normalisation of the text features, their gradient -- since the handle was created); UMuDPT: "umudpt.G" (the generator's output)
+ * and "umudpt.dG" (its gradient as the vision tower's backward left it), each [depth, n_ctx, v_width].  host_out may be NULL to query *numel. */
 int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch, float* host_out, size_t capacity, size_t* numel);
 
 /* Debug knobs of ONE handle, for A/B measurements in one process and for tests (tools/gemm_bench.py, bench.py flags, tests/).  Nothing is
@@ -413,6 +426,29 @@ int mudpt_cocoop_prompts(float* x0, const float* emb_pos, const float* ctx, cons
                          int32_t d, int32_t n, void* stream);
 int mudpt_coop_splice(float* x, const float* ctx, const float* tpos, const int32_t* rows, const int32_t* pos, int32_t C, int32_t n, int32_t d,
                       int32_t csc, void* stream);
+/* UMuDPT's prompt generator in fp32 (mudpt_amd/csrc/promptgen.hip), kernel by kernel:
+ *   layernorm_bwd_affine  dx = (dres +) LN'(dy) and dgamma[j] (+)= sum_r dy[r, j] xhat[r, j], dbeta[j] (+)= sum_r dy[r, j] in row order (two runs
+ *                         agree bit for bit); x / mean / rstd as mudpt_layernorm_fwd with out_f32 left them
+ *   pg_attention_fwd      softmax(q k^T / 8) v on packed qkv [N, L, 3*H*64], 1 <= L <= 16, no mask; probs [N, H, L, L] saved for the backward
+ *   pg_attention_bwd      dqkv [N, L, 3*H*64] from qkv, probs and dout [N, L, H*64];  d_model must equal H * 64
+ *   quickgelu_fwd / _bwd  y = u sigmoid(1.702 u) / du = dy QuickGELU'(u) (du may be dy) */
+int mudpt_layernorm_bwd_affine(const float* x, int32_t ldx, const float* mean, const float* rstd, const float* gamma, const float* dy, int32_t lddy,
+                               const float* dres, int32_t lddres, float* dx, int32_t lddx, float* dgamma, float* dbeta, int32_t accumulate, int32_t rows,
+                               int32_t d, void* stream);
+int mudpt_pg_attention_fwd(const float* qkv, float* out, float* probs, int32_t N, int32_t L, int32_t H, int32_t d_model, void* stream);
+int mudpt_pg_attention_bwd(const float* qkv, const float* probs, const float* dout, float* dqkv, int32_t N, int32_t L, int32_t H, int32_t d_model, void* stream);
+int mudpt_quickgelu_fwd(const float* u, float* y, size_t n, void* stream);
+int mudpt_quickgelu_bwd(const float* dy, const float* u, float* du, size_t n, void* stream);
+/* The whole generator, the code the UMuDPT model path runs.  params: its 18 tensors in one flat fp32 buffer in the order of mudpt_param_info
+ * (tensors 2 .. 19); X [depth * n_ctx, d_t] = cat(ctx, deep_prompts); G [depth * n_ctx, d_v].  workspace: fp32, at least
+ * mudpt_promptgen_workspace(...) elements; the forward leaves there what the backward reads.  The backward WRITES grads (laid out as params)
+ * and dX [depth * n_ctx, d_t].  Refused before any launch: depth < 1, n_ctx outside 1..16, d_t % 64 != 0, a short workspace. */
+size_t mudpt_promptgen_workspace(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v);
+size_t mudpt_promptgen_param_numel(int32_t d_t, int32_t d_v);
+int mudpt_promptgen_forward(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v, const float* params, const float* X, float* G, float* workspace,
+                            size_t workspace_numel, void* stream);
+int mudpt_promptgen_backward(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v, const float* params, const float* X, const float* dG, float* dX,
+                             float* grads, float* workspace, size_t workspace_numel, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("MUDPT_LIB") or os.path.join(HERE, "lib", "libmudpt_hi
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "mudpt.h")
 
 BF16, F16, F32 = 0, 1, 2  # F32: the parity mode (include/mudpt.h MUDPT_F32)
-VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARIANT_MPT = 0, 1, 2, 3, 4, 5
+VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARIANT_MPT, VARIANT_UMUDPT = 0, 1, 2, 3, 4, 5, 6
 CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = 0, 1, 2  # TRAINER.COOP.CLASS_TOKEN_POSITION "end" / "middle" / "front"
 ABI_VERSION = 7
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = range(6)
@@ -108,6 +108,15 @@ SIGNATURES = {
     "mudpt_relu_bwd": (_i32, [_vp, _vp, _sz, _vp]),
     "mudpt_cocoop_prompts": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mudpt_coop_splice": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_layernorm_bwd_affine": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "mudpt_pg_attention_fwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_pg_attention_bwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_quickgelu_fwd": (_i32, [_vp, _vp, _sz, _vp]),
+    "mudpt_quickgelu_bwd": (_i32, [_vp, _vp, _vp, _sz, _vp]),
+    "mudpt_promptgen_workspace": (_sz, [_i32, _i32, _i32, _i32]),
+    "mudpt_promptgen_param_numel": (_sz, [_i32, _i32]),
+    "mudpt_promptgen_forward": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mudpt_promptgen_backward": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -220,4 +220,47 @@ int launch_relu_bwd(float* dy, const float* y, size_t n, hipStream_t s);
 int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay,
                float dampening, bool nesterov, bool first_step, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------
+// UMuDPT's prompt generator (promptgen.hip; trainers/umudpt.py:56-76,161-178): fp32 end to end, TRAINABLE weights
+// ------------------------------------------------------------------------------------------------
+// LayerNorm backward that also produces the affine gradients: dx = (dres +) LN'(dy), dgamma[j] (+)= sum_r dy[r][j] xhat[r][j],
+// dbeta[j] (+)= sum_r dy[r][j], the row sums in row order (no atomics).  The forward is launch_ln_fwd with out_f32.
+struct LnBwdAffineArgs {
+    const float* x = nullptr; int ldx = 0;   // LN input rows
+    const float* mean = nullptr; const float* rstd = nullptr; const float* gamma = nullptr;  // saved statistics [rows], gamma [d]
+    const float* dy = nullptr; int lddy = 0;
+    const float* dres = nullptr; int lddres = 0;  // optional residual gradient added to dx
+    float* dx = nullptr; int lddx = 0;
+    float* dgamma = nullptr; float* dbeta = nullptr; bool accumulate = false;  // accumulate: += instead of = (as launch_colsum)
+    int rows = 0, d = 0;
+};
+int launch_ln_bwd_affine(const LnBwdAffineArgs& a, hipStream_t s);
+// fp32 attention on packed qkv [N, L, 3*H*64] (the layout of AttnArgs), 1 <= L <= 16, no mask, q scaled by 1/8; d_model must be H * 64.
+// The forward saves the probabilities [N, H, L, L]; the backward reads them and writes dqkv [N, L, 3*H*64].
+int launch_pg_attn_fwd(const float* qkv, float* out, float* probs, int N, int L, int H, int d_model, hipStream_t s);
+int launch_pg_attn_bwd(const float* qkv, const float* probs, const float* dout, float* dqkv, int N, int L, int H, int d_model, hipStream_t s);
+// y = u sigmoid(1.702 u); du = dy QuickGELU'(u), recomputed from u (du may be dy)
+int launch_quickgelu_fwd(const float* u, float* y, size_t n, hipStream_t s);
+int launch_quickgelu_bwd(const float* dy, const float* u, float* du, size_t n, hipStream_t s);
+// The generator's 18 tensors in ONE flat fp32 buffer, in the reference's named_parameters() order (the bucket's tensors 2 .. 19)
+enum PgTensor : int { PG_LN_PRE_G = 0, PG_LN_PRE_B, PG_W_IN, PG_B_IN, PG_W_OUT, PG_B_OUT, PG_LN1_G, PG_LN1_B, PG_W_FC, PG_B_FC, PG_W_PROJ, PG_B_PROJ,
+                      PG_LN2_G, PG_LN2_B, PG_LN_POST_G, PG_LN_POST_B, PG_W_VIS, PG_B_VIS, PG_TENSORS };
+struct PgParams {
+    const float* base = nullptr;
+    size_t off[PG_TENSORS] = {}, total = 0;
+    const float* at(int i) const { return base + off[i]; }
+};
+PgParams pg_params(const float* base, int d_t, int d_v);
+// activations the backward needs + the backward's scratch, carved from one fp32 buffer of *numel elements (ws null: sizes only)
+struct PgWork {
+    float *h0 = nullptr, *a1 = nullptr, *qkv = nullptr, *attn = nullptr, *o = nullptr, *y = nullptr, *a2 = nullptr, *u = nullptr, *g = nullptr, *p = nullptr,
+          *z = nullptr, *a3 = nullptr, *probs = nullptr, *mean[4] = {}, *rstd[4] = {};
+    float *da3 = nullptr, *dz = nullptr, *dg = nullptr, *da2 = nullptr, *dy = nullptr, *dattn = nullptr, *dqkv = nullptr, *da1 = nullptr, *dh0 = nullptr;
+};
+PgWork pg_carve(float* ws, int depth, int n_ctx, int d_t, size_t* numel);
+int pg_check_shape(const char* what, int depth, int n_ctx, int d_t, int d_v);
+// G [depth * n_ctx, d_v] from X [depth * n_ctx, d_t]; the backward WRITES the 18 gradients (laid out as the parameters) and dX
+int pg_forward(int depth, int n_ctx, int d_t, int d_v, const PgParams& P, const float* X, float* G, const PgWork& w, hipStream_t s);
+int pg_backward(int depth, int n_ctx, int d_t, int d_v, const PgParams& P, const float* X, const float* dG, float* dX, float* grads, const PgWork& w, hipStream_t s);
+
 }  // namespace mudpt

@@ -222,6 +222,14 @@ struct mudpt_model {
     size_t t_ctx_off = 0, t_deep_off = 0, v_ctx_off = 0, v_deep_off = 0;
     std::vector<std::string> pnames;  // the reference's keys (named_parameters() order)
     std::vector<int64_t> prows, pcols;
+    // UMuDPT variant (trainers/umudpt.py): MuDPT's towers; the bucket holds ctx, deep_prompts and the 18 tensors of the prompt generator
+    // (promptgen.hip).  X = cat(ctx, deep_prompts) is the bucket's first depth * n_ctx rows as they lie; G = generator(X) [depth, n, dv] feeds the
+    // vision tower (row group 0: the input prompt rows, 1..: the deep prompts), pg_dG collects its gradient from the vision tower's backward
+    bool umudpt = false;
+    float *pg_G = nullptr, *pg_dG = nullptr, *pg_dX = nullptr, *pg_ws = nullptr;
+    PgWork pg_w;
+    std::vector<int> pnd;  // ... ndim and shape of its 20 tensors (pnames holds the keys)
+    std::vector<int64_t> pshape;
     long text_launches = 0;  // text-tower passes + text-side head launches (mudpt_debug_read "text_launches")
     float *mn_hid = nullptr, *mn_bias = nullptr, *mn_dbias = nullptr, *mn_dhid = nullptr;  // [B, hid], [B, dt], [B, dt], [B, hid]
     float loss_scale = 128.f;  // static, power of two; see mudpt_forward_backward
@@ -380,6 +388,13 @@ static const char* kCocoopNames[5] = {
 enum { Q_CTX = 0, Q_W1, Q_B1, Q_W2, Q_B2 };
 // CoOp: the one trainable under CustomCLIP (trainers/coop.py:74,206; only prompt_learner is registered, :255-259)
 static const char* kCoopName = "prompt_learner.ctx";
+// UMuDPT: ctx, deep_prompts, then the generator's 18 tensors (kernels.h PgTensor) in named_parameters() order (trainers/umudpt.py:110-124)
+static const char* kUmudptNames[20] = {
+    "ctx", "deep_prompts", "ln_pre.weight", "ln_pre.bias", "self_attn.attn.in_proj_weight", "self_attn.attn.in_proj_bias",
+    "self_attn.attn.out_proj.weight", "self_attn.attn.out_proj.bias", "self_attn.ln_1.weight", "self_attn.ln_1.bias",
+    "self_attn.mlp.c_fc.weight", "self_attn.mlp.c_fc.bias", "self_attn.mlp.c_proj.weight", "self_attn.mlp.c_proj.bias",
+    "self_attn.ln_2.weight", "self_attn.ln_2.bias", "ln_post.weight", "ln_post.bias", "visual_proj.weight", "visual_proj.bias",
+};
 
 
 static int dev_alloc(mudpt_model* m, void** out, size_t bytes) {
@@ -480,10 +495,11 @@ extern "C" const char* mudpt_last_error(void) { return get_error(); }
 
 static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out) {
     ARG_CHECK(c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F16 || c->dtype == MUDPT_F32, "create: dtype must be MUDPT_BF16, MUDPT_F16 or MUDPT_F32");
-    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_MPT, "create: unknown variant %d", c->variant);
+    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_UMUDPT, "create: unknown variant %d", c->variant);
     const bool cocoop = c->variant == MUDPT_VARIANT_COCOOP;
     const bool coop = c->variant == MUDPT_VARIANT_COOP || c->variant == MUDPT_VARIANT_COOP_CSC;
     const bool vpt = c->variant == MUDPT_VARIANT_VPT, mpt = c->variant == MUDPT_VARIANT_MPT, indep = vpt || mpt;
+    const bool umudpt = c->variant == MUDPT_VARIANT_UMUDPT;
     const bool vanilla = cocoop || coop;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
     ARG_CHECK(vanilla || indep || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
     ARG_CHECK((indep || c->n_ctx > 0) && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
@@ -492,6 +508,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     ARG_CHECK(c->v_width % 64 == 0 && c->t_width % 64 == 0 && c->v_width <= 1024 && c->t_width <= 1024, "create: widths must be multiples of 64, <= 1024");
     ARG_CHECK(c->embed_dim == c->t_width, "create: embed_dim must equal t_width (visual_ctx_deep_projections output is added to text prompts)");
     ARG_CHECK(indep || 1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
+    if (umudpt) { if (int r = pg_check_shape("create (UMuDPT)", c->depth, c->n_ctx, c->t_width, c->v_width)) return r; }
     // prompt rows and deep-prompt layers per tower (Tower::n, Tower::D1)
     int nv = vanilla ? 0 : c->n_ctx, D1v = vanilla ? 0 : c->depth - 1, nt = c->n_ctx, D1t = vanilla ? 0 : c->depth - 1;
     if (indep) {
@@ -540,6 +557,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     m->coop = coop;
     m->csc = c->variant == MUDPT_VARIANT_COOP_CSC;
     m->vpt = vpt; m->mpt = mpt; m->indep = indep;
+    m->umudpt = umudpt;
     m->ct = c->n_cls;
     if (vanilla || indep) m->cfg.depth = 1;  // no MuDPT deep prompts
     if (indep) m->cfg.n_ctx = nt;            // the text prompt rows (mudpt_set_class_prompts)
@@ -584,6 +602,13 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
             ALLOC(m->mn_bias, (size_t)B * dt * 4); ALLOC(m->mn_dbias, (size_t)B * dt * 4);
         }
         if (coop) ALLOC(m->coop_pos, (size_t)C * n * 4);
+        if (umudpt) {
+            const size_t R = (size_t)c->depth * n;
+            size_t ws = 0;
+            (void)pg_carve(nullptr, c->depth, n, dt, &ws);
+            ALLOC(m->pg_G, R * dv * 4); ALLOC(m->pg_dG, R * dv * 4); ALLOC(m->pg_dX, R * dt * 4); ALLOC(m->pg_ws, ws * 4);
+            m->pg_w = pg_carve(m->pg_ws, c->depth, n, dt, nullptr);
+        }
         ALLOC(m->gemm_scratch, mudpt_model::kScratchElems * 4); ALLOC(m->gemm_scratch2, mudpt_model::kScratchElems * 4);
         HIP_TRY(hipStreamCreateWithFlags(&m->s2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&m->ev_fork, &m->ev_join, &m->ev_fork_b, &m->ev_join_b}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -628,13 +653,28 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
         m->v_ctx_off = mpt ? (size_t)(1 + D1t) * nt * dt : 0;
         m->v_deep_off = m->v_ctx_off + (size_t)nv * dv;
     }
-    m->nparams = cocoop ? 5 : coop ? 1 : indep ? (int)m->pnames.size() : 10;
+    if (umudpt) {  // trainers/umudpt.py:110-124: ctx, deep_prompts ([0, n, dt] at depth 1: no elements, still listed), then the generator
+        const int64_t D = dt, V = dv;
+        const int64_t shp[20][3] = {{n, D, 0}, {D1, n, D}, {D, 0, 0}, {D, 0, 0}, {3 * D, D, 0}, {3 * D, 0, 0}, {D, D, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0},
+                                    {4 * D, D, 0}, {4 * D, 0, 0}, {D, 4 * D, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0}, {V, D, 0}, {V, 0, 0}};
+        const int nd[20] = {2, 3, 1, 1, 2, 1, 2, 1, 1, 1, 2, 1, 2, 1, 1, 1, 1, 1, 2, 1};
+        for (int i = 0; i < 20; ++i) {
+            m->pnames.push_back(std::string("umudpt_prompt_learner.") + kUmudptNames[i]);
+            m->pnd.push_back(nd[i]);
+            for (int k = 0; k < 3; ++k) m->pshape.push_back(shp[i][k]);
+        }
+    }
+    m->nparams = cocoop ? 5 : coop ? 1 : indep ? (int)m->pnames.size() : umudpt ? 20 : 10;
     m->off.assign(std::max(m->nparams, 1), 0);
     m->numel.assign(std::max(m->nparams, 1), 0);
     size_t o = 0;
     for (int i = 0; i < m->nparams; ++i) {
         m->off[i] = o;
         m->numel[i] = cocoop ? cshapes[i] : coop ? coop_numel : indep ? (size_t)(m->prows[i] * m->pcols[i]) : shapes[i];
+        if (umudpt) {
+            m->numel[i] = 1;
+            for (int k = 0; k < m->pnd[i]; ++k) m->numel[i] *= (size_t)m->pshape[3 * i + k];
+        }
         o += m->numel[i];
     }
     m->total = o;
@@ -996,6 +1036,14 @@ extern "C" int mudpt_param_info(const mudpt_model* m, int i, const char** name, 
         if (shape) { shape[0] = m->prows[i]; shape[1] = m->pcols[i]; shape[2] = 0; }
         return MUDPT_OK;
     }
+    if (m->umudpt) {  // trainers/umudpt.py:110-124
+        if (name) *name = m->pnames[i].c_str();
+        if (offset) *offset = m->off[i];
+        if (numel) *numel = m->numel[i];
+        if (ndim) *ndim = m->pnd[i];
+        if (shape) for (int k = 0; k < 3; ++k) shape[k] = m->pshape[3 * i + k];
+        return MUDPT_OK;
+    }
     if (m->coop) {  // trainers/coop.py:60-76
         if (name) *name = kCoopName;
         if (offset) *offset = m->off[0];
@@ -1323,7 +1371,8 @@ static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_
     const int P = (c.image_size / c.patch) * (c.image_size / c.patch), Lv = m->vis.L, K0 = (3 * c.patch * c.patch + 63) / 64 * 64;
     float* Pm = m->params;
     // VPT / MPT: block i's rows are its own visual_ctx in the bucket; MuDPT: the prompt learner's projections (prompt_learner_forward)
-    const float* deep = m->indep ? Pm + m->v_deep_off : m->vis_deep;
+    // UMuDPT: the generator's output, row groups 1 .. (clip/model.py:556-597)
+    const float* deep = m->indep ? Pm + m->v_deep_off : m->umudpt ? m->pg_G + (size_t)n * dv : m->vis_deep;
     const int m_patch = site_mode(m->vis, SITE_PATCH, K0);  // parity mode: split pixels (an fp16 pixel alone carries 2.4e-4 of rounding into block 0)
     if (m_patch != LO_NONE) TRY(launch_patchify_split(m->dtype, images, m->patches, m->patches_lo, m_patch, B, c.image_size, c.patch, K0, s));
     else TRY(launch_patchify(m->dtype, images, m->patches, B, c.image_size, c.patch, K0, s));
@@ -1333,7 +1382,9 @@ static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_
     TRY(gemm_call(m, EPI_PATCH, pe, s));
     TRY(launch_set_rows(m->xpre, B, Lv, dv, 0, 1, m->cls, m->vpos, s));
     // prompt rows after the positional embedding, before ln_pre: MuDPT visual_ctx + shared (clip/model.py:534), VPT / MPT visual_ctx (:463-465)
-    if (n > 0) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, Pm + (m->indep ? m->v_ctx_off : m->off[P_VCTX]), m->indep ? nullptr : m->shared, s));
+    // UMuDPT: G[0] alone, the tower has no visual_ctx of its own (clip/model.py:573-576)
+    if (m->umudpt) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, m->pg_G, nullptr, s));
+    else if (n > 0) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, Pm + (m->indep ? m->v_ctx_off : m->off[P_VCTX]), m->indep ? nullptr : m->shared, s));
     LnFwdArgs lp; lp.x = m->xpre; lp.ldx = dv; lp.gamma = m->ln_pre_g; lp.beta = m->ln_pre_b; lp.out = m->vis.a[0].x_in; lp.ldo = dv; lp.out_f32 = true;
     lp.mean = m->pre_mean; lp.rstd = m->pre_rstd; lp.rows = B * Lv; lp.d = dv;
     TRY(launch_ln_fwd(m->dtype, lp, s));
@@ -1450,6 +1501,8 @@ static int prompt_learner_forward(mudpt_model* m, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, dt = c.t_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1;
     float* Pm = m->params;
+    if (m->umudpt)  // trainers/umudpt.py:170-176: the vision prompts of every layer from the text prompts of every layer
+        return pg_forward(c.depth, n, dt, dv, pg_params(Pm + m->off[2], dt, dv), Pm + m->off[P_CTX], m->pg_G, m->pg_w, s);
     TRY(launch_sgemm(false, true, n, dv, dt, 1.f, Pm + m->off[P_CTX], dt, Pm + m->off[P_EW], dt, 0.f, m->shared, dv, Pm + m->off[P_EB], s));
     if (D1 > 0) {
         TRY(launch_sgemm(false, true, D1 * n, dv, dt, 1.f, Pm + m->off[P_DEEP], dt, Pm + m->off[P_DW], dt, 0.f, m->t2v, dv, Pm + m->off[P_DB], s));
@@ -1467,7 +1520,8 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
     float* Pm = m->params;
     const std::vector<Tower::Seg> segs = tower_segs(m->txt, Ct);
     const bool packed = segs.size() > 1;
-    const float* deep = m->indep ? Pm + m->t_deep_off : m->txt_deep;  // MPT: the text blocks' own visual_ctx in the bucket
+    // MPT: the text blocks' own visual_ctx in the bucket; UMuDPT: deep_prompts as they are (trainers/umudpt.py:178,222)
+    const float* deep = m->indep ? Pm + m->t_deep_off : m->umudpt ? Pm + m->off[P_DEEP] : m->txt_deep;
     ++m->text_launches;
     HIP_TRY(hipMemcpyAsync(m->txt.a[0].x_in, m->emb_pos, (size_t)tower_rows(m->txt, Ct) * dt * 4, hipMemcpyDeviceToDevice, s2));
     if (m->coop)  // trainers/coop.py:166-175,187-188: the context rows at every class's own positions, all buckets in one launch
@@ -1495,12 +1549,15 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
 // parameters: the reference recomputes the text tower for every test batch, trainers/mudpt.py:170-184) the text
 // features of the previous call are kept.
 static int towers_forward(mudpt_model* m, const float* images, int B, hipStream_t s, bool reuse_text) {
-    TRY(prompt_learner_forward(m, s));
+    // UMuDPT: the text tower reads no generator output, so it forks before the generator is enqueued, and only the vision tower's prompt
+    // splice (behind the generator on s) waits for G; with reuse_text G is kept like the text features (same parameters, same G)
+    if (!m->umudpt) TRY(prompt_learner_forward(m, s));
     if (!reuse_text) {
         HIP_TRY(hipEventRecord(m->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork, 0));
         TRY(text_forward(m, m->s2));
         HIP_TRY(hipEventRecord(m->ev_join, m->s2));
+        if (m->umudpt) TRY(prompt_learner_forward(m, s));
     }
     TRY(vision_forward(m, images, B, s));  // clip/model.py:526-553
     if (!reuse_text) HIP_TRY(hipStreamWaitEvent(s, m->ev_join, 0));
@@ -1587,7 +1644,7 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
     const int dt = c.t_width, e = c.embed_dim, n = m->txt.n, D1 = m->txt.D1, Ct = m->ct;
     float* G = m->grads;
     Tower& X = m->txt;
-    float* d_deep = m->indep ? G + m->t_deep_off : m->d_txt_deep;  // MPT: straight into the gradient bucket
+    float* d_deep = m->indep ? G + m->t_deep_off : m->umudpt ? G + m->off[P_DEEP] : m->d_txt_deep;  // MPT / UMuDPT: straight into the gradient bucket
     ++m->text_launches;
     const std::vector<Tower::Seg> segs = tower_segs(X, Ct);
     const float* dfeat = m->dtxt + (size_t)m->c0 * e;
@@ -1622,8 +1679,9 @@ static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) 
     const int Lv = m->vis.L;
     Tower& V = m->vis;
     // VPT / MPT: the blocks' and the input prompt's gradients go straight into the gradient bucket (MuDPT: into the prompt learner's backward)
-    float* d_deep = m->indep ? m->grads + m->v_deep_off : m->d_vis_deep;
-    float* d_p0 = m->indep ? m->grads + m->v_ctx_off : m->d_vprompt0;
+    // UMuDPT: into dG, row group 0 the input prompt rows' gradient, 1 .. the deep prompts' (the generator's backward reads it)
+    float* d_deep = m->indep ? m->grads + m->v_deep_off : m->umudpt ? m->pg_dG + (size_t)n * dv : m->d_vis_deep;
+    float* d_p0 = m->indep ? m->grads + m->v_ctx_off : m->umudpt ? m->pg_dG : m->d_vprompt0;
     TRY(launch_sgemm(false, true, B, dv, e, 1.f, m->dimg, e, m->vproj, e, 0.f, m->df_ln, dv, nullptr, s));
     LnBwdArgs bq; bq.dy = m->df_ln; bq.lddy = dv; bq.dy_f32 = true; bq.x = V.xout_sel; bq.ldx = dv; bq.mean = m->post_mean; bq.rstd = m->post_rstd;
     bq.gamma = m->ln_post_g; bq.dx = m->lp_grad ? nullptr : V.dsel; bq.lddx = dv; bq.dx_lp = V.dsel_lp; bq.lddx_lp = dv; bq.rows = B; bq.d = dv;
@@ -1703,6 +1761,20 @@ static int prompt_learner_backward(mudpt_model* m, hipStream_t s) {  // both hal
     return prompt_learner_backward_vision(m, s);
 }
 
+// UMuDPT: the generator's backward, behind the vision tower's (which leaves dG) and the join with the text stream.  The text tower's backward
+// has by then added d_txt_deep into grad(deep_prompts) and the text-input gradient of rows 1..n into grad(ctx), both from zero; dX is the
+// second and last term of either tensor, so the sums are bit-identical to any other order of the two (the argument above).
+static int umudpt_backward(mudpt_model* m, hipStream_t s) {
+    const mudpt_config& c = m->cfg;
+    const int dv = c.v_width, dt = c.t_width, n = c.n_ctx, R = c.depth * n;
+    float *Pm = m->params, *G = m->grads;
+    // layers >= depth never consume a prompt: their rows of dG get no gradient from the tower
+    const int used = (1 + (m->vis.layers - 1 < c.depth - 1 ? m->vis.layers - 1 : c.depth - 1)) * n;
+    if (used < R) HIP_TRY(hipMemsetAsync(m->pg_dG + (size_t)used * dv, 0, (size_t)(R - used) * dv * 4, s));
+    TRY(pg_backward(c.depth, n, dt, dv, pg_params(Pm + m->off[2], dt, dv), Pm + m->off[P_CTX], m->pg_dG, m->pg_dX, G + m->off[2], m->pg_w, s));
+    return launch_add(G + m->off[P_CTX], m->pg_dX, G + m->off[P_CTX], (size_t)R * dt, s);  // ctx and deep_prompts lie one behind the other
+}
+
 // VPT / MPT (trainers/vpt.py:168-200, mpt.py:224-256): forward, cross-entropy, backward straight into the gradient bucket.  VPT: the text
 // tower runs on the first step only (its features depend on no trainable), the head skips its text half, and the step is vision forward,
 // head and vision backward.  MPT: both towers' backward, concurrently as MuDPT's; with the vanilla vision tower (no vision prompt) the text
@@ -1743,11 +1815,11 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
     HIP_TRY(hipEventRecord(m->ev_fork_b, s));
     HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork_b, 0));
     TRY(text_backward(m, m->cp_unscale, m->s2));
-    TRY(prompt_learner_backward_text(m, m->s2));
+    if (!m->umudpt) TRY(prompt_learner_backward_text(m, m->s2));
     HIP_TRY(hipEventRecord(m->ev_join_b, m->s2));
     TRY(vision_backward(m, B, m->cp_unscale, s));
     HIP_TRY(hipStreamWaitEvent(s, m->ev_join_b, 0));
-    return prompt_learner_backward_vision(m, s);
+    return m->umudpt ? umudpt_backward(m, s) : prompt_learner_backward_vision(m, s);
 }
 
 // ---- class-parallel phases (SURVEY 8e second axis; the reference runs all C prompts on every replica, trainers/mudpt.py:142-156,230-233) ----
@@ -1763,6 +1835,7 @@ extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
     if (m->cocoop) { set_error("set_class_shard: CoCoOp's text features depend on the image; shard the batch instead"); return MUDPT_ERR_ARG; }
     if (m->coop) { set_error("set_class_shard: class-parallel CoOp is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
     if (m->indep) { set_error("set_class_shard: class-parallel VPT / MPT is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
+    if (m->umudpt) { set_error("set_class_shard: class-parallel UMuDPT is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
     ARG_CHECK(c0 >= 0 && c1 > c0 && c1 <= m->cfg.n_cls, "set_class_shard: [%d, %d) is not a non-empty range of the %d classes", c0, c1, m->cfg.n_cls);
     m->c0 = c0; m->ct = c1 - c0;
     m->sharded = !(c0 == 0 && c1 == m->cfg.n_cls);
@@ -1773,7 +1846,7 @@ extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
 }
 extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, size_t* numel) {
     ARG_CHECK(m && !m->cocoop, "cp_buffers: not a MuDPT model");
-    ARG_CHECK(!m->coop && !m->indep, "cp_buffers: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!m->coop && !m->indep && !m->umudpt, "cp_buffers: not a MuDPT model (the class-parallel phases run MuDPT only)");
     if (feat) *feat = m->txt_f;
     if (dfeat) *dfeat = m->dtxt;
     if (numel) *numel = (size_t)m->cfg.n_cls * m->cfg.embed_dim;
@@ -1781,7 +1854,7 @@ extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, siz
 }
 extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, int32_t flags, void* stream) {
     TRY(ready(m, B, false));
-    ARG_CHECK(!m->coop && !m->indep, "cp_forward: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!m->coop && !m->indep && !m->umudpt, "cp_forward: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(images && !m->cocoop, "cp_forward: null images / not a MuDPT model");
     const bool reuse = (flags & MUDPT_FWD_REUSE_TEXT) != 0;
     if (reuse && !m->text_valid) { set_error("cp_forward: MUDPT_FWD_REUSE_TEXT before any text-tower pass"); return MUDPT_ERR_STATE; }
@@ -1792,7 +1865,7 @@ extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, 
 }
 extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, float grad_scale, float* loss, float* logits, int32_t flags, void* stream) {
     TRY(ready(m, B, labels != nullptr));
-    ARG_CHECK(!m->coop && !m->indep, "cp_head: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!m->coop && !m->indep && !m->umudpt, "cp_head: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(!m->cocoop && (labels ? loss != nullptr : logits != nullptr), "cp_head: training needs labels and loss, inference needs logits");
     if (m->cp_stage < 1 || m->cp_B != B) { set_error("cp_head: call mudpt_cp_forward with the same batch first"); return MUDPT_ERR_STATE; }
     hipStream_t s = (hipStream_t)stream;
@@ -1808,7 +1881,7 @@ extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, f
     return MUDPT_OK;
 }
 extern "C" int mudpt_cp_backward(mudpt_model* m, int32_t part, void* stream) {
-    ARG_CHECK(!(m && (m->coop || m->indep)), "cp_backward: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    ARG_CHECK(!(m && (m->coop || m->indep || m->umudpt)), "cp_backward: not a MuDPT model (the class-parallel phases run MuDPT only)");
     ARG_CHECK(m && !m->cocoop && (part == MUDPT_CP_VISION || part == MUDPT_CP_TEXT), "cp_backward: part must be MUDPT_CP_VISION or MUDPT_CP_TEXT");
     hipStream_t s = (hipStream_t)stream;
     if (part == MUDPT_CP_VISION) {
@@ -1978,6 +2051,7 @@ extern "C" int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch,
     else if (k.rfind("txt.", 0) == 0) tower(m->txt, k.substr(4), m->ct);  // this handle's classes
     else if (k == "image_features") { src = m->img_f; n = (size_t)batch * c.embed_dim; }
     else if (k == "text_features") { src = m->txt_f; n = (size_t)c.n_cls * c.embed_dim; }
+    else if (m->umudpt && (k == "umudpt.G" || k == "umudpt.dG")) { src = k == "umudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
     else if (k == "text_launches") {  // a host counter, not a device tensor
         *numel = 1;
         if (host_out) { ARG_CHECK(capacity >= 1, "debug_read: capacity 0"); host_out[0] = (float)m->text_launches; }
@@ -2230,4 +2304,44 @@ extern "C" int mudpt_cocoop_prompts(float* x0, const float* emb_pos, const float
 extern "C" int mudpt_coop_splice(float* x, const float* ctx, const float* tpos, const int32_t* rows, const int32_t* pos, int32_t C, int32_t n, int32_t d,
                                  int32_t csc, void* stream) {
     return launch_coop_splice(x, ctx, tpos, rows, pos, C, n, d, csc != 0, (hipStream_t)stream);
+}
+// UMuDPT's prompt generator (promptgen.hip): its three kernels, and the whole block as the model path runs it
+extern "C" int mudpt_layernorm_bwd_affine(const float* x, int32_t ldx, const float* mean, const float* rstd, const float* gamma, const float* dy, int32_t lddy,
+                                          const float* dres, int32_t lddres, float* dx, int32_t lddx, float* dgamma, float* dbeta, int32_t accumulate,
+                                          int32_t rows, int32_t d, void* stream) {
+    LnBwdAffineArgs a; a.x = x; a.ldx = ldx; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.dy = dy; a.lddy = lddy; a.dres = dres; a.lddres = lddres;
+    a.dx = dx; a.lddx = lddx; a.dgamma = dgamma; a.dbeta = dbeta; a.accumulate = accumulate != 0; a.rows = rows; a.d = d;
+    return launch_ln_bwd_affine(a, (hipStream_t)stream);
+}
+extern "C" int mudpt_pg_attention_fwd(const float* qkv, float* out, float* probs, int32_t N, int32_t L, int32_t H, int32_t d_model, void* stream) {
+    return launch_pg_attn_fwd(qkv, out, probs, N, L, H, d_model, (hipStream_t)stream);
+}
+extern "C" int mudpt_pg_attention_bwd(const float* qkv, const float* probs, const float* dout, float* dqkv, int32_t N, int32_t L, int32_t H, int32_t d_model,
+                                      void* stream) {
+    return launch_pg_attn_bwd(qkv, probs, dout, dqkv, N, L, H, d_model, (hipStream_t)stream);
+}
+extern "C" int mudpt_quickgelu_fwd(const float* u, float* y, size_t n, void* stream) { return launch_quickgelu_fwd(u, y, n, (hipStream_t)stream); }
+extern "C" int mudpt_quickgelu_bwd(const float* dy, const float* u, float* du, size_t n, void* stream) { return launch_quickgelu_bwd(dy, u, du, n, (hipStream_t)stream); }
+extern "C" size_t mudpt_promptgen_workspace(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v) {
+    size_t ws = 0;
+    if (pg_check_shape("promptgen_workspace", depth, n_ctx, d_t, d_v)) return 0;
+    (void)pg_carve(nullptr, depth, n_ctx, d_t, &ws);
+    return ws;
+}
+extern "C" size_t mudpt_promptgen_param_numel(int32_t d_t, int32_t d_v) { return d_t > 0 && d_v > 0 ? pg_params(nullptr, d_t, d_v).total : 0; }
+static int promptgen_workspace_ok(const char* what, int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v, const float* ws, size_t ws_numel) {
+    if (int r = pg_check_shape(what, depth, n_ctx, d_t, d_v)) return r;
+    ARG_CHECK(ws && ws_numel >= mudpt_promptgen_workspace(depth, n_ctx, d_t, d_v), "%s: workspace of %zu elements, needs %zu", what, ws_numel,
+              mudpt_promptgen_workspace(depth, n_ctx, d_t, d_v));
+    return MUDPT_OK;
+}
+extern "C" int mudpt_promptgen_forward(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v, const float* params, const float* X, float* G, float* workspace,
+                                       size_t workspace_numel, void* stream) {
+    if (int r = promptgen_workspace_ok("promptgen_forward", depth, n_ctx, d_t, d_v, workspace, workspace_numel)) return r;
+    return pg_forward(depth, n_ctx, d_t, d_v, pg_params(params, d_t, d_v), X, G, pg_carve(workspace, depth, n_ctx, d_t, nullptr), (hipStream_t)stream);
+}
+extern "C" int mudpt_promptgen_backward(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v, const float* params, const float* X, const float* dG, float* dX,
+                                        float* grads, float* workspace, size_t workspace_numel, void* stream) {
+    if (int r = promptgen_workspace_ok("promptgen_backward", depth, n_ctx, d_t, d_v, workspace, workspace_numel)) return r;
+    return pg_backward(depth, n_ctx, d_t, d_v, pg_params(params, d_t, d_v), X, dG, dX, grads, pg_carve(workspace, depth, n_ctx, d_t, nullptr), (hipStream_t)stream);
 }

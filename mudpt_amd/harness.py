@@ -3,6 +3,7 @@
     python -m mudpt_amd.harness --epochs 2 --batch 4 --n-ctx 4 --depth 12 [--prec fp16|amp] [--eval-only --model-dir D]
     python -m mudpt_amd.harness --trainer CoOp --epochs 2 [--csc] [--class-token-position end|middle|front]
     python -m mudpt_amd.harness --trainer VPT|MPT --epochs 2 [--deep-text-n-ctx N --text-prompt-depth D --deep-visual-n-ctx N --visual-prompt-depth D]
+    python -m mudpt_amd.harness --trainer UMuDPT --epochs 2 [--n-ctx N --depth D]
 
 Mirrors what ``train.py`` (reference :153-173) does after config assembly: build_trainer(cfg) -> train() / test()."""
 from __future__ import annotations
@@ -11,12 +12,13 @@ import argparse
 
 import torch
 
-from . import cocoop, coop, dassl_lite, parallel, trainer, vpt  # noqa: F401  (importing trainer / cocoop / coop / vpt registers MuDPT / CoCoOp / CoOp / VPT, MPT)
+from . import cocoop, coop, dassl_lite, parallel, trainer, umudpt, vpt  # noqa: F401  (importing the plugin modules registers MuDPT / CoCoOp / CoOp / VPT, MPT / UMuDPT)
 
 
-def main(argv=None):
+def run(argv=None):
+    """Build the trainer the arguments name, then train (or, with --eval-only, load and test); returns the trainer, its outcome in ``.result``."""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--trainer", default="MuDPT", choices=["MuDPT", "CoCoOp", "CoOp", "VPT", "MPT"])
+    ap.add_argument("--trainer", default="MuDPT", choices=["MuDPT", "CoCoOp", "CoOp", "VPT", "MPT", "UMuDPT"])
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--classes", type=int, default=11)
@@ -46,6 +48,7 @@ def main(argv=None):
     cfg.MODEL.BACKBONE.PATH = a.backbone_path
     cfg.TRAINER.NAME = a.trainer
     cfg.TRAINER.MUDPT.N_CTX, cfg.TRAINER.MUDPT.DEEP_PROMPT_DEPTH, cfg.TRAINER.MUDPT.PREC = a.n_ctx, a.depth, a.prec
+    cfg.TRAINER.UMUDPT.N_CTX, cfg.TRAINER.UMUDPT.DEEP_PROMPT_DEPTH, cfg.TRAINER.UMUDPT.PREC = a.n_ctx, a.depth, a.prec
     cfg.TRAINER.COCOOP.PREC = a.prec
     cfg.TRAINER.COOP.N_CTX, cfg.TRAINER.COOP.PREC, cfg.TRAINER.COOP.CSC = a.n_ctx, a.prec, a.csc
     cfg.TRAINER.COOP.CLASS_TOKEN_POSITION = a.class_token_position
@@ -58,11 +61,17 @@ def main(argv=None):
     torch.manual_seed(cfg.SEED)
     t = trainer.TRAINER_REGISTRY.get(a.trainer)(cfg) if not trainer.HAVE_DASSL else None
     if t is None:
-        raise SystemExit("Dassl is installed: use the reference's train.py --trainer MuDPT / CoCoOp / CoOp / VPT / MPT (see INTEGRATION.md)")
+        raise SystemExit("Dassl is installed: use the reference's train.py --trainer MuDPT / CoCoOp / CoOp / VPT / MPT / UMuDPT (see INTEGRATION.md)")
     if a.eval_only:
         t.load_model(a.model_dir, epoch=a.load_epoch)
-        return t.test()
-    return t.train()
+        t.result = t.test()
+    else:
+        t.result = t.train()
+    return t
+
+
+def main(argv=None):
+    return run(argv).result
 
 
 if __name__ == "__main__":

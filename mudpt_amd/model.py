@@ -50,6 +50,34 @@ class ModelShape:
                           n_ctx=n_ctx, depth=depth)
 
 
+def umudpt_init_tensors(n_ctx: int, depth: int, d_t: int, d_v: int, ctx_rows: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Initial values of UMuDPT's 20 trainables, drawn as the reference draws them (trainers/umudpt.py:96-124): the same torch modules
+    constructed on the CPU in the same order -- ctx (the CTX_INIT rows, or normal_(std=0.02)), deep_prompts normal_(std=0.02), ln_pre, the
+    block's nn.MultiheadAttention, ln_1, c_fc, c_proj, ln_2, ln_post, visual_proj -- so that under one torch.manual_seed the draws equal
+    the reference's.  Keys carry no prefix ("ctx", "self_attn.attn.in_proj_weight", ...), in named_parameters() order."""
+    from collections import OrderedDict
+    if ctx_rows is None:
+        ctx = torch.empty(n_ctx, d_t)
+        nn.init.normal_(ctx, std=0.02)
+    else:
+        ctx = ctx_rows.detach().to(torch.float32).clone()
+    deep = torch.empty(depth - 1, n_ctx, d_t)
+    nn.init.normal_(deep, std=0.02)
+    ln_pre = nn.LayerNorm(d_t)
+    block = nn.Module()
+    block.attn = nn.MultiheadAttention(d_t, d_t // 64)
+    block.ln_1 = nn.LayerNorm(d_t)
+    block.mlp = nn.Sequential(OrderedDict([("c_fc", nn.Linear(d_t, d_t * 4)), ("c_proj", nn.Linear(d_t * 4, d_t))]))
+    block.ln_2 = nn.LayerNorm(d_t)
+    ln_post = nn.LayerNorm(d_t)
+    visual_proj = nn.Linear(d_t, d_v)
+    out = OrderedDict([("ctx", ctx), ("deep_prompts", deep)])
+    for prefix, mod in (("ln_pre", ln_pre), ("self_attn", block), ("ln_post", ln_post), ("visual_proj", visual_proj)):
+        for k, v in mod.named_parameters():
+            out[prefix + "." + k] = v.detach()
+    return out
+
+
 class _Holder(nn.Module):
     """Namespace module so parameters get the reference's dotted state-dict keys."""
 
@@ -79,6 +107,9 @@ class CustomCLIP(nn.Module):
         # own under the reference's key); prompt_shape = (DEEP_TEXT_N_CTX, TEXT_PROMPT_DEPTH, DEEP_VISUAL_N_CTX, VISUAL_PROMPT_DEPTH) of
         # TRAINER.VPT / TRAINER.MPT (include/mudpt.h mudpt_prompt_shape); shape.n_ctx / depth are not used.  MPT's ctx_token_ids: the
         # TEXT_CTX_INIT tokens that initialise text_prompt_learner.visual_ctx (trainers/mpt.py:55-62)
+        # "umudpt": trainers/umudpt.py's CustomCLIP (MuDPT's towers; the vision prompts of every layer are generated from ctx / deep_prompts by a
+        # trainable transformer block): 20 trainables under "umudpt_prompt_learner.*"; shape.n_ctx (1..16) / depth are TRAINER.UMUDPT.N_CTX /
+        # DEEP_PROMPT_DEPTH
         if variant == "coop_csc" and ctx_token_ids is not None:
             variant = "coop"  # trainers/coop.py:52-61: the CTX_INIT path builds one shared context whatever CSC says
         self.variant = variant
@@ -86,7 +117,8 @@ class CustomCLIP(nn.Module):
                           shape.t_layers, shape.t_heads, shape.ctx_len, shape.embed_dim, shape.n_ctx, shape.depth,
                           self.n_cls, self.max_batch, {"bf16": capi.BF16, "fp16": capi.F16, "fp32": capi.F32}[dtype],
                           {"mudpt": capi.VARIANT_MUDPT, "cocoop": capi.VARIANT_COCOOP, "coop": capi.VARIANT_COOP,
-                           "coop_csc": capi.VARIANT_COOP_CSC, "vpt": capi.VARIANT_VPT, "mpt": capi.VARIANT_MPT}[variant])
+                           "coop_csc": capi.VARIANT_COOP_CSC, "vpt": capi.VARIANT_VPT, "mpt": capi.VARIANT_MPT,
+                           "umudpt": capi.VARIANT_UMUDPT}[variant])
         assert (prompt_shape is not None) == (variant in ("vpt", "mpt")), "prompt_shape is the VPT / MPT setting, and they need it"
         self.prompt_shape = None if prompt_shape is None else tuple(int(v) for v in prompt_shape)
         torch.cuda.set_device(self.device)
@@ -160,8 +192,18 @@ class CustomCLIP(nn.Module):
 
     # -- initialisation of the trainables, trainers/mudpt.py:57-81 and clip/model.py:512-519 ---------------------
     def _init_trainables(self, emb_w, ctx_token_ids, seed):
-        g = torch.Generator().manual_seed(seed) if seed is not None else None
         sd = dict(self.named_parameters())
+        if self.variant == "umudpt":
+            s = self.shape
+            with torch.random.fork_rng(devices=[], enabled=seed is not None):  # a seed: the reference's draws under torch.manual_seed(seed)
+                if seed is not None:
+                    torch.manual_seed(seed)
+                init = umudpt_init_tensors(s.n_ctx, s.depth, s.t_width, s.v_width, None if ctx_token_ids is None else emb_w[list(ctx_token_ids)])
+            with torch.no_grad():
+                for k, v in init.items():
+                    sd["umudpt_prompt_learner." + k].copy_(v)
+            return
+        g = torch.Generator().manual_seed(seed) if seed is not None else None
         with torch.no_grad():
             for k, p in sd.items():
                 if k.endswith(".weight") or k.endswith(".bias"):
@@ -175,7 +217,8 @@ class CustomCLIP(nn.Module):
 
     @property
     def ctx_key(self) -> str:
-        return {"mudpt": "mudpt_prompt_learner.ctx", "mpt": "text_prompt_learner.visual_ctx"}.get(self.variant, "prompt_learner.ctx")
+        return {"mudpt": "mudpt_prompt_learner.ctx", "mpt": "text_prompt_learner.visual_ctx",
+                "umudpt": "umudpt_prompt_learner.ctx"}.get(self.variant, "prompt_learner.ctx")
 
     def set_knob(self, name: str, value: int):
         """``mudpt_model_set``: "gemm_variant", "lp_grad" and the split-operand knobs ("vis_lo", "txt_lo", "vis_sites", "txt_sites",
