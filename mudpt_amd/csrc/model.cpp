@@ -154,6 +154,14 @@ static std::vector<Tower::Seg> tower_segs(const Tower& t, int nseq) {
     return {one};
 }
 
+// One trainable tensor: the reference's state-dict key, its shape (ndim extents, the rest 0) and its place in the flat bucket (elements)
+struct Trainable {
+    std::string name;
+    int ndim = 0;
+    int64_t shape[3] = {0, 0, 0};
+    size_t off = 0, numel = 0;
+};
+
 }  // namespace mudpt
 
 using namespace mudpt;
@@ -196,11 +204,13 @@ struct mudpt_model {
     // parameters
     float *params = nullptr, *grads = nullptr, *momentum = nullptr;
     bool sgd_first = true;
-    std::vector<size_t> off, numel;  // per trainable tensor, elements (nparams entries)
+    // The variant's trainables in the reference's named_parameters() order (build_trainables): the layout of the flat bucket and what
+    // mudpt_param_info reports.  The one source of names, shapes and offsets (elements)
+    std::vector<Trainable> tr;
+    size_t off(int i) const { return tr[i].off; }
     size_t total = 0;
     // CoCoOp variant (trainers/cocoop.py): 5 trainables, vanilla vision tower (forward only), B * C text sequences
     bool cocoop = false;
-    int nparams = 10;
     // Class-parallel text tower (second axis): this handle encodes classes [c0, c0 + ct) of the n_cls only; the
     // [n_cls, e] text-feature table is completed by the caller's exchange between the mudpt_cp_* phases.  Default: all classes.
     int c0 = 0, ct = 0;
@@ -216,20 +226,15 @@ struct mudpt_model {
     std::vector<int> name_lens;  // [n_cls] (trainers/coop.py:80); empty = all 0 (END without lengths)
     int* coop_pos = nullptr;     // [n_cls * n_ctx] device
     // VPT / MPT variants (trainers/vpt.py, mpt.py): every spliced prompt is a trainable of its own, so block i's rows come straight from
-    // the bound bucket and their gradients go straight into the gradient bucket; no prompt-learner GEMMs.  Bucket offsets (elements) of the
-    // text ctx (MPT: text_prompt_learner.visual_ctx), the text blocks' [D1][n][dt], the vision visual_ctx and the vision blocks' [D1][n][dv]
+    // the bound bucket and their gradients go straight into the gradient bucket (prompt_route); no prompt-learner GEMMs
     bool vpt = false, mpt = false, indep = false;  // indep = vpt || mpt: independent prompts per tower
-    size_t t_ctx_off = 0, t_deep_off = 0, v_ctx_off = 0, v_deep_off = 0;
-    std::vector<std::string> pnames;  // the reference's keys (named_parameters() order)
-    std::vector<int64_t> prows, pcols;
+    int tr_txt0 = 0, tr_vis0 = 0;  // ... and the table index of each tower's first tensor (build_trainables)
     // UMuDPT variant (trainers/umudpt.py): MuDPT's towers; the bucket holds ctx, deep_prompts and the 18 tensors of the prompt generator
     // (promptgen.hip).  X = cat(ctx, deep_prompts) is the bucket's first depth * n_ctx rows as they lie; G = generator(X) [depth, n, dv] feeds the
     // vision tower (row group 0: the input prompt rows, 1..: the deep prompts), pg_dG collects its gradient from the vision tower's backward
     bool umudpt = false;
     float *pg_G = nullptr, *pg_dG = nullptr, *pg_dX = nullptr, *pg_ws = nullptr;
     PgWork pg_w;
-    std::vector<int> pnd;  // ... ndim and shape of its 20 tensors (pnames holds the keys)
-    std::vector<int64_t> pshape;
     long text_launches = 0;  // text-tower passes + text-side head launches (mudpt_debug_read "text_launches")
     float *mn_hid = nullptr, *mn_bias = nullptr, *mn_dbias = nullptr, *mn_dhid = nullptr;  // [B, hid], [B, dt], [B, dt], [B, hid]
     float loss_scale = 128.f;  // static, power of two; see mudpt_forward_backward
@@ -364,37 +369,82 @@ static int attn_call(mudpt_model* m, const Tower& t, const AttnArgs& a0, bool bw
     return bwd ? launch_attn_bwd(m->dtype, a, s, &lp) : launch_attn_fwd(m->dtype, a, s, &lp);
 }
 
-static const char* kParamNames[10] = {
-    "mudpt_prompt_learner.ctx",
-    "mudpt_prompt_learner.deep_prompts",
-    "mudpt_prompt_learner.embed_projection.weight",
-    "mudpt_prompt_learner.embed_projection.bias",
-    "mudpt_prompt_learner.deep_projections.weight",
-    "mudpt_prompt_learner.deep_projections.bias",
-    "image_encoder.visual_ctx",
-    "image_encoder.visual_ctx_deep_prompts",
-    "image_encoder.visual_ctx_deep_projections.weight",
-    "image_encoder.visual_ctx_deep_projections.bias",
-};
+// Indices into mudpt_model::tr, the table of the variant they belong to (build_trainables): P_* MuDPT (UMuDPT shares P_CTX, P_DEEP),
+// Q_* CoCoOp, U_GEN the first of the UMuDPT generator's 18 tensors (kernels.h PgTensor)
 enum { P_CTX = 0, P_DEEP, P_EW, P_EB, P_DW, P_DB, P_VCTX, P_VDEEP, P_VW, P_VB };
-// CoCoOp: names under CustomCLIP (trainers/cocoop.py:96-107,176; the reference registers the prompt_learner sub-module)
-static const char* kCocoopNames[5] = {
-    "prompt_learner.ctx",
-    "prompt_learner.meta_net.linear1.weight",
-    "prompt_learner.meta_net.linear1.bias",
-    "prompt_learner.meta_net.linear2.weight",
-    "prompt_learner.meta_net.linear2.bias",
-};
 enum { Q_CTX = 0, Q_W1, Q_B1, Q_W2, Q_B2 };
-// CoOp: the one trainable under CustomCLIP (trainers/coop.py:74,206; only prompt_learner is registered, :255-259)
-static const char* kCoopName = "prompt_learner.ctx";
-// UMuDPT: ctx, deep_prompts, then the generator's 18 tensors (kernels.h PgTensor) in named_parameters() order (trainers/umudpt.py:110-124)
-static const char* kUmudptNames[20] = {
-    "ctx", "deep_prompts", "ln_pre.weight", "ln_pre.bias", "self_attn.attn.in_proj_weight", "self_attn.attn.in_proj_bias",
-    "self_attn.attn.out_proj.weight", "self_attn.attn.out_proj.bias", "self_attn.ln_1.weight", "self_attn.ln_1.bias",
-    "self_attn.mlp.c_fc.weight", "self_attn.mlp.c_fc.bias", "self_attn.mlp.c_proj.weight", "self_attn.mlp.c_proj.bias",
-    "self_attn.ln_2.weight", "self_attn.ln_2.bias", "ln_post.weight", "ln_post.bias", "visual_proj.weight", "visual_proj.bias",
-};
+enum { U_GEN = 2 };
+
+// The variant's trainables: the reference's key and shape of every tensor, in its named_parameters() order -- the flat bucket's layout
+static void build_trainables(mudpt_model* m) {
+    const mudpt_config& c = m->cfg;
+    const int64_t n = c.n_ctx, D1 = c.depth - 1, dt = c.t_width, dv = c.v_width, e = c.embed_dim, hd = e / 16;
+    auto add = [&](const std::string& name, std::initializer_list<int64_t> shape) {
+        Trainable t;
+        t.name = name; t.ndim = (int)shape.size(); t.off = m->total; t.numel = 1;
+        std::copy(shape.begin(), shape.end(), t.shape);
+        for (int64_t x : shape) t.numel *= (size_t)x;
+        m->total += t.numel;
+        m->tr.push_back(t);
+    };
+    if (m->cocoop) {  // names under CustomCLIP (trainers/cocoop.py:96-107,176; the reference registers the prompt_learner sub-module)
+        add("prompt_learner.ctx", {n, dt});
+        add("prompt_learner.meta_net.linear1.weight", {hd, e});
+        add("prompt_learner.meta_net.linear1.bias", {hd});
+        add("prompt_learner.meta_net.linear2.weight", {dt, hd});
+        add("prompt_learner.meta_net.linear2.bias", {dt});
+    } else if (m->coop) {  // the one trainable under CustomCLIP (trainers/coop.py:60-76,206; only prompt_learner is registered, :255-259)
+        if (m->csc) add("prompt_learner.ctx", {c.n_cls, n, dt});
+        else add("prompt_learner.ctx", {n, dt});
+    } else if (m->indep) {
+        // VPT / MPT: every visual_ctx [n, width] in the reference's named_parameters() order (text_prompt_learner, text_encoder, image_encoder;
+        // clip/model.py:202-251); a tower's tensors follow one another, so its blocks' are the [D1][n][width] array the splice and the
+        // gradient reductions address
+        if (m->mpt) {
+            m->tr_txt0 = (int)m->tr.size();
+            add("text_prompt_learner.visual_ctx", {m->txt.n, dt});  // trainers/mpt.py:86
+            for (int i = 1; i <= m->txt.D1; ++i) add("text_encoder.transformer.resblocks." + std::to_string(i) + ".visual_ctx", {m->txt.n, dt});
+        }
+        if (m->vis.n > 0) {
+            m->tr_vis0 = (int)m->tr.size();
+            add("image_encoder.visual_ctx", {m->vis.n, dv});  // clip/model.py:459-465
+            for (int i = 1; i <= m->vis.D1; ++i) add("image_encoder.transformer.resblocks." + std::to_string(i) + ".visual_ctx", {m->vis.n, dv});
+        }
+    } else if (m->umudpt) {  // trainers/umudpt.py:110-124: ctx, deep_prompts ([0, n, dt] at depth 1: no elements, still listed), then the generator
+        const std::string p = "umudpt_prompt_learner.", a = p + "self_attn.";
+        add(p + "ctx", {n, dt});
+        add(p + "deep_prompts", {D1, n, dt});
+        add(p + "ln_pre.weight", {dt});
+        add(p + "ln_pre.bias", {dt});
+        add(a + "attn.in_proj_weight", {3 * dt, dt});
+        add(a + "attn.in_proj_bias", {3 * dt});
+        add(a + "attn.out_proj.weight", {dt, dt});
+        add(a + "attn.out_proj.bias", {dt});
+        add(a + "ln_1.weight", {dt});
+        add(a + "ln_1.bias", {dt});
+        add(a + "mlp.c_fc.weight", {4 * dt, dt});
+        add(a + "mlp.c_fc.bias", {4 * dt});
+        add(a + "mlp.c_proj.weight", {dt, 4 * dt});
+        add(a + "mlp.c_proj.bias", {dt});
+        add(a + "ln_2.weight", {dt});
+        add(a + "ln_2.bias", {dt});
+        add(p + "ln_post.weight", {dt});
+        add(p + "ln_post.bias", {dt});
+        add(p + "visual_proj.weight", {dv, dt});
+        add(p + "visual_proj.bias", {dv});
+    } else {  // MuDPT: trainers/mudpt.py:71-81, clip/model.py:512-519
+        add("mudpt_prompt_learner.ctx", {n, dt});
+        add("mudpt_prompt_learner.deep_prompts", {D1, n, dt});
+        add("mudpt_prompt_learner.embed_projection.weight", {dv, dt});
+        add("mudpt_prompt_learner.embed_projection.bias", {dv});
+        add("mudpt_prompt_learner.deep_projections.weight", {dv, dt});
+        add("mudpt_prompt_learner.deep_projections.bias", {dv});
+        add("image_encoder.visual_ctx", {n, dv});
+        add("image_encoder.visual_ctx_deep_prompts", {D1, n, dv});
+        add("image_encoder.visual_ctx_deep_projections.weight", {e, dv});
+        add("image_encoder.visual_ctx_deep_projections.bias", {e});
+    }
+}
 
 
 static int dev_alloc(mudpt_model* m, void** out, size_t bytes) {
@@ -493,30 +543,32 @@ static void expect_block_keys(mudpt_model* m, const std::string& prefix, int lay
 extern "C" int mudpt_abi_version(void) { return MUDPT_ABI_VERSION; }
 extern "C" const char* mudpt_last_error(void) { return get_error(); }
 
-static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out) {
+// Fills a fresh model; on an error the caller (create_model) destroys it
+static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model* m) {
     ARG_CHECK(c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F16 || c->dtype == MUDPT_F32, "create: dtype must be MUDPT_BF16, MUDPT_F16 or MUDPT_F32");
     ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_UMUDPT, "create: unknown variant %d", c->variant);
-    const bool cocoop = c->variant == MUDPT_VARIANT_COCOOP;
-    const bool coop = c->variant == MUDPT_VARIANT_COOP || c->variant == MUDPT_VARIANT_COOP_CSC;
-    const bool vpt = c->variant == MUDPT_VARIANT_VPT, mpt = c->variant == MUDPT_VARIANT_MPT, indep = vpt || mpt;
-    const bool umudpt = c->variant == MUDPT_VARIANT_UMUDPT;
-    const bool vanilla = cocoop || coop;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
-    ARG_CHECK(vanilla || indep || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
-    ARG_CHECK((indep || c->n_ctx > 0) && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
+    m->cocoop = c->variant == MUDPT_VARIANT_COCOOP;
+    m->csc = c->variant == MUDPT_VARIANT_COOP_CSC;
+    m->coop = c->variant == MUDPT_VARIANT_COOP || m->csc;
+    m->vpt = c->variant == MUDPT_VARIANT_VPT; m->mpt = c->variant == MUDPT_VARIANT_MPT; m->indep = m->vpt || m->mpt;
+    m->umudpt = c->variant == MUDPT_VARIANT_UMUDPT;
+    const bool vanilla = m->cocoop || m->coop;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
+    ARG_CHECK(vanilla || m->indep || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
+    ARG_CHECK((m->indep || c->n_ctx > 0) && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
     ARG_CHECK(c->patch > 0 && c->image_size % c->patch == 0, "create: image_size %d / patch %d unsupported", c->image_size, c->patch);
     ARG_CHECK(c->v_width == c->v_heads * 64 && c->t_width == c->t_heads * 64, "create: head dim must be 64");
     ARG_CHECK(c->v_width % 64 == 0 && c->t_width % 64 == 0 && c->v_width <= 1024 && c->t_width <= 1024, "create: widths must be multiples of 64, <= 1024");
     ARG_CHECK(c->embed_dim == c->t_width, "create: embed_dim must equal t_width (visual_ctx_deep_projections output is added to text prompts)");
-    ARG_CHECK(indep || 1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
-    if (umudpt) { if (int r = pg_check_shape("create (UMuDPT)", c->depth, c->n_ctx, c->t_width, c->v_width)) return r; }
+    ARG_CHECK(m->indep || 1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
+    if (m->umudpt) { if (int r = pg_check_shape("create (UMuDPT)", c->depth, c->n_ctx, c->t_width, c->v_width)) return r; }
     // prompt rows and deep-prompt layers per tower (Tower::n, Tower::D1)
     int nv = vanilla ? 0 : c->n_ctx, D1v = vanilla ? 0 : c->depth - 1, nt = c->n_ctx, D1t = vanilla ? 0 : c->depth - 1;
-    if (indep) {
-        const char* T = vpt ? "VPT" : "MPT";
+    if (m->indep) {
+        const char* T = m->vpt ? "VPT" : "MPT";
         ARG_CHECK(ps->t_n_ctx >= 0 && ps->v_n_ctx >= 0, "create_ex: TRAINER.%s.DEEP_TEXT_N_CTX %d / DEEP_VISUAL_N_CTX %d must be >= 0", T, ps->t_n_ctx, ps->v_n_ctx);
         // the vision prompt exists only for 0 < VISUAL_PROMPT_DEPTH <= 12, whatever the layer count (clip/model.py:459)
         const bool vprompt = ps->v_n_ctx > 0 && ps->v_depth > 0 && ps->v_depth <= 12;
-        if (vpt) {
+        if (m->vpt) {
             ARG_CHECK(vprompt, "create_ex: VPT without a vision prompt (TRAINER.VPT.DEEP_VISUAL_N_CTX %d, TRAINER.VPT.VISUAL_PROMPT_DEPTH %d: "
                       "needs > 0 and 1..12) has nothing to train", ps->v_n_ctx, ps->v_depth);
             ARG_CHECK(!(ps->t_n_ctx > 0 && ps->t_depth > 1), "create_ex: VPT with text deep prompts (TRAINER.VPT.DEEP_TEXT_N_CTX %d, "
@@ -527,14 +579,13 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
         }
         nv = vprompt ? ps->v_n_ctx : 0;
         D1v = vprompt ? std::min(ps->v_depth, c->v_layers) - 1 : 0;  // blocks 1 <= i < depth own a visual_ctx (clip/model.py:404-416)
-        nt = mpt ? ps->t_n_ctx : 0;
-        D1t = mpt ? std::max(0, std::min(ps->t_depth, c->t_layers) - 1) : 0;  // no cap on the text depth (clip/model.py:752-770)
+        nt = m->mpt ? ps->t_n_ctx : 0;
+        D1t = m->mpt ? std::max(0, std::min(ps->t_depth, c->t_layers) - 1) : 0;  // no cap on the text depth (clip/model.py:752-770)
     }
     const int P = (c->image_size / c->patch) * (c->image_size / c->patch);
     const int Lv = 1 + P + nv;  // CoCoOp's / CoOp's image encoder is the vanilla ViT (trainers/cocoop.py:38, coop.py:37, clip/model.py:443-496)
     ARG_CHECK(Lv <= 4096 && c->ctx_len <= 4096, "create: sequence length %d/%d exceeds the attention limit (4096)", Lv, c->ctx_len);
 
-    mudpt_model* m = new mudpt_model();
     m->cfg = *c;
     // MUDPT_F32 (the parity mode): the kernels' operand type is fp16.  Text tower: every forward GEMM operand a 22-bit
     // (hi, lo) pair and the attention forward in fp32 -- each of its rounding sites alone costs 2.5e-3 on the logits at logit scale 100.
@@ -553,132 +604,74 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     m->lp_grad = (c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F32);
     m->lp_upd = (c->dtype == MUDPT_BF16);
     m->gelu_q8 = (c->dtype == MUDPT_BF16);
-    m->cocoop = cocoop;
-    m->coop = coop;
-    m->csc = c->variant == MUDPT_VARIANT_COOP_CSC;
-    m->vpt = vpt; m->mpt = mpt; m->indep = indep;
-    m->umudpt = umudpt;
     m->ct = c->n_cls;
-    if (vanilla || indep) m->cfg.depth = 1;  // no MuDPT deep prompts
-    if (indep) m->cfg.n_ctx = nt;            // the text prompt rows (mudpt_set_class_prompts)
+    if (vanilla || m->indep) m->cfg.depth = 1;  // no MuDPT deep prompts
+    if (m->indep) m->cfg.n_ctx = nt;            // the text prompt rows (mudpt_set_class_prompts)
     m->vis.n = nv; m->vis.D1 = D1v; m->txt.n = nt; m->txt.D1 = D1t;
     const int dv = c->v_width, dt = c->t_width, e = c->embed_dim, n = m->cfg.n_ctx, D1 = m->cfg.depth - 1, B = c->max_batch, C = c->n_cls;
-    const int TS = cocoop ? B * C : C;  // text sequences per step: one per (image, class) pair in CoCoOp (trainers/cocoop.py:187-194)
-    auto fail = [&](int code) { mudpt_destroy(m); return code; };
-    if (int r = alloc_tower_weights(m, m->vis, dv, c->v_layers, c->v_heads, false, Lv - nv, m->exact)) return fail(r);  // e4m3 weight copies: vision tower of the parity mode
-    if (int r = alloc_tower_acts(m, m->vis, Lv, B)) return fail(r);
+    const int TS = m->cocoop ? B * C : C;  // text sequences per step: one per (image, class) pair in CoCoOp (trainers/cocoop.py:187-194)
+    if (int r = alloc_tower_weights(m, m->vis, dv, c->v_layers, c->v_heads, false, Lv - nv, m->exact)) return r;  // e4m3 weight copies: vision tower of the parity mode
+    if (int r = alloc_tower_acts(m, m->vis, Lv, B)) return r;
     // the text tower's activations are sized by mudpt_set_class_prompts: its trimmed length (max(eot) + 1 of ctx_len positions) and, for
     // CoCoOp, the number of images whose B * C prompts fit the memory budget at once are only known there
-    if (int r = alloc_tower_weights(m, m->txt, dt, c->t_layers, c->t_heads, true, 1, false)) return fail(r);
+    if (int r = alloc_tower_weights(m, m->txt, dt, c->t_layers, c->t_heads, true, 1, false)) return r;
     m->txt.L = c->ctx_len; m->txt.Lp = attn_padded_len(c->ctx_len);
-    auto body = [&]() -> int {
-        const int K0 = (3 * c->patch * c->patch + 63) / 64 * 64;  // conv-as-GEMM K, zero-padded to the GEMM's granularity (ViT-L/14: 588 -> 640)
-        ALLOC(m->conv_w, (size_t)dv * K0 * 2);
-        if (m->exact) { ALLOC(m->conv_w8, (size_t)dv * K0 * 2); ALLOC(m->patches_lo, (size_t)B * P * K0 * 2); }  // split pixels (vision tower's site 4)
-        ALLOC(m->cls, dv * 4); ALLOC(m->vpos, (size_t)(1 + P) * dv * 4);
-        ALLOC(m->ln_pre_g, dv * 4); ALLOC(m->ln_pre_b, dv * 4); ALLOC(m->ln_post_g, dv * 4); ALLOC(m->ln_post_b, dv * 4);
-        ALLOC(m->vproj, (size_t)dv * e * 4);
-        ALLOC(m->patches, (size_t)B * P * K0 * 2);
-        ALLOC(m->xpre, (size_t)B * Lv * dv * 4); ALLOC(m->pre_mean, (size_t)B * Lv * 4); ALLOC(m->pre_rstd, (size_t)B * Lv * 4);
-        ALLOC(m->f_ln, (size_t)B * dv * 4); ALLOC(m->post_mean, B * 4); ALLOC(m->post_rstd, B * 4); ALLOC(m->df_ln, (size_t)B * dv * 4);
-        ALLOC(m->cls_rows, B * 4); ALLOC(m->vprompt_rows, (size_t)B * nv * 4);
-        ALLOC(m->tpos, (size_t)c->ctx_len * dt * 4); ALLOC(m->ln_fin_g, dt * 4); ALLOC(m->ln_fin_b, dt * 4);
-        ALLOC(m->tproj, (size_t)dt * e * 4);
-        ALLOC(m->emb_pos, (size_t)C * c->ctx_len * dt * 4); ALLOC(m->eot_rows, TS * 4); ALLOC(m->eot_local, TS * 4); ALLOC(m->class_perm, C * 4);
-        ALLOC(m->txt_sorted, (size_t)C * e * 4); ALLOC(m->dtxt_sorted, (size_t)C * e * 4);
-        ALLOC(m->t_ln, (size_t)TS * dt * 4); ALLOC(m->fin_mean, TS * 4); ALLOC(m->fin_rstd, TS * 4); ALLOC(m->dt_ln, (size_t)TS * dt * 4);
-        const size_t dn = (size_t)(D1 > 0 ? D1 : 1) * n;
-        ALLOC(m->shared, (size_t)n * dv * 4); ALLOC(m->t2v, dn * dv * 4); ALLOC(m->v2t, dn * e * 4);
-        ALLOC(m->vis_deep, dn * dv * 4); ALLOC(m->txt_deep, dn * dt * 4);
-        ALLOC(m->vsplice, (size_t)B * (D1v > 0 ? D1v : 1) * nv * dv * 4);
-        ALLOC(m->d_vis_deep, dn * dv * 4); ALLOC(m->d_txt_deep, dn * dt * 4); ALLOC(m->d_vprompt0, (size_t)n * dv * 4);
-        ALLOC(m->img_f, (size_t)B * e * 4); ALLOC(m->txt_f, (size_t)TS * e * 4); ALLOC(m->img_n, (size_t)B * e * 4); ALLOC(m->txt_n, (size_t)TS * e * 4);
-        ALLOC(m->img_inv, B * 4); ALLOC(m->txt_inv, TS * 4);
-        ALLOC(m->logits, (size_t)B * C * 4); ALLOC(m->dlogits, (size_t)B * C * 4); ALLOC(m->row_loss, B * 4);
-        ALLOC(m->dimg, (size_t)B * e * 4); ALLOC(m->dtxt, (size_t)TS * e * 4); ALLOC(m->loss, 16);
-        if (cocoop) {
-            m->hid = e / 16;
-            ALLOC(m->mn_hid, (size_t)B * m->hid * 4); ALLOC(m->mn_dhid, (size_t)B * m->hid * 4);
-            ALLOC(m->mn_bias, (size_t)B * dt * 4); ALLOC(m->mn_dbias, (size_t)B * dt * 4);
-        }
-        if (coop) ALLOC(m->coop_pos, (size_t)C * n * 4);
-        if (umudpt) {
-            const size_t R = (size_t)c->depth * n;
-            size_t ws = 0;
-            (void)pg_carve(nullptr, c->depth, n, dt, &ws);
-            ALLOC(m->pg_G, R * dv * 4); ALLOC(m->pg_dG, R * dv * 4); ALLOC(m->pg_dX, R * dt * 4); ALLOC(m->pg_ws, ws * 4);
-            m->pg_w = pg_carve(m->pg_ws, c->depth, n, dt, nullptr);
-        }
-        ALLOC(m->gemm_scratch, mudpt_model::kScratchElems * 4); ALLOC(m->gemm_scratch2, mudpt_model::kScratchElems * 4);
-        HIP_TRY(hipStreamCreateWithFlags(&m->s2, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&m->ev_fork, &m->ev_join, &m->ev_fork_b, &m->ev_join_b}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        // row index tables
-        std::vector<int> cr(B), pr((size_t)B * nv);
-        for (int b = 0; b < B; ++b) {
-            cr[b] = b * Lv;
-            for (int i = 0; i < nv; ++i) pr[(size_t)b * nv + i] = b * Lv + (Lv - nv) + i;
-        }
-        HIP_TRY(hipMemcpy(m->cls_rows, cr.data(), cr.size() * 4, hipMemcpyHostToDevice));
-        m->vis.tail_rows = m->cls_rows;
-        m->vis.head_rows = nv > 0 ? m->vprompt_rows : nullptr;
-        ALLOC(m->tprompt_rows, (size_t)TS * nt * 4);
-        m->txt.head_rows = nt > 0 ? m->tprompt_rows : nullptr;  // ctx rows of every prompt; this table and the next are filled by mudpt_set_class_prompts
-        m->txt.tail_rows = m->eot_rows;
-        HIP_TRY(hipMemcpy(m->vprompt_rows, pr.data(), pr.size() * 4, hipMemcpyHostToDevice));
-        return MUDPT_OK;
-    };
-    if (int r = body()) return fail(r);
+    const int K0 = (3 * c->patch * c->patch + 63) / 64 * 64;  // conv-as-GEMM K, zero-padded to the GEMM's granularity (ViT-L/14: 588 -> 640)
+    ALLOC(m->conv_w, (size_t)dv * K0 * 2);
+    if (m->exact) { ALLOC(m->conv_w8, (size_t)dv * K0 * 2); ALLOC(m->patches_lo, (size_t)B * P * K0 * 2); }  // split pixels (vision tower's site 4)
+    ALLOC(m->cls, dv * 4); ALLOC(m->vpos, (size_t)(1 + P) * dv * 4);
+    ALLOC(m->ln_pre_g, dv * 4); ALLOC(m->ln_pre_b, dv * 4); ALLOC(m->ln_post_g, dv * 4); ALLOC(m->ln_post_b, dv * 4);
+    ALLOC(m->vproj, (size_t)dv * e * 4);
+    ALLOC(m->patches, (size_t)B * P * K0 * 2);
+    ALLOC(m->xpre, (size_t)B * Lv * dv * 4); ALLOC(m->pre_mean, (size_t)B * Lv * 4); ALLOC(m->pre_rstd, (size_t)B * Lv * 4);
+    ALLOC(m->f_ln, (size_t)B * dv * 4); ALLOC(m->post_mean, B * 4); ALLOC(m->post_rstd, B * 4); ALLOC(m->df_ln, (size_t)B * dv * 4);
+    ALLOC(m->cls_rows, B * 4); ALLOC(m->vprompt_rows, (size_t)B * nv * 4);
+    ALLOC(m->tpos, (size_t)c->ctx_len * dt * 4); ALLOC(m->ln_fin_g, dt * 4); ALLOC(m->ln_fin_b, dt * 4);
+    ALLOC(m->tproj, (size_t)dt * e * 4);
+    ALLOC(m->emb_pos, (size_t)C * c->ctx_len * dt * 4); ALLOC(m->eot_rows, TS * 4); ALLOC(m->eot_local, TS * 4); ALLOC(m->class_perm, C * 4);
+    ALLOC(m->txt_sorted, (size_t)C * e * 4); ALLOC(m->dtxt_sorted, (size_t)C * e * 4);
+    ALLOC(m->t_ln, (size_t)TS * dt * 4); ALLOC(m->fin_mean, TS * 4); ALLOC(m->fin_rstd, TS * 4); ALLOC(m->dt_ln, (size_t)TS * dt * 4);
+    const size_t dn = (size_t)(D1 > 0 ? D1 : 1) * n;
+    ALLOC(m->shared, (size_t)n * dv * 4); ALLOC(m->t2v, dn * dv * 4); ALLOC(m->v2t, dn * e * 4);
+    ALLOC(m->vis_deep, dn * dv * 4); ALLOC(m->txt_deep, dn * dt * 4);
+    ALLOC(m->vsplice, (size_t)B * (D1v > 0 ? D1v : 1) * nv * dv * 4);
+    ALLOC(m->d_vis_deep, dn * dv * 4); ALLOC(m->d_txt_deep, dn * dt * 4); ALLOC(m->d_vprompt0, (size_t)n * dv * 4);
+    ALLOC(m->img_f, (size_t)B * e * 4); ALLOC(m->txt_f, (size_t)TS * e * 4); ALLOC(m->img_n, (size_t)B * e * 4); ALLOC(m->txt_n, (size_t)TS * e * 4);
+    ALLOC(m->img_inv, B * 4); ALLOC(m->txt_inv, TS * 4);
+    ALLOC(m->logits, (size_t)B * C * 4); ALLOC(m->dlogits, (size_t)B * C * 4); ALLOC(m->row_loss, B * 4);
+    ALLOC(m->dimg, (size_t)B * e * 4); ALLOC(m->dtxt, (size_t)TS * e * 4); ALLOC(m->loss, 16);
+    if (m->cocoop) {
+        m->hid = e / 16;
+        ALLOC(m->mn_hid, (size_t)B * m->hid * 4); ALLOC(m->mn_dhid, (size_t)B * m->hid * 4);
+        ALLOC(m->mn_bias, (size_t)B * dt * 4); ALLOC(m->mn_dbias, (size_t)B * dt * 4);
+    }
+    if (m->coop) ALLOC(m->coop_pos, (size_t)C * n * 4);
+    if (m->umudpt) {
+        const size_t R = (size_t)c->depth * n;
+        size_t ws = 0;
+        (void)pg_carve(nullptr, c->depth, n, dt, &ws);
+        ALLOC(m->pg_G, R * dv * 4); ALLOC(m->pg_dG, R * dv * 4); ALLOC(m->pg_dX, R * dt * 4); ALLOC(m->pg_ws, ws * 4);
+        m->pg_w = pg_carve(m->pg_ws, c->depth, n, dt, nullptr);
+    }
+    ALLOC(m->gemm_scratch, mudpt_model::kScratchElems * 4); ALLOC(m->gemm_scratch2, mudpt_model::kScratchElems * 4);
+    HIP_TRY(hipStreamCreateWithFlags(&m->s2, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&m->ev_fork, &m->ev_join, &m->ev_fork_b, &m->ev_join_b}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    // row index tables
+    std::vector<int> cr(B), pr((size_t)B * nv);
+    for (int b = 0; b < B; ++b) {
+        cr[b] = b * Lv;
+        for (int i = 0; i < nv; ++i) pr[(size_t)b * nv + i] = b * Lv + (Lv - nv) + i;
+    }
+    HIP_TRY(hipMemcpy(m->cls_rows, cr.data(), cr.size() * 4, hipMemcpyHostToDevice));
+    m->vis.tail_rows = m->cls_rows;
+    m->vis.head_rows = nv > 0 ? m->vprompt_rows : nullptr;
+    ALLOC(m->tprompt_rows, (size_t)TS * nt * 4);
+    m->txt.head_rows = nt > 0 ? m->tprompt_rows : nullptr;  // ctx rows of every prompt; this table and the next are filled by mudpt_set_class_prompts
+    m->txt.tail_rows = m->eot_rows;
+    HIP_TRY(hipMemcpy(m->vprompt_rows, pr.data(), pr.size() * 4, hipMemcpyHostToDevice));
 
-    // flat bucket layout, reference order/shapes: trainers/mudpt.py:71-81, clip/model.py:512-519
-    const size_t shapes[10] = {(size_t)n * dt, (size_t)D1 * n * dt, (size_t)dv * dt, (size_t)dv, (size_t)dv * dt, (size_t)dv,
-                               (size_t)n * dv, (size_t)D1 * n * dv, (size_t)e * dv, (size_t)e};
-    // CoCoOp: ctx [n, dt], meta_net.linear1 [e/16, e] + [e/16], meta_net.linear2 [dt, e/16] + [dt]  (trainers/cocoop.py:96-107)
-    const size_t cshapes[5] = {(size_t)n * dt, (size_t)(e / 16) * e, (size_t)(e / 16), (size_t)dt * (e / 16), (size_t)dt};
-    // CoOp: ctx [n, dt], or [n_cls, n, dt] with CSC (trainers/coop.py:60-76)
-    const size_t coop_numel = (size_t)(m->csc ? C : 1) * n * dt;
-    // VPT / MPT: every visual_ctx [n, width] in the reference's named_parameters() order (text_prompt_learner, text_encoder, image_encoder);
-    // the blocks' tensors follow one another, so they are the [D1][n][width] array the splice and the gradient reductions address
-    if (indep) {
-        auto add = [&](const std::string& k, int64_t rows, int64_t cols) { m->pnames.push_back(k); m->prows.push_back(rows); m->pcols.push_back(cols); };
-        if (mpt) {
-            add("text_prompt_learner.visual_ctx", nt, dt);  // trainers/mpt.py:86
-            for (int i = 1; i <= D1t; ++i) add("text_encoder.transformer.resblocks." + std::to_string(i) + ".visual_ctx", nt, dt);
-        }
-        if (nv > 0) {
-            add("image_encoder.visual_ctx", nv, dv);  // clip/model.py:459-465
-            for (int i = 1; i <= D1v; ++i) add("image_encoder.transformer.resblocks." + std::to_string(i) + ".visual_ctx", nv, dv);
-        }
-        m->t_ctx_off = 0;
-        m->t_deep_off = (size_t)nt * dt;
-        m->v_ctx_off = mpt ? (size_t)(1 + D1t) * nt * dt : 0;
-        m->v_deep_off = m->v_ctx_off + (size_t)nv * dv;
-    }
-    if (umudpt) {  // trainers/umudpt.py:110-124: ctx, deep_prompts ([0, n, dt] at depth 1: no elements, still listed), then the generator
-        const int64_t D = dt, V = dv;
-        const int64_t shp[20][3] = {{n, D, 0}, {D1, n, D}, {D, 0, 0}, {D, 0, 0}, {3 * D, D, 0}, {3 * D, 0, 0}, {D, D, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0},
-                                    {4 * D, D, 0}, {4 * D, 0, 0}, {D, 4 * D, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0}, {D, 0, 0}, {V, D, 0}, {V, 0, 0}};
-        const int nd[20] = {2, 3, 1, 1, 2, 1, 2, 1, 1, 1, 2, 1, 2, 1, 1, 1, 1, 1, 2, 1};
-        for (int i = 0; i < 20; ++i) {
-            m->pnames.push_back(std::string("umudpt_prompt_learner.") + kUmudptNames[i]);
-            m->pnd.push_back(nd[i]);
-            for (int k = 0; k < 3; ++k) m->pshape.push_back(shp[i][k]);
-        }
-    }
-    m->nparams = cocoop ? 5 : coop ? 1 : indep ? (int)m->pnames.size() : umudpt ? 20 : 10;
-    m->off.assign(std::max(m->nparams, 1), 0);
-    m->numel.assign(std::max(m->nparams, 1), 0);
-    size_t o = 0;
-    for (int i = 0; i < m->nparams; ++i) {
-        m->off[i] = o;
-        m->numel[i] = cocoop ? cshapes[i] : coop ? coop_numel : indep ? (size_t)(m->prows[i] * m->pcols[i]) : shapes[i];
-        if (umudpt) {
-            m->numel[i] = 1;
-            for (int k = 0; k < m->pnd[i]; ++k) m->numel[i] *= (size_t)m->pshape[3 * i + k];
-        }
-        o += m->numel[i];
-    }
-    m->total = o;
-    if (int r = dev_alloc(m, (void**)&m->momentum, o * 4)) return fail(r);
+    build_trainables(m);
+    ALLOC(m->momentum, m->total * 4);
 
     // frozen weights the path needs before it may run
     for (const char* k : {"visual.conv1.weight", "visual.class_embedding", "visual.positional_embedding", "visual.ln_pre.weight",
@@ -687,6 +680,12 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
         m->missing.push_back(k);
     expect_block_keys(m, "visual.transformer", c->v_layers);
     expect_block_keys(m, "transformer", c->t_layers);
+    return MUDPT_OK;
+}
+
+static int create_model(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out) {
+    mudpt_model* m = new mudpt_model();
+    if (int rc = create_impl(c, ps, m)) { mudpt_destroy(m); return rc; }
     *out = m;
     return MUDPT_OK;
 }
@@ -695,15 +694,16 @@ extern "C" int mudpt_create(const mudpt_config* c, mudpt_model** out) {
     ARG_CHECK(c && out, "create: null argument");
     ARG_CHECK(c->variant != MUDPT_VARIANT_VPT && c->variant != MUDPT_VARIANT_MPT,
               "create: variant %d (VPT / MPT) needs the per-tower prompt shape: use mudpt_create_ex", c->variant);
-    return create_impl(c, nullptr, out);
+    return create_model(c, nullptr, out);
 }
 
 extern "C" int mudpt_create_ex(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out) {
     ARG_CHECK(c && out, "create_ex: null argument");
-    const bool indep = c->variant == MUDPT_VARIANT_VPT || c->variant == MUDPT_VARIANT_MPT;
-    ARG_CHECK(!indep || ps, "create_ex: variant %d (VPT / MPT) needs a mudpt_prompt_shape", c->variant);
-    ARG_CHECK(indep || !ps, "create_ex: a mudpt_prompt_shape is for VPT / MPT only (variant %d: pass NULL)", c->variant);
-    return create_impl(c, ps, out);
+    // whether a shape must come with the call is decided before a model exists; the model's own flags are derived in create_impl
+    const bool per_tower = c->variant == MUDPT_VARIANT_VPT || c->variant == MUDPT_VARIANT_MPT;
+    ARG_CHECK(!per_tower || ps, "create_ex: variant %d (VPT / MPT) needs a mudpt_prompt_shape", c->variant);
+    ARG_CHECK(per_tower || !ps, "create_ex: a mudpt_prompt_shape is for VPT / MPT only (variant %d: pass NULL)", c->variant);
+    return create_model(c, ps, out);
 }
 
 extern "C" int mudpt_destroy(mudpt_model* m) {
@@ -1022,57 +1022,16 @@ extern "C" int mudpt_text_layout(const mudpt_model* m, int32_t* rows, int32_t* b
     return MUDPT_OK;
 }
 
-extern "C" int mudpt_param_count(const mudpt_model* m) { return m ? m->nparams : 0; }
+extern "C" int mudpt_param_count(const mudpt_model* m) { return m ? (int)m->tr.size() : 0; }
 extern "C" size_t mudpt_param_numel(const mudpt_model* m) { return m ? m->total : 0; }
 extern "C" int mudpt_param_info(const mudpt_model* m, int i, const char** name, size_t* offset, size_t* numel, int32_t* ndim, int64_t shape[3]) {
-    ARG_CHECK(m && i >= 0 && i < m->nparams, "param_info: bad index %d", i);
-    const mudpt_config& c = m->cfg;
-    const int64_t n = c.n_ctx, D1 = c.depth - 1, dt = c.t_width, dv = c.v_width, e = c.embed_dim;
-    if (m->indep) {  // every visual_ctx [n, width] (clip/model.py:202-251,459-465, trainers/mpt.py:86)
-        if (name) *name = m->pnames[i].c_str();
-        if (offset) *offset = m->off[i];
-        if (numel) *numel = m->numel[i];
-        if (ndim) *ndim = 2;
-        if (shape) { shape[0] = m->prows[i]; shape[1] = m->pcols[i]; shape[2] = 0; }
-        return MUDPT_OK;
-    }
-    if (m->umudpt) {  // trainers/umudpt.py:110-124
-        if (name) *name = m->pnames[i].c_str();
-        if (offset) *offset = m->off[i];
-        if (numel) *numel = m->numel[i];
-        if (ndim) *ndim = m->pnd[i];
-        if (shape) for (int k = 0; k < 3; ++k) shape[k] = m->pshape[3 * i + k];
-        return MUDPT_OK;
-    }
-    if (m->coop) {  // trainers/coop.py:60-76
-        if (name) *name = kCoopName;
-        if (offset) *offset = m->off[0];
-        if (numel) *numel = m->numel[0];
-        if (ndim) *ndim = m->csc ? 3 : 2;
-        if (shape) {
-            const int64_t s3[3] = {(int64_t)c.n_cls, n, dt}, s2[3] = {n, dt, 0};
-            for (int k = 0; k < 3; ++k) shape[k] = m->csc ? s3[k] : s2[k];
-        }
-        return MUDPT_OK;
-    }
-    if (m->cocoop) {
-        const int64_t hd = e / 16;
-        const int64_t cshp[5][3] = {{n, dt, 0}, {hd, e, 0}, {hd, 0, 0}, {dt, hd, 0}, {dt, 0, 0}};
-        const int cnd[5] = {2, 2, 1, 2, 1};
-        if (name) *name = kCocoopNames[i];
-        if (offset) *offset = m->off[i];
-        if (numel) *numel = m->numel[i];
-        if (ndim) *ndim = cnd[i];
-        if (shape) for (int k = 0; k < 3; ++k) shape[k] = cshp[i][k];
-        return MUDPT_OK;
-    }
-    const int64_t shp[10][3] = {{n, dt, 0}, {D1, n, dt}, {dv, dt, 0}, {dv, 0, 0}, {dv, dt, 0}, {dv, 0, 0}, {n, dv, 0}, {D1, n, dv}, {e, dv, 0}, {e, 0, 0}};
-    const int nd[10] = {2, 3, 2, 1, 2, 1, 2, 3, 2, 1};
-    if (name) *name = kParamNames[i];
-    if (offset) *offset = m->off[i];
-    if (numel) *numel = m->numel[i];
-    if (ndim) *ndim = nd[i];
-    if (shape) for (int k = 0; k < 3; ++k) shape[k] = shp[i][k];
+    ARG_CHECK(m && i >= 0 && i < (int)m->tr.size(), "param_info: bad index %d", i);
+    const Trainable& t = m->tr[i];
+    if (name) *name = t.name.c_str();
+    if (offset) *offset = t.off;
+    if (numel) *numel = t.numel;
+    if (ndim) *ndim = t.ndim;
+    if (shape) for (int k = 0; k < 3; ++k) shape[k] = t.shape[k];
     return MUDPT_OK;
 }
 extern "C" int mudpt_bind_params(mudpt_model* m, float* p, float* g) {
@@ -1363,16 +1322,50 @@ static int block_bwd(mudpt_model* m, Tower& t, int i, int nseq, hipStream_t s, f
     return MUDPT_OK;
 }
 
+// Where a tower's prompt rows come from and where their gradients are reduced to, resolved per call (mudpt_bind_params may rebind the
+// buckets).  The one place that knows which variant keeps them where; a tower without prompt rows has no route.
+struct PromptRoute {
+    const float* in0 = nullptr;      // the n rows spliced at the tower's input
+    const float* in0_add = nullptr;  // what is added to them
+    const float* deep = nullptr;     // the [D1][n][d] rows of blocks 1 .. D1
+    float* d_in0 = nullptr;          // where the gradient of in0 is reduced to
+    float* d_deep = nullptr;         // where the gradient of deep is reduced to
+};
+static PromptRoute prompt_route(const mudpt_model* m, const Tower& t) {
+    PromptRoute r;
+    if (t.n == 0) return r;
+    const bool vision = &t == &m->vis;
+    const size_t group = (size_t)t.n * t.d;  // one block's rows
+    float* P = m->params;
+    auto G = [&](size_t o) { return m->grads ? m->grads + o : nullptr; };  // inference binds no gradient bucket
+    if (!vision) r.in0_add = m->tpos + t.d;  // rows 1..n with the positional embedding (trainers/mudpt.py:97-115,143, mpt.py:108-125)
+    if (m->indep) {
+        // VPT / MPT: the tower's visual_ctx and, right behind it, its blocks' own visual_ctx, read from and reduced into the buckets directly
+        // (clip/model.py:463-465)
+        const size_t o = m->off(vision ? m->tr_vis0 : m->tr_txt0);
+        r.in0 = P + o; r.deep = P + o + group; r.d_in0 = G(o); r.d_deep = G(o + group);
+    } else if (m->umudpt && vision) {
+        // the generator's output G [depth][n][dv]: row group 0 the input rows (alone: the tower has no visual_ctx of its own, clip/model.py:573-576),
+        // 1 .. the deep prompts (:556-597); pg_dG collects the gradients likewise and the generator's backward reads it
+        r.in0 = m->pg_G; r.deep = m->pg_G + group; r.d_in0 = m->pg_dG; r.d_deep = m->pg_dG + group;
+    } else if (vision) {  // MuDPT: visual_ctx + shared (clip/model.py:534) and the prompt learner's projections; gradients into its backward
+        r.in0 = P + m->off(P_VCTX); r.in0_add = m->shared; r.deep = m->vis_deep; r.d_in0 = m->d_vprompt0; r.d_deep = m->d_vis_deep;
+    } else {  // MuDPT / UMuDPT: ctx, its gradient summed over the class prompts straight into the bucket
+        r.in0 = P + m->off(P_CTX); r.d_in0 = G(m->off(P_CTX));
+        // UMuDPT: deep_prompts as they are in the bucket (trainers/umudpt.py:178,222); MuDPT: the prompt learner's sums
+        r.deep = m->umudpt ? P + m->off(P_DEEP) : m->txt_deep;
+        r.d_deep = m->umudpt ? G(m->off(P_DEEP)) : m->d_txt_deep;
+    }
+    return r;
+}
+
 // Vision tower forward, clip/model.py:526-553 (MuDPT: prompt rows appended before ln_pre, deep prompts spliced per block) or
 // clip/model.py:478-496 (CoCoOp: the vanilla ViT, no prompt rows) -> m->img_f [B, e]
 static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, e = c.embed_dim, n = m->vis.n, D1 = m->vis.D1;
     const int P = (c.image_size / c.patch) * (c.image_size / c.patch), Lv = m->vis.L, K0 = (3 * c.patch * c.patch + 63) / 64 * 64;
-    float* Pm = m->params;
-    // VPT / MPT: block i's rows are its own visual_ctx in the bucket; MuDPT: the prompt learner's projections (prompt_learner_forward)
-    // UMuDPT: the generator's output, row groups 1 .. (clip/model.py:556-597)
-    const float* deep = m->indep ? Pm + m->v_deep_off : m->umudpt ? m->pg_G + (size_t)n * dv : m->vis_deep;
+    const PromptRoute pr = prompt_route(m, m->vis);
     const int m_patch = site_mode(m->vis, SITE_PATCH, K0);  // parity mode: split pixels (an fp16 pixel alone carries 2.4e-4 of rounding into block 0)
     if (m_patch != LO_NONE) TRY(launch_patchify_split(m->dtype, images, m->patches, m->patches_lo, m_patch, B, c.image_size, c.patch, K0, s));
     else TRY(launch_patchify(m->dtype, images, m->patches, B, c.image_size, c.patch, K0, s));
@@ -1381,15 +1374,13 @@ static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_
     pe.patches = P; pe.seq_len = Lv; pe.pos = m->vpos;
     TRY(gemm_call(m, EPI_PATCH, pe, s));
     TRY(launch_set_rows(m->xpre, B, Lv, dv, 0, 1, m->cls, m->vpos, s));
-    // prompt rows after the positional embedding, before ln_pre: MuDPT visual_ctx + shared (clip/model.py:534), VPT / MPT visual_ctx (:463-465)
-    // UMuDPT: G[0] alone, the tower has no visual_ctx of its own (clip/model.py:573-576)
-    if (m->umudpt) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, m->pg_G, nullptr, s));
-    else if (n > 0) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, Pm + (m->indep ? m->v_ctx_off : m->off[P_VCTX]), m->indep ? nullptr : m->shared, s));
+    // prompt rows after the positional embedding, before ln_pre
+    if (n > 0) TRY(launch_set_rows(m->xpre, B, Lv, dv, Lv - n, n, pr.in0, pr.in0_add, s));
     LnFwdArgs lp; lp.x = m->xpre; lp.ldx = dv; lp.gamma = m->ln_pre_g; lp.beta = m->ln_pre_b; lp.out = m->vis.a[0].x_in; lp.ldo = dv; lp.out_f32 = true;
     lp.mean = m->pre_mean; lp.rstd = m->pre_rstd; lp.rows = B * Lv; lp.d = dv;
     TRY(launch_ln_fwd(m->dtype, lp, s));
     for (int i = 0; i < m->vis.layers; ++i) {
-        TRY(block_fwd(m, m->vis, i, B, (i >= 1 && i - 1 < D1) ? deep + (size_t)(i - 1) * n * dv : nullptr, s));
+        TRY(block_fwd(m, m->vis, i, B, (i >= 1 && i - 1 < D1) ? pr.deep + (size_t)(i - 1) * n * dv : nullptr, s));
     }
     LnFwdArgs lq; lq.x = m->vis.xout_sel; lq.ldx = dv; lq.gamma = m->ln_post_g; lq.beta = m->ln_post_b; lq.out = m->f_ln; lq.ldo = dv;
     lq.out_f32 = true; lq.mean = m->post_mean; lq.rstd = m->post_rstd; lq.rows = B; lq.d = dv;
@@ -1407,7 +1398,7 @@ static int cocoop_text_chunk(mudpt_model* m, int i0, int nb, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     const int dt = c.t_width, e = c.embed_dim, n = c.n_ctx, C = c.n_cls, Lt = m->txt.L, TS = nb * C;
     const size_t r0 = (size_t)i0 * C;
-    TRY(launch_cocoop_prompts(m->txt.a[0].x_in, m->emb_pos, m->params + m->off[Q_CTX], m->mn_bias + (size_t)i0 * dt, m->tpos, nb, C, Lt, dt, n, s));
+    TRY(launch_cocoop_prompts(m->txt.a[0].x_in, m->emb_pos, m->params + m->off(Q_CTX), m->mn_bias + (size_t)i0 * dt, m->tpos, nb, C, Lt, dt, n, s));
     for (int i = 0; i < m->txt.layers; ++i) TRY(block_fwd(m, m->txt, i, TS, nullptr, s));
     LnFwdArgs lf; lf.x = m->txt.xout_sel; lf.ldx = dt; lf.gamma = m->ln_fin_g; lf.beta = m->ln_fin_b; lf.out = m->t_ln + r0 * dt; lf.ldo = dt;
     lf.out_f32 = true; lf.mean = m->fin_mean + r0; lf.rstd = m->fin_rstd + r0; lf.rows = TS; lf.d = dt;
@@ -1434,9 +1425,9 @@ static int cocoop_image_side(mudpt_model* m, const float* images, int B, hipStre
     float* Pm = m->params;
     TRY(vision_forward(m, images, B, s));
     TRY(launch_l2norm(m->img_f, m->img_n, m->img_inv, B, e, s));
-    TRY(launch_sgemm(false, true, B, hd, e, 1.f, m->img_n, e, Pm + m->off[Q_W1], e, 0.f, m->mn_hid, hd, Pm + m->off[Q_B1], s));
+    TRY(launch_sgemm(false, true, B, hd, e, 1.f, m->img_n, e, Pm + m->off(Q_W1), e, 0.f, m->mn_hid, hd, Pm + m->off(Q_B1), s));
     TRY(launch_relu(m->mn_hid, (size_t)B * hd, s));
-    TRY(launch_sgemm(false, true, B, dt, hd, 1.f, m->mn_hid, hd, Pm + m->off[Q_W2], hd, 0.f, m->mn_bias, dt, Pm + m->off[Q_B2], s));
+    TRY(launch_sgemm(false, true, B, dt, hd, 1.f, m->mn_hid, hd, Pm + m->off(Q_W2), hd, 0.f, m->mn_bias, dt, Pm + m->off(Q_B2), s));
     return MUDPT_OK;
 }
 
@@ -1478,39 +1469,43 @@ static int cocoop_forward_backward(mudpt_model* m, const float* images, const in
             if (i == X.layers - 1) TRY(block_bwd_tail(m, X, TS, s)); else TRY(block_bwd(m, X, i, TS, s));
         }
         // d ctx += sum over the chunk's (image, class) prompts of the context rows' gradient; d bias[i] = the same sum over image i's prompts
-        TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, TS, Lt, dt, 1, n, G + m->off[Q_CTX], false, true, unscale, s));
+        TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, TS, Lt, dt, 1, n, G + m->off(Q_CTX), false, true, unscale, s));
         TRY(launch_cocoop_dbias(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, m->mn_dbias + (size_t)i0 * dt, nb, C, Lt, dt, n, unscale, s));
     }
     TRY(launch_mean(m->row_loss, B, m->loss, s));
     HIP_TRY(hipMemcpyAsync(loss, m->loss, 4, hipMemcpyDeviceToDevice, s));
     if (logits) HIP_TRY(hipMemcpyAsync(logits, m->logits, (size_t)B * C * 4, hipMemcpyDeviceToDevice, s));
     // meta_net backward (fp32, tiny): linear2, ReLU, linear1; its input (the normalised image features) is a constant
-    TRY(launch_sgemm(true, false, dt, hd, B, 1.f, m->mn_dbias, dt, m->mn_hid, hd, 0.f, G + m->off[Q_W2], hd, nullptr, s));
-    TRY(launch_colsum(m->mn_dbias, B, dt, dt, G + m->off[Q_B2], false, s));
-    TRY(launch_sgemm(false, false, B, hd, dt, 1.f, m->mn_dbias, dt, Pm + m->off[Q_W2], hd, 0.f, m->mn_dhid, hd, nullptr, s));
+    TRY(launch_sgemm(true, false, dt, hd, B, 1.f, m->mn_dbias, dt, m->mn_hid, hd, 0.f, G + m->off(Q_W2), hd, nullptr, s));
+    TRY(launch_colsum(m->mn_dbias, B, dt, dt, G + m->off(Q_B2), false, s));
+    TRY(launch_sgemm(false, false, B, hd, dt, 1.f, m->mn_dbias, dt, Pm + m->off(Q_W2), hd, 0.f, m->mn_dhid, hd, nullptr, s));
     TRY(launch_relu_bwd(m->mn_dhid, m->mn_hid, (size_t)B * hd, s));
-    TRY(launch_sgemm(true, false, hd, e, B, 1.f, m->mn_dhid, hd, m->img_n, e, 0.f, G + m->off[Q_W1], e, nullptr, s));
-    TRY(launch_colsum(m->mn_dhid, B, hd, hd, G + m->off[Q_B1], false, s));
+    TRY(launch_sgemm(true, false, hd, e, B, 1.f, m->mn_dhid, hd, m->img_n, e, 0.f, G + m->off(Q_W1), e, nullptr, s));
+    TRY(launch_colsum(m->mn_dhid, B, hd, hd, G + m->off(Q_B1), false, s));
     return MUDPT_OK;
 }
 
 // ---- the MuDPT step in pieces (the monolithic entry points and the class-parallel phases share them) ------------------------------
 // prompt learner, trainers/mudpt.py:117-130 + clip/model.py:534-539
 static int prompt_learner_forward(mudpt_model* m, hipStream_t s) {
-    if (m->coop || m->indep) return MUDPT_OK;  // CoOp / VPT / MPT: the trainables go into the towers as they are (trainers/coop.py:166-175)
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, dt = c.t_width, e = c.embed_dim, n = c.n_ctx, D1 = c.depth - 1;
     float* Pm = m->params;
-    if (m->umudpt)  // trainers/umudpt.py:170-176: the vision prompts of every layer from the text prompts of every layer
-        return pg_forward(c.depth, n, dt, dv, pg_params(Pm + m->off[2], dt, dv), Pm + m->off[P_CTX], m->pg_G, m->pg_w, s);
-    TRY(launch_sgemm(false, true, n, dv, dt, 1.f, Pm + m->off[P_CTX], dt, Pm + m->off[P_EW], dt, 0.f, m->shared, dv, Pm + m->off[P_EB], s));
+    TRY(launch_sgemm(false, true, n, dv, dt, 1.f, Pm + m->off(P_CTX), dt, Pm + m->off(P_EW), dt, 0.f, m->shared, dv, Pm + m->off(P_EB), s));
     if (D1 > 0) {
-        TRY(launch_sgemm(false, true, D1 * n, dv, dt, 1.f, Pm + m->off[P_DEEP], dt, Pm + m->off[P_DW], dt, 0.f, m->t2v, dv, Pm + m->off[P_DB], s));
-        TRY(launch_sgemm(false, true, D1 * n, e, dv, 1.f, Pm + m->off[P_VDEEP], dv, Pm + m->off[P_VW], dv, 0.f, m->v2t, e, Pm + m->off[P_VB], s));
-        TRY(launch_add(m->t2v, Pm + m->off[P_VDEEP], m->vis_deep, (size_t)D1 * n * dv, s));
-        TRY(launch_add(m->v2t, Pm + m->off[P_DEEP], m->txt_deep, (size_t)D1 * n * dt, s));
+        TRY(launch_sgemm(false, true, D1 * n, dv, dt, 1.f, Pm + m->off(P_DEEP), dt, Pm + m->off(P_DW), dt, 0.f, m->t2v, dv, Pm + m->off(P_DB), s));
+        TRY(launch_sgemm(false, true, D1 * n, e, dv, 1.f, Pm + m->off(P_VDEEP), dv, Pm + m->off(P_VW), dv, 0.f, m->v2t, e, Pm + m->off(P_VB), s));
+        TRY(launch_add(m->t2v, Pm + m->off(P_VDEEP), m->vis_deep, (size_t)D1 * n * dv, s));
+        TRY(launch_add(m->v2t, Pm + m->off(P_DEEP), m->txt_deep, (size_t)D1 * n * dt, s));
     }
     return MUDPT_OK;
+}
+
+// UMuDPT, trainers/umudpt.py:170-176: the vision prompts of every layer from the text prompts of every layer
+static int umudpt_forward(mudpt_model* m, hipStream_t s) {
+    const mudpt_config& c = m->cfg;
+    float* Pm = m->params;
+    return pg_forward(c.depth, c.n_ctx, c.t_width, c.v_width, pg_params(Pm + m->off(U_GEN), c.t_width, c.v_width), Pm + m->off(P_CTX), m->pg_G, m->pg_w, s);
 }
 
 // text tower, trainers/mudpt.py:142-156, over this handle's classes [c0, c0 + ct): rows c0.. of the [n_cls, e] feature table
@@ -1520,17 +1515,16 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
     float* Pm = m->params;
     const std::vector<Tower::Seg> segs = tower_segs(m->txt, Ct);
     const bool packed = segs.size() > 1;
-    // MPT: the text blocks' own visual_ctx in the bucket; UMuDPT: deep_prompts as they are (trainers/umudpt.py:178,222)
-    const float* deep = m->indep ? Pm + m->t_deep_off : m->umudpt ? Pm + m->off[P_DEEP] : m->txt_deep;
+    const PromptRoute pr = prompt_route(m, m->txt);
     ++m->text_launches;
     HIP_TRY(hipMemcpyAsync(m->txt.a[0].x_in, m->emb_pos, (size_t)tower_rows(m->txt, Ct) * dt * 4, hipMemcpyDeviceToDevice, s2));
     if (m->coop)  // trainers/coop.py:166-175,187-188: the context rows at every class's own positions, all buckets in one launch
-        TRY(launch_coop_splice(m->txt.a[0].x_in, Pm + m->off[0], m->tpos, m->tprompt_rows, m->coop_pos, Ct, n, dt, m->csc, s2));
-    else if (n > 0)  // MuDPT ctx / MPT text_prompt_learner.visual_ctx at rows 1..n, with the positional embedding (trainers/mpt.py:108-125)
+        TRY(launch_coop_splice(m->txt.a[0].x_in, Pm + m->off(0), m->tpos, m->tprompt_rows, m->coop_pos, Ct, n, dt, m->csc, s2));
+    else if (n > 0)  // MuDPT ctx / MPT text_prompt_learner.visual_ctx at rows 1..n
         for (const Tower::Seg& g : segs)
-            TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, Pm + (m->indep ? m->t_ctx_off : m->off[P_CTX]), m->tpos + dt, s2));
+            TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, pr.in0, pr.in0_add, s2));
     for (int i = 0; i < m->txt.layers; ++i) {
-        TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? deep + (size_t)(i - 1) * n * dt : nullptr, s2));
+        TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? pr.deep + (size_t)(i - 1) * n * dt : nullptr, s2));
     }
     LnFwdArgs lf; lf.x = m->txt.xout_sel; lf.ldx = dt; lf.gamma = m->ln_fin_g; lf.beta = m->ln_fin_b; lf.out = m->t_ln; lf.ldo = dt;
     lf.out_f32 = true; lf.mean = m->fin_mean; lf.rstd = m->fin_rstd; lf.rows = Ct; lf.d = dt;
@@ -1543,21 +1537,32 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
     return MUDPT_OK;
 }
 
+// The variant's trainable front end around the towers, each hook null where the variant has none (learner(), below its last hook):
+//   fwd         before the fork: both towers read its output
+//   fwd_vision  after the fork, on the vision stream: the text tower reads none of its output, so only the vision tower's prompt splice waits
+//               for it; with reuse_text its output is kept like the text features (same parameters, same output)
+//   bwd_text    on the text stream behind that tower's backward, before the join: needs the text tower's prompt gradients only
+//   bwd         after the join
+struct Learner {
+    typedef int (*Hook)(mudpt_model*, hipStream_t);
+    Hook fwd = nullptr, fwd_vision = nullptr, bwd_text = nullptr, bwd = nullptr;
+};
+static Learner learner(const mudpt_model* m);
+
 // Both towers' forward.  The text tower is independent of the vision tower once the prompt learner has run, so it goes to the side
 // stream (enqueued first): its ~200 small launch-latency-bound kernels fill the CUs the big vision kernels leave idle (tails of the
 // persistent GEMMs, memory-bound LayerNorms) instead of serialising behind them.  With reuse_text (inference with unchanged
 // parameters: the reference recomputes the text tower for every test batch, trainers/mudpt.py:170-184) the text
 // features of the previous call are kept.
 static int towers_forward(mudpt_model* m, const float* images, int B, hipStream_t s, bool reuse_text) {
-    // UMuDPT: the text tower reads no generator output, so it forks before the generator is enqueued, and only the vision tower's prompt
-    // splice (behind the generator on s) waits for G; with reuse_text G is kept like the text features (same parameters, same G)
-    if (!m->umudpt) TRY(prompt_learner_forward(m, s));
+    const Learner L = learner(m);
+    if (L.fwd) TRY(L.fwd(m, s));
     if (!reuse_text) {
         HIP_TRY(hipEventRecord(m->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork, 0));
         TRY(text_forward(m, m->s2));
         HIP_TRY(hipEventRecord(m->ev_join, m->s2));
-        if (m->umudpt) TRY(prompt_learner_forward(m, s));
+        if (L.fwd_vision) TRY(L.fwd_vision(m, s));
     }
     TRY(vision_forward(m, images, B, s));  // clip/model.py:526-553
     if (!reuse_text) HIP_TRY(hipStreamWaitEvent(s, m->ev_join, 0));
@@ -1644,7 +1649,7 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
     const int dt = c.t_width, e = c.embed_dim, n = m->txt.n, D1 = m->txt.D1, Ct = m->ct;
     float* G = m->grads;
     Tower& X = m->txt;
-    float* d_deep = m->indep ? G + m->t_deep_off : m->umudpt ? G + m->off[P_DEEP] : m->d_txt_deep;  // MPT / UMuDPT: straight into the gradient bucket
+    const PromptRoute pr = prompt_route(m, X);
     ++m->text_launches;
     const std::vector<Tower::Seg> segs = tower_segs(X, Ct);
     const float* dfeat = m->dtxt + (size_t)m->c0 * e;
@@ -1661,15 +1666,15 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
         if (i >= 1 && i - 1 < D1)
             for (const Tower::Seg& g : segs)  // bucket after bucket in a fixed order: deterministic
                 TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, (char*)X.dx_lp + (size_t)g.row0 * dt * 2, g.nseq, g.L, dt, 1, n,
-                                       d_deep + (size_t)(i - 1) * n * dt, true, g.seq0 > 0, unscale, s2));
+                                       pr.d_deep + (size_t)(i - 1) * n * dt, true, g.seq0 > 0, unscale, s2));
     }
     // CoOp: d ctx from the context rows of every class (shared: summed over the classes in a fixed order; CSC: per class), coop.hip
     if (m->coop)
-        return launch_coop_dctx(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, m->tprompt_rows, G + m->off[0], Ct, n, dt, m->csc, unscale, s2);
+        return launch_coop_dctx(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, m->tprompt_rows, G + m->off(0), Ct, n, dt, m->csc, unscale, s2);
     // d ctx (text side): rows 1..n of the first block's input, summed over the class prompts
     for (const Tower::Seg& g : segs)
         TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, m->lp_grad ? (char*)X.dx_lp + (size_t)g.row0 * dt * 2 : nullptr, g.nseq, g.L, dt, 1, n,
-                               G + (m->indep ? m->t_ctx_off : m->off[P_CTX]), false, true, unscale, s2));
+                               pr.d_in0, false, true, unscale, s2));
     return MUDPT_OK;
 }
 
@@ -1678,10 +1683,7 @@ static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) 
     const int dv = c.v_width, e = c.embed_dim, n = m->vis.n, D1 = m->vis.D1;
     const int Lv = m->vis.L;
     Tower& V = m->vis;
-    // VPT / MPT: the blocks' and the input prompt's gradients go straight into the gradient bucket (MuDPT: into the prompt learner's backward)
-    // UMuDPT: into dG, row group 0 the input prompt rows' gradient, 1 .. the deep prompts' (the generator's backward reads it)
-    float* d_deep = m->indep ? m->grads + m->v_deep_off : m->umudpt ? m->pg_dG + (size_t)n * dv : m->d_vis_deep;
-    float* d_p0 = m->indep ? m->grads + m->v_ctx_off : m->umudpt ? m->pg_dG : m->d_vprompt0;
+    const PromptRoute pr = prompt_route(m, V);
     TRY(launch_sgemm(false, true, B, dv, e, 1.f, m->dimg, e, m->vproj, e, 0.f, m->df_ln, dv, nullptr, s));
     LnBwdArgs bq; bq.dy = m->df_ln; bq.lddy = dv; bq.dy_f32 = true; bq.x = V.xout_sel; bq.ldx = dv; bq.mean = m->post_mean; bq.rstd = m->post_rstd;
     bq.gamma = m->ln_post_g; bq.dx = m->lp_grad ? nullptr : V.dsel; bq.lddx = dv; bq.dx_lp = V.dsel_lp; bq.lddx_lp = dv; bq.rows = B; bq.d = dv;
@@ -1696,7 +1698,7 @@ static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) 
         if (i == V.layers - 1) {
             TRY(block_bwd_tail(m, V, B, s));
             if (spliced) {  // the tail's ln_1 backward is not fused: take the rows from the stream
-                TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : V.dx, V.dx_lp, B, Lv, dv, Lv - n, n, d_deep + (size_t)(i - 1) * n * dv, true, false, unscale, s));
+                TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : V.dx, V.dx_lp, B, Lv, dv, Lv - n, n, pr.d_deep + (size_t)(i - 1) * n * dv, true, false, unscale, s));
             }
         } else {
             TRY(block_bwd(m, V, i, B, s, spliced ? m->vsplice + (size_t)(i - 1) * n * dv : nullptr, side_ldb));
@@ -1705,13 +1707,13 @@ static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) 
     {
         // blocks 1 .. layers-2 (the fused ones): rows 0 .. n (layers - 2) of every image's side block
         const int fused = (V.layers - 2 < D1 ? V.layers - 2 : D1) * n;
-        if (fused > 0) TRY(launch_reduce_rows(m->dtype, m->vsplice, nullptr, B, used, dv, 0, fused, d_deep, false, false, unscale, s));
+        if (fused > 0) TRY(launch_reduce_rows(m->dtype, m->vsplice, nullptr, B, used, dv, 0, fused, pr.d_deep, false, false, unscale, s));
     }
     // ln_pre backward on the prompt rows only (patch / CLS rows have no trainable ancestor), in place
     LnBwdArgs bp; bp.dy = m->lp_grad ? (const void*)V.dx_lp : (const void*)V.dx; bp.lddy = dv; bp.dy_f32 = !m->lp_grad; bp.x = m->xpre; bp.ldx = dv; bp.row_index = m->vprompt_rows; bp.mean = m->pre_mean; bp.rstd = m->pre_rstd;
     bp.gamma = m->ln_pre_g; bp.dx = V.dx; bp.lddx = dv; bp.rows = B * n; bp.d = dv; bp.by_token = true;
     TRY(launch_ln_bwd(m->dtype, bp, s));
-    TRY(launch_reduce_rows(m->dtype, V.dx, nullptr, B, Lv, dv, Lv - n, n, d_p0, false, false, unscale, s));
+    TRY(launch_reduce_rows(m->dtype, V.dx, nullptr, B, Lv, dv, Lv - n, n, pr.d_in0, false, false, unscale, s));
     return MUDPT_OK;
 }
 
@@ -1729,10 +1731,10 @@ static int prompt_learner_backward_text(mudpt_model* m, hipStream_t s) {
     const int used_t = (m->txt.layers - 1 < D1 ? m->txt.layers - 1 : D1) * n;
     if (used_t < R) HIP_TRY(hipMemsetAsync(m->d_txt_deep + (size_t)used_t * dt, 0, (size_t)(R - used_t) * dt * 4, s));
     // txt_deep = deep_prompts + visual_ctx_deep_projections(visual_ctx_deep_prompts)   (mudpt.py:175, clip/model.py:539)
-    TRY(launch_add(G + m->off[P_DEEP], m->d_txt_deep, G + m->off[P_DEEP], (size_t)R * dt, s));
-    TRY(launch_sgemm(true, false, e, dv, R, 1.f, m->d_txt_deep, e, Pm + m->off[P_VDEEP], dv, 1.f, G + m->off[P_VW], dv, nullptr, s));
-    TRY(launch_colsum(m->d_txt_deep, R, e, e, G + m->off[P_VB], true, s));
-    TRY(launch_sgemm(false, false, R, dv, e, 1.f, m->d_txt_deep, e, Pm + m->off[P_VW], dv, 1.f, G + m->off[P_VDEEP], dv, nullptr, s));
+    TRY(launch_add(G + m->off(P_DEEP), m->d_txt_deep, G + m->off(P_DEEP), (size_t)R * dt, s));
+    TRY(launch_sgemm(true, false, e, dv, R, 1.f, m->d_txt_deep, e, Pm + m->off(P_VDEEP), dv, 1.f, G + m->off(P_VW), dv, nullptr, s));
+    TRY(launch_colsum(m->d_txt_deep, R, e, e, G + m->off(P_VB), true, s));
+    TRY(launch_sgemm(false, false, R, dv, e, 1.f, m->d_txt_deep, e, Pm + m->off(P_VW), dv, 1.f, G + m->off(P_VDEEP), dv, nullptr, s));
     return MUDPT_OK;
 }
 static int prompt_learner_backward_vision(mudpt_model* m, hipStream_t s) {
@@ -1740,19 +1742,19 @@ static int prompt_learner_backward_vision(mudpt_model* m, hipStream_t s) {
     const int dv = c.v_width, dt = c.t_width, n = c.n_ctx, D1 = c.depth - 1;
     float *Pm = m->params, *G = m->grads;
     // visual_ctx and shared = embed_projection(ctx) both receive d_vprompt0 (clip/model.py:534)
-    TRY(launch_add(G + m->off[P_VCTX], m->d_vprompt0, G + m->off[P_VCTX], (size_t)n * dv, s));
-    TRY(launch_sgemm(true, false, dv, dt, n, 1.f, m->d_vprompt0, dv, Pm + m->off[P_CTX], dt, 1.f, G + m->off[P_EW], dt, nullptr, s));
-    TRY(launch_colsum(m->d_vprompt0, n, dv, dv, G + m->off[P_EB], true, s));
-    TRY(launch_sgemm(false, false, n, dt, dv, 1.f, m->d_vprompt0, dv, Pm + m->off[P_EW], dt, 1.f, G + m->off[P_CTX], dt, nullptr, s));
+    TRY(launch_add(G + m->off(P_VCTX), m->d_vprompt0, G + m->off(P_VCTX), (size_t)n * dv, s));
+    TRY(launch_sgemm(true, false, dv, dt, n, 1.f, m->d_vprompt0, dv, Pm + m->off(P_CTX), dt, 1.f, G + m->off(P_EW), dt, nullptr, s));
+    TRY(launch_colsum(m->d_vprompt0, n, dv, dv, G + m->off(P_EB), true, s));
+    TRY(launch_sgemm(false, false, n, dt, dv, 1.f, m->d_vprompt0, dv, Pm + m->off(P_EW), dt, 1.f, G + m->off(P_CTX), dt, nullptr, s));
     if (D1 > 0) {
         const int R = D1 * n;
         const int used_v = (m->vis.layers - 1 < D1 ? m->vis.layers - 1 : D1) * n;
         if (used_v < R) HIP_TRY(hipMemsetAsync(m->d_vis_deep + (size_t)used_v * dv, 0, (size_t)(R - used_v) * dv * 4, s));
         // vis_deep = deep_projections(deep_prompts) + visual_ctx_deep_prompts   (clip/model.py:537, mudpt.py:127)
-        TRY(launch_add(G + m->off[P_VDEEP], m->d_vis_deep, G + m->off[P_VDEEP], (size_t)R * dv, s));
-        TRY(launch_sgemm(true, false, dv, dt, R, 1.f, m->d_vis_deep, dv, Pm + m->off[P_DEEP], dt, 1.f, G + m->off[P_DW], dt, nullptr, s));
-        TRY(launch_colsum(m->d_vis_deep, R, dv, dv, G + m->off[P_DB], true, s));
-        TRY(launch_sgemm(false, false, R, dt, dv, 1.f, m->d_vis_deep, dv, Pm + m->off[P_DW], dt, 1.f, G + m->off[P_DEEP], dt, nullptr, s));
+        TRY(launch_add(G + m->off(P_VDEEP), m->d_vis_deep, G + m->off(P_VDEEP), (size_t)R * dv, s));
+        TRY(launch_sgemm(true, false, dv, dt, R, 1.f, m->d_vis_deep, dv, Pm + m->off(P_DEEP), dt, 1.f, G + m->off(P_DW), dt, nullptr, s));
+        TRY(launch_colsum(m->d_vis_deep, R, dv, dv, G + m->off(P_DB), true, s));
+        TRY(launch_sgemm(false, false, R, dt, dv, 1.f, m->d_vis_deep, dv, Pm + m->off(P_DW), dt, 1.f, G + m->off(P_DEEP), dt, nullptr, s));
     }
     return MUDPT_OK;
 }
@@ -1771,31 +1773,23 @@ static int umudpt_backward(mudpt_model* m, hipStream_t s) {
     // layers >= depth never consume a prompt: their rows of dG get no gradient from the tower
     const int used = (1 + (m->vis.layers - 1 < c.depth - 1 ? m->vis.layers - 1 : c.depth - 1)) * n;
     if (used < R) HIP_TRY(hipMemsetAsync(m->pg_dG + (size_t)used * dv, 0, (size_t)(R - used) * dv * 4, s));
-    TRY(pg_backward(c.depth, n, dt, dv, pg_params(Pm + m->off[2], dt, dv), Pm + m->off[P_CTX], m->pg_dG, m->pg_dX, G + m->off[2], m->pg_w, s));
-    return launch_add(G + m->off[P_CTX], m->pg_dX, G + m->off[P_CTX], (size_t)R * dt, s);  // ctx and deep_prompts lie one behind the other
+    TRY(pg_backward(c.depth, n, dt, dv, pg_params(Pm + m->off(U_GEN), dt, dv), Pm + m->off(P_CTX), m->pg_dG, m->pg_dX, G + m->off(U_GEN), m->pg_w, s));
+    return launch_add(G + m->off(P_CTX), m->pg_dX, G + m->off(P_CTX), (size_t)R * dt, s);  // ctx and deep_prompts lie one behind the other
 }
 
-// VPT / MPT (trainers/vpt.py:168-200, mpt.py:224-256): forward, cross-entropy, backward straight into the gradient bucket.  VPT: the text
-// tower runs on the first step only (its features depend on no trainable), the head skips its text half, and the step is vision forward,
-// head and vision backward.  MPT: both towers' backward, concurrently as MuDPT's; with the vanilla vision tower (no vision prompt) the text
-// tower's backward alone.
-static int indep_forward_backward(mudpt_model* m, const float* images, const int64_t* labels, int B, float grad_scale, float* loss, float* logits,
-                                  hipStream_t s) {
-    const bool reuse = m->vpt && m->text_valid;
-    TRY(towers_forward(m, images, B, s, reuse));
-    HIP_TRY(hipMemsetAsync(m->grads, 0, m->total * 4, s));
-    TRY(head_train(m, labels, B, grad_scale, loss, logits, s, reuse, !m->vpt));
-    if (m->vpt) return vision_backward(m, B, m->cp_unscale, s);
-    if (!m->vis.head_rows) return text_backward(m, m->cp_unscale, s);
-    HIP_TRY(hipEventRecord(m->ev_fork_b, s));
-    HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork_b, 0));
-    TRY(text_backward(m, m->cp_unscale, m->s2));
-    HIP_TRY(hipEventRecord(m->ev_join_b, m->s2));
-    TRY(vision_backward(m, B, m->cp_unscale, s));
-    HIP_TRY(hipStreamWaitEvent(s, m->ev_join_b, 0));
-    return MUDPT_OK;
+// The one place a variant names its learner: CoOp / VPT / MPT have none, their trainables go into the towers as they are
+// (trainers/coop.py:166-175); CoCoOp's meta_net is part of its own step
+static Learner learner(const mudpt_model* m) {
+    Learner L;
+    if (m->umudpt) { L.fwd_vision = umudpt_forward; L.bwd = umudpt_backward; }
+    else if (!m->cocoop && !m->coop && !m->indep) { L.fwd = prompt_learner_forward; L.bwd_text = prompt_learner_backward_text; L.bwd = prompt_learner_backward_vision; }
+    return L;
 }
 
+// One training step of every variant but CoCoOp: forward, cross-entropy, the backward of each tower that has a trainable ancestor, the
+// learner's backward.  VPT (trainers/vpt.py:168-200): the text tower runs on the first step only (its features depend on no trainable), the
+// head skips its text half, and the step is vision forward, head and vision backward.  A vanilla vision tower (CoOp, trainers/coop.py:281-296;
+// MPT without a vision prompt, mpt.py:224-256): the text tower's backward alone, on the main stream.
 extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const int64_t* labels, int32_t B, float grad_scale,
                                       float* loss, float* logits, void* stream) {
     TRY(ready(m, B, true));
@@ -1804,22 +1798,22 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
     m->train_fwd = true;
     if (m->cocoop) return cocoop_forward_backward(m, images, labels, B, grad_scale, loss, logits, s);
     TRY(not_sharded(m, "forward_backward"));
-    if (m->indep) return indep_forward_backward(m, images, labels, B, grad_scale, loss, logits, s);
-    TRY(towers_forward(m, images, B, s, false));
+    const Learner L = learner(m);
+    const bool reuse = m->vpt && m->text_valid;
+    TRY(towers_forward(m, images, B, s, reuse));
     HIP_TRY(hipMemsetAsync(m->grads, 0, m->total * 4, s));
-    TRY(head_train(m, labels, B, grad_scale, loss, logits, s));
-    // CoOp (trainers/coop.py:281-296): only the context is trainable, and it feeds the text tower alone -- no vision backward, no
-    // prompt-learner GEMMs: the text tower's backward and the context gradient, on the main stream
-    if (m->coop) return text_backward(m, m->cp_unscale, s);
-    // text tower backward on the side stream (enqueued first; joins before the prompt-learner backward)
+    TRY(head_train(m, labels, B, grad_scale, loss, logits, s, reuse, !m->vpt));
+    if (m->vpt) return vision_backward(m, B, m->cp_unscale, s);
+    if (!m->vis.head_rows) return text_backward(m, m->cp_unscale, s);
+    // text tower backward on the side stream (enqueued first; joins before the learner's backward)
     HIP_TRY(hipEventRecord(m->ev_fork_b, s));
     HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork_b, 0));
     TRY(text_backward(m, m->cp_unscale, m->s2));
-    if (!m->umudpt) TRY(prompt_learner_backward_text(m, m->s2));
+    if (L.bwd_text) TRY(L.bwd_text(m, m->s2));
     HIP_TRY(hipEventRecord(m->ev_join_b, m->s2));
     TRY(vision_backward(m, B, m->cp_unscale, s));
     HIP_TRY(hipStreamWaitEvent(s, m->ev_join_b, 0));
-    return m->umudpt ? umudpt_backward(m, s) : prompt_learner_backward_vision(m, s);
+    return L.bwd ? L.bwd(m, s) : MUDPT_OK;
 }
 
 // ---- class-parallel phases (SURVEY 8e second axis; the reference runs all C prompts on every replica, trainers/mudpt.py:142-156,230-233) ----
@@ -1844,9 +1838,14 @@ extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
     m->cp_stage = 0;
     return MUDPT_OK;
 }
+// the class-parallel phases' refusal of every variant but MuDPT (CoCoOp: the phases' own argument checks)
+static int cp_mudpt_only(const mudpt_model* m, const char* what) {
+    ARG_CHECK(!(m && (m->coop || m->indep || m->umudpt)), "%s: not a MuDPT model (the class-parallel phases run MuDPT only)", what);
+    return MUDPT_OK;
+}
 extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, size_t* numel) {
     ARG_CHECK(m && !m->cocoop, "cp_buffers: not a MuDPT model");
-    ARG_CHECK(!m->coop && !m->indep && !m->umudpt, "cp_buffers: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    TRY(cp_mudpt_only(m, "cp_buffers"));
     if (feat) *feat = m->txt_f;
     if (dfeat) *dfeat = m->dtxt;
     if (numel) *numel = (size_t)m->cfg.n_cls * m->cfg.embed_dim;
@@ -1854,7 +1853,7 @@ extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, siz
 }
 extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, int32_t flags, void* stream) {
     TRY(ready(m, B, false));
-    ARG_CHECK(!m->coop && !m->indep && !m->umudpt, "cp_forward: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    TRY(cp_mudpt_only(m, "cp_forward"));
     ARG_CHECK(images && !m->cocoop, "cp_forward: null images / not a MuDPT model");
     const bool reuse = (flags & MUDPT_FWD_REUSE_TEXT) != 0;
     if (reuse && !m->text_valid) { set_error("cp_forward: MUDPT_FWD_REUSE_TEXT before any text-tower pass"); return MUDPT_ERR_STATE; }
@@ -1865,7 +1864,7 @@ extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, 
 }
 extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, float grad_scale, float* loss, float* logits, int32_t flags, void* stream) {
     TRY(ready(m, B, labels != nullptr));
-    ARG_CHECK(!m->coop && !m->indep && !m->umudpt, "cp_head: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    TRY(cp_mudpt_only(m, "cp_head"));
     ARG_CHECK(!m->cocoop && (labels ? loss != nullptr : logits != nullptr), "cp_head: training needs labels and loss, inference needs logits");
     if (m->cp_stage < 1 || m->cp_B != B) { set_error("cp_head: call mudpt_cp_forward with the same batch first"); return MUDPT_ERR_STATE; }
     hipStream_t s = (hipStream_t)stream;
@@ -1881,7 +1880,7 @@ extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, f
     return MUDPT_OK;
 }
 extern "C" int mudpt_cp_backward(mudpt_model* m, int32_t part, void* stream) {
-    ARG_CHECK(!(m && (m->coop || m->indep || m->umudpt)), "cp_backward: not a MuDPT model (the class-parallel phases run MuDPT only)");
+    TRY(cp_mudpt_only(m, "cp_backward"));
     ARG_CHECK(m && !m->cocoop && (part == MUDPT_CP_VISION || part == MUDPT_CP_TEXT), "cp_backward: part must be MUDPT_CP_VISION or MUDPT_CP_TEXT");
     hipStream_t s = (hipStream_t)stream;
     if (part == MUDPT_CP_VISION) {
