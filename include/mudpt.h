@@ -311,16 +311,31 @@ int mudpt_attention_fwd(int32_t dtype, const void* qkv, void* out, float* lse, i
  * fp16 = 2 ld_out bytes, 0 = H*64), lse, and -- if qkv_lp is not NULL -- the fp16 copy of q | k | v the backward kernels read. */
 int mudpt_attention_fwd_exact(const float* qkv32, void* qkv_lp, void* out_hi, void* out_lo, int32_t lo_mode, int32_t ld_out, float* lse, int32_t B,
                               int32_t L, int32_t H, int32_t causal, void* stream);
-/* causal: bit 0 = causal mask.  Kernel choice (tests / A-B).  Default: padded length <= 96 (the text tower): the fused two-sweep pass over
- * resident Q, K, V, dO; longer non-causal sequences up to 224 (the vision tower): the single-sweep kernel (S, dP, exp computed once, dS
- * crosses LDS for dQ); otherwise a dQ kernel + dK/dV kernel pair (delta through `delta`): for L > 224 the resident pair while both operands of a
- * (sequence, head) fit LDS (L <= 608), else (and for the window form, and with bit 1) the staged pair.  bit 1 = force the (staged) two kernels, bit 3 = force the
- * fused two-sweep pass, bit 2 = the same with two 16-row blocks per wave, bit 4 = force the single sweep (non-causal, L <= 224).
- * Window form (block 0 of a tower needs its input gradient on the prompt rows only): bits 20-27 = n > 0 wanted rows per sequence starting
- * at row bits 8-19.  The 16-row blocks (L > 224: 128-row groups) holding a wanted row are computed exactly as without the window; all other
- * rows of dqkv are left unwritten. */
+/* causal: bit 0 = causal mask; the other bits choose among kernels that compute the same gradients (tests / A-B): bit 1 = two kernels, bit 3 =
+ * force the fused pass, bit 2 = the same with two 16-row blocks per wave, bit 4 = sweep, bits 20-27 = n > 0: the window form on the n rows
+ * per sequence from row bits 8-19 on (block 0 of a tower needs its input gradient on the prompt rows only: the 16-row blocks -- L > 224:
+ * 128-row groups -- that hold a wanted row are computed exactly as without the window, all other rows of dqkv are left unwritten).
+ * Which form runs (mudpt_attention_form names it; the kernels behind each: mudpt_amd/csrc/attention.hip):
+ *   L <= 224, the first rule that matches:  1. one wanted row (mudpt_attention_bwd_sel), a window, or bit 1 -> TWO (dQ kernel + dK/dV kernel)
+ *      2. bit 3 or 2 -> FUSED_W2, with bit 2 FUSED_W1 (bit 4 loses)   3. non-causal and (L >= 97 or bit 4) -> SWEEP (the vision tower)
+ *      4. L <= 96 -> FUSED_W2 (the text tower; FUSED_W1 under the model knob attn_fused_w1)   5. causal, 97 .. 224 -> TWO
+ *   L > 224:  L <= 608 (both operands of a (sequence, head) pair fit LDS) and none of rule 1 -> RESIDENT, else STAGED; bits 2 - 4 are ignored. */
 int mudpt_attention_bwd(int32_t dtype, const void* qkv, const void* out, const void* dout, const float* lse,
                         float* delta, void* dqkv, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream);
+/* HOST arithmetic only: the form mudpt_attention_fwd (bwd = 0; L <= 224: PAIR if causal, else PERSISTENT, bit 1 ignored; 225 .. 640: RESIDENT,
+ * with bit 1 STAGED; beyond: STAGED) or mudpt_attention_bwd (bwd != 0; sel != 0: mudpt_attention_bwd_sel) runs for sequence length L and the
+ * `causal` argument `flags`.  -1 for L outside 1 .. 4096. */
+#define MUDPT_ATTN_FWD_PAIR 0       /* attn_fwd_pair_kernel: one workgroup per pair */
+#define MUDPT_ATTN_FWD_PERSISTENT 1 /* attn_fwd_kernel: resident workgroups walk the pairs */
+#define MUDPT_ATTN_FWD_RESIDENT 2   /* attn_fwd_resident_kernel: K and V of a pair in one CU's whole LDS */
+#define MUDPT_ATTN_FWD_STAGED 3     /* attn_fwd_tiled_kernel: K and V stream through 64-row stages */
+#define MUDPT_ATTN_BWD_TWO 4        /* attn_bwd_dq_kernel + attn_bwd_dkv_kernel */
+#define MUDPT_ATTN_BWD_FUSED_W2 5   /* attn_bwd_fused_kernel, one 16-row block per wave */
+#define MUDPT_ATTN_BWD_FUSED_W1 6   /* attn_bwd_fused_kernel, two 16-row blocks per wave */
+#define MUDPT_ATTN_BWD_SWEEP 7      /* attn_bwd_sweep_kernel */
+#define MUDPT_ATTN_BWD_RESIDENT 8   /* attn_bwd_dq_resident_kernel + attn_bwd_dkv_resident_kernel */
+#define MUDPT_ATTN_BWD_STAGED 9     /* attn_bwd_dq_tiled_kernel + attn_bwd_dkv_tiled_kernel */
+int mudpt_attention_form(int32_t bwd, int32_t L, int32_t flags, int32_t sel);
 /* Single-query attention of a tower's LAST block (only the CLS / EOT row of its output is used, clip/model.py:549, trainers/mudpt.py:154):
  * one query per sequence -- q_sel [B, H*64], the query of token row sel_rows[b] (= b * L + position) -- against the K / V thirds of the
  * packed qkv buffer (causal: keys 0 .. position).  Forward: out_sel [B, H*64], lse_sel [B, H].  Backward: dq_sel [B, H*64] and the k, v

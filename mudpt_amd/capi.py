@@ -14,6 +14,9 @@ VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARI
 CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = 0, 1, 2  # TRAINER.COOP.CLASS_TOKEN_POSITION "end" / "middle" / "front"
 ABI_VERSION = 7
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = range(6)
+# mudpt_attention_form's codes (include/mudpt.h MUDPT_ATTN_*), by name
+ATTN_FORMS = ("FWD_PAIR", "FWD_PERSISTENT", "FWD_RESIDENT", "FWD_STAGED", "BWD_TWO", "BWD_FUSED_W2", "BWD_FUSED_W1", "BWD_SWEEP", "BWD_RESIDENT",
+              "BWD_STAGED")
 
 
 class MudptError(RuntimeError):
@@ -76,6 +79,7 @@ SIGNATURES = {
                                    _i32, _i32, _i32, _vp]),
     "mudpt_attention_padded_len": (_i32, [_i32]),
     "mudpt_attention_fwd": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_attention_form": (_i32, [_i32, _i32, _i32, _i32]),
     "mudpt_attention_fwd_exact": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mudpt_attention_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mudpt_attention_fwd_single": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -8,12 +8,13 @@
 //
 // v_mfma_f32_16x16x32 everywhere (A: row = lane & 15, k = 8 (lane >> 4) + j; B: k likewise, col = lane & 15;
 // C/D: col = lane & 15, row = 4 (lane >> 4) + r).  With 16-row blocks a block's whole score column set is 14 x 4
-// registers, so a wave needs ~100 VGPRs and two workgroups (14 waves) share a CU and hide each other's latency.
+// registers, so a wave needs ~100 VGPRs; how many workgroups then share a CU is each form's own matter (its LDS per
+// workgroup: the *_cfg launchers at the end of this file, and the comment on each kernel).
 //
-// LDS holds ONLY row-major images [rows][64] with a 160-byte row stride: conflict-free both for ds_read_b128 row
-// fragments and for ds_read_b64_tr_b16, the hardware-transposed read that produces the operand of the products
-// contracting over the image's ROW index (P.V over keys, dS^T.K over keys, dO^T.P and Q^T.dS over queries):
-// no transposed copy is ever staged.
+// LDS holds ONLY row-major images [rows][64] with dense 128-byte rows (RS = 64): the 16-byte chunk c of row r sits in slot
+// c ^ (r & 7).  That XOR swizzle is conflict-free both for ds_read_b128 row fragments and for ds_read_b64_tr_b16, the
+// hardware-transposed read that produces the operand of the products contracting over the image's ROW index (P.V over
+// keys, dS^T.K over keys, dO^T.P and Q^T.dS over queries): no transposed copy is ever staged.
 //   fwd / dq pass -- "query on the lane":  S^T = K Q^T (A = K rows, B = Q fragment from HBM); a query's scores are
 //     in 4 lanes (lane, ^16, ^32, ^48), softmax needs two xor-shuffles; the converted accumulators of two
 //     consecutive 16-key tiles are directly the B operand of O^T = V^T P^T / dQ^T = K^T dS^T (the contraction index
@@ -23,6 +24,20 @@
 //     dV^T += dO^T P, dK^T += Q^T dS.
 // dQ comes from its own sweep instead of atomics or a cross-wave reduction: bitwise reproducible, at the price of
 // recomputing S and dP once (attention is < 10 % of the step's FLOPs).
+//
+// The forms (kernels.h AttnForm).  attn_form() below decides which one a launch runs -- every threshold and A/B switch is there and
+// nowhere else -- and the launchers only pick the instantiation (T, NC = padded length / 32, mask) of the form it returns:
+//   FWD_PAIR        attn_fwd_pair_kernel                                     one workgroup per pair (causal, L <= 224: the text tower)
+//   FWD_PERSISTENT  attn_fwd_kernel                                          resident workgroups walk the pairs (non-causal, L <= 224: vision)
+//   FWD_RESIDENT    attn_fwd_resident_kernel (attention_resident.hip)        K | V of a pair in one CU's whole LDS (224 < L <= 640)
+//   FWD_STAGED      attn_fwd_tiled_kernel                                    K | V through 64-row stages (longer, or by switch)
+//   BWD_TWO         attn_bwd_dq_kernel + attn_bwd_dkv_kernel                 L <= 224: causal above 96 rows, one wanted row, the window form
+//   BWD_FUSED_W2    attn_bwd_fused_kernel<.., 2>                             Q, K, V, dO resident, two sweeps (padded length <= 96: the text tower)
+//   BWD_FUSED_W1    attn_bwd_fused_kernel<.., 1>                             the same with two 16-row blocks per wave (switch only)
+//   BWD_SWEEP       attn_bwd_sweep_kernel                                    S, dP, exp once, dS through LDS (non-causal, 97 <= L <= 224: vision)
+//   BWD_RESIDENT    attn_bwd_dq_resident_kernel + attn_bwd_dkv_resident_kernel (attention_resident.hip)   224 < L <= 608
+//   BWD_STAGED      attn_bwd_dq_tiled_kernel + attn_bwd_dkv_tiled_kernel     longer, one wanted row, the window form, or by switch
+// mudpt_attention_form (include/mudpt.h) exports the decision; tests/test_capi_cpu.py holds it to a table.
 #include "kernels.h"
 
 namespace mudpt {
@@ -1226,30 +1241,23 @@ __global__ __launch_bounds__(TW * 64) void attn_bwd_dkv_tiled_kernel(AttnArgs p,
     }
 }
 
+// the staged forms (FWD_STAGED / BWD_STAGED): one workgroup per TROWS-query (backward dK/dV: TROWS-key) group of a pair
 template <typename T, bool BWD>
-static int tiled_launch(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
+static int staged_launch(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
     const LaunchProf p1{prof ? prof->start : nullptr, nullptr}, p2{nullptr, prof ? prof->stop : nullptr};
     const int nsb = (a.L + TROWS - 1) / TROWS;
     const size_t nwg = (size_t)a.B * a.H * nsb;
     ARG_CHECK(nwg < 0x7fffffffull, "attention: too many workgroups (%zu)", nwg);
     const dim3 grid((unsigned)nwg), block(TW * 64);
     if (!BWD) {
-        if (!a.tiled_fwd_16 && attn_resident_fits(a.L, false)) {  // K and V of a pair fit one CU's LDS (L <= 640): one workgroup per pair
-            return launch_attn_fwd_resident(T::id, a, s, prof);
-        } else {  // the staged 16-query-block form
-            if (a.causal) MUDPT_LAUNCH((attn_fwd_tiled_kernel<T, true>), grid, block, 0, s, prof, a, nsb);
-            else MUDPT_LAUNCH((attn_fwd_tiled_kernel<T, false>), grid, block, 0, s, prof, a, nsb);
-        }
-    } else if (!a.two_kernels && !a.sel_rows && a.win_n <= 0 && attn_resident_fits(a.L, true)) {
-        return launch_attn_bwd_resident(T::id, a, s, prof);
+        if (a.causal) MUDPT_LAUNCH((attn_fwd_tiled_kernel<T, true>), grid, block, 0, s, prof, a, nsb);
+        else MUDPT_LAUNCH((attn_fwd_tiled_kernel<T, false>), grid, block, 0, s, prof, a, nsb);
+    } else if (a.causal) {
+        MUDPT_LAUNCH((attn_bwd_dq_tiled_kernel<T, true>), grid, block, 0, s, &p1, a, (const void*)a.out, nsb);
+        MUDPT_LAUNCH((attn_bwd_dkv_tiled_kernel<T, true>), grid, block, 0, s, &p2, a, nsb);
     } else {
-        if (a.causal) {
-            MUDPT_LAUNCH((attn_bwd_dq_tiled_kernel<T, true>), grid, block, 0, s, &p1, a, (const void*)a.out, nsb);
-            MUDPT_LAUNCH((attn_bwd_dkv_tiled_kernel<T, true>), grid, block, 0, s, &p2, a, nsb);
-        } else {
-            MUDPT_LAUNCH((attn_bwd_dq_tiled_kernel<T, false>), grid, block, 0, s, &p1, a, (const void*)a.out, nsb);
-            MUDPT_LAUNCH((attn_bwd_dkv_tiled_kernel<T, false>), grid, block, 0, s, &p2, a, nsb);
-        }
+        MUDPT_LAUNCH((attn_bwd_dq_tiled_kernel<T, false>), grid, block, 0, s, &p1, a, (const void*)a.out, nsb);
+        MUDPT_LAUNCH((attn_bwd_dkv_tiled_kernel<T, false>), grid, block, 0, s, &p2, a, nsb);
     }
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -1270,37 +1278,46 @@ static int check(const AttnArgs& a, bool bwd) {
     return MUDPT_OK;
 }
 
-template <typename K>
-static int set_lds(K kern, int bytes) {
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    return MUDPT_OK;
+// Who runs when.  Up to L = 224 (padded: 7 x 32 rows) a pair's operand images fit LDS beside the kernel's working set: the whole-pair
+// kernels of this file (the resident forms measured 28 / 52 % slower at L = 201).  Beyond that the other operand either stays resident
+// in a CU's whole LDS -- Lp x 256 bytes forward (L <= 640), + 8 Lp for lse | delta backward (L <= 608) -- or streams through 64-row stages.
+constexpr int WHOLE_PAIR_MAX_L = 224, CU_LDS = 160 * 1024;
+AttnForm attn_form(const AttnArgs& a, const AttnOpts& o, bool bwd) {
+    const int Lp = attn_padded_len(a.L);
+    if (!bwd) {
+        if (a.L <= WHOLE_PAIR_MAX_L) return a.causal ? FWD_PAIR : FWD_PERSISTENT;
+        return !o.tiled_fwd_16 && Lp * 256 <= CU_LDS ? FWD_RESIDENT : FWD_STAGED;
+    }
+    // one wanted row per sequence and the window form exist in the two-kernel forms only
+    const bool two = a.sel_rows || a.win_n > 0 || o.two_kernels;
+    if (a.L > WHOLE_PAIR_MAX_L) return !two && Lp * (256 + 8) <= CU_LDS ? BWD_RESIDENT : BWD_STAGED;
+    if (two) return BWD_TWO;
+    const AttnForm fused = o.fused_w1 ? BWD_FUSED_W1 : BWD_FUSED_W2;
+    if (o.force_fused) return fused;
+    if (!a.causal && (Lp >= 128 || o.sweep)) return BWD_SWEEP;  // the vision tower
+    return Lp <= 96 ? fused : BWD_TWO;                          // the text tower: several workgroups of the fused form share a CU
 }
 
-template <typename T, int NC, bool CAUSAL>
+template <typename T, int NC>
 static int fwd_pair_cfg(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
     constexpr int lds = 2 * NC * 32 * RS * 2 + NC * 32 * 4;
-    auto kern = attn_fwd_pair_kernel<T, NC, CAUSAL>;
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) { if (int e = set_lds(kern, lds)) return e; pd.done[dev] = true; }
+    constexpr auto kern = attn_fwd_pair_kernel<T, NC, true>;
+    // Never launched, but kept in the code object: it shares fwd_qblock / fwd_scores / fwd_pv_store with the pair kernel, and without it the
+    // compiler schedules the pair kernel differently (up to 29 more instructions at NC = 7; 0.5 % of a batch-4 step).
+    [[maybe_unused]] constexpr auto keep = attn_fwd_kernel<T, NC, true>;
+    if (int e = lds_limit_once<kern>(current_device(), lds)) return e;
     MUDPT_LAUNCH(kern, dim3(a.B * a.H), dim3(NC * 64), lds, s, prof, a);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }
 
-template <typename T, int NC, bool CAUSAL>
+template <typename T, int NC>
 static int fwd_cfg(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
-    if constexpr (CAUSAL) return fwd_pair_cfg<T, NC, CAUSAL>(a, s, prof);
     constexpr int lds = 4 * NC * 32 * 128 + NC * 32 * 4;  // two (K, V) image pairs + the key mask
-    auto kern = attn_fwd_kernel<T, NC, CAUSAL>;
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) {
-        if (int e = set_lds(kern, lds)) return e;
-        HIP_TRY(hipDeviceGetAttribute(&pd.ncu[dev], hipDeviceAttributeMultiprocessorCount, dev));
-        pd.done[dev] = true;
-    }
-    const int ncu = pd.ncu[dev];
+    constexpr auto kern = attn_fwd_kernel<T, NC, false>;
+    const int dev = current_device(), ncu = device_cus(dev);
+    if (ncu <= 0) return MUDPT_ERR_HIP;
+    if (int e = lds_limit_once<kern>(dev, lds)) return e;
     const int npairs = a.B * a.H, per_cu = 163840 / lds > 0 ? 163840 / lds : 1;
     const int cap = ncu * (per_cu * 2 * NC <= 32 ? per_cu : 32 / (2 * NC));  // resident workgroups: LDS and the 32-wave limit
     MUDPT_LAUNCH(kern, dim3(npairs < cap ? npairs : cap), dim3(NC * 128), lds, s, prof, a, npairs);
@@ -1313,37 +1330,29 @@ static int bwd_cfg(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
     const LaunchProf p1{prof ? prof->start : nullptr, nullptr}, p2{nullptr, prof ? prof->stop : nullptr};
     constexpr int lds1 = 2 * NC * 32 * RS * 2 + NC * 32 * 4;
     constexpr int lds2 = 2 * NC * 32 * RS * 2 + 2 * NC * 32 * 4;
-    auto k1 = attn_bwd_dq_kernel<T, NC, CAUSAL>;
-    auto k2 = attn_bwd_dkv_kernel<T, NC, CAUSAL>;
-    static PerDevice pd;
+    constexpr auto k1 = attn_bwd_dq_kernel<T, NC, CAUSAL>;
+    constexpr auto k2 = attn_bwd_dkv_kernel<T, NC, CAUSAL>;
     const int dev = current_device();
-    if (!pd.done[dev]) {
-        if (int e = set_lds(k1, lds1)) return e;
-        if (int e = set_lds(k2, lds2)) return e;
-        pd.done[dev] = true;
-    }
+    if (int e = lds_limit_once<k1>(dev, lds1)) return e;
+    if (int e = lds_limit_once<k2>(dev, lds2)) return e;
     MUDPT_LAUNCH(k1, dim3(a.B * a.H), dim3(NC * 64), lds1, s, &p1, a, (const void*)a.out);
     MUDPT_LAUNCH(k2, dim3(a.B * a.H), dim3(NC * 64), lds2, s, &p2, a);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }
 
-// fused backward (one resident pass): everything except the sel_rows form of the last block
+// fused backward (one resident pass)
 template <typename T, int NC, bool CAUSAL, int W2>
 static int bwd_fused_cfg(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
     constexpr int lds = 4 * NC * 32 * 128 + 3 * NC * 32 * 4;
-    auto kern = attn_bwd_fused_kernel<T, NC, CAUSAL, W2>;
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) {
-        if (int e = set_lds(kern, lds)) return e;
-        HIP_TRY(hipDeviceGetAttribute(&pd.ncu[dev], hipDeviceAttributeMultiprocessorCount, dev));
-        pd.done[dev] = true;
-    }
+    constexpr auto kern = attn_bwd_fused_kernel<T, NC, CAUSAL, W2>;
+    const int dev = current_device(), ncu = device_cus(dev);
+    if (ncu <= 0) return MUDPT_ERR_HIP;
+    if (int e = lds_limit_once<kern>(dev, lds)) return e;
     const int npairs = a.B * a.H, by_lds = 163840 / lds, by_waves = 32 / (NC * W2);
     int per_cu = by_lds < by_waves ? by_lds : by_waves;
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int cap = pd.ncu[dev] * per_cu;
+    const int cap = ncu * per_cu;
     MUDPT_LAUNCH(kern, dim3(npairs < cap ? npairs : cap), dim3(NC * 64 * W2), lds, s, prof, a, (const void*)a.out, npairs);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -1354,57 +1363,57 @@ template <typename T, int NC>
 static int bwd_sweep_cfg(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
     constexpr int lds = 2 * NC * 32 * 128 + NC * 32 * NC * 32 * 2 + 2 * NC * 32 * 4;
     static_assert(lds <= 163840, "attn_bwd_sweep_kernel: LDS");
-    auto kern = attn_bwd_sweep_kernel<T, NC>;
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) { if (int e = set_lds(kern, lds)) return e; pd.done[dev] = true; }
+    constexpr auto kern = attn_bwd_sweep_kernel<T, NC>;
+    if (int e = lds_limit_once<kern>(current_device(), lds)) return e;
     MUDPT_LAUNCH(kern, dim3(a.B * a.H), dim3(NC * 128), lds, s, prof, a, (const void*)a.out);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }
 
-template <typename T, bool BWD>
-static int dispatch(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
-    if (a.L > 224) return tiled_launch<T, BWD>(a, s, prof);  // the other operand streams through 64-row stages
-    const int nc = attn_padded_len(a.L) / 32;
-#define MUDPT_ATTN_CASE(N)                                                                     \
-    case N:                                                                                    \
-        if (BWD && a.win_n > 0 && !a.sel_rows) return a.causal ? bwd_cfg<T, N, true>(a, s, prof) : bwd_cfg<T, N, false>(a, s, prof); /* window: two kernels */ \
-        if (BWD && !a.sel_rows && !a.causal && !a.two_kernels && !a.force_fused && (N >= 4 || a.sweep)) return bwd_sweep_cfg<T, N>(a, s, prof); \
-        if (BWD && !a.sel_rows && !a.two_kernels && (N <= 3 || a.force_fused)) {                   \
-            if (a.fused_w1) return a.causal ? bwd_fused_cfg<T, N, true, 1>(a, s, prof) : bwd_fused_cfg<T, N, false, 1>(a, s, prof); \
-            return a.causal ? bwd_fused_cfg<T, N, true, 2>(a, s, prof) : bwd_fused_cfg<T, N, false, 2>(a, s, prof); \
-        }                                                                                          \
-        if (a.causal) return BWD ? bwd_cfg<T, N, true>(a, s, prof) : fwd_cfg<T, N, true>(a, s, prof);      \
-        return BWD ? bwd_cfg<T, N, false>(a, s, prof) : fwd_cfg<T, N, false>(a, s, prof);
-    switch (nc) {
-        MUDPT_ATTN_CASE(1)
-        MUDPT_ATTN_CASE(2)
-        MUDPT_ATTN_CASE(3)
-        MUDPT_ATTN_CASE(4)
-        MUDPT_ATTN_CASE(5)
-        MUDPT_ATTN_CASE(6)
-        MUDPT_ATTN_CASE(7)
+// the whole-pair forms (L <= 224): the kernel instantiation of form f for NC = padded length / 32 and the mask
+template <typename T, int NC, bool CAUSAL>
+static int whole_pair_launch(AttnForm f, const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
+    switch (f) {
+        case FWD_PAIR: if constexpr (CAUSAL) return fwd_pair_cfg<T, NC>(a, s, prof); break;
+        case FWD_PERSISTENT: if constexpr (!CAUSAL) return fwd_cfg<T, NC>(a, s, prof); break;
+        case BWD_TWO: return bwd_cfg<T, NC, CAUSAL>(a, s, prof);
+        case BWD_FUSED_W2: return bwd_fused_cfg<T, NC, CAUSAL, 2>(a, s, prof);
+        case BWD_FUSED_W1: return bwd_fused_cfg<T, NC, CAUSAL, 1>(a, s, prof);
+        case BWD_SWEEP: if constexpr (!CAUSAL) return bwd_sweep_cfg<T, NC>(a, s, prof); break;
+        default: break;
     }
-#undef MUDPT_ATTN_CASE
-    set_error("attention: unsupported padded length %d", nc * 32);
+    set_error("attention: form %d does not run L=%d causal=%d", (int)f, a.L, (int)CAUSAL);
     return MUDPT_ERR_ARG;
 }
 
-int launch_attn_fwd(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
-    if (int e = check(a, false)) return e;
-    if (dtype == DT_BF16) return dispatch<BF16, false>(a, s, prof);
-    if (dtype == DT_F16) return dispatch<F16, false>(a, s, prof);
-    set_error("attention: unknown dtype %d", dtype);
+template <typename T>
+static int launch_form(const AttnArgs& a, hipStream_t s, const AttnOpts& o, bool bwd) {
+    const AttnForm f = attn_form(a, o, bwd);
+    switch (f) {
+        case FWD_RESIDENT: return launch_attn_fwd_resident(T::id, a, s, o);
+        case BWD_RESIDENT: return launch_attn_bwd_resident(T::id, a, s, o);
+        case FWD_STAGED: return staged_launch<T, false>(a, s, o.prof);
+        case BWD_STAGED: return staged_launch<T, true>(a, s, o.prof);
+        default: break;
+    }
+#define MUDPT_ATTN_NC(N) \
+    case N: return a.causal ? whole_pair_launch<T, N, true>(f, a, s, o.prof) : whole_pair_launch<T, N, false>(f, a, s, o.prof);
+    switch (attn_padded_len(a.L) / 32) {
+        MUDPT_ATTN_NC(1) MUDPT_ATTN_NC(2) MUDPT_ATTN_NC(3) MUDPT_ATTN_NC(4) MUDPT_ATTN_NC(5) MUDPT_ATTN_NC(6) MUDPT_ATTN_NC(7)
+    }
+#undef MUDPT_ATTN_NC
+    set_error("attention: unsupported padded length %d", attn_padded_len(a.L));
     return MUDPT_ERR_ARG;
 }
 
-int launch_attn_bwd(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
-    if (int e = check(a, true)) return e;
-    if (dtype == DT_BF16) return dispatch<BF16, true>(a, s, prof);
-    if (dtype == DT_F16) return dispatch<F16, true>(a, s, prof);
+static int launch_attn(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o, bool bwd) {
+    if (int e = check(a, bwd)) return e;
+    if (dtype == DT_BF16) return launch_form<BF16>(a, s, o, bwd);
+    if (dtype == DT_F16) return launch_form<F16>(a, s, o, bwd);
     set_error("attention: unknown dtype %d", dtype);
     return MUDPT_ERR_ARG;
 }
+int launch_attn_fwd(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o) { return launch_attn(dtype, a, s, o, false); }
+int launch_attn_bwd(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o) { return launch_attn(dtype, a, s, o, true); }
 
 }  // namespace mudpt

@@ -431,60 +431,43 @@ __global__ __launch_bounds__(RES_W_BWD * 64) void attn_bwd_dkv_resident_kernel(A
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-bool attn_resident_fits(int L, bool bwd) {
-    const int Lr = (L + 31) & ~31;
-    return L > 224 && Lr * (256 + (bwd ? 8 : 0)) <= RES_LDS_MAX;  // L <= 224: the whole-pair kernels of attention.hip (resident forms measured 28 / 52 % slower at L = 201)
-}
-
-template <typename T>
+// Lr x 256 bytes of K | V
+template <typename T, bool CAUSAL>
 static int fwd_resident(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
     const int Lr = (a.L + 31) & ~31, lds = Lr * 256;
     const int nqb = Lr / 32, nwv = nqb <= RES_W_MAX ? nqb : RES_W;  // one round if the blocks fit the workgroup, else 3 waves per SIMD
-    static PerDevice pd[2];
-    const int dev = current_device();
-    if (!pd[a.causal].done[dev]) {
-        const void* k = a.causal ? (const void*)attn_fwd_resident_kernel<T, true> : (const void*)attn_fwd_resident_kernel<T, false>;
-        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_MAX));
-        pd[a.causal].done[dev] = true;
-    }
-    if (a.causal) MUDPT_LAUNCH((attn_fwd_resident_kernel<T, true>), dim3(a.B * a.H), dim3(nwv * 64), lds, s, prof, a);
-    else MUDPT_LAUNCH((attn_fwd_resident_kernel<T, false>), dim3(a.B * a.H), dim3(nwv * 64), lds, s, prof, a);
+    constexpr auto kern = attn_fwd_resident_kernel<T, CAUSAL>;
+    if (int e = lds_limit_once<kern>(current_device(), RES_LDS_MAX)) return e;
+    MUDPT_LAUNCH(kern, dim3(a.B * a.H), dim3(nwv * 64), lds, s, prof, a);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }
 
 // K | V (dQ kernel, which also writes delta), then Q | dO | lse | delta (dK/dV kernel) of a pair in LDS
-template <typename T>
+template <typename T, bool CAUSAL>
 static int bwd_resident(const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
     const LaunchProf p1{prof ? prof->start : nullptr, nullptr}, p2{nullptr, prof ? prof->stop : nullptr};
     const int Lr = (a.L + 31) & ~31, lds1 = Lr * 256, lds2 = Lr * (256 + 8), nb = Lr / 32;
     const int nw1 = nb <= RES_W ? nb : RES_W, nw2 = nb <= RES_W_BWD ? nb : RES_W_BWD;  // dQ: 164 VGPRs fit three waves per SIMD
-    static PerDevice pd[2];
+    constexpr auto k1 = attn_bwd_dq_resident_kernel<T, CAUSAL>;
+    constexpr auto k2 = attn_bwd_dkv_resident_kernel<T, CAUSAL>;
     const int dev = current_device();
-    if (!pd[a.causal].done[dev]) {
-        const void* k1 = a.causal ? (const void*)attn_bwd_dq_resident_kernel<T, true> : (const void*)attn_bwd_dq_resident_kernel<T, false>;
-        const void* k2 = a.causal ? (const void*)attn_bwd_dkv_resident_kernel<T, true> : (const void*)attn_bwd_dkv_resident_kernel<T, false>;
-        HIP_TRY(hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_MAX));
-        HIP_TRY(hipFuncSetAttribute(k2, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_MAX));
-        pd[a.causal].done[dev] = true;
-    }
-    const dim3 gp(a.B * a.H);
-    if (a.causal) {
-        MUDPT_LAUNCH((attn_bwd_dq_resident_kernel<T, true>), gp, dim3(nw1 * 64), lds1, s, &p1, a, (const void*)a.out);
-        MUDPT_LAUNCH((attn_bwd_dkv_resident_kernel<T, true>), gp, dim3(nw2 * 64), lds2, s, &p2, a);
-    } else {
-        MUDPT_LAUNCH((attn_bwd_dq_resident_kernel<T, false>), gp, dim3(nw1 * 64), lds1, s, &p1, a, (const void*)a.out);
-        MUDPT_LAUNCH((attn_bwd_dkv_resident_kernel<T, false>), gp, dim3(nw2 * 64), lds2, s, &p2, a);
-    }
+    if (int e = lds_limit_once<k1>(dev, RES_LDS_MAX)) return e;
+    if (int e = lds_limit_once<k2>(dev, RES_LDS_MAX)) return e;
+    MUDPT_LAUNCH(k1, dim3(a.B * a.H), dim3(nw1 * 64), lds1, s, &p1, a, (const void*)a.out);
+    MUDPT_LAUNCH(k2, dim3(a.B * a.H), dim3(nw2 * 64), lds2, s, &p2, a);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }
 
-int launch_attn_fwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
-    return dtype == DT_BF16 ? fwd_resident<BF16>(a, s, prof) : fwd_resident<F16>(a, s, prof);
+// Called where attn_form (attention.hip) chose the resident form: its LDS limits guarantee lds <= RES_LDS_MAX here
+int launch_attn_fwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o) {
+    if (dtype == DT_BF16) return a.causal ? fwd_resident<BF16, true>(a, s, o.prof) : fwd_resident<BF16, false>(a, s, o.prof);
+    return a.causal ? fwd_resident<F16, true>(a, s, o.prof) : fwd_resident<F16, false>(a, s, o.prof);
 }
-int launch_attn_bwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof) {
-    return dtype == DT_BF16 ? bwd_resident<BF16>(a, s, prof) : bwd_resident<F16>(a, s, prof);
+int launch_attn_bwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o) {
+    if (dtype == DT_BF16) return a.causal ? bwd_resident<BF16, true>(a, s, o.prof) : bwd_resident<BF16, false>(a, s, o.prof);
+    return a.causal ? bwd_resident<F16, true>(a, s, o.prof) : bwd_resident<F16, false>(a, s, o.prof);
 }
 
 }  // namespace mudpt

@@ -202,17 +202,6 @@ __global__ __launch_bounds__(256) void attn_bwd_single_kernel(AttnArgs p, const 
     if (rg == 0) *(vec8*)((elem*)dq_sel + (size_t)b * HD + hd * 64 + ch * 8) = dqo;
 }
 
-static int single_attrs() {  // the per-wave score arrays can exceed the default 64 KiB of dynamic LDS (L up to 4096)
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)attn_fwd_single_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)attn_fwd_single_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        pd.done[dev] = true;
-    }
-    return MUDPT_OK;
-}
-
 static int check_single(const AttnArgs& a) {
     ARG_CHECK(a.qkv && a.sel_rows && a.B > 0 && a.L > 0 && a.H > 0, "attention (single query): bad arguments B=%d L=%d H=%d", a.B, a.L, a.H);
     ARG_CHECK(a.L <= 4096, "attention (single query): L=%d exceeds the supported 4096 rows", a.L);
@@ -227,10 +216,12 @@ int launch_attn_fwd_single(int dtype, const AttnArgs& a, const void* q_sel, void
     ARG_CHECK((uintptr_t)q_sel % 16 == 0 && (uintptr_t)out_sel % 16 == 0 && (uintptr_t)out_lo % 16 == 0 && ld_out % 8 == 0, "attention (single query) fwd: operands must be 16-byte aligned");
     ARG_CHECK(!out_lo || a.lo_mode == LO_F16 || a.lo_mode == LO_F8, "attention (single query) fwd: out_lo needs lo_mode 1 / 2 (got %d)", a.lo_mode);
     const int Lpad = (a.L + 63) & ~63, lds = 4 * Lpad * 4, grid = (a.B * a.H + 3) / 4;
-    if (int e = single_attrs()) return e;
+    ARG_CHECK(dtype == DT_BF16 || dtype == DT_F16, "attention: unknown dtype %d", dtype);
+    // the per-wave score arrays can exceed the default 64 KiB of dynamic LDS (L up to 4096)
+    if (int e = dtype == DT_BF16 ? lds_limit_once<attn_fwd_single_kernel<BF16>>(current_device(), 160 * 1024)
+                                 : lds_limit_once<attn_fwd_single_kernel<F16>>(current_device(), 160 * 1024)) return e;
     if (dtype == DT_BF16) hipLaunchKernelGGL(attn_fwd_single_kernel<BF16>, dim3(grid), dim3(256), lds, s, a, q_sel, out_sel, out_lo, ld_out, lse_sel, Lpad);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(attn_fwd_single_kernel<F16>, dim3(grid), dim3(256), lds, s, a, q_sel, out_sel, out_lo, ld_out, lse_sel, Lpad);
-    else { set_error("attention: unknown dtype %d", dtype); return MUDPT_ERR_ARG; }
+    else hipLaunchKernelGGL(attn_fwd_single_kernel<F16>, dim3(grid), dim3(256), lds, s, a, q_sel, out_sel, out_lo, ld_out, lse_sel, Lpad);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }

@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "../../include/mudpt.h"  // MUDPT_OK / MUDPT_ERR_*, MUDPT_ATTN_*
+
 namespace mudpt {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -161,21 +163,11 @@ __device__ inline int xcd_remap(int bid, int nwg) {
 }  // namespace mudpt
 
 // ---- host-side error plumbing (no exceptions cross the C ABI) -------------------------------
-#define MUDPT_OK 0
-#define MUDPT_ERR_ARG 1
-#define MUDPT_ERR_HIP 2
-#define MUDPT_ERR_STATE 3
-
 namespace mudpt {
 void set_error(const char* fmt, ...);
 }
 
 namespace mudpt {
-// One-time-per-DEVICE launch setup (function attributes and CU counts belong to a device; one process may drive several GPUs).
-struct PerDevice {
-    bool done[64] = {};
-    int ncu[64] = {};
-};
 // Optional HIP events that ride on a kernel's own dispatch packet (measurement legs of bench.py): start is recorded when the kernel
 // begins, stop when it ends; no marker packets between kernels.
 struct LaunchProf {
@@ -210,3 +202,22 @@ inline int current_device() {
             return MUDPT_ERR_ARG;                                                           \
         }                                                                                   \
     } while (0)
+
+namespace mudpt {
+// One-time-per-DEVICE launch setup (function attributes and CU counts belong to a device; one process may drive several GPUs).  dev is
+// the launcher's current_device(): one hipGetDevice per launch serves every helper it calls.
+// Raise Kern's dynamic-LDS limit before its first launch on dev (one set of flags per kernel instantiation; static: a kernel is
+// launched from the one translation unit that defines it, and the flags stay out of the library's dynamic symbols).
+template <auto Kern>
+static int lds_limit_once(int dev, int bytes) {
+    static bool done[64] = {};
+    if (!done[dev]) {
+        HIP_TRY(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        done[dev] = true;
+    }
+    return MUDPT_OK;
+}
+// Compute units of dev, asked once; defined in gemm.hip.  0 if the runtime refuses, with the error set (its file and line name device_cus,
+// not the launcher that asked) -- the launcher then returns MUDPT_ERR_HIP
+int device_cus(int dev);
+}  // namespace mudpt

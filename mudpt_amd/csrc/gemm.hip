@@ -238,13 +238,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_nt_kernel(GemmArgs p) {
 template <typename T, int BM, int BN, int WM, int WN, int EPI, int NS = 2, int BK = 64>
 static int launch_cfg(const GemmArgs& a, hipStream_t s) {
     constexpr int lds = NS * (BM + BN) * BK * 2;
-    auto kern = gemm_nt_kernel<T, BM, BN, WM, WN, EPI, NS, BK>;
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        pd.done[dev] = true;
-    }
+    constexpr auto kern = gemm_nt_kernel<T, BM, BN, WM, WN, EPI, NS, BK>;
+    if (int e = lds_limit_once<kern>(current_device(), lds)) return e;
     const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
     hipLaunchKernelGGL(kern, dim3(ntm * ntn, a.ksplit ? a.K / a.ksplit : 1), dim3(WM * WN * 64), lds, s, a);
     HIP_TRY(hipGetLastError());
@@ -259,14 +254,21 @@ static inline bool small_tiles(const GemmArgs& a) {
     return t64 <= 1280 || (t64 <= 2560 && a.K <= 512);
 }
 
-static int device_cus() {
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) {
-        if (hipDeviceGetAttribute(&pd.ncu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-        pd.done[dev] = true;
+int device_cus(int dev) {
+    static int ncu[64] = {};
+    if (ncu[dev] <= 0) {
+        const hipError_t e = hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) {
+            set_error("%s:%d: hipDeviceGetAttribute(MultiprocessorCount, device %d) -> %s", __FILE__, __LINE__, dev, hipGetErrorString(e));
+            return ncu[dev] = 0;
+        }
     }
-    return pd.ncu[dev];
+    return ncu[dev];
+}
+// the size decisions below are heuristics: they fall back to the MI355X's 256 CUs instead of failing the launch
+static int cus_or_256() {
+    const int n = device_cus(current_device());
+    return n > 0 ? n : 256;
 }
 
 // Round 4: 128-deep K-tiles for the 64 x 64 kernel while ALL its workgroups are resident at two per CU (64 KB of LDS each) -- these grids are
@@ -277,7 +279,7 @@ static int device_cus() {
 // 16.2 us unsplit against 14.1 for three slices of 128-deep tiles + their sum, the text tower's shapes +-0).
 static inline bool deep_k_tiles(const GemmArgs& a, int slices, int variant) {
     const size_t t64 = (size_t)((a.M + 63) / 64) * ((a.N + 63) / 64);
-    return (variant & 0xff) != 12 && a.lo_mode == LO_NONE && (a.K / slices) % 128 == 0 && t64 * slices <= (size_t)2 * device_cus();
+    return (variant & 0xff) != 12 && a.lo_mode == LO_NONE && (a.K / slices) % 128 == 0 && t64 * slices <= (size_t)2 * cus_or_256();
 }
 
 // variant: tuning knob (mudpt_model_set "gemm_variant" / mudpt_gemm's last argument): 0 = default kernel choice, 1/2/4 = force a simple tile,
@@ -347,7 +349,7 @@ static int split_k_slices(int epi, const GemmArgs& a, const GemmOpts& o, bool& d
     deep = false;
     const int v = o.variant & 0xff;
     if (!(epi == EPI_STORE || epi == EPI_STORE_F32) || !o.scratch || (v != 0 && v != 12) || a.lo_mode != LO_NONE) return 1;
-    const int ncu = device_cus();
+    const int ncu = cus_or_256();
     const size_t tiles = (size_t)((a.M + 63) / 64) * ((a.N + 63) / 64);  // 64 x 64 tiles, five workgroups to a CU
     if (tiles * 2 > (size_t)ncu * 5 || a.K < 1536) return 1;
     // with 128-deep K-tiles two workgroups share a CU: three or four slices of those beat four of the 64-deep form (deep_k_tiles)

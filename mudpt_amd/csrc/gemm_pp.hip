@@ -506,15 +506,10 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p, int ntn, int n
 template <typename T, int EPI, bool F8 = false, int ST = 0, int LD = 0, int ABL = 0>
 static int launch_pp(const GemmArgs& a, hipStream_t s, const GemmOpts& o) {
     constexpr int lds = 2 * 65536;
-    auto kern = gemm_pp_kernel<T, EPI, F8, ST, LD, ABL>;
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipDeviceGetAttribute(&pd.ncu[dev], hipDeviceAttributeMultiprocessorCount, dev));
-        pd.done[dev] = true;
-    }
-    const int ncu = pd.ncu[dev];
+    constexpr auto kern = gemm_pp_kernel<T, EPI, F8, ST, LD, ABL>;
+    const int dev = current_device(), ncu = device_cus(dev);
+    if (ncu <= 0) return MUDPT_ERR_HIP;
+    if (int e = lds_limit_once<kern>(dev, lds)) return e;
     const int ntm = (a.M + 255) / 256, ntn = (a.N + 255) / 256, ntiles = ntm * ntn;
     // grid = CUs; a last partial wave of R tiles with 2 R <= grid is run as 2 R half tiles (see the kernel); fewer tiles
     // than half the CUs: every tile is split

@@ -228,14 +228,7 @@ int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s) {
     if (a.txt)
         if (int rc = launch_l2norm(a.txt, a.txt_n, a.txt_inv, a.C, a.e, s)) return rc;
     const int Cpad = (a.C + 15) / 16 * 16, lds = head_lds_bytes(a, false);
-    static PerDevice pd;
-    const int dev = current_device();
-    if (!pd.done[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)head_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840 - 256));
-        HIP_TRY(hipFuncSetAttribute((const void*)head_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840 - 256));
-        HIP_TRY(hipFuncSetAttribute((const void*)head_dtxt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-        pd.done[dev] = true;
-    }
+    if (int e = lds_limit_once<head_rows_kernel<false>>(current_device(), 163840 - 256)) return e;
     hipLaunchKernelGGL(head_rows_kernel<false>, dim3((a.B + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), lds, s, a, Cpad);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
@@ -251,14 +244,9 @@ int launch_head_fused_train(const HeadArgs& a, hipStream_t s) {
     if (a.txt)
         if (int rc = launch_l2norm(a.txt, a.txt_n, a.txt_inv, a.C, a.e, s)) return rc;
     const int Cpad = (a.C + 15) / 16 * 16, lds = head_lds_bytes(a, true);
-    static PerDevice pd;
     const int dev = current_device();
-    if (!pd.done[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)head_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840 - 256));
-        HIP_TRY(hipFuncSetAttribute((const void*)head_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840 - 256));
-        HIP_TRY(hipFuncSetAttribute((const void*)head_dtxt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-        pd.done[dev] = true;
-    }
+    if (int e = lds_limit_once<head_rows_kernel<true>>(dev, 163840 - 256)) return e;
+    if (int e = lds_limit_once<head_dtxt_kernel>(dev, 65536)) return e;
     hipLaunchKernelGGL(head_rows_kernel<true>, dim3((a.B + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), lds, s, a, Cpad);
     HIP_TRY(hipGetLastError());
     if (a.B_total <= 0)

@@ -112,16 +112,11 @@ struct AttnArgs {
     // bwd, optional: dout is zero except on ONE row per sequence, token row sel_rows[b] (the last block: only the CLS / EOT row of its
     // output is used): dQ is computed for that row's 16-query block only (zero elsewhere) and dK / dV sum over that block's chunk
     const int* sel_rows = nullptr;
-    bool sweep = false;         // bwd, non-causal: the single-sweep kernel (S / dP computed once, dS through LDS)
-    bool force_fused = false;   // bwd: the fused single pass also where the dispatcher prefers the two kernels (NC > 3; A/B, tests)
-    bool fused_w1 = false;      // bwd, fused form: NC waves with two 16-row blocks each instead of 2 NC waves with one (A/B)
-    bool two_kernels = false;   // bwd: the dQ kernel + dK/dV kernel pair instead of the fused single pass (A/B runs, tests)
     // bwd, optional: only the dqkv rows win_row0 .. win_row0 + win_n - 1 of every sequence are wanted (block 0 of a tower: its input
     // gradient is needed on the prompt rows only).  The 16-row blocks that hold such a row are computed in full -- dQ from all keys,
     // dK / dV from all queries, same sums in the same order as without the window -- and every other row of dqkv is left UNWRITTEN.
-    // Honoured by the two-kernel form (whole sequence on chip, non-causal) and the tiled kernels; elsewhere everything is computed.
+    // A window selects the two-kernel / staged form (attn_form), whose kernels honour it.
     int win_row0 = 0, win_n = 0;
-    bool tiled_fwd_16 = false;  // fwd, 224 < L <= 640: the staged 16-query-block kernel instead of the resident form (A/B runs, tests)
     int B = 0, L = 0, H = 0; bool causal = false;
     // exact-fp32 forward (attention_exact.hip): q | k | v in fp32 [B, L, 3*H*64] and, optionally, where to leave their T copy for the backward
     const float* qkv32 = nullptr;
@@ -134,15 +129,32 @@ int launch_attn_fwd_single(int dtype, const AttnArgs& a, const void* q_sel, void
 int launch_attn_bwd_single(int dtype, const AttnArgs& a, const void* q_sel, const void* out_sel, int ld_out, const void* dout_sel, const float* lse_sel,
                            void* dq_sel, hipStream_t s);
 int attn_padded_len(int L);
-int launch_attn_fwd(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof = nullptr);
-int launch_attn_bwd(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof = nullptr);  // prof spans both kernels
+// Host-side options of one launch (never passed to the device), as GemmOpts: the A/B switches of the model's knobs and of the test exports
+struct AttnOpts {
+    bool tiled_fwd_16 = false;  // fwd, 224 < L <= 640: the staged 16-query-block kernel instead of the resident form
+    bool two_kernels = false;   // bwd: the dQ kernel + dK/dV kernel pair (L > 224: the staged pair) instead of the default form
+    bool force_fused = false;   // bwd, L <= 224: the fused single pass also where the default is another form
+    bool fused_w1 = false;      // bwd, fused form: NC waves with two 16-row blocks each instead of 2 NC waves with one
+    bool sweep = false;         // bwd, L <= 96, non-causal: the single-sweep kernel (the default only from L = 97 on)
+    const LaunchProf* prof = nullptr;  // events around the launch (both kernels of a two-kernel form)
+};
+// Which kernels run a launch: EVERY threshold and switch is decided here, in host arithmetic with no HIP call (1 <= a.L <= 4096; reads
+// a.L, a.causal, a.sel_rows, a.win_n).  The launchers switch on the result; attention.hip's header lists the kernels behind each form.
+enum AttnForm : int {
+    FWD_PAIR = MUDPT_ATTN_FWD_PAIR, FWD_PERSISTENT = MUDPT_ATTN_FWD_PERSISTENT, FWD_RESIDENT = MUDPT_ATTN_FWD_RESIDENT,
+    FWD_STAGED = MUDPT_ATTN_FWD_STAGED, BWD_TWO = MUDPT_ATTN_BWD_TWO, BWD_FUSED_W2 = MUDPT_ATTN_BWD_FUSED_W2,
+    BWD_FUSED_W1 = MUDPT_ATTN_BWD_FUSED_W1, BWD_SWEEP = MUDPT_ATTN_BWD_SWEEP, BWD_RESIDENT = MUDPT_ATTN_BWD_RESIDENT,
+    BWD_STAGED = MUDPT_ATTN_BWD_STAGED
+};
+AttnForm attn_form(const AttnArgs& a, const AttnOpts& o, bool bwd);
+int launch_attn_fwd(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o = AttnOpts());
+int launch_attn_bwd(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o = AttnOpts());
 // Exact-fp32 forward (the "fp32" mode): reads a.qkv32, writes a.out (fp16 hi) + a.out_lo (fp16 lo, optional) + a.lse and, if a.qkv_lp
 // is set, the fp16 copy of q, k, v that the backward kernels read.
 int launch_attn_fwd_exact(const AttnArgs& a, hipStream_t s, const LaunchProf* prof = nullptr);
-// attention_resident.hip: both streamed operands of a (sequence, head) pair resident in LDS (224 < L, Lr * 256 (+ 8 Lr backward) <= 160 KB)
-bool attn_resident_fits(int L, bool bwd);
-int launch_attn_fwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof = nullptr);
-int launch_attn_bwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const LaunchProf* prof = nullptr);  // dQ (+ delta) kernel, then dK/dV kernel
+// attention_resident.hip: both streamed operands of a (sequence, head) pair resident in LDS; only where attn_form says FWD_ / BWD_RESIDENT
+int launch_attn_fwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o);
+int launch_attn_bwd_resident(int dtype, const AttnArgs& a, hipStream_t s, const AttnOpts& o);  // dQ (+ delta) kernel, then dK/dV kernel
 
 // ------------------------------------------------------------------------------------------------
 // Small / HBM-bound helpers

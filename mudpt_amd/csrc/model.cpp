@@ -351,22 +351,23 @@ static int ln_bwd_call(mudpt_model* m, const Tower& t, const LnBwdArgs& a, hipSt
     if (int rc = prof_next(m, PC_LN_BWD, per_elem * a.rows * a.d, &lp)) return rc;
     return launch_ln_bwd(m->dtype, a, s, &lp);
 }
-static int attn_call(mudpt_model* m, const Tower& t, const AttnArgs& a0, bool bwd, hipStream_t s) {
-    AttnArgs a = a0;
-    a.two_kernels = m->attn_two_kernels;
-    a.fused_w1 = m->attn_fused_w1;
+static int attn_call(mudpt_model* m, const Tower& t, const AttnArgs& a, bool bwd, hipStream_t s) {
+    AttnOpts o;
+    o.two_kernels = m->attn_two_kernels;
+    o.fused_w1 = m->attn_fused_w1;
     // executed MFMA FLOPs: forward S = QK^T and PV (2 products of 2 L^2 64 each per head); backward 7 products (dQ sweep: S, dP, dQ;
     // dK/dV sweep: S, dP, dV, dK); the causal tower does about half of each
     const double prod = 2.0 * a.L * (double)a.L * 64.0 * a.H * a.B * (a.causal ? 0.5 : 1.0);
     const bool exact_fwd = !bwd && a.qkv32;  // fp32 attention forward: fp32 matrix-core FLOPs are not counted as executed bf16 / fp16 MFMA work
     if (m->prof && !a.sel_rows && !exact_fwd) m->exec_flop += (bwd ? 7.0 : 2.0) * prod;
     if (exact_fwd) return launch_attn_fwd_exact(a, s);
-    if (!prof_big(m, t, a.B * a.L) || a.sel_rows) return bwd ? launch_attn_bwd(m->dtype, a, s) : launch_attn_fwd(m->dtype, a, s);
+    if (!prof_big(m, t, a.B * a.L) || a.sel_rows) return bwd ? launch_attn_bwd(m->dtype, a, s, o) : launch_attn_fwd(m->dtype, a, s, o);
     // algorithmic bytes: forward reads q, k, v and writes o (+ its low half in split mode); backward reads q, k, v, o, do and writes dq, dk, dv
     const double tok = (double)a.B * a.L * a.H * 128.0;
     LaunchProf lp;
     if (int rc = prof_next(m, bwd ? PC_ATTN_BWD : PC_ATTN_FWD, bwd ? 8.0 * tok : (4.0 + (a.out_lo ? 1.0 : 0.0)) * tok, &lp)) return rc;
-    return bwd ? launch_attn_bwd(m->dtype, a, s, &lp) : launch_attn_fwd(m->dtype, a, s, &lp);
+    o.prof = &lp;
+    return bwd ? launch_attn_bwd(m->dtype, a, s, o) : launch_attn_fwd(m->dtype, a, s, o);
 }
 
 // Indices into mudpt_model::tr, the table of the variant they belong to (build_trainables): P_* MuDPT (UMuDPT shares P_CTX, P_DEEP),
@@ -2171,10 +2172,30 @@ extern "C" int mudpt_attention_bwd_single(int32_t dtype, const void* qkv, const 
     return launch_attn_bwd_single(dtype, a, q_sel, out_sel, H * 64, dout_sel, lse_sel, dq_sel, (hipStream_t)stream);
 }
 extern "C" int mudpt_attention_padded_len(int32_t L) { return attn_padded_len(L); }
+// The `causal` argument of mudpt_attention_fwd / _fwd_split / _bwd / _bwd_sel and the `flags` of mudpt_attention_form (bit meanings: include/mudpt.h at
+// mudpt_attention_bwd): the mask and the window go into a, the kernel-choice switches are returned.
+static AttnOpts attn_flags(int32_t flags, bool bwd, AttnArgs& a) {
+    AttnOpts o;
+    a.causal = (flags & 1) != 0;
+    if (!bwd) {
+        o.tiled_fwd_16 = (flags & 2) != 0;
+        return o;
+    }
+    o.two_kernels = (flags & 2) != 0; o.fused_w1 = (flags & 4) != 0; o.force_fused = (flags & 12) != 0; o.sweep = (flags & 16) != 0;
+    a.win_row0 = (flags >> 8) & 0xfff; a.win_n = (flags >> 20) & 0xff;
+    return o;
+}
+extern "C" int mudpt_attention_form(int32_t bwd, int32_t L, int32_t flags, int32_t sel) {
+    if (L < 1 || L > 4096) return -1;
+    static const int one_row = 0;
+    AttnArgs a; a.L = L; a.sel_rows = bwd && sel ? &one_row : nullptr;
+    const AttnOpts o = attn_flags(sel ? flags & 1 : flags, bwd != 0, a);  // mudpt_attention_bwd_sel reads bit 0 only
+    return attn_form(a, o, bwd != 0);
+}
 extern "C" int mudpt_attention_fwd(int32_t dtype, const void* qkv, void* out, float* lse, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream) {
-    AttnArgs a; a.qkv = qkv; a.out = out; a.lse = lse; a.B = B; a.L = L; a.H = H; a.causal = (causal & 1) != 0;
-    a.tiled_fwd_16 = (causal & 2) != 0;  // 224 < L <= 640: the staged 16-query-block kernel instead of the resident form (A/B, tests)
-    return launch_attn_fwd(dtype, a, (hipStream_t)stream);
+    AttnArgs a; a.qkv = qkv; a.out = out; a.lse = lse; a.B = B; a.L = L; a.H = H;
+    const AttnOpts o = attn_flags(causal, false, a);
+    return launch_attn_fwd(dtype, a, (hipStream_t)stream, o);
 }
 extern "C" int mudpt_attention_fwd_exact(const float* qkv32, void* qkv_lp, void* out_hi, void* out_lo, int32_t lo_mode, int32_t ld_out, float* lse, int32_t B, int32_t L,
                                          int32_t H, int32_t causal, void* stream) {
@@ -2184,9 +2205,8 @@ extern "C" int mudpt_attention_fwd_exact(const float* qkv32, void* qkv_lp, void*
 extern "C" int mudpt_attention_bwd(int32_t dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int32_t B,
                                    int32_t L, int32_t H, int32_t causal, void* stream) {
     AttnArgs a; a.qkv = qkv; a.out = (void*)out; a.dout = dout; a.lse = (float*)lse; a.delta = delta; a.dqkv = dqkv; a.B = B; a.L = L; a.H = H;
-    a.causal = (causal & 1) != 0; a.two_kernels = (causal & 2) != 0; a.fused_w1 = (causal & 4) != 0; a.force_fused = (causal & 12) != 0; a.sweep = (causal & 16) != 0;
-    a.win_n = (causal >> 20) & 0xff; a.win_row0 = (causal >> 8) & 0xfff;  // bits 8-19: first wanted row, bits 20-27: number of wanted rows (0 = all)
-    return launch_attn_bwd(dtype, a, (hipStream_t)stream);
+    const AttnOpts o = attn_flags(causal, true, a);
+    return launch_attn_bwd(dtype, a, (hipStream_t)stream, o);
 }
 // ---- the launchers' production forms, one thin argument-packing export each (tests/test_kernels_gpu.py, tests/test_movers_gpu.py) ----
 extern "C" int mudpt_layernorm_bwd_ex(int32_t dtype, const void* dy, int32_t lddy, int32_t dy_f32, const float* x, int32_t ldx, const int32_t* row_index,
@@ -2213,8 +2233,8 @@ extern "C" int mudpt_layernorm_fwd_ex(int32_t dtype, const float* x, int32_t ldx
 extern "C" int mudpt_attention_fwd_split(int32_t dtype, const void* qkv, void* out, void* out_lo, int32_t lo_mode, int32_t ld_out, float* lse, int32_t B, int32_t L,
                                          int32_t H, int32_t causal, void* stream) {
     AttnArgs a; a.qkv = qkv; a.out = out; a.out_lo = out_lo; a.lo_mode = lo_mode; a.ld_out = ld_out; a.lse = lse; a.B = B; a.L = L; a.H = H;
-    a.causal = (causal & 1) != 0; a.tiled_fwd_16 = (causal & 2) != 0;
-    return launch_attn_fwd(dtype, a, (hipStream_t)stream);
+    const AttnOpts o = attn_flags(causal, false, a);
+    return launch_attn_fwd(dtype, a, (hipStream_t)stream, o);
 }
 extern "C" int mudpt_attention_fwd_single_split(int32_t dtype, const void* qkv, const void* q_sel, const int32_t* sel_rows, void* out_sel, void* out_lo,
                                                 int32_t lo_mode, int32_t ld_out, float* lse_sel, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream) {
@@ -2225,8 +2245,8 @@ extern "C" int mudpt_attention_bwd_sel(int32_t dtype, const void* qkv, const voi
                                        const int32_t* sel_rows, int32_t B, int32_t L, int32_t H, int32_t causal, void* stream) {
     ARG_CHECK(sel_rows, "attention_bwd_sel: null sel_rows");
     AttnArgs a; a.qkv = qkv; a.out = (void*)out; a.dout = dout; a.lse = (float*)lse; a.delta = delta; a.dqkv = dqkv; a.sel_rows = sel_rows; a.B = B; a.L = L; a.H = H;
-    a.causal = (causal & 1) != 0;
-    return launch_attn_bwd(dtype, a, (hipStream_t)stream);
+    const AttnOpts o = attn_flags(causal & 1, true, a);  // bit 0 only: one wanted row leaves no kernel choice and takes no window
+    return launch_attn_bwd(dtype, a, (hipStream_t)stream, o);
 }
 extern "C" int mudpt_head_ex(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
                              int32_t e, float* txt_n, float* txt_inv, float* logits, float* loss, float* row_loss, float* dimg, float* dtxt, int32_t path,

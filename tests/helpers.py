@@ -110,3 +110,54 @@ def patchify_threads(form, B, S, p, ldk):
     if form == "any":
         return B * (S // p) ** 2 * ldk, 16384 * 256
     return B * (S // p) ** 2 * (ldk // 4), 16384 * 256
+
+
+# ---- attention cases of test_kernels_gpu.py, kept here so that test_capi_cpu.py can check, without a GPU, which kernel forms they reach ----
+# (B, L, H, causal) of test_attention_fwd_bwd
+ATTN_CASES = [(3, 201, 12, False), (11, 77, 8, True), (2, 7, 3, False), (2, 33, 2, True), (1, 224, 1, False), (2, 64, 2, True),
+              # L > 224: the tiled (online-softmax) kernels; 581 = ViT-L/14@336's 577 tokens + 4 prompt rows (BASELINE configs[4])
+              # (forward: K and V of a pair resident in LDS up to L = 640, one workgroup per pair; above that the staged 16-query-block form)
+              (2, 300, 2, False), (1, 581, 3, False), (2, 260, 2, True), (1, 225, 1, False), (1, 640, 2, False), (1, 641, 1, False),
+              (2, 513, 2, True), (70, 300, 4, False),
+              # backward: Q | dO | lse | delta of a pair resident up to L = 608; 609 .. 640: resident forward, staged backward
+              (1, 608, 1, False), (1, 609, 1, True),
+              # more (sequence, head) pairs than resident workgroups: the persistent loops of the forward and the fused backward walk
+              # several pairs per workgroup (images of the next pair stream in while the current one is computed)
+              (150, 201, 2, False), (700, 20, 8, True),
+              # a causal sequence of padded length >= 128: the default causal route at 97 .. 224 (pair forward, two-kernel backward, NC = 4)
+              (2, 100, 2, True)]
+ATTN_LONG_FWD_CASES = [(2, 581, 3, False, 1.0), (2, 581, 3, False, 3.0), (3, 400, 2, True, 2.5), (1, 640, 1, False, 0.05)]  # (B, L, H, causal, gain)
+ATTN_WINDOW_CASES = [(3, 201, 12, False, 197, 4), (2, 77, 8, True, 1, 4), (3, 150, 2, False, 14, 4), (2, 581, 4, False, 577, 4),
+                     (2, 581, 2, False, 62, 5), (4, 26, 8, True, 1, 16)]  # (B, L, H, causal, row0, n)
+ATTN_SEL_CASES = [(26, 8, True), (77, 8, True), (201, 12, False), (581, 3, False)]  # (L, H, causal)
+
+
+def attn_bwd_form_flags(L, causal):
+    """The kernel-choice bits test_attention_fwd_bwd adds to the backward after the default run; bit 4 (sweep) where a sweep kernel exists."""
+    return (2, 4, 8) if causal or L > 224 else (2, 4, 8, 16)
+
+
+ATTN_LONG_FWD_FLAGS = (0, 2)  # test_attention_long_forward_forms: the default form and the staged one (bit 1)
+ATTN_WINDOW_FULL_FLAG = 2     # test_attention_backward_window_form: its reference run, the two-kernel form on all rows
+ATTN_SEL_COMPARE = ((2, True), (0, False))  # test_attention_bwd_sel_rows: (flag of the general backward it compares with, equal bit for bit?)
+
+
+def attn_window_flags(row0, n):
+    """The window form of mudpt_attention_bwd: n rows per sequence from row0 on."""
+    return (row0 << 8) | (n << 20)
+
+
+def attention_test_launches():
+    """(bwd, L, flags, sel) of every mudpt_attention_fwd / _bwd / _bwd_sel call that test_attention_fwd_bwd, test_attention_long_forward_forms,
+    test_attention_backward_window_form and test_attention_bwd_sel_rows make: the arguments of mudpt_attention_form."""
+    calls = []
+    for _, L, _, causal in ATTN_CASES:
+        c = int(causal)
+        calls += [(0, L, c, 0), (1, L, c, 0)] + [(1, L, c | f, 0) for f in attn_bwd_form_flags(L, causal)]
+    for _, L, _, causal, _ in ATTN_LONG_FWD_CASES:
+        calls += [(0, L, int(causal) | f, 0) for f in ATTN_LONG_FWD_FLAGS]
+    for _, L, _, causal, row0, n in ATTN_WINDOW_CASES:
+        calls += [(0, L, int(causal), 0), (1, L, int(causal) | ATTN_WINDOW_FULL_FLAG, 0), (1, L, int(causal) | attn_window_flags(row0, n), 0)]
+    for L, _, causal in ATTN_SEL_CASES:
+        calls += [(0, L, int(causal), 0), (1, L, int(causal), 1)] + [(1, L, int(causal) | f, 0) for f, _ in ATTN_SEL_COMPARE]
+    return calls

@@ -84,8 +84,8 @@ def test_host_e4m3_conversion_matches_torch():
 # direct float64 test reaches it some other way.
 LAUNCHERS_WITHOUT_AN_EXPORT = {
     "launch_gemm_pp": "a form launch_gemm dispatches to (gemm_uses_pp); mudpt_gemm reaches it at the large shapes of test_gemm_pingpong_epilogues",
-    "launch_attn_fwd_resident": "a form launch_attn_fwd dispatches to for 224 < L <= 640; mudpt_attention_fwd reaches it (ATTN_CASES, L = 581)",
-    "launch_attn_bwd_resident": "a form launch_attn_bwd dispatches to for 224 < L <= 608; mudpt_attention_bwd reaches it (ATTN_CASES, L = 581)",
+    "launch_attn_fwd_resident": "the FWD_RESIDENT form of launch_attn_fwd; test_attention_gpu_cases_reach_every_form holds mudpt_attention_fwd's cases to it",
+    "launch_attn_bwd_resident": "the BWD_RESIDENT form of launch_attn_bwd; test_attention_gpu_cases_reach_every_form holds mudpt_attention_bwd's cases to it",
     "launch_sgd": "exported above the single-kernel section as mudpt_sgd_step, which test_model_gpu.py::test_sgd_step_matches_torch holds to torch.optim.SGD",
 }
 
@@ -111,6 +111,45 @@ def test_every_launcher_is_called_from_a_test_export():
     stale = [f for f in LAUNCHERS_WITHOUT_AN_EXPORT if f not in launchers or f in called]
     assert not stale, f"allowlist entries that are no longer needed: {stale}"
     assert all(len(reason) > 20 for reason in LAUNCHERS_WITHOUT_AN_EXPORT.values())
+
+
+W = (1 << 8) | (4 << 20)  # the window form: 4 rows from row 1 on
+# (bwd, L, flags, sel) -> form of mudpt_attention_fwd / _bwd / _bwd_sel, as measured on the dispatch this table replaced
+ATTN_FORM_TABLE = [
+    (0, 201, 0, 0, "FWD_PERSISTENT"), (0, 224, 2, 0, "FWD_PERSISTENT"), (0, 77, 1, 0, "FWD_PAIR"), (0, 225, 0, 0, "FWD_RESIDENT"),
+    (0, 581, 1, 0, "FWD_RESIDENT"), (0, 640, 0, 0, "FWD_RESIDENT"), (0, 581, 2, 0, "FWD_STAGED"), (0, 641, 0, 0, "FWD_STAGED"),
+    (0, 4096, 1, 0, "FWD_STAGED"),
+    (1, 77, 1, 0, "BWD_FUSED_W2"), (1, 77, 1 | 16, 0, "BWD_FUSED_W2"),
+    (1, 96, 0, 0, "BWD_FUSED_W2"), (1, 96, 16, 0, "BWD_SWEEP"),
+    (1, 97, 0, 0, "BWD_SWEEP"),
+    (1, 128, 1, 0, "BWD_TWO"), (1, 128, 1 | 16, 0, "BWD_TWO"),
+    (1, 201, 0, 0, "BWD_SWEEP"), (1, 201, 2, 0, "BWD_TWO"), (1, 201, 4, 0, "BWD_FUSED_W1"), (1, 201, 8, 0, "BWD_FUSED_W2"),
+    (1, 201, 24, 0, "BWD_FUSED_W2"), (1, 201, W, 0, "BWD_TWO"), (1, 201, W | 8, 0, "BWD_TWO"), (1, 201, 0, 1, "BWD_TWO"),
+    (1, 77, 1, 1, "BWD_TWO"),
+    (1, 225, 0, 0, "BWD_RESIDENT"), (1, 225, 1, 0, "BWD_RESIDENT"),
+    (1, 581, 0, 0, "BWD_RESIDENT"), (1, 581, 4, 0, "BWD_RESIDENT"), (1, 581, 8, 0, "BWD_RESIDENT"), (1, 581, 16, 0, "BWD_RESIDENT"),
+    (1, 581, 2, 0, "BWD_STAGED"), (1, 581, W, 0, "BWD_STAGED"), (1, 581, 0, 1, "BWD_STAGED"),
+    (1, 608, 1, 0, "BWD_RESIDENT"),
+] + [(1, 609, c | f, s, "BWD_STAGED") for c in (0, 1) for f in (0, 2, 4, 8, 16, W) for s in (0, 1)]
+
+
+def test_attention_form_table(lib):
+    """Which kernels a launch runs is host arithmetic (attn_form, exported as mudpt_attention_form): every form computes the same numbers,
+    so only this table notices a wrong edit to the dispatch before the benchmark does."""
+    header = open(capi.HEADER_PATH).read()
+    for code, name in enumerate(capi.ATTN_FORMS):
+        assert f"#define MUDPT_ATTN_{name} {code} " in header, name
+    for bwd, L, flags, sel, want in ATTN_FORM_TABLE:
+        got = lib.mudpt_attention_form(bwd, L, flags, sel)
+        assert got == capi.ATTN_FORMS.index(want), (bwd, L, flags, sel, want, capi.ATTN_FORMS[got] if got >= 0 else got)
+    assert [lib.mudpt_attention_form(b, L, 0, 0) for b in (0, 1) for L in (0, 4097)] == [-1] * 4
+
+
+def test_attention_gpu_cases_reach_every_form(lib):
+    """The (case, flags) pairs the attention tests of test_kernels_gpu.py run reach all ten forms, the two resident launchers among them."""
+    from tests.helpers import attention_test_launches
+    reached = {lib.mudpt_attention_form(*call) for call in attention_test_launches()}
+    assert reached == set(range(len(capi.ATTN_FORMS))), sorted(capi.ATTN_FORMS[i] for i in set(range(10)) - reached)
 
 
 def test_patchify_cases_wrap_every_grid_stride_loop():

@@ -5,7 +5,8 @@ import pytest
 import torch
 
 from oracle import mudpt_oracle as O
-from tests.helpers import SENT, P, e4m3_spacing, ok, refused
+from tests.helpers import (ATTN_CASES, ATTN_LONG_FWD_CASES, ATTN_LONG_FWD_FLAGS, ATTN_SEL_CASES, ATTN_SEL_COMPARE, ATTN_WINDOW_CASES,
+                           ATTN_WINDOW_FULL_FLAG, SENT, P, attn_bwd_form_flags, attn_window_flags, e4m3_spacing, ok, refused)
 
 pytestmark = pytest.mark.gpu
 
@@ -423,18 +424,6 @@ def test_layernorm_gather_scatter(lib):
     torch.testing.assert_close(dx.cpu(), full, atol=2e-5, rtol=2e-5)
 
 
-ATTN_CASES = [(3, 201, 12, False), (11, 77, 8, True), (2, 7, 3, False), (2, 33, 2, True), (1, 224, 1, False), (2, 64, 2, True),
-              # L > 224: the tiled (online-softmax) kernels; 581 = ViT-L/14@336's 577 tokens + 4 prompt rows (BASELINE configs[4])
-              # (forward: K and V of a pair resident in LDS up to L = 640, one workgroup per pair; above that the staged 16-query-block form)
-              (2, 300, 2, False), (1, 581, 3, False), (2, 260, 2, True), (1, 225, 1, False), (1, 640, 2, False), (1, 641, 1, False),
-              (2, 513, 2, True), (70, 300, 4, False),
-              # backward: Q | dO | lse | delta of a pair resident up to L = 608; 609 .. 640: resident forward, staged backward
-              (1, 608, 1, False), (1, 609, 1, True),
-              # more (sequence, head) pairs than resident workgroups: the persistent loops of the forward and the fused backward walk
-              # several pairs per workgroup (images of the next pair stream in while the current one is computed)
-              (150, 201, 2, False), (700, 20, 8, True)]
-
-
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 @pytest.mark.parametrize("B,L,H,causal", ATTN_CASES)
 def test_attention_fwd_bwd(lib, dtype, B, L, H, causal):
@@ -475,8 +464,7 @@ def test_attention_fwd_bwd(lib, dtype, B, L, H, causal):
     assert torch.equal(again, dqkv)
     # bit 4: the single-sweep kernel (non-causal, L <= 224): S / dP / exp computed once, dS rounded to T crosses LDS for dQ -- the same
     # rounding point as the other forms (they round dS to T for the dQ product too)
-    forms = (2, 4, 8) if causal or L > 224 else (2, 4, 8, 16)
-    for form in forms:
+    for form in attn_bwd_form_flags(L, causal):
         other = torch.full_like(dqkv, float("nan"))
         ok(lib, lib.mudpt_attention_bwd(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(other), B, L, H, int(causal) | form, None))
         torch.cuda.synchronize()
@@ -489,7 +477,7 @@ def test_attention_fwd_bwd(lib, dtype, B, L, H, causal):
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
-@pytest.mark.parametrize("B,L,H,causal,gain", [(2, 581, 3, False, 1.0), (2, 581, 3, False, 3.0), (3, 400, 2, True, 2.5), (1, 640, 1, False, 0.05)])
+@pytest.mark.parametrize("B,L,H,causal,gain", ATTN_LONG_FWD_CASES)
 def test_attention_long_forward_forms(lib, dtype, B, L, H, causal, gain):
     """224 < L <= 640: the resident forward (32 queries per wave, rescale deferred until a row's maximum outgrows its reference by 2^6)
     against the staged 16-query-block kernel (flag bit 1) and the definition.  gain 3: scores of +-100 and more, the reference moves at
@@ -502,7 +490,7 @@ def test_attention_long_forward_forms(lib, dtype, B, L, H, causal, gain):
     Lp = lib.mudpt_attention_padded_len(L)
     qc = qkv.cuda()
     outs, lses = [], []
-    for flag in (0, 2):
+    for flag in ATTN_LONG_FWD_FLAGS:
         out = torch.full((B, L, H * 64), float("nan"), device="cuda", dtype=tt)
         lse = torch.full((B, H, Lp), float("nan"), device="cuda")
         ok(lib, lib.mudpt_attention_fwd(dt, P(qc), P(out), P(lse), B, L, H, int(causal) | flag, None))
@@ -561,8 +549,7 @@ def test_attention_single_query(lib, dtype, B, L, H, causal):
     assert torch.equal(again[..., H * 64:], dqkv[..., H * 64:]) and torch.equal(dq2, dq_sel)
 
 
-@pytest.mark.parametrize("B,L,H,causal,row0,n", [(3, 201, 12, False, 197, 4), (2, 77, 8, True, 1, 4), (3, 150, 2, False, 14, 4), (2, 581, 4, False, 577, 4),
-                                                 (2, 581, 2, False, 62, 5), (4, 26, 8, True, 1, 16)])
+@pytest.mark.parametrize("B,L,H,causal,row0,n", ATTN_WINDOW_CASES)
 def test_attention_backward_window_form(lib, B, L, H, causal, row0, n):
     """Block 0 of a tower needs d(qkv) on the prompt rows only: the window form computes the 16-row blocks (L > 224: 128-row groups) that hold
     rows row0 .. row0 + n - 1 of every sequence -- dQ from all keys, dK / dV from all queries -- and leaves the other rows unwritten.  The
@@ -576,12 +563,12 @@ def test_attention_backward_window_form(lib, B, L, H, causal, row0, n):
     out, lse, delta = torch.empty(B, L, H * 64, device="cuda", dtype=tt), torch.zeros(B, H, Lp, device="cuda"), torch.zeros(B, H, Lp, device="cuda")
     ok(lib, lib.mudpt_attention_fwd(dt, P(qkv), P(out), P(lse), B, L, H, int(causal), None))
     full = torch.empty_like(qkv)
-    ok(lib, lib.mudpt_attention_bwd(dt, P(qkv), P(out), P(dout), P(lse), P(delta), P(full), B, L, H, int(causal) | 2, None))
+    ok(lib, lib.mudpt_attention_bwd(dt, P(qkv), P(out), P(dout), P(lse), P(delta), P(full), B, L, H, int(causal) | ATTN_WINDOW_FULL_FLAG, None))
     torch.cuda.synchronize()
     delta_full = delta.clone()
     win = torch.full_like(qkv, 3.0)
     delta.zero_()
-    ok(lib, lib.mudpt_attention_bwd(dt, P(qkv), P(out), P(dout), P(lse), P(delta), P(win), B, L, H, int(causal) | (row0 << 8) | (n << 20), None))
+    ok(lib, lib.mudpt_attention_bwd(dt, P(qkv), P(out), P(dout), P(lse), P(delta), P(win), B, L, H, int(causal) | attn_window_flags(row0, n), None))
     torch.cuda.synchronize()
     assert torch.equal(win[:, row0:row0 + n], full[:, row0:row0 + n])
     assert torch.equal(delta[..., :L], delta_full[..., :L])  # delta of every query feeds the dK / dV pass
@@ -865,7 +852,7 @@ def test_attention_single_query_split_output(lib, dtype, B, L, H, causal):
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
-@pytest.mark.parametrize("L,H,causal", [(26, 8, True), (77, 8, True), (201, 12, False), (581, 3, False)])
+@pytest.mark.parametrize("L,H,causal", ATTN_SEL_CASES)
 def test_attention_bwd_sel_rows(lib, dtype, L, H, causal):
     """The backward where dout is zero except on ONE row per sequence (the last block with last_single = 0, the class-parallel path): one
     sequence per row position -- first block, last row, and both sides of every 16 / 32 / 64 / 128 boundary below L (under the causal mask:
@@ -896,7 +883,7 @@ def test_attention_bwd_sel_rows(lib, dtype, L, H, causal):
     assert torch.equal(res[0].view(torch.int16), res[1].view(torch.int16))
     scale = dref.abs().max().item()
     torch.testing.assert_close(res[0].double(), dref, atol=12 * EPS[dtype] * scale, rtol=8 * EPS[dtype])
-    for flag, same in ((2, True), (0, False)):
+    for flag, same in ATTN_SEL_COMPARE:
         gen = torch.full((B, L, 3 * Hd), float("nan"), device="cuda", dtype=tt)
         ok(lib, lib.mudpt_attention_bwd(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(gen), B, L, H, int(causal) | flag, None))
         torch.cuda.synchronize()
