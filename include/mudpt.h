@@ -279,6 +279,27 @@ int mudpt_gemm(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K,
 /* variant: kernel-choice knob for tests / tuning (0 = the default dispatch).  Bit 16: allow split K.  Bit 17: QuickGELU' in 8 bits (what the
  * bf16 mode keeps for the backward instead of u): epilogue 1 writes out0 = byte codes rint((QuickGELU'(u) + 0.1) * 212) with a row stride of
  * ldo0 BYTES, epilogue 3 reads such codes from aux (row stride ldaux bytes). */
+/* HOST arithmetic only: the kernel mudpt_gemm / mudpt_gemm_split runs for these arguments on a device of ncu compute units, as
+ * form | slices << 8 (slices = 1 except for the split-K forms); -1 for arguments the launcher refuses (the checks that read no pointer:
+ * shape, ldo0 / ldo1 / ldaux, epilogue, lo_mode).  variant as in mudpt_gemm: the low byte is the knob, bit 16 = scratch for split K is
+ * available; the other bits do not change the form.  The first rule that matches (mudpt_amd/csrc/gemm.hip gemm_form):
+ *   1. PP: knob 0 | 3 | 5 | 6 | 12, epilogue 0 | 1 | 3 | 5, at least 128 tiles of 256 x 256 (knob 3: 256), ldo0 % 8 == 0 (epilogue 1: ldo1, 3: ldaux too)
+ *   2. SPLITK_K128 / _K64: epilogue 0 | 5, scratch, knob 0 | 12, no split operand, K >= 1536, 2 * (64 x 64 tiles) <= 5 ncu, and 2 .. 4 slices fit
+ *   3. M * N >= 256 * 128 * 512: T256x256; knob 2: T128x256; knob 4: T256x128
+ *   4. T64x64_K128 / T64x64 on small grids (knob 0; 12: never K128) or under knob 10 / 9;  5. T128x64_RING4: knob 6, or at most 128 tiles of
+ *      128 x 128 and not knob 5;  6. T128x128. */
+#define MUDPT_GEMM_PP 0            /* gemm_pp_kernel: persistent 256 x 256 ping-pong tiles */
+#define MUDPT_GEMM_T256x256 1      /* gemm_nt_kernel 256 x 256 x 64, 8 waves */
+#define MUDPT_GEMM_T128x256 2      /* gemm_nt_kernel 128 x 256 x 64, 8 waves */
+#define MUDPT_GEMM_T256x128 3      /* gemm_nt_kernel 256 x 128 x 64, 8 waves */
+#define MUDPT_GEMM_T64x64_K128 4   /* gemm_nt_kernel 64 x 64 x 128, 4 waves */
+#define MUDPT_GEMM_T64x64 5        /* gemm_nt_kernel 64 x 64 x 64, 4 waves */
+#define MUDPT_GEMM_T128x64_RING4 6 /* gemm_nt_kernel 128 x 64 x 64, 4 waves, 4-deep operand ring */
+#define MUDPT_GEMM_T128x128 7      /* gemm_nt_kernel 128 x 128 x 64, 4 waves */
+#define MUDPT_GEMM_SPLITK_K128 8   /* K slices of the 64 x 64 x 128 kernel + splitk_reduce_kernel */
+#define MUDPT_GEMM_SPLITK_K64 9    /* K slices of the 64 x 64 x 64 kernel + splitk_reduce_kernel */
+int mudpt_gemm_form(int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t ldo0, int32_t ldo1, int32_t ldaux, int32_t lo_mode, int32_t variant,
+                    int32_t ncu);
 /* A GEMM with a SPLIT A operand (the forward GEMMs of the parity mode): A = T(v), A_lo = the remainder v - A in a second buffer
  * with the row stride of A in bytes.  lo_mode 1: A_lo holds T values and a second pass contracts it against the same B (22 bits); lo_mode 2:
  * A_lo holds OCP e4m3 bytes of (v - A) * 2^12 (the first K bytes of each row) and the second pass runs on the MX-scaled fp8 matrix

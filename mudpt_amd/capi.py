@@ -17,6 +17,8 @@ EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = rang
 # mudpt_attention_form's codes (include/mudpt.h MUDPT_ATTN_*), by name
 ATTN_FORMS = ("FWD_PAIR", "FWD_PERSISTENT", "FWD_RESIDENT", "FWD_STAGED", "BWD_TWO", "BWD_FUSED_W2", "BWD_FUSED_W1", "BWD_SWEEP", "BWD_RESIDENT",
               "BWD_STAGED")
+# mudpt_gemm_form's codes (include/mudpt.h MUDPT_GEMM_*), by name
+GEMM_FORMS = ("PP", "T256x256", "T128x256", "T256x128", "T64x64_K128", "T64x64", "T128x64_RING4", "T128x128", "SPLITK_K128", "SPLITK_K64")
 
 
 class MudptError(RuntimeError):
@@ -71,6 +73,7 @@ SIGNATURES = {
     "mudpt_profile_read_classes": (_i32, [_vp, C.POINTER(C.c_double * 5), C.POINTER(C.c_double * 5), C.POINTER(C.c_int64 * 5), C.POINTER(C.c_double)]),
     "mudpt_gemm": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
                           _i32, _i32, _vp, _i32, _vp]),
+    "mudpt_gemm_form": (_i32, [_i32] * 10),
     "mudpt_gemm_split": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "mudpt_e4m3_from_f32": (_i32, [_vp, _vp, _sz, _i32]),
     "mudpt_layernorm_fwd_split": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

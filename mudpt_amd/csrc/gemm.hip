@@ -277,22 +277,21 @@ static int cus_or_256() {
 // (same order of the k-steps).  Grids beyond two workgroups per CU lose (fc 804 x 3072 x 768, 624 tiles: 13.7 -> 16.2): they keep 64 (a 64 x 96 x 128
 // tile that would make them fit lost on every shape: fc 13.9 -> 14.3, qkv 8.9 -> 10.0; 256-deep tiles at one workgroup per CU: proj 804 x 768 x 3072
 // 16.2 us unsplit against 14.1 for three slices of 128-deep tiles + their sum, the text tower's shapes +-0).
-static inline bool deep_k_tiles(const GemmArgs& a, int slices, int variant) {
+static inline bool deep_k_tiles(const GemmArgs& a, int slices, int variant, int ncu) {
     const size_t t64 = (size_t)((a.M + 63) / 64) * ((a.N + 63) / 64);
-    return (variant & 0xff) != 12 && a.lo_mode == LO_NONE && (a.K / slices) % 128 == 0 && t64 * slices <= (size_t)2 * cus_or_256();
+    return (variant & 0xff) != 12 && a.lo_mode == LO_NONE && (a.K / slices) % 128 == 0 && t64 * slices <= (size_t)2 * ncu;
 }
 
 // variant: tuning knob (mudpt_model_set "gemm_variant" / mudpt_gemm's last argument): 0 = default kernel choice, 1/2/4 = force a simple tile,
 // 12 = the default choice without the 128-deep K-tiles (A/B)
-template <typename T, int EPI>
-static int launch_epi(const GemmArgs& a, hipStream_t s, int variant) {
+static GemmForm tile_form(const GemmArgs& a, int variant, int ncu) {
     // Large problems that do not go to the persistent ping-pong kernel (gemm_pp.hip): 256 x 256 tile on 8 waves;
     // small problems (text tower, tiny shapes): 128 x 128 on 4 waves.
     if ((size_t)a.M * a.N >= (size_t)256 * 128 * 512) {
         switch (variant & 0xff) {
-            case 2: return launch_cfg<T, 128, 256, 2, 4, EPI>(a, s);
-            case 4: return launch_cfg<T, 256, 128, 4, 2, EPI>(a, s);
-            default: return launch_cfg<T, 256, 256, 2, 4, EPI>(a, s);
+            case 2: return GEMM_T128x256;
+            case 4: return GEMM_T256x128;
+            default: return GEMM_T256x256;
         }
     }
     // fewer 128 x 128 tiles than half the CUs: every workgroup is a latency chain over K -- narrower tiles (twice the
@@ -303,21 +302,38 @@ static int launch_epi(const GemmArgs& a, hipStream_t s, int variant) {
     // tile on 4 waves with the plain double buffer wins on every shape measured (tools/gemm_bench.py --set small / text: sum of a block's
     // GEMMs 217 -> 167 us at M = 804): 32 KB of LDS lets five workgroups share a CU, and these grids are latency chains, not MFMA-bound.
     // gemm_variant 5 / 6 force the earlier 128 x 128 shallow / 128 x 64 deep forms, 9 this one (A/B runs).
-    if (((v == 0 && small_tiles(a)) || v == 10) && deep_k_tiles(a, 1, variant)) return launch_cfg<T, 64, 64, 2, 2, EPI, 2, 128>(a, s);
-    if (((v == 0 || v == 12) && small_tiles(a)) || v == 9 || v == 10) return launch_cfg<T, 64, 64, 2, 2, EPI, 2>(a, s);
-    if ((t128 <= 128 && v != 5) || v == 6) return launch_cfg<T, 128, 64, 2, 2, EPI, 4>(a, s);
-    return launch_cfg<T, 128, 128, 2, 2, EPI>(a, s);
+    if (((v == 0 && small_tiles(a)) || v == 10) && deep_k_tiles(a, 1, variant, ncu)) return GEMM_T64x64_K128;
+    if (((v == 0 || v == 12) && small_tiles(a)) || v == 9 || v == 10) return GEMM_T64x64;
+    if ((t128 <= 128 && v != 5) || v == 6) return GEMM_T128x64_RING4;
+    return GEMM_T128x128;
+}
+
+// the gemm_nt_kernel instantiation behind each simple-tile form
+template <typename T, int EPI>
+static int launch_epi(GemmForm f, const GemmArgs& a, hipStream_t s) {
+    switch (f) {
+        case GEMM_T256x256: return launch_cfg<T, 256, 256, 2, 4, EPI>(a, s);
+        case GEMM_T128x256: return launch_cfg<T, 128, 256, 2, 4, EPI>(a, s);
+        case GEMM_T256x128: return launch_cfg<T, 256, 128, 4, 2, EPI>(a, s);
+        case GEMM_T64x64_K128: return launch_cfg<T, 64, 64, 2, 2, EPI, 2, 128>(a, s);
+        case GEMM_T64x64: return launch_cfg<T, 64, 64, 2, 2, EPI, 2>(a, s);
+        case GEMM_T128x64_RING4: return launch_cfg<T, 128, 64, 2, 2, EPI, 4>(a, s);
+        case GEMM_T128x128: return launch_cfg<T, 128, 128, 2, 2, EPI>(a, s);
+        default: break;  // GEMM_PP and the split-K forms are launched by launch_gemm itself
+    }
+    set_error("gemm: form %d is not a simple tile", (int)f);
+    return MUDPT_ERR_ARG;
 }
 
 template <typename T>
-static int launch_t(int epi, const GemmArgs& a, hipStream_t s, int variant) {
+static int launch_t(int epi, GemmForm f, const GemmArgs& a, hipStream_t s) {
     switch (epi) {
-        case EPI_STORE: return launch_epi<T, EPI_STORE>(a, s, variant);
-        case EPI_GELU: return launch_epi<T, EPI_GELU>(a, s, variant);
-        case EPI_RESIDUAL: return launch_epi<T, EPI_RESIDUAL>(a, s, variant);
-        case EPI_GELU_BWD: return launch_epi<T, EPI_GELU_BWD>(a, s, variant);
-        case EPI_PATCH: return launch_epi<T, EPI_PATCH>(a, s, variant);
-        case EPI_STORE_F32: return launch_epi<T, EPI_STORE_F32>(a, s, variant);
+        case EPI_STORE: return launch_epi<T, EPI_STORE>(f, a, s);
+        case EPI_GELU: return launch_epi<T, EPI_GELU>(f, a, s);
+        case EPI_RESIDUAL: return launch_epi<T, EPI_RESIDUAL>(f, a, s);
+        case EPI_GELU_BWD: return launch_epi<T, EPI_GELU_BWD>(f, a, s);
+        case EPI_PATCH: return launch_epi<T, EPI_PATCH>(f, a, s);
+        case EPI_STORE_F32: return launch_epi<T, EPI_STORE_F32>(f, a, s);
     }
     set_error("gemm: unknown epilogue %d", epi);
     return MUDPT_ERR_ARG;
@@ -345,18 +361,17 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // Split K for the store GEMMs whose grid is a fraction of the chip and whose contraction is long (small batches: M = B L = 804 rows at
 // the reference's training batch of 4, K = 2304 / 3072): a 128 x 64 tile per workgroup leaves 2/3 of the CUs idle while every workgroup
 // walks 36-48 K-steps.  S slices of K fill the chip; their fp32 partials go through the caller's scratch and are summed in slice order.
-static int split_k_slices(int epi, const GemmArgs& a, const GemmOpts& o, bool& deep) {
+static int split_k_slices(int epi, const GemmArgs& a, const GemmOpts& o, int ncu, bool& deep) {
     deep = false;
     const int v = o.variant & 0xff;
     if (!(epi == EPI_STORE || epi == EPI_STORE_F32) || !o.scratch || (v != 0 && v != 12) || a.lo_mode != LO_NONE) return 1;
-    const int ncu = cus_or_256();
     const size_t tiles = (size_t)((a.M + 63) / 64) * ((a.N + 63) / 64);  // 64 x 64 tiles, five workgroups to a CU
     if (tiles * 2 > (size_t)ncu * 5 || a.K < 1536) return 1;
     // with 128-deep K-tiles two workgroups share a CU: three or four slices of those beat four of the 64-deep form (deep_k_tiles)
     int S = (int)((size_t)ncu * 2 / tiles);
     if (S > 4) S = 4;
     while (S > 1 && (a.K % (S * 128) != 0 || a.K / S < 512)) --S;
-    if (S >= 3 && deep_k_tiles(a, S, o.variant) && (size_t)S * a.M * a.N <= o.scratch_elems) { deep = true; return S; }
+    if (S >= 3 && deep_k_tiles(a, S, o.variant, ncu) && (size_t)S * a.M * a.N <= o.scratch_elems) { deep = true; return S; }
     S = (int)((size_t)ncu * 5 / tiles);
     if (S > 4) S = 4;
     while (S > 1 && (a.K % (S * 64) != 0 || a.K / S < 512)) --S;
@@ -375,6 +390,25 @@ bool gemm_uses_pp(int epi, const GemmArgs& a, int variant) {
     const size_t tiles = (size_t)((a.M + 255) / 256) * ((a.N + 255) / 256);
     return (v == 0 || v == 3 || v == 5 || v == 6 || v == 12) && pp_epi && tiles >= (v == 3 ? 256 : 128) && a.ldo0 % 8 == 0 && (epi != EPI_GELU || a.ldo1 % 8 == 0) &&
            (epi != EPI_GELU_BWD || a.ldaux % 8 == 0);
+}
+
+// The one place that decides which kernel runs a launch (kernels.h GemmForm), in the order launch_gemm has always asked: the persistent
+// kernel, then split K, then the simple tiles.  mudpt_gemm_form (include/mudpt.h) exports the decision; tests/test_capi_cpu.py holds it to a table.
+GemmPlan gemm_form(int epi, const GemmArgs& a, const GemmOpts& o, int ncu) {
+    if (gemm_uses_pp(epi, a, o.variant)) return {GEMM_PP, 1};
+    bool deep = false;
+    if (const int S = split_k_slices(epi, a, o, ncu, deep); S > 1) return {deep ? GEMM_SPLITK_K128 : GEMM_SPLITK_K64, S};
+    return {tile_form(a, o.variant, ncu), 1};
+}
+
+bool gemm_shape_ok(int epi, const GemmArgs& a) {
+    if (epi < EPI_STORE || epi > EPI_STORE_F32) return false;
+    if (!(a.M > 0 && a.N > 0 && a.K > 0) || a.K % 64 != 0 || a.N % 16 != 0) return false;
+    if (!(a.ldo0 >= a.N && a.ldo0 % 4 == 0)) return false;
+    if (epi == EPI_GELU && !(a.ldo1 >= a.N && a.ldo1 % 4 == 0)) return false;
+    if ((epi == EPI_RESIDUAL || epi == EPI_GELU_BWD) && !(a.ldaux >= a.N && a.ldaux % 4 == 0)) return false;
+    if (!(a.lo_mode == LO_NONE || a.lo_mode == LO_F16 || a.lo_mode == LO_F8)) return false;
+    return a.lo_mode != LO_F8 || a.K % 128 == 0;
 }
 
 int launch_gemm(int dtype, int epi, const GemmArgs& a, hipStream_t s, const GemmOpts& o) {
@@ -404,9 +438,11 @@ int launch_gemm(int dtype, int epi, const GemmArgs& a, hipStream_t s, const Gemm
     b.flags |= ((variant >> 10) & 3) << 4;  // gemm_pp timing-only ablations (bits 10, 11 of the knob): no LDS fragment reads / no operand DMA
     b.flags |= ((variant >> 12) & 0xff) << 8;  // bits 12..19 of the knob: column-tile group width GN of gemm_pp (0 = default)
     // default: the persistent ping-pong kernel for the big GEMMs whose epilogue needs no operand load besides bias / u
-    if (gemm_uses_pp(epi, a, o.variant)) return launch_gemm_pp(dtype, epi, b, s, o);
-    bool deep = false;
-    if (const int S = split_k_slices(epi, a, o, deep); S > 1) {
+    const GemmPlan plan = gemm_form(epi, a, o, cus_or_256());
+    if (plan.form == GEMM_PP) return launch_gemm_pp(dtype, epi, b, s, o);
+    if (plan.slices > 1) {
+        const int S = plan.slices;
+        const bool deep = plan.form == GEMM_SPLITK_K128;
         GemmArgs q = b;
         q.bias = nullptr; q.out0 = o.scratch; q.ldo0 = a.N; q.ksplit = a.K / S; q.split_stride = (size_t)a.M * a.N;
         if (dtype == DT_BF16) { if (int rc = deep ? launch_cfg<BF16, 64, 64, 2, 2, EPI_STORE_F32, 2, 128>(q, s) : launch_cfg<BF16, 64, 64, 2, 2, EPI_STORE_F32, 2>(q, s)) return rc; }
@@ -419,8 +455,8 @@ int launch_gemm(int dtype, int epi, const GemmArgs& a, hipStream_t s, const Gemm
         HIP_TRY(hipGetLastError());
         return MUDPT_OK;
     }
-    if (dtype == DT_BF16) return launch_t<BF16>(epi, b, s, o.variant);
-    if (dtype == DT_F16) return launch_t<F16>(epi, b, s, o.variant);
+    if (dtype == DT_BF16) return launch_t<BF16>(epi, plan.form, b, s);
+    if (dtype == DT_F16) return launch_t<F16>(epi, plan.form, b, s);
     set_error("gemm: unknown dtype %d", dtype);
     return MUDPT_ERR_ARG;
 }

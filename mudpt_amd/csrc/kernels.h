@@ -52,6 +52,18 @@ struct GemmOpts {
 };
 int launch_gemm(int dtype, int epi, const GemmArgs& a, hipStream_t s, const GemmOpts& o = GemmOpts());
 bool gemm_uses_pp(int epi, const GemmArgs& a, int variant = 0);  // true if launch_gemm dispatches to gemm_pp_kernel
+// Which kernel runs a launch: EVERY threshold and knob value is decided here, in host arithmetic with no HIP call (reads a.M, a.N, a.K,
+// a.ldo0, a.ldo1, a.ldaux, a.lo_mode; o.variant, o.scratch, o.scratch_elems; ncu = the device's compute units).  launch_gemm switches on the
+// result; include/mudpt.h (MUDPT_GEMM_*) names the kernel behind each form.  slices > 1 only for the two split-K forms.
+enum GemmForm : int {
+    GEMM_PP = MUDPT_GEMM_PP, GEMM_T256x256 = MUDPT_GEMM_T256x256, GEMM_T128x256 = MUDPT_GEMM_T128x256, GEMM_T256x128 = MUDPT_GEMM_T256x128,
+    GEMM_T64x64_K128 = MUDPT_GEMM_T64x64_K128, GEMM_T64x64 = MUDPT_GEMM_T64x64, GEMM_T128x64_RING4 = MUDPT_GEMM_T128x64_RING4,
+    GEMM_T128x128 = MUDPT_GEMM_T128x128, GEMM_SPLITK_K128 = MUDPT_GEMM_SPLITK_K128, GEMM_SPLITK_K64 = MUDPT_GEMM_SPLITK_K64
+};
+struct GemmPlan { GemmForm form; int slices; };
+GemmPlan gemm_form(int epi, const GemmArgs& a, const GemmOpts& o, int ncu);
+// the checks of launch_gemm that read no pointer (shape, strides, epilogue and split-operand codes): what mudpt_gemm_form can refuse
+bool gemm_shape_ok(int epi, const GemmArgs& a);
 int launch_gemm_pp(int dtype, int epi, const GemmArgs& a, hipStream_t s, const GemmOpts& o);  // persistent 256x256 ping-pong kernel (gemm_pp.hip)
 
 // ------------------------------------------------------------------------------------------------

@@ -2084,6 +2084,17 @@ extern "C" int mudpt_gemm(int32_t dtype, int32_t epi, int32_t M, int32_t N, int3
     a.gelu_q8 = (variant & 0x20000) != 0;  // unit-test hook: QuickGELU' in 8 bits (epilogues 1 / 3; ldo0 / ldaux are then BYTE strides)
     return launch_gemm(dtype, epi, a, (hipStream_t)stream, o);
 }
+// the decision launch_gemm takes for mudpt_gemm's / mudpt_gemm_split's arguments (bit 16 of variant: the scratch mudpt_gemm would pass)
+extern "C" int mudpt_gemm_form(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ldo0, int32_t ldo1, int32_t ldaux, int32_t lo_mode, int32_t variant, int32_t ncu) {
+    static float some_scratch = 0.f;  // never dereferenced: gemm_form only asks whether there is one
+    GemmOpts o;
+    o.variant = variant & ~0x30000;
+    if (variant & 0x10000) { o.scratch = &some_scratch; o.scratch_elems = mudpt_model::kScratchElems; }
+    GemmArgs a; a.M = M; a.N = N; a.K = K; a.ldo0 = ldo0; a.ldo1 = ldo1; a.ldaux = ldaux; a.lo_mode = lo_mode;
+    if (ncu <= 0 || !gemm_shape_ok(epi, a)) return -1;
+    const GemmPlan p = gemm_form(epi, a, o, ncu);
+    return (int)p.form | p.slices << 8;
+}
 extern "C" int mudpt_gemm_split(int32_t dtype, int32_t epi, int32_t M, int32_t N, int32_t K, const void* A, const void* A_lo, int32_t lo_mode, int32_t lda,
                                 const void* B, const void* B8, int32_t b8_scale, int32_t ldb, const float* bias, void* out0, int32_t ldo0, void* out1,
                                 void* out1_lo, int32_t out1_lo_mode, int32_t ldo1, const void* aux, int32_t ldaux, int32_t variant, void* stream) {

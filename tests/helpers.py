@@ -2,6 +2,7 @@
 import ast
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -161,3 +162,119 @@ def attention_test_launches():
     for L, _, causal in ATTN_SEL_CASES:
         calls += [(0, L, int(causal), 0), (1, L, int(causal), 1)] + [(1, L, int(causal) | f, 0) for f, _ in ATTN_SEL_COMPARE]
     return calls
+
+
+# ---- GEMM cases of test_gemm_forms_gpu.py, kept here so that test_capi_cpu.py can check, without a GPU, which kernel forms and which regimes of
+# the persistent kernel they reach ----
+class GemmCase(namedtuple("GemmCase", "name form variant M N K epis slices win patch grid order", defaults=(1, None, None, None, None))):
+    """One launch shape of test_gemm_forms_gpu.py: the form (capi.GEMM_FORMS) and split-K slices it must take at 256 compute units under
+    `variant` (mudpt_gemm's knob), the epilogues it runs, the (pad, off) of the operand windows it overrides (GEMM_WINDOWS), (P, L) of the
+    patch epilogue, and -- persistent cases -- the grid and tile-order regime it is there for."""
+    __slots__ = ()
+
+
+# (pad, off) in elements, multiples of 16: an operand is the window [rows, width] at column off of a buffer whose row stride is width + pad.
+# Different for every operand, so that a stride or base taken from the wrong one shows.
+GEMM_WINDOWS = {"A": (48, 16), "B": (32, 32), "out0": (48, 32), "out1": (32, 16), "aux": (64, 48)}
+GEMM_GUARD_ROWS = 32  # rows of NaN (operands) / sentinel (outputs) before and after every window
+_F32, _ST, _RES, _PATCH, _SPLIT = 5, 0, 2, 4, 0x10000  # epilogues (capi.EPI_*) and mudpt_gemm's "split K allowed" bit
+
+
+def _cases(stem, form, variant, M, N, Ks, epis, **kw):
+    return [GemmCase(f"{stem}_k{K}", form, variant, M, N, K, epis, **kw) for K in Ks]
+
+
+# Every M is ragged against its tile and against 16; N is one 16-column group past a tile edge (80, 144, 1040, 1296, 3088) or one short (1008).
+GEMM_FORM_CASES = (
+    _cases("t64", "T64x64", 0, 131, 80, (64, 192), (_F32, _ST, _RES))
+    + _cases("t64deep", "T64x64_K128", 0, 131, 80, (128, 384), (_F32, _ST, _RES))
+    # the 4-deep ring: K below / at / above its prologue depth of three K-tiles
+    + _cases("ring4_v6", "T128x64_RING4", 6, 259, 80, (64, 128, 192, 256), (_F32, _ST, _RES))
+    + _cases("t128_v5", "T128x128", 5, 259, 144, (64, 192), (_F32, _ST, _RES))
+    + _cases("t128", "T128x128", 0, 4100, 1296, (3072,), (_F32, _RES))
+    + _cases("t64_v9", "T64x64", 9, 131, 80, (192,), (_F32, _ST)) + _cases("t64deep_v10", "T64x64_K128", 10, 131, 80, (128,), (_F32, _ST))
+    + _cases("t64_v10", "T64x64", 10, 131, 80, (192,), (_F32, _ST)) + _cases("t64_v12", "T64x64", 12, 131, 80, (128,), (_F32, _ST))
+    + _cases("t256_res", "T256x256", 0, 16141, 1040, (64, 192), (_RES,))
+    + _cases("t256_patch", "T256x256", 0, 16170, 1040, (64, 192), (_PATCH,), patch=(98, 103))  # 165 images
+    + _cases("t256_v1", "T256x256", 1, 16141, 1040, (64, 192), (_F32, _ST))
+    + _cases("t128x256_v2", "T128x256", 2, 16141, 1040, (192,), (_F32, _ST, _RES))
+    + _cases("t256x128_v4", "T256x128", 4, 16141, 1040, (192,), (_F32, _ST, _RES))
+    + _cases("splitk_deep", "SPLITK_K128", _SPLIT, 804, 784, (3072,), (_F32, _ST), slices=3)
+    + _cases("splitk", "SPLITK_K64", _SPLIT, 804, 784, (1728,), (_F32, _ST), slices=3)
+    # the persistent kernel.  32 x 4 = 128 tiles: every tile split into halves
+    + _cases("pp_all_split", "PP", 0, 8003, 1008, (64, 192), (_F32, _ST), grid="all_split", order="one_group")
+    + _cases("pp_one_ntn5", "PP", 0, 8205, 1040, (128,), (_F32, _ST), grid="one_per_workgroup", order="one_group")  # 33 x 5 = 165 tiles
+    + _cases("pp_half_tail", "PP", 0, 13069, 1296, (192,), (_F32, _ST), grid="half_tile_tail", order="full_groups")  # 52 x 6 = 312 = 256 + 56
+    + _cases("pp_whole_tail", "PP", 0, 19469, 1040, (64,), (_F32, _ST), grid="whole_tile_tail", order="one_group")  # 77 x 5 = 385 = 256 + 129
+    + _cases("pp_leftover_ntn16", "PP", 0, 2061, 4096, (64, 192), (_F32, _ST), grid="one_per_workgroup", order="leftover_group")  # ViT-L/14's fc
+    + _cases("pp_leftover_ntn13", "PP", 0, 2600, 3088, (128,), (_F32, _ST), grid="one_per_workgroup", order="leftover_group")
+    # as the model launches them (model.cpp): the kv GEMM writes 2 d columns at column d of the 3 d-wide qkv buffer; the last block's dX GEMM
+    # reads A = dqkv + d and B = w_in_t + d, both 3 d wide
+    + _cases("pp_kv", "PP", 0, 5640, 1536, (768,), (_ST,), win={"out0": (768, 768)}, grid="one_per_workgroup", order="full_groups")
+    + _cases("pp_dx_last", "PP", 0, 10763, 768, (1536,), (_F32, _ST), win={"A": (768, 768), "B": (768, 768)}, grid="one_per_workgroup", order="one_group")
+)
+# one ragged, strided case per form that builds the QuickGELU epilogues (the split-K forms are store-only)
+GEMM_GELU_CASES = ("t64_k64", "t64deep_k128", "ring4_v6_k64", "t128_v5_k64", "t256_v1_k64", "t128x256_v2_k192", "t256x128_v4_k192", "pp_all_split_k64")
+# a persistent-kernel-sized launch whose ldo0 is no multiple of 8 elements falls to a simple tile (out0 pad 4)
+GEMM_REFUSAL_CASES = _cases("pp_size_ldo0_mod8", "T64x64", 0, 8003, 1008, (64,), (_F32, _ST), win={"out0": (4, 0)})
+
+
+def gemm_windows(case, windowed=True):
+    return dict(GEMM_WINDOWS, **(case.win or {})) if windowed else dict.fromkeys(GEMM_WINDOWS, (0, 0))
+
+
+def gemm_form_args(case, epi, ncu, windowed=True):
+    """mudpt_gemm_form's arguments for epilogue `epi` of a case, with the output strides of its windows."""
+    w = gemm_windows(case, windowed)
+    return (epi, case.M, case.N, case.K, case.N + w["out0"][0], case.N + w["out1"][0], case.N + w["aux"][0], 0, case.variant, ncu)
+
+
+# Mirrors of launch_pp's grid arithmetic and of gemm_pp_kernel's tile order (gemm_pp.hip); GN lives in device code.
+def pp_grid(M, N, ncu):
+    """(tiles, grid, rem_half) of launch_pp: rem_half > 0 = that many tiles of the last, partial wave run as two half tiles each."""
+    nt = -(-M // 256) * -(-N // 256)
+    grid = (2 * nt if 2 * nt <= ncu else nt) if nt < ncu else ncu
+    rem = nt % grid
+    return nt, grid, rem if rem > 0 and 2 * rem <= grid else 0
+
+
+def pp_grid_regime(M, N, ncu):
+    nt, grid, rem_half = pp_grid(M, N, ncu)
+    if nt < ncu:
+        return "all_split" if grid == 2 * nt else "one_per_workgroup"
+    return "half_tile_tail" if rem_half else ("whole_tile_tail" if nt % grid else "whole_waves")
+
+
+def pp_group_width(ntn):
+    return 6 if ntn >= 12 else (3 if ntn >= 6 and ntn % 3 == 0 else ntn)
+
+
+def pp_order_regime(N):
+    ntn = -(-N // 256)
+    gn = pp_group_width(ntn)
+    return "one_group" if gn == ntn else ("full_groups" if ntn % gn == 0 else "leftover_group")
+
+
+def pp_tile_mn(tile, ntm, ntn):
+    """tile_mn: (row panel, column tile) of the tile-th tile in the kernel's order."""
+    gn = pp_group_width(ntn)
+    tpg, full = ntm * gn, ntn // gn
+    ng = tile // tpg
+    if ng < full:
+        rem = tile - ng * tpg
+        return rem // gn, ng * gn + rem % gn
+    wl, rem = ntn - full * gn, tile - full * tpg
+    return rem // wl, full * gn + rem % wl
+
+
+def pp_case_for(case, ncu):
+    """A persistent case on a device of ncu compute units: itself at 256; otherwise the smallest row count (same ragged edge) that reaches its
+    grid regime there, or None where none does (the kernel takes 128 tiles or more: "all_split" needs at least 256 units)."""
+    if case.grid is None or pp_grid_regime(case.M, case.N, ncu) == case.grid:
+        return case
+    ntn = -(-case.N // 256)
+    for ntm in range(-(-128 // ntn), 4 * ncu):
+        M = (ntm - 1) * 256 + (case.M - 1) % 256 + 1
+        if pp_grid_regime(M, case.N, ncu) == case.grid:
+            return case._replace(M=M)
+    return None

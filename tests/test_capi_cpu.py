@@ -161,3 +161,110 @@ def test_patchify_cases_wrap_every_grid_stride_loop():
     assert any(vector(c[2], c[3]) and over("vector", c) for c in PATCH_CASES)
     assert any(not vector(c[2], c[3]) and over("any", c) for c in PATCH_CASES)
     assert any(over("split", c) for c in PATCH_SPLIT_CASES)
+
+
+def _g(epi, M, N, K, want, slices=1, variant=0, ldo0=None, ldo1=None, ldaux=None, lo_mode=0, ncu=256):
+    """One row of GEMM_FORM_TABLE: mudpt_gemm_form's arguments (contiguous outputs unless a stride is given) and the form it must name."""
+    return (epi, M, N, K, N if ldo0 is None else ldo0, N if ldo1 is None else ldo1, N if ldaux is None else ldaux, lo_mode, variant, ncu), (want, slices)
+
+
+S16 = 0x10000  # bit 16 of mudpt_gemm's variant: scratch for split K is available
+# Worked out by hand from the dispatch this table replaced (gemm_uses_pp -> split_k_slices -> launch_epi, with small_tiles and deep_k_tiles), at
+# 256 compute units unless a row says otherwise.  t64 / t128 / t256 = tiles of 64 x 64 / 128 x 128 / 256 x 256 (ragged edges count as tiles).
+GEMM_FORM_TABLE = [
+    # M * N against 256 * 128 * 512 = 16 777 216 (epilogue 2 never takes the persistent kernel); below it t64 = 4096 and t128 = 1024 leave 128 x 128
+    _g(2, 16384, 1024, 192, "T256x256"), _g(2, 16383, 1024, 192, "T128x128"), _g(2, 16384, 1024, 192, "T128x256", variant=2),
+    _g(2, 16384, 1024, 192, "T256x128", variant=4), _g(2, 16383, 1024, 192, "T128x128", variant=2),
+    # small_tiles: t64 = 1280 | 1281 (= 61 x 21) at K > 512, and t64 = 2560 | 2561 (= 197 x 13) with K = 512 | 576
+    _g(2, 5120, 1024, 576, "T64x64"), _g(2, 3904, 1344, 576, "T128x128"),
+    _g(2, 10240, 1024, 512, "T64x64"), _g(2, 10240, 1024, 576, "T128x128"), _g(2, 12608, 832, 512, "T128x128"),
+    # deep_k_tiles: t64 = 512 | 513 (= 27 x 19) against 2 ncu, K % 128, a split operand, knob 12
+    _g(2, 2048, 1024, 128, "T64x64_K128"), _g(2, 2048, 1024, 192, "T64x64"), _g(2, 1728, 1216, 128, "T64x64"),
+    _g(2, 2048, 1024, 128, "T64x64", lo_mode=1), _g(2, 2048, 1024, 128, "T64x64", variant=12),
+    # t128 = 128 | 129 (= 43 x 3) decides ring against 128 x 128 once small_tiles is out of the way (knob 1 below the large-problem size)
+    _g(5, 2048, 1024, 576, "T128x64_RING4", variant=1), _g(5, 5504, 384, 576, "T128x128", variant=1), _g(5, 2048, 1024, 576, "T128x128", variant=5),
+    # the persistent kernel: t256 = 127 | 128; knob 3: 255 | 256 (128 is not enough); epilogues 2 and 4 never
+    _g(0, 32512, 256, 64, "T64x64"), _g(0, 32768, 256, 64, "PP"), _g(0, 65280, 256, 64, "T128x128", variant=3), _g(0, 65536, 256, 64, "PP", variant=3),
+    _g(0, 32768, 256, 64, "T128x128", variant=3), _g(2, 32768, 256, 64, "T64x64"), _g(4, 32768, 256, 64, "T64x64"),
+    # ... and its stride conditions: ldo0 always, ldo1 under epilogue 1 only, ldaux under epilogue 3 only (8003 x 1008: t256 = 128, t64 = 2016)
+    _g(0, 8003, 1008, 64, "T64x64", ldo0=1012), _g(0, 8003, 1008, 64, "PP", ldo0=1016), _g(5, 8003, 1008, 64, "T64x64", ldo0=1012),
+    _g(1, 8003, 1008, 64, "T64x64", ldo1=1012), _g(1, 8003, 1008, 64, "PP", ldo1=1016),
+    _g(3, 8003, 1008, 64, "T64x64", ldaux=1012), _g(3, 8003, 1008, 64, "PP", ldaux=1016),
+    _g(0, 8003, 1008, 64, "PP", ldo1=1012, ldaux=1012), _g(3, 8003, 1008, 64, "PP", ldo1=1012),
+    # split K (804 x 784: t64 = 169): K = 1472 | 1536; no scratch, another epilogue, a split operand, a knob other than 0 | 12: never;
+    # knob 12 takes the 64-deep slices (1280 / 169 = 7 -> 4) where knob 0 takes three 128-deep ones (512 / 169 = 3)
+    _g(0, 804, 784, 1472, "T64x64", variant=S16), _g(0, 804, 784, 1536, "SPLITK_K128", 3, variant=S16),
+    _g(5, 804, 784, 3072, "SPLITK_K128", 3, variant=S16), _g(5, 804, 784, 1728, "SPLITK_K64", 3, variant=S16),
+    _g(5, 804, 784, 3072, "T64x64_K128"), _g(2, 804, 784, 3072, "T64x64_K128", variant=S16), _g(5, 804, 784, 3072, "T64x64", variant=S16, lo_mode=1),
+    _g(5, 804, 784, 3072, "SPLITK_K64", 4, variant=S16 | 12), _g(5, 804, 784, 3072, "T64x64", variant=S16 | 9),
+    # ... slice counts around t64 * slices = 512: t64 = 128 -> 4 deep slices, 130 -> 3, 171 (= 9 x 19) -> 2 deep ones are too few: 4 of the 64-deep form
+    _g(0, 512, 1024, 3072, "SPLITK_K128", 4, variant=S16), _g(0, 640, 832, 3072, "SPLITK_K128", 3, variant=S16),
+    _g(0, 576, 1216, 3072, "SPLITK_K64", 4, variant=S16),
+    # ... 2 t64 against 5 ncu.  At 256 units the 4 Mi-element scratch of mudpt_gemm refuses two slices of 640 tiles before the tile bound does
+    # (t64 = 640 | 656: unsplit either way), so the bound itself is bracketed at 64 units: t64 = 160 | 161 (= 23 x 7)
+    _g(0, 2560, 1024, 3072, "T64x64", variant=S16), _g(0, 2497, 976, 3072, "T64x64", variant=S16), _g(0, 2624, 1024, 3072, "T64x64", variant=S16),
+    _g(0, 640, 1024, 3072, "SPLITK_K64", 2, variant=S16, ncu=64), _g(0, 1472, 448, 3072, "T64x64", variant=S16, ncu=64),
+    # ... the shapes of test_gemm_split_k
+    _g(5, 804, 768, 3072, "SPLITK_K128", 3, variant=S16), _g(5, 804, 768, 2304, "SPLITK_K128", 3, variant=S16),
+    _g(5, 450, 512, 2048, "SPLITK_K128", 4, variant=S16), _g(5, 201, 768, 3072, "SPLITK_K128", 4, variant=S16),
+    _g(5, 1000, 768, 1536, "SPLITK_K64", 3, variant=S16),
+    # the knobs: 1 | 2 | 4 a simple tile instead of the persistent kernel (16141 x 1040: t256 = 320, M N above the large-problem size)
+    _g(5, 16141, 1040, 192, "PP"), _g(5, 16141, 1040, 192, "T256x256", variant=1), _g(5, 16141, 1040, 192, "T128x256", variant=2),
+    _g(5, 16141, 1040, 192, "T256x128", variant=4), _g(2, 16141, 1040, 192, "T256x256"), _g(4, 16170, 1040, 192, "T256x256"),
+    # 5 | 6: 128 x 128 | the ring whatever the grid; 9 | 10: 64 x 64 (10: 128-deep where K allows); 12: the default without 128-deep tiles
+    _g(5, 259, 144, 192, "T128x128", variant=5), _g(5, 259, 80, 192, "T128x64_RING4", variant=6), _g(5, 259, 80, 192, "T64x64"),
+    _g(5, 131, 80, 192, "T64x64", variant=9), _g(5, 131, 80, 128, "T64x64", variant=9), _g(5, 131, 80, 128, "T64x64_K128", variant=10),
+    _g(5, 131, 80, 192, "T64x64", variant=10), _g(5, 131, 80, 128, "T64x64", variant=12), _g(5, 131, 80, 128, "T64x64_K128"),
+    # ... on a grid past small_tiles (4100 x 1296 x 3072: t64 = 1365, t128 = 363)
+    _g(5, 4100, 1296, 3072, "T128x128"), _g(5, 4100, 1296, 3072, "T128x64_RING4", variant=6), _g(5, 4100, 1296, 3072, "T64x64", variant=9),
+    _g(5, 4100, 1296, 3072, "T64x64", variant=10), _g(5, 4100, 1296, 3072, "T128x128", variant=12),
+    # ... and at the persistent kernel's sizes: 5 | 6 | 12 leave it in place, 9 | 10 fall to the large simple tile
+    _g(5, 33000, 768, 768, "PP", variant=5), _g(5, 33000, 768, 768, "PP", variant=6), _g(5, 33000, 768, 768, "PP", variant=12),
+    _g(5, 33000, 768, 768, "T256x256", variant=9), _g(5, 33000, 768, 768, "T256x256", variant=10),
+]
+# arguments launch_gemm refuses: K % 64, N % 16, ldo0 < N, ldo0 % 4, ldo1 / ldaux where the epilogue reads them, epilogue, lo_mode, e4m3 pass at K % 128
+GEMM_FORM_REFUSED = [_g(0, 64, 64, 96, None), _g(0, 64, 72, 64, None), _g(0, 64, 64, 64, None, ldo0=48), _g(0, 64, 64, 64, None, ldo0=66),
+                     _g(1, 64, 64, 64, None, ldo1=48), _g(1, 64, 64, 64, None, ldo1=66), _g(2, 64, 64, 64, None, ldaux=48), _g(3, 64, 64, 64, None, ldaux=66),
+                     _g(6, 64, 64, 64, None), _g(-1, 64, 64, 64, None), _g(0, 64, 64, 64, None, lo_mode=3), _g(0, 64, 64, 192, None, lo_mode=2),
+                     _g(0, 0, 64, 64, None), _g(0, 64, 64, 64, None, ncu=0)]
+
+
+def test_gemm_form_table(lib):
+    """Which GEMM kernel a launch runs is host arithmetic (gemm_form, exported as mudpt_gemm_form): every form computes the same numbers bit for
+    bit, so only this table notices a wrong edit to the dispatch before the benchmark does.  Every threshold is bracketed on both sides."""
+    header = open(capi.HEADER_PATH).read()
+    for code, name in enumerate(capi.GEMM_FORMS):
+        assert f"#define MUDPT_GEMM_{name} {code} " in header, name
+    for args, (want, slices) in GEMM_FORM_TABLE:
+        got = lib.mudpt_gemm_form(*args)
+        assert got == (capi.GEMM_FORMS.index(want) | slices << 8), (args, want, slices, (capi.GEMM_FORMS[got & 0xff], got >> 8) if got >= 0 else got)
+    assert {want for _, (want, _) in GEMM_FORM_TABLE} == set(capi.GEMM_FORMS)
+    # epilogue 0 does not read ldo1 / ldaux: strides that epilogues 1 / 3 refuse are accepted
+    assert lib.mudpt_gemm_form(0, 64, 64, 64, 64, 0, 0, 0, 0, 256) == (capi.GEMM_FORMS.index("T64x64") | 1 << 8)
+    for args, _ in GEMM_FORM_REFUSED:
+        assert lib.mudpt_gemm_form(*args) == -1, args
+
+
+def test_gemm_gpu_cases_reach_every_form(lib):
+    """The cases tests/test_gemm_forms_gpu.py runs reach, at 256 compute units, all ten forms with the form each names, every grid regime of
+    launch_pp and every tile-order regime of gemm_pp_kernel's tile_mn (a Python mirror of their formulas: GN lives in device code); and the
+    mirrored tile order visits every tile of every persistent case exactly once."""
+    from tests import helpers as H
+    reached = set()
+    for c in H.GEMM_FORM_CASES + H.GEMM_REFUSAL_CASES:
+        for epi in c.epis:
+            got = lib.mudpt_gemm_form(*H.gemm_form_args(c, epi, 256))
+            assert got == (capi.GEMM_FORMS.index(c.form) | c.slices << 8), (c.name, epi, got)
+            reached.add(got & 0xff)
+    assert reached == set(range(len(capi.GEMM_FORMS))), sorted(capi.GEMM_FORMS[i] for i in set(range(10)) - reached)
+    assert {c.name for c in H.GEMM_FORM_CASES} >= set(H.GEMM_GELU_CASES)
+    assert {c.form for c in H.GEMM_FORM_CASES if c.name in H.GEMM_GELU_CASES} == set(capi.GEMM_FORMS) - {"SPLITK_K128", "SPLITK_K64"}
+    pp = [c for c in H.GEMM_FORM_CASES if c.form == "PP"]
+    for c in pp:
+        assert (H.pp_grid_regime(c.M, c.N, 256), H.pp_order_regime(c.N)) == (c.grid, c.order), c.name
+        ntm, ntn = -(-c.M // 256), -(-c.N // 256)
+        assert sorted(H.pp_tile_mn(t, ntm, ntn) for t in range(ntm * ntn)) == [(m, n) for m in range(ntm) for n in range(ntn)], c.name
+    assert {c.grid for c in pp} == {"all_split", "one_per_workgroup", "half_tile_tail", "whole_tile_tail"}
+    assert {c.order for c in pp} == {"one_group", "full_groups", "leftover_group"}
+    # K = 64 (one K-step per tile: the prefetch crosses a tile boundary every step) and 128 run on the persistent kernel too
+    assert {64, 128} <= {c.K for c in pp}

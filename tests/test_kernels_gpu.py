@@ -69,8 +69,9 @@ def test_gemm_exact_integers_full_size(lib, dtype):
 def test_gemm_epilogues(lib, dtype, shape):
     """All fused epilogues against a float64 product.  The last two shapes leave a partial last wave of 256 x 256 tiles on 256
     CUs (261 = 256 + 5 and 603 = 2 * 256 + 91 tiles), which the persistent kernel runs as half tiles; both have a ragged
-    last row panel (22100: the lower half tile is entirely out of range).  The 99-row shapes are the trimmed text tower's: the
-    small-grid kernel with its 4-deep operand ring (K = 192: exactly the ring's prologue depth)."""
+    last row panel (22100: the lower half tile is entirely out of range).  The 99-row shapes are the trimmed text tower's: small grids,
+    which run the 64 x 64 kernel (t64 = 16 tiles; K = 512 in 128-deep K-tiles).  The 4-deep operand ring those shapes once ran is reachable
+    through gemm_variant 6 only: tests/test_gemm_forms_gpu.py runs it."""
     dt, tt = DT[dtype]
     M, N, K = shape
     g = torch.Generator().manual_seed(M + N + K)
