@@ -304,6 +304,7 @@ __global__ __launch_bounds__(NC * 64) void attn_fwd_pair_kernel(AttnArgs p) {
 
     if (qbA < nqb) fwd_qblock<T, NC, CAUSAL>(p, Ks, Vs, kmask, pair, qbA, qa0, qa1, lane);
     if (qbB < nqb) fwd_qblock<T, NC, CAUSAL>(p, Ks, Vs, kmask, pair, qbB, qb0, qb1, lane);
+    else if (qbB == nqb && lane < 16 && p.lse) p.lse[(size_t)pair * Lp + nqb * 16 + lane] = 0.f;  // L <= 32 NC - 16: the all-padding block's lse rows are zero too
 }
 
 // Persistent forward: one workgroup of 2 NC waves per CU walks (sequence, head) pairs; wave w owns query block w (L <= 32 NC,
@@ -372,6 +373,7 @@ __global__ __launch_bounds__(NC * 128) void attn_fwd_kernel(AttnArgs p, int npai
         }
         const elem* Ks = (const elem*)(smem + cur * 2 * IMG);
         if (wave < nqb) fwd_qblock<T, NC, CAUSAL>(p, Ks, Ks + Lp * RS, kmask, pair, wave, q0, q1, lane);
+        else if (lane < 16 && p.lse) p.lse[(size_t)pair * Lp + wave * 16 + lane] = 0.f;  // L <= 32 NC - 16: the all-padding block's lse rows are zero too
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next pair's images have landed (and this wave's stores are out)
         __syncthreads();                                  // ... for every wave, and everyone is done reading the current images
         q0 = n0;

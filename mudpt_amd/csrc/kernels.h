@@ -110,6 +110,13 @@ int launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s, const LaunchProf
 
 // ------------------------------------------------------------------------------------------------
 // Attention on packed qkv [B, L, 3*H*64] (q | k | v, heads contiguous inside each third), head dim 64.
+// Sequences are independent, on one condition: ROWS OF ANOTHER SEQUENCE MUST BE FINITE.  The kernels work on rows padded to Lp = 32 * ceil(L / 32)
+// and several of them load whole padded images (LDS-DMA): image rows L .. Lp - 1 of sequence b are the first rows of sequence b + 1 in
+// qkv and dout (zeros past the end of the tensor: the loads are bounds-checked against B * L rows, nothing beyond the tensors is read).
+// Those rows only ever meet P = 0 (padded keys start their scores at -inf, padded queries carry lse = -inf), and 0 x finite adds an exact
+// zero: a sequence's out, lse, dqkv and delta do not depend on its neighbours' VALUES -- but an Inf / NaN row would poison the sequence
+// before it (masking K and V instead would cost the hot path).  Nothing is written outside [B, L] rows of out / dqkv and [B, H, Lp] of
+// lse / delta; the forward leaves lse[.., L:Lp] = 0.  tests/test_attention_forms_gpu.py holds every instantiation to this.
 // ------------------------------------------------------------------------------------------------
 struct AttnArgs {
     const void* qkv = nullptr;  // T [B, L, 3*H*64]

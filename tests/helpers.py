@@ -133,6 +133,40 @@ ATTN_WINDOW_CASES = [(3, 201, 12, False, 197, 4), (2, 77, 8, True, 1, 4), (3, 15
 ATTN_SEL_CASES = [(26, 8, True), (77, 8, True), (201, 12, False), (581, 3, False)]  # (L, H, causal)
 
 
+def attn64(qkv, H, causal):
+    """softmax(q k^T / 8 [+ causal mask]) v per head in float64; qkv [B, L, 3 H 64] packed q | k | v, heads contiguous in each third."""
+    B, L, _ = qkv.shape
+    q, k, v = (t.reshape(B, L, H, 64).transpose(1, 2).double() for t in qkv.split(H * 64, dim=-1))
+    s = q @ k.transpose(-1, -2) / 8.0
+    if causal:
+        s = s + torch.full((L, L), float("-inf"), dtype=torch.float64).triu_(1)
+    return (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(B, L, H * 64)
+
+
+def attn64_fwd_bwd(qkv, dout, H, causal, round_to=None):
+    """(out [B, L, H 64], lse [B, H, L], dqkv [B, L, 3 H 64]) of attn64 and its gradient under dout, in float64 without autograd (so that the
+    4096-row case needs no graph).  round_to = a 16-bit torch dtype T: the same sums with the values rounded to T where the kernels round them
+    (test_attention_forms_gpu.py lists the points); every product and sum stays float64."""
+    rnd = (lambda x: x) if round_to is None else (lambda x: x.to(round_to).double())
+    B, L, _ = qkv.shape
+    q, k, v = (t.reshape(B, L, H, 64).transpose(1, 2).double() for t in qkv.split(H * 64, dim=-1))
+    g = dout.reshape(B, L, H, 64).transpose(1, 2).double()
+    s = q @ k.transpose(-1, -2) / 8.0
+    if causal:
+        s = s + torch.full((L, L), float("-inf"), dtype=torch.float64).triu_(1)
+    m = s.max(dim=-1, keepdim=True).values
+    e = torch.exp(s - m)
+    l = e.sum(dim=-1, keepdim=True)
+    lse = m + torch.log(l)
+    o = rnd((rnd(e) @ v) / l)  # forward: exp(s - max) to T before P.V, the row sum from the unrounded values, O to T
+    p = torch.exp(s - lse)     # backward: the normalised probabilities again, from lse
+    delta = (g * o).sum(dim=-1, keepdim=True)
+    ds = rnd(p * (g @ v.transpose(-1, -2) - delta))
+    dq, dk, dv = ds @ k / 8.0, ds.transpose(-1, -2) @ q / 8.0, rnd(p).transpose(-1, -2) @ g
+    flat = lambda t: t.transpose(1, 2).reshape(B, L, H * 64)  # noqa: E731
+    return flat(o), lse.squeeze(-1), rnd(torch.cat([flat(dq), flat(dk), flat(dv)], dim=-1))
+
+
 def attn_bwd_form_flags(L, causal):
     """The kernel-choice bits test_attention_fwd_bwd adds to the backward after the default run; bit 4 (sweep) where a sweep kernel exists."""
     return (2, 4, 8) if causal or L > 224 else (2, 4, 8, 16)
@@ -161,6 +195,105 @@ def attention_test_launches():
         calls += [(0, L, int(causal), 0), (1, L, int(causal) | ATTN_WINDOW_FULL_FLAG, 0), (1, L, int(causal) | attn_window_flags(row0, n), 0)]
     for L, _, causal in ATTN_SEL_CASES:
         calls += [(0, L, int(causal), 0), (1, L, int(causal), 1)] + [(1, L, int(causal) | f, 0) for f, _ in ATTN_SEL_COMPARE]
+    return calls
+
+
+# ---- attention cases of test_attention_forms_gpu.py: every (form, NC = padded length / 32, mask) instantiation of the whole-pair kernels, the
+# persistent loops over pairs, the single-query edges and the long forms; test_capi_cpu.py holds them to mudpt_attention_form without a GPU ----
+ATTN_GUARD_ROWS = 64  # rows of NaN (operands) / sentinel (outputs) before and after every tensor
+ATTN_NCS = range(1, 8)
+
+
+def attn_instance_lengths(NC):
+    """First length of the NC range, the two lengths around "the last 16-key tile is all padding", the full padded length; L = 1 is NC = 1's first."""
+    return sorted({32 * (NC - 1) + 1, 32 * NC - 16, 32 * NC - 15, 32 * NC})
+
+
+# (B, L, H, causal): three sequences (a middle one for the isolation test), two heads (a head offset)
+ATTN_INSTANCE_CASES = [(3, L, 2, causal) for NC in ATTN_NCS for causal in (False, True) for L in attn_instance_lengths(NC)]
+ATTN_PEAKED_CASES = [(3, 32 * NC - 15, 2, causal) for NC in ATTN_NCS for causal in (False, True)]  # one L per NC: padding inside the last real tile
+ATTN_PEAKED_GAIN = 3.0  # on q and k, as test_attention_long_forward_forms; v and dout stay O(1)
+
+
+def attn_instance_launches(L, causal):
+    """(bwd, flags, form) of the forward and of every backward kernel-choice flag at L <= 224: default, 2 (two kernels), 4 (fused, two blocks
+    per wave), 8 (fused), and 16 (sweep) where a sweep kernel exists (no mask).  flags carry the mask in bit 0, as mudpt_attention_form takes them."""
+    assert L <= 224
+    c, Lp = int(causal), -(-L // 32) * 32
+    default = ("BWD_FUSED_W2" if Lp <= 96 else "BWD_TWO") if causal else ("BWD_SWEEP" if Lp >= 128 else "BWD_FUSED_W2")
+    calls = [(0, c, "FWD_PAIR" if causal else "FWD_PERSISTENT"), (1, c, default), (1, c | 2, "BWD_TWO"), (1, c | 4, "BWD_FUSED_W1"), (1, c | 8, "BWD_FUSED_W2")]
+    return calls if causal else calls + [(1, 16, "BWD_SWEEP")]
+
+
+# Long sequences, (B, L, H, causal): the staged form at its largest L and above 1024 under the mask, then the edges of the resident forms
+# (forward <= 640, backward <= 608) that ATTN_CASES holds, here between guards
+ATTN_LONG_CASES = [(1, 4096, 1, False), (1, 1025, 2, True),
+                   (1, 225, 1, False), (2, 260, 2, True), (2, 513, 2, True), (1, 581, 3, False), (1, 608, 1, False), (1, 609, 1, True), (1, 640, 2, False),
+                   (1, 641, 1, False)]
+
+
+def attn_long_launches(L, causal):
+    """(bwd, flags, form) at L > 224: the default and the staged form by switch (bit 1), forward and backward."""
+    assert L > 224
+    c, Lp = int(causal), -(-L // 32) * 32
+    fwd, bwd = ("FWD_RESIDENT" if Lp * 256 <= 160 * 1024 else "FWD_STAGED"), ("BWD_RESIDENT" if Lp * 264 <= 160 * 1024 else "BWD_STAGED")
+    return [(0, c, fwd), (0, c | 2, "FWD_STAGED"), (1, c, bwd), (1, c | 2, "BWD_STAGED")]
+
+
+# The persistent kernels walk pairs = B * H (sequence, head) pairs with at most `cap` resident workgroups: mirrors of fwd_cfg / bwd_fused_cfg (attention.hip)
+def attn_fwd_cap(NC, ncu):
+    lds = 4 * NC * 32 * 128 + NC * 32 * 4
+    per_cu = max(163840 // lds, 1)
+    return ncu * (per_cu if per_cu * 2 * NC <= 32 else 32 // (2 * NC))
+
+
+def attn_fused_cap(NC, W2, ncu):
+    lds = 4 * NC * 32 * 128 + 3 * NC * 32 * 4
+    return ncu * min(max(min(163840 // lds, 32 // (NC * W2)), 1), 4)
+
+
+class AttnMultiPairCase(namedtuple("AttnMultiPairCase", "kernel NC L H causal")):
+    """More pairs than resident workgroups of one persistent kernel ("fwd": attn_fwd_kernel, "fused_w2" / "fused_w1": attn_bwd_fused_kernel)."""
+    __slots__ = ()
+
+    @property
+    def flags(self):  # of mudpt_attention_bwd; the forward takes the mask alone
+        return int(self.causal) | {"fwd": 0, "fused_w2": 8, "fused_w1": 4}[self.kernel]
+
+    @property
+    def form(self):
+        return {"fwd": "FWD_PERSISTENT", "fused_w2": "BWD_FUSED_W2", "fused_w1": "BWD_FUSED_W1"}[self.kernel]
+
+    def cap(self, ncu):
+        return attn_fwd_cap(self.NC, ncu) if self.kernel == "fwd" else attn_fused_cap(self.NC, 2 if self.kernel == "fused_w2" else 1, ncu)
+
+    def batch(self, ncu):
+        """Sequences on a device of ncu compute units: the fewest that give about 1.3 caps of pairs and a ragged last round."""
+        cap = self.cap(ncu)
+        B = -(-13 * cap // (10 * self.H))
+        while B * self.H % cap == 0:
+            B += 1
+        return B
+
+
+_MULTI_LH = {1: (17, 8), 2: (54, 12), 3: (77, 8), 4: (100, 3), 5: (150, 3), 6: (180, 3), 7: (201, 3)}  # NC -> (L, H); 54 x 12: ViT-B/32 with 4 prompt rows
+ATTN_MULTI_PAIR_CASES = ([AttnMultiPairCase("fwd", NC, *_MULTI_LH[NC], False) for NC in ATTN_NCS]
+                         + [AttnMultiPairCase(k, NC, *_MULTI_LH[NC], causal) for k in ("fused_w2", "fused_w1") for NC in ATTN_NCS for causal in (False, True)])
+
+# Single-query edges, (B, L, H, causal, positions | None): under the mask position 0 (one visible key) and L - 1 in every case, L = 1 under both masks
+ATTN_SINGLE_EDGE_CASES = [(4, 26, 8, True, (0, 25, 0, 13)), (3, 77, 2, True, (76, 0, 1)), (2, 1, 3, True, (0, 0)), (2, 1, 3, False, None), (3, 201, 2, False, None),
+                          (2, 581, 2, True, (0, 580))]
+
+
+def attention_form_launches():
+    """(bwd, L, flags, sel, form) of every launch of test_attention_forms_gpu.py whose form a table above names."""
+    calls = []
+    for _, L, _, causal in ATTN_INSTANCE_CASES + ATTN_PEAKED_CASES:
+        calls += [(bwd, L, flags, 0, form) for bwd, flags, form in attn_instance_launches(L, causal)]
+    for _, L, _, causal in ATTN_LONG_CASES:
+        calls += [(bwd, L, flags, 0, form) for bwd, flags, form in attn_long_launches(L, causal)]
+    for c in ATTN_MULTI_PAIR_CASES:
+        calls += [(0, c.L, int(c.causal), 0, "FWD_PAIR" if c.causal else "FWD_PERSISTENT")] + ([] if c.kernel == "fwd" else [(1, c.L, c.flags, 0, c.form)])
     return calls
 
 

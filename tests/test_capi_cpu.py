@@ -152,6 +152,55 @@ def test_attention_gpu_cases_reach_every_form(lib):
     assert reached == set(range(len(capi.ATTN_FORMS))), sorted(capi.ATTN_FORMS[i] for i in set(range(10)) - reached)
 
 
+def test_attention_gpu_cases_reach_every_instantiation(lib):
+    """A form is not a kernel: for L <= 224 every whole-pair form is instantiated per NC = padded length / 32 and per mask.  The cases of
+    test_attention_forms_gpu.py take the form their tables name, and the (form, NC, mask) they reach are all 9 x 7 = 63; the multi-pair cases
+    hold more pairs than their persistent kernel has resident workgroups at 256 units, with a ragged last round."""
+    from tests import helpers as h
+    reached = set()
+    for bwd, L, flags, sel, want in h.attention_form_launches():
+        got = lib.mudpt_attention_form(bwd, L, flags, sel)
+        assert got == capi.ATTN_FORMS.index(want), (bwd, L, flags, sel, want, capi.ATTN_FORMS[got] if got >= 0 else got)
+        if L <= 224:
+            reached.add((want, lib.mudpt_attention_padded_len(L) // 32, flags & 1))
+    whole_pair = [("FWD_PERSISTENT", 0), ("FWD_PAIR", 1), ("BWD_SWEEP", 0)] + [(f, m) for f in ("BWD_TWO", "BWD_FUSED_W2", "BWD_FUSED_W1") for m in (0, 1)]
+    want = {(f, NC, m) for f, m in whole_pair for NC in h.ATTN_NCS}
+    assert len(want) == 63 and reached == want, sorted(want - reached) + sorted(reached - want)
+    # every instance length is there, L = 1 and the lengths around an all-padding last tile among them
+    assert {L for _, L, _, _ in h.ATTN_INSTANCE_CASES} >= {1, 16, 17, 32, 33, 208, 209, 224}
+    assert [h.attn_fwd_cap(NC, 256) for NC in h.ATTN_NCS] == [2304, 1024, 768, 512, 256, 256, 256]
+    for W2 in (2, 1):
+        assert [h.attn_fused_cap(NC, W2, 256) for NC in h.ATTN_NCS] == [1024, 1024, 768, 512, 256, 256, 256]
+    kernels = set()
+    for c in h.ATTN_MULTI_PAIR_CASES:
+        assert lib.mudpt_attention_padded_len(c.L) // 32 == c.NC
+        for ncu in (256, 304, 64):
+            pairs, cap = c.batch(ncu) * c.H, c.cap(ncu)
+            assert cap < pairs <= 1.5 * cap and pairs % cap != 0, (c, ncu, pairs, cap)
+        kernels.add((c.kernel, c.NC))
+    assert kernels == {(k, NC) for k in ("fwd", "fused_w2", "fused_w1") for NC in h.ATTN_NCS}
+    assert {(L, causal) for _, L, _, causal in h.ATTN_LONG_CASES} >= {(4096, False), (1025, True)}
+
+
+def test_attention_float64_reference_is_the_gradient_of_attn64():
+    """helpers.attn64_fwd_bwd (explicit sums, so that 4096 rows need no autograd graph) against autograd through attn64; with round_to it moves
+    by roundings of T only."""
+    import torch
+    from tests.helpers import attn64, attn64_fwd_bwd
+    g = torch.Generator().manual_seed(5)
+    for L, H, causal in ((1, 2, True), (17, 2, False), (49, 3, True)):
+        qkv = torch.randn(2, L, 3 * H * 64, generator=g).double().requires_grad_(True)
+        dout = torch.randn(2, L, H * 64, generator=g).double()
+        ref = attn64(qkv, H, causal)
+        (dref,) = torch.autograd.grad(ref, qkv, dout)
+        out, lse, dqkv = attn64_fwd_bwd(qkv.detach(), dout, H, causal)
+        torch.testing.assert_close(out, ref.detach(), atol=1e-13, rtol=1e-12)
+        torch.testing.assert_close(dqkv, dref, atol=1e-12, rtol=1e-11)
+        assert lse.shape == (2, H, L)
+        _, _, emu = attn64_fwd_bwd(qkv.detach(), dout, H, causal, round_to=torch.float16)
+        assert 0 < (emu - dref).abs().max().item() <= 16 * 2.0 ** -11 * dref.abs().max().item()
+
+
 def test_patchify_cases_wrap_every_grid_stride_loop():
     """Arithmetic only, from the launchers' formulas: among the shapes test_movers_gpu.py runs, at least one per patchify kernel has more
     work than its capped grid holds in one pass (B = 64 vector form, B = 16 at p = 14, B = 128 split form at p = 16)."""

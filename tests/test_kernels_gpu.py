@@ -6,7 +6,7 @@ import torch
 
 from oracle import mudpt_oracle as O
 from tests.helpers import (ATTN_CASES, ATTN_LONG_FWD_CASES, ATTN_LONG_FWD_FLAGS, ATTN_SEL_CASES, ATTN_SEL_COMPARE, ATTN_WINDOW_CASES,
-                           ATTN_WINDOW_FULL_FLAG, SENT, P, attn_bwd_form_flags, attn_window_flags, e4m3_spacing, ok, refused)
+                           ATTN_WINDOW_FULL_FLAG, SENT, P, attn64, attn_bwd_form_flags, attn_window_flags, e4m3_spacing, ok, refused)
 
 pytestmark = pytest.mark.gpu
 
@@ -745,16 +745,6 @@ def test_layernorm_bwd_token_index_modes(lib, dtype, mode, total, R, d):
     rest = torch.ones(total, dtype=torch.bool)
     rest[idx] = False
     assert (got[rest] == SENT).all() and (got_lp[rest] == SENT).all()
-
-
-def attn64(qkv, H, causal):
-    """softmax(q k^T / 8 [+ causal mask]) v per head in float64; qkv [B, L, 3 H 64] packed q | k | v, heads contiguous in each third."""
-    B, L, _ = qkv.shape
-    q, k, v = (t.reshape(B, L, H, 64).transpose(1, 2).double() for t in qkv.split(H * 64, dim=-1))
-    s = q @ k.transpose(-1, -2) / 8.0
-    if causal:
-        s = s + torch.full((L, L), float("-inf"), dtype=torch.float64).triu_(1)
-    return (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(B, L, H * 64)
 
 
 def check_split_pair(dtype, hi, lo16, lo8, ref):
