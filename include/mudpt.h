@@ -46,6 +46,17 @@
  *                                        deep_prompts as they are.  MUDPT_FWD_REUSE_TEXT keeps G as well as the text features.
  *   mudpt_forward_backward               trainers/umudpt.py:292-294  forward, F.cross_entropy, backward w.r.t. all 20 tensors
  *   (mudpt_set_class_shard, mudpt_cp_* and mudpt_set_class_token_position refuse the variant.)
+ * With MUDPT_VARIANT_UUMUDPT they run the path with a generator in either direction (trainers/uumudpt.py; clip/model.py:600-664):
+ *   mudpt_create                         trainers/uumudpt.py:84-93  TRAINER.UUMUDPT.N_CTX (1..16) / DEEP_PROMPT_DEPTH (> 0); embed_dim must equal t_width (:224)
+ *   mudpt_param_*                        trainers/uumudpt.py:111-125,255-261, clip/model.py:606-628  40 tensors: UMuDPT's 20 as "uumudpt_prompt_learner.*",
+ *                                        then the vision tower's "image_encoder.visual_ctx" [n_ctx, d_v], "visual_ctx_deep_prompts" [depth - 1, n_ctx, d_v]
+ *                                        and its own generator "visual_ctx_{ln_intra_pre, self_attn.*, ln_intra_post, text_proj}" (width d_v, output e)
+ *   mudpt_forward / _ex                  trainers/uumudpt.py:162-180,219-233  G = Gen1(cat(ctx, deep_prompts)); vision input rows G[0] + visual_ctx, vision deep
+ *                                        prompts G[1:] + visual_ctx_deep_prompts; text deep prompts deep_prompts + Gen2(visual_ctx_deep_prompts); text
+ *                                        input rows ctx.  Gen2 runs on the text stream beside Gen1 and idles at depth 1.  MUDPT_FWD_REUSE_TEXT keeps
+ *                                        all of it: every one is a function of the parameters alone.
+ *   mudpt_forward_backward               trainers/uumudpt.py:295-297  forward, F.cross_entropy, backward w.r.t. all 40 tensors
+ *   (mudpt_set_class_shard, mudpt_cp_* and mudpt_set_class_token_position refuse the variant.)
  *
  * Conventions: every function returns 0 on success or a MUDPT_ERR_* code; mudpt_last_error() gives
  * the message of the calling thread's last failure.  No exceptions cross the ABI.  A model handle is
@@ -92,6 +103,7 @@ extern "C" {
 #define MUDPT_VARIANT_VPT 4      /* trainers/vpt.py: deep vision prompts only; mudpt_create_ex, n_ctx / depth are ignored */
 #define MUDPT_VARIANT_MPT 5      /* trainers/mpt.py: independent deep prompts in each tower; mudpt_create_ex, n_ctx / depth are ignored */
 #define MUDPT_VARIANT_UMUDPT 6   /* trainers/umudpt.py: MuDPT's towers, the vision prompts GENERATED from the text prompts by a trainable block; 20 trainables */
+#define MUDPT_VARIANT_UUMUDPT 7  /* trainers/uumudpt.py: UMuDPT plus a second generator, vision deep prompts -> an addend of the text deep prompts; 40 trainables */
 
 /* CoOp's TRAINER.COOP.CLASS_TOKEN_POSITION (trainers/coop.py:99-164): where the class-name tokens sit relative to the context rows */
 #define MUDPT_CLASS_TOKEN_END 0    /* [SOS, ctx, name, ".", EOT]                        (default) */
@@ -153,7 +165,7 @@ int mudpt_set_class_token_position(mudpt_model* m, int32_t position, const int32
 int mudpt_text_layout(const mudpt_model* m, int32_t* rows, int32_t* buckets, int32_t* max_len);
 
 /* The 10 trainable tensors live in ONE flat fp32 bucket (= the data-parallel all-reduce payload). */
-int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT), 5 (CoCoOp), 1 (CoOp), 1 + vision blocks (VPT) or that + 1 + text blocks (MPT), 20 (UMuDPT) */
+int mudpt_param_count(const mudpt_model* m);   /* 10 (MuDPT), 5 (CoCoOp), 1 (CoOp), 1 + vision blocks (VPT) or that + 1 + text blocks (MPT), 20 (UMuDPT), 40 (UUMuDPT) */
 size_t mudpt_param_numel(const mudpt_model* m); /* elements of the flat bucket */
 /* name = the reference's CustomCLIP state-dict key; shape has ndim entries (ndim <= 3). */
 int mudpt_param_info(const mudpt_model* m, int index, const char** name, size_t* offset, size_t* numel,
@@ -228,7 +240,9 @@ int mudpt_sgd_reset(mudpt_model* m);
  * (output of the last block on the ONE row per sequence the model uses -- CLS / EOT token -- [seq, d]: the tail of the last
  * block runs on those rows only), "image_features", "text_features", "text_launches" (1 value: text-tower passes plus text-side head
  * launches -- normalisation of the text features, their gradient -- since the handle was created); UMuDPT: "umudpt.G" (the generator's output)
- * and "umudpt.dG" (its gradient as the vision tower's backward left it), each [depth, n_ctx, v_width].  host_out may be NULL to query *numel. */
+ * and "umudpt.dG" (its gradient as the vision tower's backward left it), each [depth, n_ctx, v_width]; UUMuDPT: "uumudpt.G" / "uumudpt.dG"
+ * likewise and, at depth > 1, "uumudpt.T" (the second generator's output) / "uumudpt.dT" (its gradient as the text tower's backward left it),
+ * each [depth - 1, n_ctx, embed_dim].  host_out may be NULL to query *numel. */
 int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch, float* host_out, size_t capacity, size_t* numel);
 
 /* Debug knobs of ONE handle, for A/B measurements in one process and for tests (tools/gemm_bench.py, bench.py flags, tests/).  Nothing is
@@ -453,6 +467,10 @@ int mudpt_set_rows(float* x, int32_t B, int32_t L, int32_t d, int32_t row0, int3
 int mudpt_gather_rows(const void* src, size_t src_stride, const int32_t* rows, void* dst, size_t dst_stride, int32_t nrows, int32_t row_bytes, void* stream);
 int mudpt_scatter_rows(const void* src, size_t src_stride, const int32_t* rows, void* dst, size_t dst_stride, int32_t nrows, int32_t row_bytes, void* stream);
 int mudpt_add_rows(int32_t dtype, const void* src, const int32_t* rows, void* dst, int32_t nrows, int32_t d, void* stream);
+/* Backward of one trained Linear y = x W^T + b in ONE launch (x [R, in], W [out, in], dy [R, out], dense fp32): dW = dy^T x, db = column sums of
+ * dy, dx = dy W, all written; bit-identical to mudpt_sgemm(tA) + mudpt_colsum + mudpt_sgemm on the same operands.  Refused on the host: a null
+ * pointer, a size < 1, dW / db / dx overlapping an input or each other. */
+int mudpt_linear_bwd(int32_t R, int32_t out, int32_t in, const float* dy, const float* x, const float* W, float* dW, float* db, float* dx, void* stream);
 int mudpt_colsum(const float* A, int32_t M, int32_t N, int32_t lda, float* out, int32_t accumulate, void* stream);
 int mudpt_add(const float* a, const float* b, float* y, size_t n, void* stream);
 int mudpt_cast(int32_t dtype, const float* x, void* y, size_t n, void* stream);

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("MUDPT_LIB") or os.path.join(HERE, "lib", "libmudpt_hi
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "mudpt.h")
 
 BF16, F16, F32 = 0, 1, 2  # F32: the parity mode (include/mudpt.h MUDPT_F32)
-VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARIANT_MPT, VARIANT_UMUDPT = 0, 1, 2, 3, 4, 5, 6
+VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARIANT_MPT, VARIANT_UMUDPT, VARIANT_UUMUDPT = 0, 1, 2, 3, 4, 5, 6, 7
 CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = 0, 1, 2  # TRAINER.COOP.CLASS_TOKEN_POSITION "end" / "middle" / "front"
 ABI_VERSION = 7
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = range(6)
@@ -108,6 +108,7 @@ SIGNATURES = {
     "mudpt_gather_rows": (_i32, [_vp, _sz, _vp, _vp, _sz, _i32, _i32, _vp]),
     "mudpt_scatter_rows": (_i32, [_vp, _sz, _vp, _vp, _sz, _i32, _i32, _vp]),
     "mudpt_add_rows": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mudpt_linear_bwd": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mudpt_colsum": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp]),
     "mudpt_add": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "mudpt_cast": (_i32, [_i32, _vp, _vp, _sz, _vp]),

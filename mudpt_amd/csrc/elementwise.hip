@@ -249,13 +249,11 @@ int launch_reduce_rows(int dtype, float* src, void* src_lp, int B, int L, int d,
 // with all of its loads of up to 96 k in flight before the first MFMA, and the 8 partial tiles are summed through LDS in wave order
 // (fixed order: bitwise reproducible).  K = 768: one round trip of 24 loads per lane instead of 12 dependent chunk round trips.
 constexpr int SG_WAVES = 8, SG_STEPS = 6;  // waves per tile; 16-k steps whose loads travel together
-__global__ __launch_bounds__(SG_WAVES * 64) void sgemm_kernel(bool tA, bool tB, int M, int N, int K, float alpha, const float* __restrict__ A, int lda,
-                                                              const float* __restrict__ B, int ldb, float beta, float* __restrict__ C, int ldc,
-                                                              const float* __restrict__ bias) {
-    __shared__ float part[SG_WAVES][16][17];
+// The tile at (m0, n0), by the whole workgroup (every thread calls it: it holds a barrier): what sgemm_kernel and linear_bwd_kernel share
+__device__ __forceinline__ void sgemm_tile(float (*part)[16][17], int m0, int n0, bool tA, bool tB, int M, int N, int K, float alpha, const float* __restrict__ A,
+                                           int lda, const float* __restrict__ B, int ldb, float beta, float* __restrict__ C, int ldc, const float* __restrict__ bias) {
     const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
     const int per = ((K + SG_WAVES - 1) / SG_WAVES + 15) & ~15;  // k per wave, a multiple of the 16-k step
     const int kb = wave * per, ke = kb + per < K ? kb + per : K;
     const bool row_ok = m0 + r < M, col_ok = n0 + r < N;
@@ -293,6 +291,12 @@ __global__ __launch_bounds__(SG_WAVES * 64) void sgemm_kernel(bool tA, bool tB, 
         }
     }
 }
+__global__ __launch_bounds__(SG_WAVES * 64) void sgemm_kernel(bool tA, bool tB, int M, int N, int K, float alpha, const float* __restrict__ A, int lda,
+                                                              const float* __restrict__ B, int ldb, float beta, float* __restrict__ C, int ldc,
+                                                              const float* __restrict__ bias) {
+    __shared__ float part[SG_WAVES][16][17];
+    sgemm_tile(part, blockIdx.y * 16, blockIdx.x * 16, tA, tB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias);
+}
 
 int launch_sgemm(bool tA, bool tB, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb, float beta,
                  float* C, int ldc, const float* bias, hipStream_t s) {
@@ -316,6 +320,55 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ A
 int launch_colsum(const float* A, int M, int N, int lda, float* out, bool accumulate, hipStream_t s) {
     ARG_CHECK(A && out && M > 0 && N > 0 && lda >= N, "colsum: bad arguments M=%d N=%d lda=%d", M, N, lda);
     hipLaunchKernelGGL(colsum_kernel, dim3((N + 255) / 256), dim3(256), 0, s, A, M, N, lda, out, accumulate);
+    HIP_TRY(hipGetLastError());
+    return MUDPT_OK;
+}
+
+// ---- backward of one trained Linear y = x W^T + b (x [R, in], W [out, in], dy [R, out], all dense) in ONE launch -------------------------
+// dW = dy^T x, dx = dy W and db = the column sums of dy depend on nothing of each other; as three launches they are three links of a
+// launch-latency chain (the prompt generators' backward: 15 of its 21).  One grid, the role by block index as in ln_bwd_affine_kernel:
+//   blocks 0 .. w_tiles - 1              the 16 x 16 tiles of dW [out, in]  = sgemm(tA, out, in, K = R)   (sgemm_tile)
+//   the next x_tiles                     the 16 x 16 tiles of dx [R, in]    = sgemm(R, in, K = out)       (sgemm_tile)
+//   the rest, SG_WAVES * 64 columns each db[j] = sum_r dy[r][j] in row order                              (as colsum_kernel)
+// Every element is computed by the same instructions in the same order as by launch_sgemm / launch_colsum: bit-identical to the three
+// launches.  No atomics, no block reads what another writes.
+__global__ __launch_bounds__(SG_WAVES * 64) void linear_bwd_kernel(int R, int out, int in, const float* __restrict__ dy, const float* __restrict__ x,
+                                                                   const float* __restrict__ W, float* __restrict__ dW, float* __restrict__ db,
+                                                                   float* __restrict__ dx, int w_tiles, int x_tiles) {
+    __shared__ float part[SG_WAVES][16][17];
+    const int tn = (in + 15) / 16;  // tiles per row of dW and of dx
+    int b = blockIdx.x;
+    if (b < w_tiles) {
+        sgemm_tile(part, b / tn * 16, b % tn * 16, true, false, out, in, R, 1.f, dy, out, x, in, 0.f, dW, in, nullptr);
+        return;
+    }
+    b -= w_tiles;
+    if (b < x_tiles) {
+        sgemm_tile(part, b / tn * 16, b % tn * 16, false, false, R, in, out, 1.f, dy, out, W, in, 0.f, dx, in, nullptr);
+        return;
+    }
+    const int j = (b - x_tiles) * (SG_WAVES * 64) + threadIdx.x;
+    if (j >= out) return;
+    float acc = 0.f;
+    for (int r = 0; r < R; ++r) acc += dy[(size_t)r * out + j];
+    db[j] = acc;
+}
+
+int launch_linear_bwd(int R, int out, int in, const float* dy, const float* x, const float* W, float* dW, float* db, float* dx, hipStream_t s) {
+    ARG_CHECK(dy && x && W && dW && db && dx, "linear_bwd: null operand");
+    ARG_CHECK(R > 0 && out > 0 && in > 0, "linear_bwd: bad arguments R=%d out=%d in=%d", R, out, in);
+    const long long w_tiles = (long long)((out + 15) / 16) * ((in + 15) / 16), x_tiles = (long long)((R + 15) / 16) * ((in + 15) / 16);
+    const long long blocks = w_tiles + x_tiles + (out + SG_WAVES * 64 - 1) / (SG_WAVES * 64);
+    ARG_CHECK(blocks <= 0x7fffffffLL, "linear_bwd: R=%d out=%d in=%d needs %lld workgroups", R, out, in, blocks);
+    // the kernel's blocks run in any order: an output that overlaps an input (or another output) would be read after it was written
+    const size_t n_dy = (size_t)R * out, n_x = (size_t)R * in, n_W = (size_t)out * in;
+    auto overlap = [](const float* a, size_t na, const float* b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + 4 * nb && (uintptr_t)b < (uintptr_t)a + 4 * na; };
+    const struct { const float* p; size_t n; const char* name; } ins[3] = {{dy, n_dy, "dy"}, {x, n_x, "x"}, {W, n_W, "W"}}, outs[3] = {{dW, n_W, "dW"}, {db, (size_t)out, "db"}, {dx, n_x, "dx"}};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 3; ++i) ARG_CHECK(!overlap(outs[o].p, outs[o].n, ins[i].p, ins[i].n), "linear_bwd: %s aliases the input %s", outs[o].name, ins[i].name);
+        for (int i = o + 1; i < 3; ++i) ARG_CHECK(!overlap(outs[o].p, outs[o].n, outs[i].p, outs[i].n), "linear_bwd: %s aliases %s", outs[o].name, outs[i].name);
+    }
+    hipLaunchKernelGGL(linear_bwd_kernel, dim3((unsigned)blocks), dim3(SG_WAVES * 64), 0, s, R, out, in, dy, x, W, dW, db, dx, (int)w_tiles, (int)x_tiles);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }

@@ -199,6 +199,9 @@ int launch_sgemm(bool transA, bool transB, int M, int N, int K, float alpha, con
                  const float* B, int ldb, float beta, float* C, int ldc, const float* bias, hipStream_t s);
 // out[n] (+)= sum_m A[m, n]
 int launch_colsum(const float* A, int M, int N, int lda, float* out, bool accumulate, hipStream_t s);
+// Backward of one trained Linear y = x W^T + b in one launch: dW [out, in] = dy^T x, db [out] = column sums of dy, dx [R, in] = dy W, all dense
+// fp32 and WRITTEN; bit-identical to launch_sgemm(tA) + launch_colsum + launch_sgemm on the same operands.  No output may overlap anything.
+int launch_linear_bwd(int R, int out, int in, const float* dy, const float* x, const float* W, float* dW, float* db, float* dx, hipStream_t s);
 // y = a + b (elementwise fp32)
 int launch_add(const float* a, const float* b, float* y, size_t n, hipStream_t s);
 // cast fp32 -> T

@@ -235,6 +235,13 @@ struct mudpt_model {
     bool umudpt = false;
     float *pg_G = nullptr, *pg_dG = nullptr, *pg_dX = nullptr, *pg_ws = nullptr;
     PgWork pg_w;
+    // UUMuDPT variant (trainers/uumudpt.py): UMuDPT (umudpt is set too: Gen1 and everything above serve both) plus the other direction.  The
+    // vision tower owns visual_ctx, visual_ctx_deep_prompts and a SECOND generator of width dv (clip/model.py:600-664) behind Gen1's tensors in
+    // the bucket: vision input rows G[0] + visual_ctx, vision deep prompts vis_deep = G[1:] + visual_ctx_deep_prompts, text deep prompts
+    // txt_deep = deep_prompts + T with T = Gen2(visual_ctx_deep_prompts) [depth - 1, n, e]; d_txt_deep is dT.  Gen2 idles at depth 1
+    bool uumudpt = false;
+    float *pg2_T = nullptr, *pg2_ws = nullptr;
+    PgWork pg2_w;
     long text_launches = 0;  // text-tower passes + text-side head launches (mudpt_debug_read "text_launches")
     float *mn_hid = nullptr, *mn_bias = nullptr, *mn_dbias = nullptr, *mn_dhid = nullptr;  // [B, hid], [B, dt], [B, dt], [B, hid]
     float loss_scale = 128.f;  // static, power of two; see mudpt_forward_backward
@@ -371,10 +378,11 @@ static int attn_call(mudpt_model* m, const Tower& t, const AttnArgs& a, bool bwd
 }
 
 // Indices into mudpt_model::tr, the table of the variant they belong to (build_trainables): P_* MuDPT (UMuDPT shares P_CTX, P_DEEP),
-// Q_* CoCoOp, U_GEN the first of the UMuDPT generator's 18 tensors (kernels.h PgTensor)
+// Q_* CoCoOp, U_GEN the first of the UMuDPT generator's 18 tensors (kernels.h PgTensor), UU_* what UUMuDPT adds behind those
 enum { P_CTX = 0, P_DEEP, P_EW, P_EB, P_DW, P_DB, P_VCTX, P_VDEEP, P_VW, P_VB };
 enum { Q_CTX = 0, Q_W1, Q_B1, Q_W2, Q_B2 };
 enum { U_GEN = 2 };
+enum { UU_VCTX = 20, UU_VDEEP, UU_GEN2 };  // UUMuDPT behind UMuDPT's 20: visual_ctx, visual_ctx_deep_prompts, the first of Gen2's 18 tensors
 
 // The variant's trainables: the reference's key and shape of every tensor, in its named_parameters() order -- the flat bucket's layout
 static void build_trainables(mudpt_model* m) {
@@ -411,28 +419,40 @@ static void build_trainables(mudpt_model* m) {
             add("image_encoder.visual_ctx", {m->vis.n, dv});  // clip/model.py:459-465
             for (int i = 1; i <= m->vis.D1; ++i) add("image_encoder.transformer.resblocks." + std::to_string(i) + ".visual_ctx", {m->vis.n, dv});
         }
-    } else if (m->umudpt) {  // trainers/umudpt.py:110-124: ctx, deep_prompts ([0, n, dt] at depth 1: no elements, still listed), then the generator
-        const std::string p = "umudpt_prompt_learner.", a = p + "self_attn.";
+    } else if (m->umudpt) {
+        // trainers/umudpt.py:110-124: ctx, deep_prompts ([0, n, dt] at depth 1: no elements, still listed), then the generator.  UUMuDPT
+        // (trainers/uumudpt.py:111-125, clip/model.py:606-628): the same 20 under its own prefix, then the vision tower's 20.
+        // generator: the 18 tensors of one generator of width d (kernels.h PgTensor) -- ln_pre, the block, ln_post, the output Linear
+        auto generator = [&](const std::string& p, const std::string& a, const std::string& post, const std::string& proj, int64_t d, int64_t d_out) {
+            add(p + ".weight", {d});
+            add(p + ".bias", {d});
+            add(a + "attn.in_proj_weight", {3 * d, d});
+            add(a + "attn.in_proj_bias", {3 * d});
+            add(a + "attn.out_proj.weight", {d, d});
+            add(a + "attn.out_proj.bias", {d});
+            add(a + "ln_1.weight", {d});
+            add(a + "ln_1.bias", {d});
+            add(a + "mlp.c_fc.weight", {4 * d, d});
+            add(a + "mlp.c_fc.bias", {4 * d});
+            add(a + "mlp.c_proj.weight", {d, 4 * d});
+            add(a + "mlp.c_proj.bias", {d});
+            add(a + "ln_2.weight", {d});
+            add(a + "ln_2.bias", {d});
+            add(post + ".weight", {d});
+            add(post + ".bias", {d});
+            add(proj + ".weight", {d_out, d});
+            add(proj + ".bias", {d_out});
+        };
+        const std::string p = m->uumudpt ? "uumudpt_prompt_learner." : "umudpt_prompt_learner.";
         add(p + "ctx", {n, dt});
         add(p + "deep_prompts", {D1, n, dt});
-        add(p + "ln_pre.weight", {dt});
-        add(p + "ln_pre.bias", {dt});
-        add(a + "attn.in_proj_weight", {3 * dt, dt});
-        add(a + "attn.in_proj_bias", {3 * dt});
-        add(a + "attn.out_proj.weight", {dt, dt});
-        add(a + "attn.out_proj.bias", {dt});
-        add(a + "ln_1.weight", {dt});
-        add(a + "ln_1.bias", {dt});
-        add(a + "mlp.c_fc.weight", {4 * dt, dt});
-        add(a + "mlp.c_fc.bias", {4 * dt});
-        add(a + "mlp.c_proj.weight", {dt, 4 * dt});
-        add(a + "mlp.c_proj.bias", {dt});
-        add(a + "ln_2.weight", {dt});
-        add(a + "ln_2.bias", {dt});
-        add(p + "ln_post.weight", {dt});
-        add(p + "ln_post.bias", {dt});
-        add(p + "visual_proj.weight", {dv, dt});
-        add(p + "visual_proj.bias", {dv});
+        generator(p + "ln_pre", p + "self_attn.", p + "ln_post", p + "visual_proj", dt, dv);
+        if (m->uumudpt) {
+            const std::string v = "image_encoder.visual_ctx";
+            add(v, {n, dv});
+            add(v + "_deep_prompts", {D1, n, dv});
+            generator(v + "_ln_intra_pre", v + "_self_attn.", v + "_ln_intra_post", v + "_text_proj", dv, e);
+        }
     } else {  // MuDPT: trainers/mudpt.py:71-81, clip/model.py:512-519
         add("mudpt_prompt_learner.ctx", {n, dt});
         add("mudpt_prompt_learner.deep_prompts", {D1, n, dt});
@@ -547,21 +567,25 @@ extern "C" const char* mudpt_last_error(void) { return get_error(); }
 // Fills a fresh model; on an error the caller (create_model) destroys it
 static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model* m) {
     ARG_CHECK(c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F16 || c->dtype == MUDPT_F32, "create: dtype must be MUDPT_BF16, MUDPT_F16 or MUDPT_F32");
-    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_UMUDPT, "create: unknown variant %d", c->variant);
+    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_UUMUDPT, "create: unknown variant %d", c->variant);
     m->cocoop = c->variant == MUDPT_VARIANT_COCOOP;
     m->csc = c->variant == MUDPT_VARIANT_COOP_CSC;
     m->coop = c->variant == MUDPT_VARIANT_COOP || m->csc;
     m->vpt = c->variant == MUDPT_VARIANT_VPT; m->mpt = c->variant == MUDPT_VARIANT_MPT; m->indep = m->vpt || m->mpt;
-    m->umudpt = c->variant == MUDPT_VARIANT_UMUDPT;
+    m->uumudpt = c->variant == MUDPT_VARIANT_UUMUDPT;
+    m->umudpt = c->variant == MUDPT_VARIANT_UMUDPT || m->uumudpt;
     const bool vanilla = m->cocoop || m->coop;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
     ARG_CHECK(vanilla || m->indep || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
     ARG_CHECK((m->indep || c->n_ctx > 0) && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
     ARG_CHECK(c->patch > 0 && c->image_size % c->patch == 0, "create: image_size %d / patch %d unsupported", c->image_size, c->patch);
     ARG_CHECK(c->v_width == c->v_heads * 64 && c->t_width == c->t_heads * 64, "create: head dim must be 64");
     ARG_CHECK(c->v_width % 64 == 0 && c->t_width % 64 == 0 && c->v_width <= 1024 && c->t_width <= 1024, "create: widths must be multiples of 64, <= 1024");
+    ARG_CHECK(!m->uumudpt || c->embed_dim == c->t_width, "create (UUMuDPT): embed_dim %d must equal t_width %d (visual_ctx_text_proj's output is added to "
+              "deep_prompts, trainers/uumudpt.py:224)", c->embed_dim, c->t_width);
     ARG_CHECK(c->embed_dim == c->t_width, "create: embed_dim must equal t_width (visual_ctx_deep_projections output is added to text prompts)");
     ARG_CHECK(m->indep || 1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
-    if (m->umudpt) { if (int r = pg_check_shape("create (UMuDPT)", c->depth, c->n_ctx, c->t_width, c->v_width)) return r; }
+    if (m->umudpt) { if (int r = pg_check_shape(m->uumudpt ? "create (UUMuDPT)" : "create (UMuDPT)", c->depth, c->n_ctx, c->t_width, c->v_width)) return r; }
+    if (m->uumudpt && c->depth > 1) { if (int r = pg_check_shape("create (UUMuDPT, the vision tower's generator)", c->depth - 1, c->n_ctx, c->v_width, c->embed_dim)) return r; }
     // prompt rows and deep-prompt layers per tower (Tower::n, Tower::D1)
     int nv = vanilla ? 0 : c->n_ctx, D1v = vanilla ? 0 : c->depth - 1, nt = c->n_ctx, D1t = vanilla ? 0 : c->depth - 1;
     if (m->indep) {
@@ -653,6 +677,12 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
         (void)pg_carve(nullptr, c->depth, n, dt, &ws);
         ALLOC(m->pg_G, R * dv * 4); ALLOC(m->pg_dG, R * dv * 4); ALLOC(m->pg_dX, R * dt * 4); ALLOC(m->pg_ws, ws * 4);
         m->pg_w = pg_carve(m->pg_ws, c->depth, n, dt, nullptr);
+    }
+    if (m->uumudpt && D1 > 0) {
+        size_t ws = 0;
+        (void)pg_carve(nullptr, D1, n, dv, &ws);
+        ALLOC(m->pg2_T, (size_t)D1 * n * e * 4); ALLOC(m->pg2_ws, ws * 4);
+        m->pg2_w = pg_carve(m->pg2_ws, D1, n, dv, nullptr);
     }
     ALLOC(m->gemm_scratch, mudpt_model::kScratchElems * 4); ALLOC(m->gemm_scratch2, mudpt_model::kScratchElems * 4);
     HIP_TRY(hipStreamCreateWithFlags(&m->s2, hipStreamNonBlocking));
@@ -1349,13 +1379,18 @@ static PromptRoute prompt_route(const mudpt_model* m, const Tower& t) {
         // the generator's output G [depth][n][dv]: row group 0 the input rows (alone: the tower has no visual_ctx of its own, clip/model.py:573-576),
         // 1 .. the deep prompts (:556-597); pg_dG collects the gradients likewise and the generator's backward reads it
         r.in0 = m->pg_G; r.deep = m->pg_G + group; r.d_in0 = m->pg_dG; r.d_deep = m->pg_dG + group;
+        // UUMuDPT: G[0] + visual_ctx and G[1:] + visual_ctx_deep_prompts (clip/model.py:637-640; the sum uumudpt_forward_vision left in vis_deep).
+        // Both are plain sums, so pg_dG is also the tower's term of grad(visual_ctx | visual_ctx_deep_prompts) (uumudpt_backward)
+        if (m->uumudpt) { r.in0_add = P + m->off(UU_VCTX); r.deep = m->vis_deep; }
     } else if (vision) {  // MuDPT: visual_ctx + shared (clip/model.py:534) and the prompt learner's projections; gradients into its backward
         r.in0 = P + m->off(P_VCTX); r.in0_add = m->shared; r.deep = m->vis_deep; r.d_in0 = m->d_vprompt0; r.d_deep = m->d_vis_deep;
     } else {  // MuDPT / UMuDPT: ctx, its gradient summed over the class prompts straight into the bucket
         r.in0 = P + m->off(P_CTX); r.d_in0 = G(m->off(P_CTX));
-        // UMuDPT: deep_prompts as they are in the bucket (trainers/umudpt.py:178,222); MuDPT: the prompt learner's sums
-        r.deep = m->umudpt ? P + m->off(P_DEEP) : m->txt_deep;
-        r.d_deep = m->umudpt ? G(m->off(P_DEEP)) : m->d_txt_deep;
+        // UMuDPT: deep_prompts as they are in the bucket (trainers/umudpt.py:178,222); MuDPT: the prompt learner's sums; UUMuDPT: deep_prompts +
+        // Gen2's output (uumudpt_forward_text), d_txt_deep then is dT as well as the text tower's term of grad(deep_prompts)
+        const bool bucket = m->umudpt && !m->uumudpt;
+        r.deep = bucket ? P + m->off(P_DEEP) : m->txt_deep;
+        r.d_deep = bucket ? G(m->off(P_DEEP)) : m->d_txt_deep;
     }
     return r;
 }
@@ -1502,11 +1537,41 @@ static int prompt_learner_forward(mudpt_model* m, hipStream_t s) {
     return MUDPT_OK;
 }
 
+struct Gen2 {  // UUMuDPT's second generator: depth - 1 layers of n rows, width d = v_width, output width e = embed_dim (= t_width)
+    int D1 = 0, n = 0, d = 0, e = 0;
+    PgParams P;
+    const float* X = nullptr;  // visual_ctx_deep_prompts in the bound parameter bucket
+};
+
 // UMuDPT, trainers/umudpt.py:170-176: the vision prompts of every layer from the text prompts of every layer
 static int umudpt_forward(mudpt_model* m, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     float* Pm = m->params;
     return pg_forward(c.depth, c.n_ctx, c.t_width, c.v_width, pg_params(Pm + m->off(U_GEN), c.t_width, c.v_width), Pm + m->off(P_CTX), m->pg_G, m->pg_w, s);
+}
+
+// UUMuDPT's two directions.  Vision stream: Gen1 as UMuDPT, then the vision deep prompts G[1:] + visual_ctx_deep_prompts (clip/model.py:640).
+// Text stream, ahead of the text tower: T = Gen2(visual_ctx_deep_prompts) and the text deep prompts deep_prompts + T (clip/model.py:630-636,
+// trainers/uumudpt.py:224).  The two generators share no buffer, so their launch chains run beside each other
+static Gen2 uumudpt_gen2(const mudpt_model* m) {
+    const mudpt_config& c = m->cfg;
+    Gen2 g;
+    g.D1 = c.depth - 1; g.n = c.n_ctx; g.d = c.v_width; g.e = c.embed_dim;
+    g.P = pg_params(m->params + m->off(UU_GEN2), g.d, g.e);
+    g.X = m->params + m->off(UU_VDEEP);
+    return g;
+}
+static int uumudpt_forward_vision(mudpt_model* m, hipStream_t s) {
+    const mudpt_config& c = m->cfg;
+    TRY(umudpt_forward(m, s));
+    const size_t group = (size_t)c.n_ctx * c.v_width, D1 = (size_t)c.depth - 1;
+    return D1 > 0 ? launch_add(m->pg_G + group, m->params + m->off(UU_VDEEP), m->vis_deep, D1 * group, s) : MUDPT_OK;
+}
+static int uumudpt_forward_text(mudpt_model* m, hipStream_t s2) {
+    const Gen2 g = uumudpt_gen2(m);
+    if (g.D1 <= 0) return MUDPT_OK;
+    TRY(pg_forward(g.D1, g.n, g.d, g.e, g.P, g.X, m->pg2_T, m->pg2_w, s2));
+    return launch_add(m->params + m->off(P_DEEP), m->pg2_T, m->txt_deep, (size_t)g.D1 * g.n * g.e, s2);
 }
 
 // text tower, trainers/mudpt.py:142-156, over this handle's classes [c0, c0 + ct): rows c0.. of the [n_cls, e] feature table
@@ -1540,13 +1605,14 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
 
 // The variant's trainable front end around the towers, each hook null where the variant has none (learner(), below its last hook):
 //   fwd         before the fork: both towers read its output
+//   fwd_text    after the fork, on the text stream ahead of the text tower: the vision tower reads none of its output; kept with reuse_text
 //   fwd_vision  after the fork, on the vision stream: the text tower reads none of its output, so only the vision tower's prompt splice waits
 //               for it; with reuse_text its output is kept like the text features (same parameters, same output)
 //   bwd_text    on the text stream behind that tower's backward, before the join: needs the text tower's prompt gradients only
 //   bwd         after the join
 struct Learner {
     typedef int (*Hook)(mudpt_model*, hipStream_t);
-    Hook fwd = nullptr, fwd_vision = nullptr, bwd_text = nullptr, bwd = nullptr;
+    Hook fwd = nullptr, fwd_text = nullptr, fwd_vision = nullptr, bwd_text = nullptr, bwd = nullptr;
 };
 static Learner learner(const mudpt_model* m);
 
@@ -1561,6 +1627,7 @@ static int towers_forward(mudpt_model* m, const float* images, int B, hipStream_
     if (!reuse_text) {
         HIP_TRY(hipEventRecord(m->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork, 0));
+        if (L.fwd_text) TRY(L.fwd_text(m, m->s2));
         TRY(text_forward(m, m->s2));
         HIP_TRY(hipEventRecord(m->ev_join, m->s2));
         if (L.fwd_vision) TRY(L.fwd_vision(m, s));
@@ -1778,11 +1845,35 @@ static int umudpt_backward(mudpt_model* m, hipStream_t s) {
     return launch_add(G + m->off(P_CTX), m->pg_dX, G + m->off(P_CTX), (size_t)R * dt, s);  // ctx and deep_prompts lie one behind the other
 }
 
+// UUMuDPT.  Text stream, behind the text tower's backward (which reduced dT = d_txt_deep and, into the zeroed bucket, grad(ctx)): grad(deep_prompts)
+// takes dT as its first term, Gen2's backward WRITES its 18 gradients and, as dX, the first term of grad(visual_ctx_deep_prompts).  After the
+// join: Gen1's backward as UMuDPT (the second term of grad(ctx | deep_prompts)), then dG, the vision tower's term, onto
+// grad(visual_ctx | visual_ctx_deep_prompts), which lie one behind the other.  Every shared tensor gets exactly two fp32 terms, one per stream
+// and the second after the join: bit-identical to any order of the two.  Depth 1: Gen2's gradients stay the zeroed bucket's zeros.
+static int uumudpt_backward_text(mudpt_model* m, hipStream_t s2) {
+    const Gen2 g = uumudpt_gen2(m);
+    if (g.D1 <= 0) return MUDPT_OK;
+    float* G = m->grads;
+    const int R = g.D1 * g.n;
+    // layers >= depth never consume a prompt: rows of dT beyond the tower depth get no gradient
+    const int used_t = (m->txt.layers - 1 < g.D1 ? m->txt.layers - 1 : g.D1) * g.n;
+    if (used_t < R) HIP_TRY(hipMemsetAsync(m->d_txt_deep + (size_t)used_t * g.e, 0, (size_t)(R - used_t) * g.e * 4, s2));
+    TRY(launch_add(G + m->off(P_DEEP), m->d_txt_deep, G + m->off(P_DEEP), (size_t)R * g.e, s2));
+    return pg_backward(g.D1, g.n, g.d, g.e, g.P, g.X, m->d_txt_deep, G + m->off(UU_VDEEP), G + m->off(UU_GEN2), m->pg2_w, s2);
+}
+static int uumudpt_backward(mudpt_model* m, hipStream_t s) {
+    const mudpt_config& c = m->cfg;
+    float* G = m->grads;
+    TRY(umudpt_backward(m, s));
+    return launch_add(G + m->off(UU_VCTX), m->pg_dG, G + m->off(UU_VCTX), (size_t)c.depth * c.n_ctx * c.v_width, s);
+}
+
 // The one place a variant names its learner: CoOp / VPT / MPT have none, their trainables go into the towers as they are
 // (trainers/coop.py:166-175); CoCoOp's meta_net is part of its own step
 static Learner learner(const mudpt_model* m) {
     Learner L;
-    if (m->umudpt) { L.fwd_vision = umudpt_forward; L.bwd = umudpt_backward; }
+    if (m->uumudpt) { L.fwd_text = uumudpt_forward_text; L.fwd_vision = uumudpt_forward_vision; L.bwd_text = uumudpt_backward_text; L.bwd = uumudpt_backward; }
+    else if (m->umudpt) { L.fwd_vision = umudpt_forward; L.bwd = umudpt_backward; }
     else if (!m->cocoop && !m->coop && !m->indep) { L.fwd = prompt_learner_forward; L.bwd_text = prompt_learner_backward_text; L.bwd = prompt_learner_backward_vision; }
     return L;
 }
@@ -2051,7 +2142,9 @@ extern "C" int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch,
     else if (k.rfind("txt.", 0) == 0) tower(m->txt, k.substr(4), m->ct);  // this handle's classes
     else if (k == "image_features") { src = m->img_f; n = (size_t)batch * c.embed_dim; }
     else if (k == "text_features") { src = m->txt_f; n = (size_t)c.n_cls * c.embed_dim; }
-    else if (m->umudpt && (k == "umudpt.G" || k == "umudpt.dG")) { src = k == "umudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
+    else if (m->umudpt && !m->uumudpt && (k == "umudpt.G" || k == "umudpt.dG")) { src = k == "umudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
+    else if (m->uumudpt && (k == "uumudpt.G" || k == "uumudpt.dG")) { src = k == "uumudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
+    else if (m->uumudpt && c.depth > 1 && (k == "uumudpt.T" || k == "uumudpt.dT")) { src = k == "uumudpt.T" ? m->pg2_T : m->d_txt_deep; n = (size_t)(c.depth - 1) * c.n_ctx * c.embed_dim; }
     else if (k == "text_launches") {  // a host counter, not a device tensor
         *numel = 1;
         if (host_out) { ARG_CHECK(capacity >= 1, "debug_read: capacity 0"); host_out[0] = (float)m->text_launches; }
@@ -2319,6 +2412,9 @@ extern "C" int mudpt_scatter_rows(const void* src, size_t src_stride, const int3
 }
 extern "C" int mudpt_add_rows(int32_t dtype, const void* src, const int32_t* rows, void* dst, int32_t nrows, int32_t d, void* stream) {
     return launch_add_rows(dtype, src, rows, dst, nrows, d, (hipStream_t)stream);
+}
+extern "C" int mudpt_linear_bwd(int32_t R, int32_t out, int32_t in, const float* dy, const float* x, const float* W, float* dW, float* db, float* dx, void* stream) {
+    return launch_linear_bwd(R, out, in, dy, x, W, dW, db, dx, (hipStream_t)stream);
 }
 extern "C" int mudpt_colsum(const float* A, int32_t M, int32_t N, int32_t lda, float* out, int32_t accumulate, void* stream) {
     return launch_colsum(A, M, N, lda, out, accumulate != 0, (hipStream_t)stream);

@@ -1,7 +1,7 @@
 // UMuDPT's prompt generator (trainers/umudpt.py:56-76,161-178): ln_pre -> one pre-LN transformer block -> ln_post -> visual_proj over the
 // R = depth * n_ctx prompt rows, forward and backward, in fp32 end to end.  Unlike everything else in the library the generator's weights
 // TRAIN: its backward produces weight, bias, gamma and beta gradients.  R is 16 at the defaults and a few hundred at most, so every kernel
-// here is a latency problem, not a throughput one: the GEMMs are launch_sgemm, the bias gradients launch_colsum, and the three kernels of
+// here is a latency problem, not a throughput one: the forward's GEMMs are launch_sgemm, a Linear's three gradients one launch_linear_bwd, and the three kernels of
 // this file -- LayerNorm backward with dgamma / dbeta, attention over the n_ctx <= 16 rows of one layer, QuickGELU -- keep every sum in a
 // fixed order (no atomics), so two runs agree bit for bit.
 #include "kernels.h"
@@ -288,12 +288,6 @@ int pg_forward(int depth, int n_ctx, int d, int dv, const PgParams& P, const flo
     return MUDPT_OK;
 }
 
-// One trained Linear y = x W^T + b with W [out, in]: dW = dy^T x, db = column sums of dy, dx = dy W  (the calls of the MuDPT prompt learner's backward)
-static int pg_linear_bwd(int R, int out, int in, const float* dy, const float* x, const float* W, float* dW, float* db, float* dx, hipStream_t s) {
-    PG_TRY(launch_sgemm(true, false, out, in, R, 1.f, dy, out, x, in, 0.f, dW, in, nullptr, s));
-    PG_TRY(launch_colsum(dy, R, out, out, db, false, s));
-    return launch_sgemm(false, false, R, in, out, 1.f, dy, out, W, in, 0.f, dx, in, nullptr, s);
-}
 static int pg_ln_bwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* dy, const float* dres, float* dx, float* dgamma,
                      float* dbeta, int R, int d, hipStream_t s) {
     LnBwdAffineArgs a; a.x = x; a.ldx = d; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.dy = dy; a.lddy = d; a.dres = dres; a.lddres = d; a.dx = dx; a.lddx = d;
@@ -307,15 +301,16 @@ int pg_backward(int depth, int n_ctx, int d, int dv, const PgParams& P, const fl
     ARG_CHECK(P.base && X && dG && dX && grads && w.h0, "promptgen_backward: null argument");
     const int R = depth * n_ctx, H = d / 64;
     auto g = [&](int i) { return grads + P.off[i]; };
-    PG_TRY(pg_linear_bwd(R, dv, d, dG, w.a3, P.at(PG_W_VIS), g(PG_W_VIS), g(PG_B_VIS), w.da3, s));
+    // a trained Linear y = x W^T + b, W [out, in]: dW = dy^T x, db = column sums of dy, dx = dy W in ONE launch_linear_bwd (elementwise.hip)
+    PG_TRY(launch_linear_bwd(R, dv, d, dG, w.a3, P.at(PG_W_VIS), g(PG_W_VIS), g(PG_B_VIS), w.da3, s));
     PG_TRY(pg_ln_bwd(w.z, w.mean[3], w.rstd[3], P.at(PG_LN_POST_G), w.da3, nullptr, w.dz, g(PG_LN_POST_G), g(PG_LN_POST_B), R, d, s));
-    PG_TRY(pg_linear_bwd(R, d, 4 * d, w.dz, w.g, P.at(PG_W_PROJ), g(PG_W_PROJ), g(PG_B_PROJ), w.dg, s));
+    PG_TRY(launch_linear_bwd(R, d, 4 * d, w.dz, w.g, P.at(PG_W_PROJ), g(PG_W_PROJ), g(PG_B_PROJ), w.dg, s));
     PG_TRY(launch_quickgelu_bwd(w.dg, w.u, w.dg, (size_t)R * 4 * d, s));
-    PG_TRY(pg_linear_bwd(R, 4 * d, d, w.dg, w.a2, P.at(PG_W_FC), g(PG_W_FC), g(PG_B_FC), w.da2, s));
+    PG_TRY(launch_linear_bwd(R, 4 * d, d, w.dg, w.a2, P.at(PG_W_FC), g(PG_W_FC), g(PG_B_FC), w.da2, s));
     PG_TRY(pg_ln_bwd(w.y, w.mean[2], w.rstd[2], P.at(PG_LN2_G), w.da2, w.dz, w.dy, g(PG_LN2_G), g(PG_LN2_B), R, d, s));  // + the residual branch
-    PG_TRY(pg_linear_bwd(R, d, d, w.dy, w.attn, P.at(PG_W_OUT), g(PG_W_OUT), g(PG_B_OUT), w.dattn, s));
+    PG_TRY(launch_linear_bwd(R, d, d, w.dy, w.attn, P.at(PG_W_OUT), g(PG_W_OUT), g(PG_B_OUT), w.dattn, s));
     PG_TRY(launch_pg_attn_bwd(w.qkv, w.probs, w.dattn, w.dqkv, depth, n_ctx, H, d, s));
-    PG_TRY(pg_linear_bwd(R, 3 * d, d, w.dqkv, w.a1, P.at(PG_W_IN), g(PG_W_IN), g(PG_B_IN), w.da1, s));
+    PG_TRY(launch_linear_bwd(R, 3 * d, d, w.dqkv, w.a1, P.at(PG_W_IN), g(PG_W_IN), g(PG_B_IN), w.da1, s));
     PG_TRY(pg_ln_bwd(w.h0, w.mean[1], w.rstd[1], P.at(PG_LN1_G), w.da1, w.dy, w.dh0, g(PG_LN1_G), g(PG_LN1_B), R, d, s));
     return pg_ln_bwd(X, w.mean[0], w.rstd[0], P.at(PG_LN_PRE_G), w.dh0, nullptr, dX, g(PG_LN_PRE_G), g(PG_LN_PRE_B), R, d, s);
 }

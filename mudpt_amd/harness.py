@@ -3,7 +3,7 @@
     python -m mudpt_amd.harness --epochs 2 --batch 4 --n-ctx 4 --depth 12 [--prec fp16|amp] [--eval-only --model-dir D]
     python -m mudpt_amd.harness --trainer CoOp --epochs 2 [--csc] [--class-token-position end|middle|front]
     python -m mudpt_amd.harness --trainer VPT|MPT --epochs 2 [--deep-text-n-ctx N --text-prompt-depth D --deep-visual-n-ctx N --visual-prompt-depth D]
-    python -m mudpt_amd.harness --trainer UMuDPT --epochs 2 [--n-ctx N --depth D]
+    python -m mudpt_amd.harness --trainer UMuDPT|UUMuDPT --epochs 2 [--n-ctx N --depth D]
 
 Mirrors what ``train.py`` (reference :153-173) does after config assembly: build_trainer(cfg) -> train() / test()."""
 from __future__ import annotations
@@ -12,13 +12,13 @@ import argparse
 
 import torch
 
-from . import cocoop, coop, dassl_lite, parallel, trainer, umudpt, vpt  # noqa: F401  (importing the plugin modules registers MuDPT / CoCoOp / CoOp / VPT, MPT / UMuDPT)
+from . import cocoop, coop, dassl_lite, parallel, trainer, umudpt, uumudpt, vpt  # noqa: F401  (importing the plugin modules registers MuDPT / CoCoOp / CoOp / VPT, MPT / UMuDPT / UUMuDPT)
 
 
 def run(argv=None):
     """Build the trainer the arguments name, then train (or, with --eval-only, load and test); returns the trainer, its outcome in ``.result``."""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--trainer", default="MuDPT", choices=["MuDPT", "CoCoOp", "CoOp", "VPT", "MPT", "UMuDPT"])
+    ap.add_argument("--trainer", default="MuDPT", choices=["MuDPT", "CoCoOp", "CoOp", "VPT", "MPT", "UMuDPT", "UUMuDPT"])
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--classes", type=int, default=11)
@@ -49,6 +49,7 @@ def run(argv=None):
     cfg.TRAINER.NAME = a.trainer
     cfg.TRAINER.MUDPT.N_CTX, cfg.TRAINER.MUDPT.DEEP_PROMPT_DEPTH, cfg.TRAINER.MUDPT.PREC = a.n_ctx, a.depth, a.prec
     cfg.TRAINER.UMUDPT.N_CTX, cfg.TRAINER.UMUDPT.DEEP_PROMPT_DEPTH, cfg.TRAINER.UMUDPT.PREC = a.n_ctx, a.depth, a.prec
+    cfg.TRAINER.UUMUDPT.N_CTX, cfg.TRAINER.UUMUDPT.DEEP_PROMPT_DEPTH, cfg.TRAINER.UUMUDPT.PREC = a.n_ctx, a.depth, a.prec
     cfg.TRAINER.COCOOP.PREC = a.prec
     cfg.TRAINER.COOP.N_CTX, cfg.TRAINER.COOP.PREC, cfg.TRAINER.COOP.CSC = a.n_ctx, a.prec, a.csc
     cfg.TRAINER.COOP.CLASS_TOKEN_POSITION = a.class_token_position
@@ -61,7 +62,7 @@ def run(argv=None):
     torch.manual_seed(cfg.SEED)
     t = trainer.TRAINER_REGISTRY.get(a.trainer)(cfg) if not trainer.HAVE_DASSL else None
     if t is None:
-        raise SystemExit("Dassl is installed: use the reference's train.py --trainer MuDPT / CoCoOp / CoOp / VPT / MPT / UMuDPT (see INTEGRATION.md)")
+        raise SystemExit("Dassl is installed: use the reference's train.py --trainer MuDPT / CoCoOp / CoOp / VPT / MPT / UMuDPT / UUMuDPT (see INTEGRATION.md)")
     if a.eval_only:
         t.load_model(a.model_dir, epoch=a.load_epoch)
         t.result = t.test()

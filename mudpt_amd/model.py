@@ -78,6 +78,32 @@ def umudpt_init_tensors(n_ctx: int, depth: int, d_t: int, d_v: int, ctx_rows: Op
     return out
 
 
+def uumudpt_init_tensors(n_ctx: int, depth: int, d_t: int, d_v: int, embed_dim: int, image_size: int, patch: int, seed: Optional[int] = None,
+                         ctx_rows: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Initial values of UUMuDPT's 40 trainables under their full keys, in named_parameters() order.  The reference draws them at TWO points:
+    the vision tower's 20 when ``CLIP(...)`` is constructed (clip/model.py:605-623 -- ``visual`` is the first thing CLIP builds, and conv1,
+    class_embedding and positional_embedding draw before visual_ctx, so they are drawn and dropped here), the prompt learner's 20 when
+    ``CustomCLIP(...)`` is constructed (trainers/uumudpt.py:97-125, the draws of :func:`umudpt_init_tensors`).  ``seed``: each half is drawn
+    right behind its own ``torch.manual_seed(seed)`` -- the two seed points the fixtures' checksums pin; None: both halves continue the
+    caller's stream, the vision half first, as one process that builds CLIP and then CustomCLIP does."""
+    from collections import OrderedDict
+    if seed is not None:
+        torch.manual_seed(seed)
+    nn.Conv2d(3, d_v, patch, patch, bias=False)
+    torch.randn(d_v)
+    torch.randn((image_size // patch) ** 2 + 1, d_v)
+    vis = umudpt_init_tensors(n_ctx, depth, d_v, embed_dim)  # the same constructors in the same order at width d_v, output width embed_dim
+    if seed is not None:
+        torch.manual_seed(seed)
+    out = OrderedDict(("uumudpt_prompt_learner." + k, v) for k, v in umudpt_init_tensors(n_ctx, depth, d_t, d_v, ctx_rows).items())
+    names = {"ctx": "", "deep_prompts": "_deep_prompts", "ln_pre": "_ln_intra_pre", "self_attn": "_self_attn", "ln_post": "_ln_intra_post",
+             "visual_proj": "_text_proj"}
+    for k, v in vis.items():
+        head, _, rest = k.partition(".")
+        out["image_encoder.visual_ctx" + names[head] + ("." + rest if rest else "")] = v
+    return out
+
+
 class _Holder(nn.Module):
     """Namespace module so parameters get the reference's dotted state-dict keys."""
 
@@ -110,6 +136,9 @@ class CustomCLIP(nn.Module):
         # "umudpt": trainers/umudpt.py's CustomCLIP (MuDPT's towers; the vision prompts of every layer are generated from ctx / deep_prompts by a
         # trainable transformer block): 20 trainables under "umudpt_prompt_learner.*"; shape.n_ctx (1..16) / depth are TRAINER.UMUDPT.N_CTX /
         # DEEP_PROMPT_DEPTH
+        # "uumudpt": trainers/uumudpt.py's CustomCLIP (UMuDPT plus the vision tower's own visual_ctx, visual_ctx_deep_prompts and a second
+        # generator that turns those into an addend of the text deep prompts): 40 trainables, "uumudpt_prompt_learner.*" then
+        # "image_encoder.visual_ctx*"; shape.n_ctx (1..16) / depth are TRAINER.UUMUDPT.N_CTX / DEEP_PROMPT_DEPTH
         if variant == "coop_csc" and ctx_token_ids is not None:
             variant = "coop"  # trainers/coop.py:52-61: the CTX_INIT path builds one shared context whatever CSC says
         self.variant = variant
@@ -118,7 +147,7 @@ class CustomCLIP(nn.Module):
                           self.n_cls, self.max_batch, {"bf16": capi.BF16, "fp16": capi.F16, "fp32": capi.F32}[dtype],
                           {"mudpt": capi.VARIANT_MUDPT, "cocoop": capi.VARIANT_COCOOP, "coop": capi.VARIANT_COOP,
                            "coop_csc": capi.VARIANT_COOP_CSC, "vpt": capi.VARIANT_VPT, "mpt": capi.VARIANT_MPT,
-                           "umudpt": capi.VARIANT_UMUDPT}[variant])
+                           "umudpt": capi.VARIANT_UMUDPT, "uumudpt": capi.VARIANT_UUMUDPT}[variant])
         assert (prompt_shape is not None) == (variant in ("vpt", "mpt")), "prompt_shape is the VPT / MPT setting, and they need it"
         self.prompt_shape = None if prompt_shape is None else tuple(int(v) for v in prompt_shape)
         torch.cuda.set_device(self.device)
@@ -203,6 +232,15 @@ class CustomCLIP(nn.Module):
                 for k, v in init.items():
                     sd["umudpt_prompt_learner." + k].copy_(v)
             return
+        if self.variant == "uumudpt":
+            s = self.shape
+            with torch.random.fork_rng(devices=[], enabled=seed is not None):
+                init = uumudpt_init_tensors(s.n_ctx, s.depth, s.t_width, s.v_width, s.embed_dim, s.image_size, s.patch, seed,
+                                            None if ctx_token_ids is None else emb_w[list(ctx_token_ids)])
+            with torch.no_grad():
+                for k, v in init.items():
+                    sd[k].copy_(v)
+            return
         g = torch.Generator().manual_seed(seed) if seed is not None else None
         with torch.no_grad():
             for k, p in sd.items():
@@ -218,7 +256,7 @@ class CustomCLIP(nn.Module):
     @property
     def ctx_key(self) -> str:
         return {"mudpt": "mudpt_prompt_learner.ctx", "mpt": "text_prompt_learner.visual_ctx",
-                "umudpt": "umudpt_prompt_learner.ctx"}.get(self.variant, "prompt_learner.ctx")
+                "umudpt": "umudpt_prompt_learner.ctx", "uumudpt": "uumudpt_prompt_learner.ctx"}.get(self.variant, "prompt_learner.ctx")
 
     def set_knob(self, name: str, value: int):
         """``mudpt_model_set``: "gemm_variant", "lp_grad" and the split-operand knobs ("vis_lo", "txt_lo", "vis_sites", "txt_sites",

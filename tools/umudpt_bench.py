@@ -4,7 +4,7 @@ SGD, bf16, synthetic images, random-init CLIP ViT-B/16, n_ctx 2, depth 8 (train.
     python tools/umudpt_bench.py [--steps 20] [--rounds 5]
 Shapes: the script shape (batch 4, 50 classes) and batch 256 with 11 classes.  At each shape the two models live in one process and are
 timed alternately, round by round, after a warm-up; the MEDIAN over the rounds is reported with the rounds themselves.  The prompt
-generator's forward + backward alone (mudpt_promptgen_forward / _backward: the code the model path runs, 11 + 21 launches on 16 rows) is
+generator's forward + backward alone (mudpt_promptgen_forward / _backward: the code the model path runs, 11 + 11 launches on 16 rows) is
 timed the same way, and so are the MuDPT prompt learner's launches it replaces (the difference of the two steps bounds what shows)."""
 import argparse
 import os
@@ -94,7 +94,7 @@ def main():
         torch.cuda.empty_cache()
     gen = generator_alone(a.steps, a.rounds)
     print(f"generator alone (depth {DEPTH}, n_ctx {N_CTX}, 512 -> 768): forward + backward median {statistics.median(gen):.3f} ms "
-          f"(rounds {', '.join(f'{x:.3f}' for x in gen)}), 32 launches", flush=True)
+          f"(rounds {', '.join(f'{x:.3f}' for x in gen)}), 22 launches", flush=True)
 
 
 if __name__ == "__main__":
