@@ -66,11 +66,6 @@ static inline uint8_t f32_to_e4m3(float f) {
     return sign | bits;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
 struct BlockW {
     void *w_in = nullptr, *w_in_t = nullptr, *w_out = nullptr, *w_out_t = nullptr;
     void *w_fc = nullptr, *w_fc_t = nullptr, *w_proj = nullptr, *w_proj_t = nullptr;
@@ -561,6 +556,9 @@ static void expect_block_keys(mudpt_model* m, const std::string& prefix, int lay
         for (const char* n : names) m->missing.push_back(prefix + ".resblocks." + std::to_string(i) + "." + n);
 }
 
+static int n_patches(const mudpt_config& c) { return (c.image_size / c.patch) * (c.image_size / c.patch); }  // per image
+static int patch_k0(const mudpt_config& c) { return (3 * c.patch * c.patch + 63) / 64 * 64; }  // conv-as-GEMM K, zero-padded to the GEMM's granularity (ViT-L/14: 588 -> 640)
+
 extern "C" int mudpt_abi_version(void) { return MUDPT_ABI_VERSION; }
 extern "C" const char* mudpt_last_error(void) { return get_error(); }
 
@@ -607,7 +605,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
         nt = m->mpt ? ps->t_n_ctx : 0;
         D1t = m->mpt ? std::max(0, std::min(ps->t_depth, c->t_layers) - 1) : 0;  // no cap on the text depth (clip/model.py:752-770)
     }
-    const int P = (c->image_size / c->patch) * (c->image_size / c->patch);
+    const int P = n_patches(*c);
     const int Lv = 1 + P + nv;  // CoCoOp's / CoOp's image encoder is the vanilla ViT (trainers/cocoop.py:38, coop.py:37, clip/model.py:443-496)
     ARG_CHECK(Lv <= 4096 && c->ctx_len <= 4096, "create: sequence length %d/%d exceeds the attention limit (4096)", Lv, c->ctx_len);
 
@@ -641,7 +639,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     // CoCoOp, the number of images whose B * C prompts fit the memory budget at once are only known there
     if (int r = alloc_tower_weights(m, m->txt, dt, c->t_layers, c->t_heads, true, 1, false)) return r;
     m->txt.L = c->ctx_len; m->txt.Lp = attn_padded_len(c->ctx_len);
-    const int K0 = (3 * c->patch * c->patch + 63) / 64 * 64;  // conv-as-GEMM K, zero-padded to the GEMM's granularity (ViT-L/14: 588 -> 640)
+    const int K0 = patch_k0(*c);
     ALLOC(m->conv_w, (size_t)dv * K0 * 2);
     if (m->exact) { ALLOC(m->conv_w8, (size_t)dv * K0 * 2); ALLOC(m->patches_lo, (size_t)B * P * K0 * 2); }  // split pixels (vision tower's site 4)
     ALLOC(m->cls, dv * 4); ALLOC(m->vpos, (size_t)(1 + P) * dv * 4);
@@ -819,7 +817,7 @@ extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* da
     const mudpt_config& c = m->cfg;
     const std::string k(key);
     const size_t dv = c.v_width, dt = c.t_width, e = c.embed_dim;
-    const size_t P = (size_t)(c.image_size / c.patch) * (c.image_size / c.patch);
+    const size_t P = (size_t)n_patches(c);
     int rc = MUDPT_OK;
     auto blk = [&](const char* prefix, Tower& t) -> int {
         const std::string rest = k.substr(strlen(prefix));
@@ -832,7 +830,7 @@ extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* da
     else if (k.rfind("transformer.resblocks.", 0) == 0) rc = blk("transformer.resblocks.", m->txt);
     else if (k == "visual.conv1.weight") {
         EXPECT(dv * 3 * c.patch * c.patch);
-        const size_t k0 = (size_t)3 * c.patch * c.patch, k0p = (k0 + 63) / 64 * 64;
+        const size_t k0 = (size_t)3 * c.patch * c.patch, k0p = (size_t)patch_k0(c);
         std::vector<float> padded(dv * k0p, 0.f);  // rows zero-padded like the im2col rows
         for (size_t r = 0; r < dv; ++r) memcpy(&padded[r * k0p], data + r * k0, k0 * 4);
         rc = upload_lp(m->dtype, m->conv_w, nullptr, padded.data(), dv, k0p);
@@ -1107,37 +1105,104 @@ static void split_operand(GemmArgs& g, int mode, const void* A_lo, const void* B
     if (mode == LO_F8) { g.B8 = B8; g.b8_scale = b8_scale; }
 }
 
+// ---- the steps of a block, each written once: block_fwd / block_fwd_tail / block_bwd_tail / block_bwd only sequence them ---------------
+static const size_t kOpBytes = 2;  // one element of T
+static char* lp_at(const void* p, size_t elems) { return (char*)p + elems * kOpBytes; }  // element `elems` of a T buffer
+// compact rows of `width` elements of esz bytes: dst[r] = src[idx[r]] (gather), dst[idx[r]] = src[r] (scatter)
+static int gather(const void* src, const int* idx, void* dst, int rows, int width, size_t esz, hipStream_t s) { return launch_gather_rows(src, width * esz, idx, dst, width * esz, rows, (int)(width * esz), s); }
+static int scatter(const void* src, const int* idx, void* dst, int rows, int width, size_t esz, hipStream_t s) { return launch_scatter_rows(src, width * esz, idx, dst, width * esz, rows, (int)(width * esz), s); }
+// ... into zeros: the other rows of dst [all_rows, width] get 0
+static int scatter_zeroed(const void* src, const int* idx, void* dst, int all_rows, int rows, int width, size_t esz, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(dst, 0, (size_t)all_rows * width * esz, s));
+    return scatter(src, idx, dst, rows, width, esz, s);
+}
+// The buffers a half-step of a block works on, for a row set: every row of the pass (rows_all) or the last block's one used row per sequence,
+// compact (rows_tail; Tower::tail_rows).  big: its LayerNorms go through ln_fwd_call / ln_bwd_call (bracketed when profiling); the tail's never do
+struct BlockRows {
+    int rows = 0; bool big = false;
+    void *h = nullptr, *h_lo = nullptr, *g = nullptr, *g_lo = nullptr, *u = nullptr, *attn = nullptr, *attn_lo = nullptr;  // T
+    float *x_in = nullptr, *x_mid = nullptr, *mean2 = nullptr, *rstd2 = nullptr, *dx = nullptr; void *dx_lp = nullptr, *dattn = nullptr;  // dx, dx_lp: the gradient stream (fp32 / T)
+};
+static BlockRows rows_all(const Tower& t, int i, int nseq) {
+    const BlockAct& a = t.a[i];
+    BlockRows r; r.rows = tower_rows(t, nseq); r.big = true; r.h = t.h; r.h_lo = t.h_lo; r.g = t.g; r.g_lo = t.g_lo; r.u = a.u; r.attn = a.attn; r.attn_lo = t.attn_lo;
+    r.x_in = a.x_in; r.x_mid = a.x_mid; r.mean2 = a.mean2; r.rstd2 = a.rstd2; r.dx = t.dx; r.dx_lp = t.dx_lp; r.dattn = t.dattn;
+    return r;
+}
+static BlockRows rows_tail(const Tower& t, int nseq) {
+    const BlockAct& a = t.a[t.layers - 1];
+    BlockRows r; r.rows = nseq; r.h = t.h_sel; r.h_lo = t.h_sel_lo; r.g = t.g_sel; r.g_lo = t.g_sel_lo; r.u = t.u_sel; r.attn = t.attn_sel; r.attn_lo = t.attn_sel_lo;
+    r.x_in = t.xin_sel; r.x_mid = t.xmid_sel; r.mean2 = a.mean2; r.rstd2 = a.rstd2; r.dx = t.dsel; r.dx_lp = t.dsel_lp; r.dattn = t.dattn_sel;
+    return r;
+}
+// Forward GEMM of a frozen Linear W [N, K] (+ bias) at split-operand site `site`; the caller adds the epilogue's operands (out0, aux)
+static GemmArgs gemm_site(const Tower& t, int site, const void* A, const void* A_lo, int rows, const void* W, const void* W8, int s8, const float* bias, int N, int K) {
+    GemmArgs g; g.A = A; g.lda = K; g.B = W; g.ldb = K; g.M = rows; g.N = N; g.K = K; g.bias = bias;
+    split_operand(g, site_mode(t, site, K), A_lo, W8, s8); return g;
+}
+// in_proj, output features n0 .. n0 + N - 1 (q | k | v: rows of the weight, of its e4m3 copy and of the bias) of the ln_1 output h
+static GemmArgs gemm_in_proj(const Tower& t, const BlockW& w, const void* h, const void* h_lo, int rows, int n0, int N) {
+    const size_t o = (size_t)n0 * t.d;  // the same element offset into the e4m3 copy: its rows have the T copy's length in bytes
+    return gemm_site(t, SITE_QKV, h, h_lo, rows, lp_at(w.w_in, o), w.w_in8 ? lp_at(w.w_in8, o) : nullptr, w.s_in8, w.b_in + n0, N, t.d);
+}
+static GemmArgs gemm_out_proj(const Tower& t, const BlockW& w, const BlockRows& r) { return gemm_site(t, SITE_OUT, r.attn, r.attn_lo, r.rows, w.w_out, w.w_out8, w.s_out8, w.b_out, t.d, t.d); }
+static GemmArgs gemm_proj(const Tower& t, const BlockW& w, const BlockRows& r) { return gemm_site(t, SITE_PROJ, r.g, r.g_lo, r.rows, w.w_proj, w.w_proj8, w.s_proj8, w.b_proj, t.d, 4 * t.d); }
+// c_fc + QuickGELU, complete: u (or, gelu_q8, byte codes of QuickGELU'(u): rows of 4 d bytes) for the backward, QuickGELU(u) (+ low half) for c_proj
+static GemmArgs gemm_fc(const mudpt_model* m, const Tower& t, const BlockW& w, const BlockRows& r) {
+    const int d = t.d, m_proj = site_mode(t, SITE_PROJ, 4 * d);
+    GemmArgs f = gemm_site(t, SITE_FC, r.h, r.h_lo, r.rows, w.w_fc, w.w_fc8, w.s_fc8, w.b_fc, 4 * d, d);
+    f.out0 = r.u; f.ldo0 = 4 * d; f.out1 = r.g; f.ldo1 = 4 * d; f.gelu_q8 = m->gelu_q8 && t.split == LO_NONE;
+    if (m_proj != LO_NONE) { f.out1_lo = r.g_lo; f.out1_lo_mode = m_proj; }
+    return f;
+}
+// dX [rows, N] = dY [rows, K] Wt^T against the transposed copy Wt [N, ldw] of a frozen Linear (K < ldw: a range of its output features)
+static GemmArgs gemm_dx(const void* dY, int lddy, const void* Wt, int ldw, int rows, int N, int K, void* dX) {
+    GemmArgs g; g.A = dY; g.lda = lddy; g.B = Wt; g.ldb = ldw; g.M = rows; g.N = N; g.K = K; g.out0 = dX; g.ldo0 = N; return g;
+}
+// ... in_proj's, from the K gradient columns k0 .. of q | k | v (dY points at the first of them)
+static GemmArgs gemm_in_proj_dx(const Tower& t, const BlockW& w, const void* dY, int lddy, int rows, int k0, int K, void* dh) { return gemm_dx(dY, lddy, lp_at(w.w_in_t, k0), 3 * t.d, rows, t.d, K, dh); }
+// ln_2 into the c_fc operand h (+ low half); the caller names the input: x alone (tail) or x + add -> xout (full rows)
+static LnFwdArgs ln_2(const Tower& t, const BlockW& w, const BlockRows& r) {
+    const int d = t.d, m_fc = site_mode(t, SITE_FC, d);
+    LnFwdArgs l; l.ldx = d; l.gamma = w.ln2_g; l.beta = w.ln2_b; l.out = r.h; l.ldo = d; l.mean = r.mean2; l.rstd = r.rstd2; l.rows = r.rows; l.d = d;
+    if (m_fc != LO_NONE) { l.out_lo = r.h_lo; l.lo_mode = m_fc; }
+    return l;
+}
+// LayerNorm backward into the gradient stream, in place (in T alone when lp_grad; the T copy is always written).  The caller adds a row map
+// (row_index / stats_by_token) or the splice's side output
+static LnBwdArgs stream_ln_bwd(const mudpt_model* m, const Tower& t, const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* stream_f32, void* stream_lp, int rows) {
+    const int d = t.d;
+    LnBwdArgs b; b.dy = dy; b.lddy = d; b.x = x; b.ldx = d; b.mean = mean; b.rstd = rstd; b.gamma = gamma; b.lddres = d;
+    if (m->lp_grad) b.dres_lp = stream_lp; else { b.dres = stream_f32; b.dx = stream_f32; }
+    b.lddx = d; b.dx_lp = stream_lp; b.lddx_lp = d; b.rows = rows; b.d = d;
+    return b;
+}
+// Attention operands of length bucket g.  saved: the block's attention output and log-sum-exp (the single-query forms keep theirs per sequence)
+static AttnArgs seg_attn(const Tower& t, const BlockAct& a, const Tower::Seg& g, bool saved = true) {
+    AttnArgs at; at.qkv = lp_at(a.qkv, (size_t)g.row0 * 3 * t.d); at.B = g.nseq; at.L = g.L; at.H = t.heads; at.causal = t.causal;
+    if (saved) { at.out = lp_at(a.attn, (size_t)g.row0 * t.d); at.lse = a.lse + g.lse0; }
+    return at;
+}
+static const int* seg_tail_rows(const Tower& t, const Tower::Seg& g) { return t.segs.size() > 1 ? t.tail_local + g.seq0 : t.tail_rows; }  // packed: relative to the bucket
+
 // Forward of the last block after its attention, on the one used row of every sequence (Tower::tail_rows): gathers the
 // rows, then out_proj (+ residual in the small GEMM's epilogue), ln_2, c_fc + QuickGELU, c_proj (+ residual) -> t.xout_sel.
 static int block_fwd_tail(mudpt_model* m, Tower& t, int nseq, hipStream_t s, bool attn_sel_ready = false) {
-    const int i = t.layers - 1, S = nseq, d = t.d, dt = m->dtype;
-    BlockW& w = t.w[i];
-    BlockAct& a = t.a[i];
-    const size_t esz = 2;
-    const int m_out = site_mode(t, SITE_OUT, d), m_fc = site_mode(t, SITE_FC, d), m_proj = site_mode(t, SITE_PROJ, 4 * d);
+    const int i = t.layers - 1, d = t.d;
+    const BlockW& w = t.w[i];
+    const BlockRows r = rows_tail(t, nseq);
     if (!attn_sel_ready) {
-        TRY(launch_gather_rows(a.attn, (size_t)d * esz, t.tail_rows, t.attn_sel, (size_t)d * esz, S, d * (int)esz, s));
-        if (m_out != LO_NONE) TRY(launch_gather_rows(t.attn_lo, (size_t)d * esz, t.tail_rows, t.attn_sel_lo, (size_t)d * esz, S, d * (int)esz, s));
+        TRY(gather(t.a[i].attn, t.tail_rows, r.attn, nseq, d, kOpBytes, s));
+        if (site_mode(t, SITE_OUT, d) != LO_NONE) TRY(gather(t.attn_lo, t.tail_rows, r.attn_lo, nseq, d, kOpBytes, s));
     }
-    TRY(launch_gather_rows(a.x_in, (size_t)d * 4, t.tail_rows, t.xin_sel, (size_t)d * 4, S, d * 4, s));
-    GemmArgs o; o.A = t.attn_sel; o.lda = d; o.B = w.w_out; o.ldb = d; o.M = S; o.N = d; o.K = d; o.bias = w.b_out;
-    split_operand(o, m_out, t.attn_sel_lo, w.w_out8, w.s_out8);
-    o.out0 = t.xmid_sel; o.ldo0 = d; o.aux = t.xin_sel; o.ldaux = d;
+    TRY(gather(t.a[i].x_in, t.tail_rows, r.x_in, nseq, d, 4, s));
+    GemmArgs o = gemm_out_proj(t, w, r); o.out0 = r.x_mid; o.ldo0 = d; o.aux = r.x_in; o.ldaux = d;
     TRY(gemm_call(m, EPI_RESIDUAL, o, s));
-    LnFwdArgs l2; l2.x = t.xmid_sel; l2.ldx = d; l2.gamma = w.ln2_g; l2.beta = w.ln2_b; l2.out = t.h_sel; l2.ldo = d; l2.mean = a.mean2; l2.rstd = a.rstd2; l2.rows = S; l2.d = d;
-    if (m_fc != LO_NONE) { l2.out_lo = t.h_sel_lo; l2.lo_mode = m_fc; }
-    TRY(launch_ln_fwd(dt, l2, s));
-    GemmArgs f; f.A = t.h_sel; f.lda = d; f.B = w.w_fc; f.ldb = d; f.M = S; f.N = 4 * d; f.K = d; f.bias = w.b_fc;
-    split_operand(f, m_fc, t.h_sel_lo, w.w_fc8, w.s_fc8);
-    f.out0 = t.u_sel; f.ldo0 = 4 * d; f.out1 = t.g_sel; f.ldo1 = 4 * d;
-    f.gelu_q8 = m->gelu_q8 && t.split == LO_NONE;
-    if (m_proj != LO_NONE) { f.out1_lo = t.g_sel_lo; f.out1_lo_mode = m_proj; }
-    TRY(gemm_call(m, EPI_GELU, f, s));
-    GemmArgs p; p.A = t.g_sel; p.lda = 4 * d; p.B = w.w_proj; p.ldb = 4 * d; p.M = S; p.N = d; p.K = 4 * d; p.bias = w.b_proj;
-    split_operand(p, m_proj, t.g_sel_lo, w.w_proj8, w.s_proj8);
-    p.out0 = t.xout_sel; p.ldo0 = d; p.aux = t.xmid_sel; p.ldaux = d;
-    TRY(gemm_call(m, EPI_RESIDUAL, p, s));
-    return MUDPT_OK;
+    LnFwdArgs l2 = ln_2(t, w, r); l2.x = r.x_mid;
+    TRY(launch_ln_fwd(m->dtype, l2, s));
+    TRY(gemm_call(m, EPI_GELU, gemm_fc(m, t, w, r), s));
+    GemmArgs p = gemm_proj(t, w, r); p.out0 = t.xout_sel; p.ldo0 = d; p.aux = r.x_mid; p.ldaux = d;
+    return gemm_call(m, EPI_RESIDUAL, p, s);
 }
 
 // Block i of a tower.  The residual adds are NOT in the GEMM epilogues: out_proj / c_proj write their fp32 result
@@ -1146,16 +1211,15 @@ static int block_fwd_tail(mudpt_model* m, Tower& t, int nseq, hipStream_t s, boo
 // vmcnt retires in order).  So LN1 of block i >= 1 computes x_in[i] = x_mid[i-1] + upd, with the deep-prompt rows
 // spliced in (splice != null), and writes it for the backward; LN2 computes x_mid[i] = x_in[i] + upd.
 static int block_fwd(mudpt_model* m, Tower& t, int i, int nseq, const float* splice, hipStream_t s) {
-    const int M = tower_rows(t, nseq), d = t.d, dt = m->dtype, n = t.n;
+    const BlockRows r = rows_all(t, i, nseq);
+    const int M = r.rows, d = t.d, dt = m->dtype, n = t.n;
     const std::vector<Tower::Seg> segs = tower_segs(t, nseq);
     // bf16 mode: the update stream (out_proj / c_proj results) is kept in T like the gradient stream -- half the store time
     // of those GEMMs and 2 bytes less per element in the LayerNorm that adds it.  The last block's c_proj stays fp32 (launch_add).
     const bool lp = m->lp_upd;
-    BlockW& w = t.w[i];
-    BlockAct& a = t.a[i];
-    const size_t esz = 2;
-    // split operands (Tower::split): the form of each site's low half (LO_NONE: the site runs on T alone)
-    const int m_qkv = site_mode(t, SITE_QKV, d), m_out = site_mode(t, SITE_OUT, d), m_fc = site_mode(t, SITE_FC, d), m_proj = site_mode(t, SITE_PROJ, 4 * d);
+    const BlockW& w = t.w[i]; const BlockAct& a = t.a[i];
+    // split operands (Tower::split): the form of the low half the producers of in_proj's / out_proj's operand write (LO_NONE: the site runs on T alone)
+    const int m_qkv = site_mode(t, SITE_QKV, d), m_out = site_mode(t, SITE_OUT, d);
     LnFwdArgs l1; l1.x = a.x_in; l1.ldx = d; l1.gamma = w.ln1_g; l1.beta = w.ln1_b; l1.out = t.h; l1.ldo = d; l1.mean = a.mean1; l1.rstd = a.rstd1; l1.rows = M; l1.d = d;
     if (m_qkv != LO_NONE) { l1.out_lo = t.h_lo; l1.lo_mode = m_qkv; }
     if (i > 0) {
@@ -1170,9 +1234,9 @@ static int block_fwd(mudpt_model* m, Tower& t, int i, int nseq, const float* spl
             const size_t r0 = (size_t)g.row0;
             b.x = l1.x + r0 * l1.ldx; b.xout = l1.xout + r0 * l1.ldxout;
             if (l1.add) b.add = l1.add + r0 * l1.ldadd;
-            if (l1.add_lp) b.add_lp = (const char*)l1.add_lp + r0 * l1.ldadd * esz;
-            b.out = (char*)l1.out + r0 * l1.ldo * esz;
-            if (l1.out_lo) b.out_lo = (char*)l1.out_lo + r0 * l1.ldo * esz;
+            if (l1.add_lp) b.add_lp = lp_at(l1.add_lp, r0 * l1.ldadd);
+            b.out = lp_at(l1.out, r0 * l1.ldo);
+            if (l1.out_lo) b.out_lo = lp_at(l1.out_lo, r0 * l1.ldo);
             b.mean = l1.mean + r0; b.rstd = l1.rstd + r0; b.rows = g.nseq * g.L; b.ov_L = g.L;
             TRY(ln_fwd_call(m, t, b, s));
         }
@@ -1184,55 +1248,50 @@ static int block_fwd(mudpt_model* m, Tower& t, int i, int nseq, const float* spl
         // d .. 3d of its weight, written into the k, v thirds of the packed qkv buffer), q for the selected rows only, single-query attention
         // straight into the compact attn_sel the tail works on.  (With the fp32 attention forward the general kernel runs instead: the
         // single-query kernels take fp16 q, k, v.)
-        GemmArgs kv; kv.A = t.h; kv.lda = d; kv.B = (const char*)w.w_in + (size_t)d * d * esz; kv.ldb = d; kv.M = M; kv.N = 2 * d; kv.K = d; kv.bias = w.b_in + d;
-        split_operand(kv, m_qkv, t.h_lo, w.w_in8 ? (const char*)w.w_in8 + (size_t)d * d * esz : nullptr, w.s_in8);
-        kv.out0 = (char*)a.qkv + (size_t)d * esz; kv.ldo0 = 3 * d;
+        GemmArgs kv = gemm_in_proj(t, w, t.h, t.h_lo, M, d, 2 * d); kv.out0 = lp_at(a.qkv, d); kv.ldo0 = 3 * d;
         TRY(gemm_call(m, EPI_STORE, kv, s));
-        TRY(launch_gather_rows(t.h, (size_t)d * esz, t.tail_rows, t.h_sel, (size_t)d * esz, nseq, d * (int)esz, s));
-        if (m_qkv != LO_NONE) TRY(launch_gather_rows(t.h_lo, (size_t)d * esz, t.tail_rows, t.h_sel_lo, (size_t)d * esz, nseq, d * (int)esz, s));
-        GemmArgs qs; qs.A = t.h_sel; qs.lda = d; qs.B = w.w_in; qs.ldb = d; qs.M = nseq; qs.N = d; qs.K = d; qs.bias = w.b_in;
-        split_operand(qs, m_qkv, t.h_sel_lo, w.w_in8, w.s_in8);
-        qs.out0 = t.q_sel; qs.ldo0 = d;
+        TRY(gather(t.h, t.tail_rows, t.h_sel, nseq, d, kOpBytes, s));
+        if (m_qkv != LO_NONE) TRY(gather(t.h_lo, t.tail_rows, t.h_sel_lo, nseq, d, kOpBytes, s));
+        GemmArgs qs = gemm_in_proj(t, w, t.h_sel, t.h_sel_lo, nseq, 0, d); qs.out0 = t.q_sel; qs.ldo0 = d;
         TRY(gemm_call(m, EPI_STORE, qs, s));
         for (const Tower::Seg& g : segs) {
-            AttnArgs at; at.qkv = (const char*)a.qkv + (size_t)g.row0 * 3 * d * esz; at.B = g.nseq; at.L = g.L; at.H = t.heads; at.causal = t.causal;
-            at.sel_rows = segs.size() > 1 ? t.tail_local + g.seq0 : t.tail_rows;
-            at.lo_mode = m_out;
-            TRY(launch_attn_fwd_single(dt, at, (const char*)t.q_sel + (size_t)g.seq0 * d * esz, (char*)t.attn_sel + (size_t)g.seq0 * d * esz,
-                                       m_out != LO_NONE ? (char*)t.attn_sel_lo + (size_t)g.seq0 * d * esz : nullptr, d, t.lse_sel + (size_t)g.seq0 * t.heads, s));
+            const size_t q0 = (size_t)g.seq0 * d;
+            AttnArgs at = seg_attn(t, a, g, false); at.sel_rows = seg_tail_rows(t, g); at.lo_mode = m_out;
+            TRY(launch_attn_fwd_single(dt, at, lp_at(t.q_sel, q0), lp_at(t.attn_sel, q0), m_out != LO_NONE ? lp_at(t.attn_sel_lo, q0) : nullptr, d,
+                                       t.lse_sel + (size_t)g.seq0 * t.heads, s));
         }
         return block_fwd_tail(m, t, nseq, s, true);
     }
-    GemmArgs q; q.A = t.h; q.lda = d; q.B = w.w_in; q.ldb = d; q.M = M; q.N = 3 * d; q.K = d; q.bias = w.b_in; q.out0 = a.qkv; q.ldo0 = 3 * d;
-    split_operand(q, m_qkv, t.h_lo, w.w_in8, w.s_in8);
+    GemmArgs q = gemm_in_proj(t, w, t.h, t.h_lo, M, 0, 3 * d); q.out0 = a.qkv; q.ldo0 = 3 * d;
     if (t.exact_attn) q.out0 = t.qkv32;  // fp32 q | k | v for the fp32 attention forward, which leaves their fp16 copy in a.qkv for the backward
     TRY(gemm_call(m, t.exact_attn ? EPI_STORE_F32 : EPI_STORE, q, s));
     for (const Tower::Seg& g : segs) {
-        AttnArgs at; at.qkv = (const char*)a.qkv + (size_t)g.row0 * 3 * d * esz; at.out = (char*)a.attn + (size_t)g.row0 * d * esz; at.lse = a.lse + g.lse0;
-        at.B = g.nseq; at.L = g.L; at.H = t.heads; at.causal = t.causal;
-        if (m_out != LO_NONE) { at.out_lo = (char*)t.attn_lo + (size_t)g.row0 * d * esz; at.lo_mode = m_out; }
-        if (t.exact_attn) { at.qkv32 = t.qkv32 + (size_t)g.row0 * 3 * d; at.qkv_lp = (char*)a.qkv + (size_t)g.row0 * 3 * d * esz; }
+        AttnArgs at = seg_attn(t, a, g);
+        if (m_out != LO_NONE) { at.out_lo = lp_at(t.attn_lo, (size_t)g.row0 * d); at.lo_mode = m_out; }
+        if (t.exact_attn) { at.qkv32 = t.qkv32 + (size_t)g.row0 * 3 * d; at.qkv_lp = lp_at(a.qkv, (size_t)g.row0 * 3 * d); }
         TRY(attn_call(m, t, at, false, s));
     }
     if (i + 1 == t.layers) return block_fwd_tail(m, t, nseq, s);
-    GemmArgs o; o.A = a.attn; o.lda = d; o.B = w.w_out; o.ldb = d; o.M = M; o.N = d; o.K = d; o.bias = w.b_out; o.out0 = t.upd; o.ldo0 = d;
-    split_operand(o, m_out, t.attn_lo, w.w_out8, w.s_out8);
     const bool fs = !t.causal && t.split == LO_NONE;  // forward split K: the vision tower's out_proj / c_proj at tiny batches only (gemm_call), never with split operands
+    GemmArgs o = gemm_out_proj(t, w, r); o.out0 = t.upd; o.ldo0 = d;
     TRY(gemm_call(m, lp ? EPI_STORE : EPI_STORE_F32, o, s, false, fs));
-    LnFwdArgs l2; l2.x = a.x_in; l2.ldx = d; if (lp) l2.add_lp = t.upd; else l2.add = t.upd; l2.ldadd = d; l2.xout = a.x_mid; l2.ldxout = d; l2.gamma = w.ln2_g; l2.beta = w.ln2_b; l2.out = t.h; l2.ldo = d;
-    if (m_fc != LO_NONE) { l2.out_lo = t.h_lo; l2.lo_mode = m_fc; }
-    l2.mean = a.mean2; l2.rstd = a.rstd2; l2.rows = M; l2.d = d;
+    LnFwdArgs l2 = ln_2(t, w, r); l2.x = r.x_in; if (lp) l2.add_lp = t.upd; else l2.add = t.upd; l2.ldadd = d; l2.xout = r.x_mid; l2.ldxout = d;
     TRY(ln_fwd_call(m, t, l2, s));
-    GemmArgs f; f.A = t.h; f.lda = d; f.B = w.w_fc; f.ldb = d; f.M = M; f.N = 4 * d; f.K = d; f.bias = w.b_fc; f.out0 = a.u; f.ldo0 = 4 * d;
-    split_operand(f, m_fc, t.h_lo, w.w_fc8, w.s_fc8);
-    f.out1 = t.g; f.ldo1 = 4 * d;
-    f.gelu_q8 = m->gelu_q8 && t.split == LO_NONE;  // a.u then holds byte codes of QuickGELU'(u) (rows of 4 d bytes)
-    if (m_proj != LO_NONE) { f.out1_lo = t.g_lo; f.out1_lo_mode = m_proj; }
-    TRY(gemm_call(m, EPI_GELU, f, s));
-    GemmArgs p; p.A = t.g; p.lda = 4 * d; p.B = w.w_proj; p.ldb = 4 * d; p.M = M; p.N = d; p.K = 4 * d; p.bias = w.b_proj; p.out0 = t.upd; p.ldo0 = d;
-    split_operand(p, m_proj, t.g_lo, w.w_proj8, w.s_proj8);
-    TRY(gemm_call(m, lp ? EPI_STORE : EPI_STORE_F32, p, s, false, fs));
-    return MUDPT_OK;
+    TRY(gemm_call(m, EPI_GELU, gemm_fc(m, t, w, r), s));
+    GemmArgs p = gemm_proj(t, w, r); p.out0 = t.upd; p.ldo0 = d;
+    return gemm_call(m, lp ? EPI_STORE : EPI_STORE_F32, p, s, false, fs);
+}
+
+// Backward of a block from its output to its attention output, on a row set: c_proj dX with QuickGELU' (as the forward stored it, gemm_fc),
+// c_fc dX, ln_2 backward into the gradient stream r.dx / r.dx_lp (then the gradient w.r.t. x_mid), out_proj dX -> r.dattn
+static int mlp_bwd(mudpt_model* m, Tower& t, int i, const BlockRows& r, hipStream_t s) {
+    const int d = t.d; const BlockW& w = t.w[i];
+    GemmArgs g1 = gemm_dx(r.dx_lp, d, w.w_proj_t, d, r.rows, 4 * d, d, r.g); g1.aux = r.u; g1.ldaux = 4 * d; g1.gelu_q8 = m->gelu_q8 && t.split == LO_NONE;
+    TRY(gemm_call(m, EPI_GELU_BWD, g1, s, !t.causal));
+    TRY(gemm_call(m, EPI_STORE, gemm_dx(r.g, 4 * d, w.w_fc_t, 4 * d, r.rows, d, 4 * d, r.h), s, !t.causal));
+    const LnBwdArgs b2 = stream_ln_bwd(m, t, r.h, r.x_mid, r.mean2, r.rstd2, w.ln2_g, r.dx, r.dx_lp, r.rows);
+    TRY(r.big ? ln_bwd_call(m, t, b2, s) : launch_ln_bwd(m->dtype, b2, s));
+    return gemm_call(m, EPI_STORE, gemm_dx(r.dx_lp, d, w.w_out_t, d, r.rows, d, d, r.dattn), s, !t.causal);
 }
 
 // Backward of the last block's tail (see Tower::tail_rows).  in: t.dsel / t.dsel_lp = gradient w.r.t. the selected rows of
@@ -1240,88 +1299,48 @@ static int block_fwd(mudpt_model* m, Tower& t, int i, int nseq, const float* spl
 static int block_bwd_tail(mudpt_model* m, Tower& t, int nseq, hipStream_t s) {
     const int i = t.layers - 1, M = tower_rows(t, nseq), S = nseq, d = t.d, dt = m->dtype;
     const std::vector<Tower::Seg> segs = tower_segs(t, nseq);
-    const size_t esz = 2;
-    BlockW& w = t.w[i];
-    BlockAct& a = t.a[i];
-    GemmArgs g1; g1.A = t.dsel_lp; g1.lda = d; g1.B = w.w_proj_t; g1.ldb = d; g1.M = S; g1.N = 4 * d; g1.K = d; g1.out0 = t.g_sel; g1.ldo0 = 4 * d; g1.aux = t.u_sel; g1.ldaux = 4 * d;
-    g1.gelu_q8 = m->gelu_q8 && t.split == LO_NONE;  // as the forward stored it (block_fwd_tail)
-    TRY(gemm_call(m, EPI_GELU_BWD, g1, s, !t.causal));
-    GemmArgs g2; g2.A = t.g_sel; g2.lda = 4 * d; g2.B = w.w_fc_t; g2.ldb = 4 * d; g2.M = S; g2.N = d; g2.K = 4 * d; g2.out0 = t.h_sel; g2.ldo0 = d;
-    TRY(gemm_call(m, EPI_STORE, g2, s, !t.causal));
-    LnBwdArgs b2; b2.dy = t.h_sel; b2.lddy = d; b2.x = t.xmid_sel; b2.ldx = d; b2.mean = a.mean2; b2.rstd = a.rstd2; b2.gamma = w.ln2_g; b2.lddres = d;
-    if (m->lp_grad) b2.dres_lp = t.dsel_lp; else { b2.dres = t.dsel; b2.dx = t.dsel; }
-    b2.lddx = d; b2.dx_lp = t.dsel_lp; b2.lddx_lp = d; b2.rows = S; b2.d = d;
-    TRY(launch_ln_bwd(dt, b2, s));  // t.dsel(_lp) = gradient w.r.t. x_mid on the selected rows
-    GemmArgs g3; g3.A = t.dsel_lp; g3.lda = d; g3.B = w.w_out_t; g3.ldb = d; g3.M = S; g3.N = d; g3.K = d; g3.out0 = t.dattn_sel; g3.ldo0 = d;
-    TRY(gemm_call(m, EPI_STORE, g3, s, !t.causal));
+    const BlockW& w = t.w[i]; const BlockAct& a = t.a[i];
+    TRY(mlp_bwd(m, t, i, rows_tail(t, nseq), s));  // t.dsel(_lp) = gradient w.r.t. x_mid on the selected rows
     if (m->last_single && !t.exact_attn) {
         // single-query attention backward: dK, dV of every row (k, v thirds of t.dqkv) and dq of the one query per sequence
         for (const Tower::Seg& g : segs) {
-            AttnArgs at; at.qkv = (const char*)a.qkv + (size_t)g.row0 * 3 * d * esz; at.dqkv = (char*)t.dqkv + (size_t)g.row0 * 3 * d * esz;
-            at.sel_rows = segs.size() > 1 ? t.tail_local + g.seq0 : t.tail_rows;
-            at.B = g.nseq; at.L = g.L; at.H = t.heads; at.causal = t.causal;
-            TRY(launch_attn_bwd_single(dt, at, (const char*)t.q_sel + (size_t)g.seq0 * d * esz, (const char*)t.attn_sel + (size_t)g.seq0 * d * esz, d,
-                                       (const char*)t.dattn_sel + (size_t)g.seq0 * d * esz, t.lse_sel + (size_t)g.seq0 * t.heads,
-                                       (char*)t.dq_sel + (size_t)g.seq0 * d * esz, s));
+            const size_t q0 = (size_t)g.seq0 * d;
+            AttnArgs at = seg_attn(t, a, g, false); at.dqkv = lp_at(t.dqkv, (size_t)g.row0 * 3 * d); at.sel_rows = seg_tail_rows(t, g);
+            TRY(launch_attn_bwd_single(dt, at, lp_at(t.q_sel, q0), lp_at(t.attn_sel, q0), d, lp_at(t.dattn_sel, q0), t.lse_sel + (size_t)g.seq0 * t.heads,
+                                       lp_at(t.dq_sel, q0), s));
         }
         // d(ln_1 output) = dK, dV rows . W_kv  (K range d .. 3d of the transposed in_proj weight)  +  on the selected rows  dq . W_q
-        GemmArgs g4; g4.A = (char*)t.dqkv + (size_t)d * esz; g4.lda = 3 * d; g4.B = (char*)w.w_in_t + (size_t)d * esz; g4.ldb = 3 * d; g4.M = M; g4.N = d; g4.K = 2 * d;
-        g4.out0 = t.h; g4.ldo0 = d;
-        TRY(gemm_call(m, EPI_STORE, g4, s, !t.causal));
-        GemmArgs g5; g5.A = t.dq_sel; g5.lda = d; g5.B = w.w_in_t; g5.ldb = 3 * d; g5.M = S; g5.N = d; g5.K = d; g5.out0 = t.dqx_sel; g5.ldo0 = d;
-        TRY(gemm_call(m, EPI_STORE, g5, s, !t.causal));
+        TRY(gemm_call(m, EPI_STORE, gemm_in_proj_dx(t, w, lp_at(t.dqkv, d), 3 * d, M, d, 2 * d, t.h), s, !t.causal));
+        TRY(gemm_call(m, EPI_STORE, gemm_in_proj_dx(t, w, t.dq_sel, d, S, 0, d, t.dqx_sel), s, !t.causal));
         TRY(launch_add_rows(dt, t.dqx_sel, t.tail_rows, t.h, S, d, s));
     } else {
-    // attention backward over all keys: d(attention output) is zero except on the selected query rows
-    HIP_TRY(hipMemsetAsync(t.dattn, 0, (size_t)M * d * esz, s));
-    TRY(launch_scatter_rows(t.dattn_sel, (size_t)d * esz, t.tail_rows, t.dattn, (size_t)d * esz, S, d * (int)esz, s));
-    for (const Tower::Seg& g : segs) {
-        AttnArgs at; at.qkv = (const char*)a.qkv + (size_t)g.row0 * 3 * d * esz; at.out = (char*)a.attn + (size_t)g.row0 * d * esz; at.lse = a.lse + g.lse0;
-        at.dout = (const char*)t.dattn + (size_t)g.row0 * d * esz; at.dqkv = (char*)t.dqkv + (size_t)g.row0 * 3 * d * esz; at.delta = t.delta + g.lse0;
-        at.B = g.nseq; at.L = g.L; at.H = t.heads; at.causal = t.causal;
-        at.sel_rows = segs.size() > 1 ? t.tail_local + g.seq0 : t.tail_rows;  // d(attention output) is zero except on those rows: the kernels skip the all-zero query blocks
-        TRY(attn_call(m, t, at, true, s));
-    }
-    GemmArgs g4; g4.A = t.dqkv; g4.lda = 3 * d; g4.B = w.w_in_t; g4.ldb = 3 * d; g4.M = M; g4.N = d; g4.K = 3 * d; g4.out0 = t.h; g4.ldo0 = d;
-    TRY(gemm_call(m, EPI_STORE, g4, s, !t.causal));
+        // attention backward over all keys: d(attention output) is zero except on the selected query rows
+        TRY(scatter_zeroed(t.dattn_sel, t.tail_rows, t.dattn, M, S, d, kOpBytes, s));
+        for (const Tower::Seg& g : segs) {
+            AttnArgs at = seg_attn(t, a, g);
+            at.dout = lp_at(t.dattn, (size_t)g.row0 * d); at.dqkv = lp_at(t.dqkv, (size_t)g.row0 * 3 * d); at.delta = t.delta + g.lse0;
+            at.sel_rows = seg_tail_rows(t, g);  // d(attention output) is zero except on those rows: the kernels skip the all-zero query blocks
+            TRY(attn_call(m, t, at, true, s));
+        }
+        TRY(gemm_call(m, EPI_STORE, gemm_in_proj_dx(t, w, t.dqkv, 3 * d, M, 0, 3 * d, t.h), s, !t.causal));
     }
     // the residual path into ln_1's input: d(x_mid), zero except on the selected rows
-    HIP_TRY(hipMemsetAsync(t.dx_lp, 0, (size_t)M * d * esz, s));
-    TRY(launch_scatter_rows(t.dsel_lp, (size_t)d * esz, t.tail_rows, t.dx_lp, (size_t)d * esz, S, d * (int)esz, s));
-    if (!m->lp_grad) {
-        HIP_TRY(hipMemsetAsync(t.dx, 0, (size_t)M * d * 4, s));
-        TRY(launch_scatter_rows(t.dsel, (size_t)d * 4, t.tail_rows, t.dx, (size_t)d * 4, S, d * 4, s));
-    }
-    LnBwdArgs b1; b1.dy = t.h; b1.lddy = d; b1.x = a.x_in; b1.ldx = d; b1.mean = a.mean1; b1.rstd = a.rstd1; b1.gamma = w.ln1_g; b1.lddres = d;
-    if (m->lp_grad) b1.dres_lp = t.dx_lp; else { b1.dres = t.dx; b1.dx = t.dx; }
-    b1.lddx = d; b1.dx_lp = t.dx_lp; b1.lddx_lp = d; b1.rows = M; b1.d = d;
-    TRY(ln_bwd_call(m, t, b1, s));
-    return MUDPT_OK;
+    TRY(scatter_zeroed(t.dsel_lp, t.tail_rows, t.dx_lp, M, S, d, kOpBytes, s));
+    if (!m->lp_grad) TRY(scatter_zeroed(t.dsel, t.tail_rows, t.dx, M, S, d, 4, s));
+    return ln_bwd_call(m, t, stream_ln_bwd(m, t, t.h, a.x_in, a.mean1, a.rstd1, w.ln1_g, t.dx, t.dx_lp, M), s);
 }
 
-// in: t.dx / t.dx_lp = gradient w.r.t. the block output; out: the same buffers = gradient w.r.t. x_in
-// side != null: block i's input had deep-prompt rows spliced in; their gradient goes to side[seq][n_ctx][d] (row stride side_ldb per
-// sequence) and the stream gets zeros on those rows (LnBwdArgs::side)
+// Backward of block i (the last one: block_bwd_tail).  in: t.dx / t.dx_lp = gradient w.r.t. the block output; out: the same buffers = gradient w.r.t. x_in
+// side != null: block i's input had deep-prompt rows spliced in; their gradient goes to side[seq][n_ctx][d] (row stride side_ldb per sequence) and the
+// stream gets zeros on those rows (LnBwdArgs::side).  The last block's ln_1 backward is not fused with the splice: it ignores side and leaves them in the stream
 static int block_bwd(mudpt_model* m, Tower& t, int i, int nseq, hipStream_t s, float* side = nullptr, size_t side_ldb = 0) {
-    const int M = tower_rows(t, nseq), d = t.d, dt = m->dtype;
-    BlockW& w = t.w[i];
-    BlockAct& a = t.a[i];
-    GemmArgs g1; g1.A = t.dx_lp; g1.lda = d; g1.B = w.w_proj_t; g1.ldb = d; g1.M = M; g1.N = 4 * d; g1.K = d; g1.out0 = t.g; g1.ldo0 = 4 * d; g1.aux = a.u; g1.ldaux = 4 * d;
-    g1.gelu_q8 = m->gelu_q8 && t.split == LO_NONE;  // as the forward stored it (block_fwd)
-    TRY(gemm_call(m, EPI_GELU_BWD, g1, s, !t.causal));
-    GemmArgs g2; g2.A = t.g; g2.lda = 4 * d; g2.B = w.w_fc_t; g2.ldb = 4 * d; g2.M = M; g2.N = d; g2.K = 4 * d; g2.out0 = t.h; g2.ldo0 = d;
-    TRY(gemm_call(m, EPI_STORE, g2, s, !t.causal));
-    LnBwdArgs b2; b2.dy = t.h; b2.lddy = d; b2.x = a.x_mid; b2.ldx = d; b2.mean = a.mean2; b2.rstd = a.rstd2; b2.gamma = w.ln2_g; b2.lddres = d;
-    if (m->lp_grad) b2.dres_lp = t.dx_lp; else { b2.dres = t.dx; b2.dx = t.dx; }
-    b2.lddx = d; b2.dx_lp = t.dx_lp; b2.lddx_lp = d; b2.rows = M; b2.d = d;
-    TRY(ln_bwd_call(m, t, b2, s));
-    GemmArgs g3; g3.A = t.dx_lp; g3.lda = d; g3.B = w.w_out_t; g3.ldb = d; g3.M = M; g3.N = d; g3.K = d; g3.out0 = t.dattn; g3.ldo0 = d;
-    TRY(gemm_call(m, EPI_STORE, g3, s, !t.causal));
+    if (i == t.layers - 1) return block_bwd_tail(m, t, nseq, s);
+    const int M = tower_rows(t, nseq), d = t.d;
+    const BlockW& w = t.w[i]; const BlockAct& a = t.a[i];
+    TRY(mlp_bwd(m, t, i, rows_all(t, i, nseq), s));
     for (const Tower::Seg& g : tower_segs(t, nseq)) {
-        const size_t esz = 2;
-        AttnArgs at; at.qkv = (const char*)a.qkv + (size_t)g.row0 * 3 * d * esz; at.out = (char*)a.attn + (size_t)g.row0 * d * esz; at.lse = a.lse + g.lse0;
-        at.dout = (const char*)t.dattn + (size_t)g.row0 * d * esz; at.dqkv = (char*)t.dqkv + (size_t)g.row0 * 3 * d * esz; at.delta = t.delta + g.lse0;
-        at.B = g.nseq; at.L = g.L; at.H = t.heads; at.causal = t.causal;
+        AttnArgs at = seg_attn(t, a, g);
+        at.dout = lp_at(t.dattn, (size_t)g.row0 * d); at.dqkv = lp_at(t.dqkv, (size_t)g.row0 * 3 * d); at.delta = t.delta + g.lse0;
         // block 0: only the prompt rows of dqkv are read below (Tower::head_rows)
         if (i == 0 && t.head_rows && t.layers > 1 && m->attn_window) {
             at.win_row0 = t.prompt_row0;
@@ -1333,24 +1352,15 @@ static int block_bwd(mudpt_model* m, Tower& t, int i, int nseq, hipStream_t s, f
         // block 0: d(x_in) on the prompt rows only (Tower::head_rows); the other rows of t.dx / t.dx_lp are left stale and
         // nothing reads them (the splice reductions and ln_pre's backward touch prompt rows only)
         const int R = nseq * t.head_n;
-        TRY(launch_gather_rows(t.dqkv, (size_t)3 * d * 2, t.head_rows, t.hd_dqkv, (size_t)3 * d * 2, R, 3 * d * 2, s));
-        GemmArgs g4; g4.A = t.hd_dqkv; g4.lda = 3 * d; g4.B = w.w_in_t; g4.ldb = 3 * d; g4.M = R; g4.N = d; g4.K = 3 * d; g4.out0 = t.hd_h; g4.ldo0 = d;
-        TRY(gemm_call(m, EPI_STORE, g4, s, !t.causal));
-        LnBwdArgs b1; b1.dy = t.hd_h; b1.lddy = d; b1.x = a.x_in; b1.ldx = d; b1.row_index = t.head_rows; b1.stats_by_token = true;
-        b1.mean = a.mean1; b1.rstd = a.rstd1; b1.gamma = w.ln1_g; b1.lddres = d;
-        if (m->lp_grad) b1.dres_lp = t.dx_lp; else { b1.dres = t.dx; b1.dx = t.dx; }
-        b1.lddx = d; b1.dx_lp = t.dx_lp; b1.lddx_lp = d; b1.rows = R; b1.d = d;
-        TRY(launch_ln_bwd(dt, b1, s));
-        return MUDPT_OK;
+        TRY(gather(t.dqkv, t.head_rows, t.hd_dqkv, R, 3 * d, kOpBytes, s));
+        TRY(gemm_call(m, EPI_STORE, gemm_in_proj_dx(t, w, t.hd_dqkv, 3 * d, R, 0, 3 * d, t.hd_h), s, !t.causal));
+        LnBwdArgs b1 = stream_ln_bwd(m, t, t.hd_h, a.x_in, a.mean1, a.rstd1, w.ln1_g, t.dx, t.dx_lp, R); b1.row_index = t.head_rows; b1.stats_by_token = true;
+        return launch_ln_bwd(m->dtype, b1, s);
     }
-    GemmArgs g4; g4.A = t.dqkv; g4.lda = 3 * d; g4.B = w.w_in_t; g4.ldb = 3 * d; g4.M = M; g4.N = d; g4.K = 3 * d; g4.out0 = t.h; g4.ldo0 = d;
-    TRY(gemm_call(m, EPI_STORE, g4, s, !t.causal));
-    LnBwdArgs b1; b1.dy = t.h; b1.lddy = d; b1.x = a.x_in; b1.ldx = d; b1.mean = a.mean1; b1.rstd = a.rstd1; b1.gamma = w.ln1_g; b1.lddres = d;
-    if (m->lp_grad) b1.dres_lp = t.dx_lp; else { b1.dres = t.dx; b1.dx = t.dx; }
-    b1.lddx = d; b1.dx_lp = t.dx_lp; b1.lddx_lp = d; b1.rows = M; b1.d = d;
+    TRY(gemm_call(m, EPI_STORE, gemm_in_proj_dx(t, w, t.dqkv, 3 * d, M, 0, 3 * d, t.h), s, !t.causal));
+    LnBwdArgs b1 = stream_ln_bwd(m, t, t.h, a.x_in, a.mean1, a.rstd1, w.ln1_g, t.dx, t.dx_lp, M);
     if (side) { b1.side = side; b1.side_row0 = t.prompt_row0; b1.side_n = t.n; b1.side_L = t.L; b1.side_ldb = side_ldb; }
-    TRY(ln_bwd_call(m, t, b1, s));
-    return MUDPT_OK;
+    return ln_bwd_call(m, t, b1, s);
 }
 
 // Where a tower's prompt rows come from and where their gradients are reduced to, resolved per call (mudpt_bind_params may rebind the
@@ -1395,12 +1405,41 @@ static PromptRoute prompt_route(const mudpt_model* m, const Tower& t) {
     return r;
 }
 
+// The head of a tower: final LayerNorm on the used rows (t.xout_sel) and the projection proj [d, e] to the embedding (fp32; clip/model.py:549-552, trainers/mudpt.py:154-156).
+// y / dy and the statistics hold one row per sequence of a step; a pass works on `rows` of them from row r0 on (CoCoOp's chunks); feat / dfeat [rows, e] are the caller's
+struct TowerHead { const float *ln_g, *ln_b, *proj; float *mean, *rstd, *y, *dy; };
+static TowerHead vision_head(const mudpt_model* m) { return {m->ln_post_g, m->ln_post_b, m->vproj, m->post_mean, m->post_rstd, m->f_ln, m->df_ln}; }
+static TowerHead text_head(const mudpt_model* m) { return {m->ln_fin_g, m->ln_fin_b, m->tproj, m->fin_mean, m->fin_rstd, m->t_ln, m->dt_ln}; }
+static int tower_head_fwd(mudpt_model* m, const Tower& t, const TowerHead& h, float* feat, int rows, size_t r0, hipStream_t s) {
+    const int d = t.d, e = m->cfg.embed_dim;
+    LnFwdArgs l; l.x = t.xout_sel; l.ldx = d; l.gamma = h.ln_g; l.beta = h.ln_b; l.out = h.y + r0 * d; l.ldo = d; l.out_f32 = true; l.mean = h.mean + r0; l.rstd = h.rstd + r0; l.rows = rows; l.d = d;
+    TRY(launch_ln_fwd(m->dtype, l, s));
+    return launch_sgemm(false, false, rows, e, d, 1.f, h.y + r0 * d, d, h.proj, e, 0.f, feat, e, nullptr, s);
+}
+// ... and its backward: dfeat -> t.dsel / t.dsel_lp, the gradient stream on the last block's tail rows
+static int tower_head_bwd(mudpt_model* m, const Tower& t, const TowerHead& h, const float* dfeat, int rows, size_t r0, hipStream_t s) {
+    const int d = t.d, e = m->cfg.embed_dim;
+    TRY(launch_sgemm(false, true, rows, d, e, 1.f, dfeat, e, h.proj, e, 0.f, h.dy + r0 * d, d, nullptr, s));
+    LnBwdArgs b; b.dy = h.dy + r0 * d; b.lddy = d; b.dy_f32 = true; b.x = t.xout_sel; b.ldx = d; b.mean = h.mean + r0; b.rstd = h.rstd + r0;
+    b.gamma = h.ln_g; b.dx = m->lp_grad ? nullptr : t.dsel; b.lddx = d; b.dx_lp = t.dsel_lp; b.lddx_lp = d; b.rows = rows; b.d = d;
+    return launch_ln_bwd(m->dtype, b, s);
+}
+
+// The gradient stream as the reductions behind a tower's backward read it, from token row row0 on: the fp32 copy, or (lp_grad) the T copy alone
+struct GradStream { float* f32; void* lp; };
+static GradStream grad_stream(const mudpt_model* m, const Tower& t, size_t row0 = 0) { return m->lp_grad ? GradStream{nullptr, lp_at(t.dx_lp, row0 * t.d)} : GradStream{t.dx + row0 * t.d, nullptr}; }
+// Deep-prompt rows a tower consumed of D1 layers' worth: blocks >= depth never splice one, so rows used .. R of a [R, d] prompt-gradient table stay zero
+static int used_prompt_rows(const Tower& t, int D1) { return (t.layers - 1 < D1 ? t.layers - 1 : D1) * t.n; }
+static int zero_unused_rows(float* dprompt, int used, int R, int d, hipStream_t s) {
+    if (used < R) HIP_TRY(hipMemsetAsync(dprompt + (size_t)used * d, 0, (size_t)(R - used) * d * 4, s));
+    return MUDPT_OK;
+}
+
 // Vision tower forward, clip/model.py:526-553 (MuDPT: prompt rows appended before ln_pre, deep prompts spliced per block) or
 // clip/model.py:478-496 (CoCoOp: the vanilla ViT, no prompt rows) -> m->img_f [B, e]
 static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_t s) {
     const mudpt_config& c = m->cfg;
-    const int dv = c.v_width, e = c.embed_dim, n = m->vis.n, D1 = m->vis.D1;
-    const int P = (c.image_size / c.patch) * (c.image_size / c.patch), Lv = m->vis.L, K0 = (3 * c.patch * c.patch + 63) / 64 * 64;
+    const int dv = c.v_width, n = m->vis.n, D1 = m->vis.D1, P = n_patches(c), Lv = m->vis.L, K0 = patch_k0(c);
     const PromptRoute pr = prompt_route(m, m->vis);
     const int m_patch = site_mode(m->vis, SITE_PATCH, K0);  // parity mode: split pixels (an fp16 pixel alone carries 2.4e-4 of rounding into block 0)
     if (m_patch != LO_NONE) TRY(launch_patchify_split(m->dtype, images, m->patches, m->patches_lo, m_patch, B, c.image_size, c.patch, K0, s));
@@ -1415,19 +1454,11 @@ static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_
     LnFwdArgs lp; lp.x = m->xpre; lp.ldx = dv; lp.gamma = m->ln_pre_g; lp.beta = m->ln_pre_b; lp.out = m->vis.a[0].x_in; lp.ldo = dv; lp.out_f32 = true;
     lp.mean = m->pre_mean; lp.rstd = m->pre_rstd; lp.rows = B * Lv; lp.d = dv;
     TRY(launch_ln_fwd(m->dtype, lp, s));
-    for (int i = 0; i < m->vis.layers; ++i) {
-        TRY(block_fwd(m, m->vis, i, B, (i >= 1 && i - 1 < D1) ? pr.deep + (size_t)(i - 1) * n * dv : nullptr, s));
-    }
-    LnFwdArgs lq; lq.x = m->vis.xout_sel; lq.ldx = dv; lq.gamma = m->ln_post_g; lq.beta = m->ln_post_b; lq.out = m->f_ln; lq.ldo = dv;
-    lq.out_f32 = true; lq.mean = m->post_mean; lq.rstd = m->post_rstd; lq.rows = B; lq.d = dv;
-    TRY(launch_ln_fwd(m->dtype, lq, s));
-    TRY(launch_sgemm(false, false, B, e, dv, 1.f, m->f_ln, dv, m->vproj, e, 0.f, m->img_f, e, nullptr, s));
-    return MUDPT_OK;
+    for (int i = 0; i < m->vis.layers; ++i) TRY(block_fwd(m, m->vis, i, B, (i >= 1 && i - 1 < D1) ? pr.deep + (size_t)(i - 1) * n * dv : nullptr, s));
+    return tower_head_fwd(m, m->vis, vision_head(m), m->img_f, B, 0, s);
 }
 
 // ---- CoCoOp (trainers/cocoop.py) ------------------------------------------------------------------------------------
-// forward (:178-198): image features of the frozen vanilla ViT -> meta_net bias per image (:141-146) -> one text-tower pass
-// over all B * C (image, class) prompts at once (the reference loops over the images, :187-194) -> logits [B, C].
 // text tower over the prompts of images [i0, i0 + nb): prompts (:148-165) + positional embedding (:52), 12 causal blocks, ln_final on
 // the EOT rows, text_projection -> rows i0 * C .. of m->txt_f
 static int cocoop_text_chunk(mudpt_model* m, int i0, int nb, hipStream_t s) {
@@ -1436,11 +1467,7 @@ static int cocoop_text_chunk(mudpt_model* m, int i0, int nb, hipStream_t s) {
     const size_t r0 = (size_t)i0 * C;
     TRY(launch_cocoop_prompts(m->txt.a[0].x_in, m->emb_pos, m->params + m->off(Q_CTX), m->mn_bias + (size_t)i0 * dt, m->tpos, nb, C, Lt, dt, n, s));
     for (int i = 0; i < m->txt.layers; ++i) TRY(block_fwd(m, m->txt, i, TS, nullptr, s));
-    LnFwdArgs lf; lf.x = m->txt.xout_sel; lf.ldx = dt; lf.gamma = m->ln_fin_g; lf.beta = m->ln_fin_b; lf.out = m->t_ln + r0 * dt; lf.ldo = dt;
-    lf.out_f32 = true; lf.mean = m->fin_mean + r0; lf.rstd = m->fin_rstd + r0; lf.rows = TS; lf.d = dt;
-    TRY(launch_ln_fwd(m->dtype, lf, s));
-    TRY(launch_sgemm(false, false, TS, e, dt, 1.f, m->t_ln + r0 * dt, dt, m->tproj, e, 0.f, m->txt_f + r0 * e, e, nullptr, s));
-    return MUDPT_OK;
+    return tower_head_fwd(m, m->txt, text_head(m), m->txt_f + r0 * e, TS, r0, s);
 }
 
 static HeadArgs cocoop_head_args(mudpt_model* m, int i0, int nb, int B) {
@@ -1497,16 +1524,12 @@ static int cocoop_forward_backward(mudpt_model* m, const float* images, const in
         h.labels = labels + i0; h.grad_scale = m->loss_scale * (float)B;
         TRY(launch_pair_head_fwd(h, s));
         TRY(launch_pair_head_bwd(h, s));  // CE rows, dlogits, d(text features) of this chunk; the mean over all B rows follows the loop
-        TRY(launch_sgemm(false, true, TS, dt, e, 1.f, m->dtxt + r0 * e, e, m->tproj, e, 0.f, m->dt_ln + r0 * dt, dt, nullptr, s));
-        LnBwdArgs bf; bf.dy = m->dt_ln + r0 * dt; bf.lddy = dt; bf.dy_f32 = true; bf.x = X.xout_sel; bf.ldx = dt; bf.mean = m->fin_mean + r0; bf.rstd = m->fin_rstd + r0;
-        bf.gamma = m->ln_fin_g; bf.dx = m->lp_grad ? nullptr : X.dsel; bf.lddx = dt; bf.dx_lp = X.dsel_lp; bf.lddx_lp = dt; bf.rows = TS; bf.d = dt;
-        TRY(launch_ln_bwd(m->dtype, bf, s));
-        for (int i = X.layers - 1; i >= 0; --i) {
-            if (i == X.layers - 1) TRY(block_bwd_tail(m, X, TS, s)); else TRY(block_bwd(m, X, i, TS, s));
-        }
+        TRY(tower_head_bwd(m, X, text_head(m), m->dtxt + r0 * e, TS, r0, s));
+        for (int i = X.layers - 1; i >= 0; --i) TRY(block_bwd(m, X, i, TS, s));
         // d ctx += sum over the chunk's (image, class) prompts of the context rows' gradient; d bias[i] = the same sum over image i's prompts
-        TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, TS, Lt, dt, 1, n, G + m->off(Q_CTX), false, true, unscale, s));
-        TRY(launch_cocoop_dbias(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, m->mn_dbias + (size_t)i0 * dt, nb, C, Lt, dt, n, unscale, s));
+        const GradStream dx = grad_stream(m, X);
+        TRY(launch_reduce_rows(m->dtype, dx.f32, dx.lp, TS, Lt, dt, 1, n, G + m->off(Q_CTX), false, true, unscale, s));
+        TRY(launch_cocoop_dbias(m->dtype, dx.f32, dx.lp, m->mn_dbias + (size_t)i0 * dt, nb, C, Lt, dt, n, unscale, s));
     }
     TRY(launch_mean(m->row_loss, B, m->loss, s));
     HIP_TRY(hipMemcpyAsync(loss, m->loss, 4, hipMemcpyDeviceToDevice, s));
@@ -1589,16 +1612,11 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
     else if (n > 0)  // MuDPT ctx / MPT text_prompt_learner.visual_ctx at rows 1..n
         for (const Tower::Seg& g : segs)
             TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, pr.in0, pr.in0_add, s2));
-    for (int i = 0; i < m->txt.layers; ++i) {
-        TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? pr.deep + (size_t)(i - 1) * n * dt : nullptr, s2));
-    }
-    LnFwdArgs lf; lf.x = m->txt.xout_sel; lf.ldx = dt; lf.gamma = m->ln_fin_g; lf.beta = m->ln_fin_b; lf.out = m->t_ln; lf.ldo = dt;
-    lf.out_f32 = true; lf.mean = m->fin_mean; lf.rstd = m->fin_rstd; lf.rows = Ct; lf.d = dt;
-    TRY(launch_ln_fwd(m->dtype, lf, s2));
+    for (int i = 0; i < m->txt.layers; ++i) TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? pr.deep + (size_t)(i - 1) * n * dt : nullptr, s2));
     if (m->sharded) HIP_TRY(hipMemsetAsync(m->txt_f, 0, (size_t)c.n_cls * e * 4, s2));  // other ranks' rows: zero, so a sum completes the table
     float* feat = m->txt_f + (size_t)m->c0 * e;
-    TRY(launch_sgemm(false, false, Ct, e, dt, 1.f, m->t_ln, dt, m->tproj, e, 0.f, packed ? m->txt_sorted : feat, e, nullptr, s2));
-    if (packed) TRY(launch_scatter_rows(m->txt_sorted, (size_t)e * 4, m->class_perm, feat, (size_t)e * 4, Ct, e * 4, s2));  // back to the caller's class order
+    TRY(tower_head_fwd(m, m->txt, text_head(m), packed ? m->txt_sorted : feat, Ct, 0, s2));
+    if (packed) TRY(scatter(m->txt_sorted, m->class_perm, feat, Ct, e, 4, s2));  // back to the caller's class order
     m->text_valid = true;
     return MUDPT_OK;
 }
@@ -1722,61 +1740,47 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
     const std::vector<Tower::Seg> segs = tower_segs(X, Ct);
     const float* dfeat = m->dtxt + (size_t)m->c0 * e;
     if (segs.size() > 1) {  // length buckets: the tower's sequences are in length-sorted order
-        TRY(launch_gather_rows(dfeat, (size_t)e * 4, m->class_perm, m->dtxt_sorted, (size_t)e * 4, Ct, e * 4, s2));
+        TRY(gather(dfeat, m->class_perm, m->dtxt_sorted, Ct, e, 4, s2));
         dfeat = m->dtxt_sorted;
     }
-    TRY(launch_sgemm(false, true, Ct, dt, e, 1.f, dfeat, e, m->tproj, e, 0.f, m->dt_ln, dt, nullptr, s2));
-    LnBwdArgs bf; bf.dy = m->dt_ln; bf.lddy = dt; bf.dy_f32 = true; bf.x = X.xout_sel; bf.ldx = dt; bf.mean = m->fin_mean; bf.rstd = m->fin_rstd;
-    bf.gamma = m->ln_fin_g; bf.dx = m->lp_grad ? nullptr : X.dsel; bf.lddx = dt; bf.dx_lp = X.dsel_lp; bf.lddx_lp = dt; bf.rows = Ct; bf.d = dt;
-    TRY(launch_ln_bwd(m->dtype, bf, s2));
+    TRY(tower_head_bwd(m, X, text_head(m), dfeat, Ct, 0, s2));
     for (int i = X.layers - 1; i >= 0; --i) {
-        if (i == X.layers - 1) TRY(block_bwd_tail(m, X, Ct, s2)); else TRY(block_bwd(m, X, i, Ct, s2));
+        TRY(block_bwd(m, X, i, Ct, s2));
+        // zero_src: the T copy is passed in both modes, since it is the copy block i - 1's dX GEMMs read and must see the zeros too
         if (i >= 1 && i - 1 < D1)
             for (const Tower::Seg& g : segs)  // bucket after bucket in a fixed order: deterministic
-                TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, (char*)X.dx_lp + (size_t)g.row0 * dt * 2, g.nseq, g.L, dt, 1, n,
+                TRY(launch_reduce_rows(m->dtype, grad_stream(m, X, g.row0).f32, lp_at(X.dx_lp, (size_t)g.row0 * dt), g.nseq, g.L, dt, 1, n,
                                        pr.d_deep + (size_t)(i - 1) * n * dt, true, g.seq0 > 0, unscale, s2));
     }
     // CoOp: d ctx from the context rows of every class (shared: summed over the classes in a fixed order; CSC: per class), coop.hip
-    if (m->coop)
-        return launch_coop_dctx(m->dtype, m->lp_grad ? nullptr : X.dx, m->lp_grad ? X.dx_lp : nullptr, m->tprompt_rows, G + m->off(0), Ct, n, dt, m->csc, unscale, s2);
+    if (m->coop) return launch_coop_dctx(m->dtype, grad_stream(m, X).f32, grad_stream(m, X).lp, m->tprompt_rows, G + m->off(0), Ct, n, dt, m->csc, unscale, s2);
     // d ctx (text side): rows 1..n of the first block's input, summed over the class prompts
     for (const Tower::Seg& g : segs)
-        TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : X.dx + (size_t)g.row0 * dt, m->lp_grad ? (char*)X.dx_lp + (size_t)g.row0 * dt * 2 : nullptr, g.nseq, g.L, dt, 1, n,
-                               pr.d_in0, false, true, unscale, s2));
+        TRY(launch_reduce_rows(m->dtype, grad_stream(m, X, g.row0).f32, grad_stream(m, X, g.row0).lp, g.nseq, g.L, dt, 1, n, pr.d_in0, false, true, unscale, s2));
     return MUDPT_OK;
 }
 
 static int vision_backward(mudpt_model* m, int B, float unscale, hipStream_t s) {
     const mudpt_config& c = m->cfg;
-    const int dv = c.v_width, e = c.embed_dim, n = m->vis.n, D1 = m->vis.D1;
-    const int Lv = m->vis.L;
+    const int dv = c.v_width, n = m->vis.n, D1 = m->vis.D1, Lv = m->vis.L;
     Tower& V = m->vis;
     const PromptRoute pr = prompt_route(m, V);
-    TRY(launch_sgemm(false, true, B, dv, e, 1.f, m->dimg, e, m->vproj, e, 0.f, m->df_ln, dv, nullptr, s));
-    LnBwdArgs bq; bq.dy = m->df_ln; bq.lddy = dv; bq.dy_f32 = true; bq.x = V.xout_sel; bq.ldx = dv; bq.mean = m->post_mean; bq.rstd = m->post_rstd;
-    bq.gamma = m->ln_post_g; bq.dx = m->lp_grad ? nullptr : V.dsel; bq.lddx = dv; bq.dx_lp = V.dsel_lp; bq.lddx_lp = dv; bq.rows = B; bq.d = dv;
-    TRY(launch_ln_bwd(m->dtype, bq, s));
+    TRY(tower_head_bwd(m, V, vision_head(m), m->dimg, B, 0, s));
     // Backward of the splice: the prompt rows of d(x_in[i]) feed d(vis_deep[i-1]) and the rows the splice overwrote get no gradient.
     // ln_1's backward writes those rows, in fp32, to vsplice[b][(i - 1) n + k][:] and zeros to the stream (LnBwdArgs::side); ONE
     // fixed-order reduction over the images after the last block replaces a reduce-and-zero launch per block on the critical path.
-    const int used = (V.layers - 1 < D1 ? V.layers - 1 : D1) * n;  // layers >= depth never consume a prompt
+    const int used = used_prompt_rows(V, D1);
     const size_t side_ldb = (size_t)used * dv;
     for (int i = V.layers - 1; i >= 0; --i) {
         const bool spliced = i >= 1 && i - 1 < D1;
-        if (i == V.layers - 1) {
-            TRY(block_bwd_tail(m, V, B, s));
-            if (spliced) {  // the tail's ln_1 backward is not fused: take the rows from the stream
-                TRY(launch_reduce_rows(m->dtype, m->lp_grad ? nullptr : V.dx, V.dx_lp, B, Lv, dv, Lv - n, n, pr.d_deep + (size_t)(i - 1) * n * dv, true, false, unscale, s));
-            }
-        } else {
-            TRY(block_bwd(m, V, i, B, s, spliced ? m->vsplice + (size_t)(i - 1) * n * dv : nullptr, side_ldb));
-        }
+        TRY(block_bwd(m, V, i, B, s, spliced ? m->vsplice + (size_t)(i - 1) * n * dv : nullptr, side_ldb));
+        // the tail's ln_1 backward is not fused: take the rows from the stream (zero_src: the T copy in both modes, as in text_backward)
+        if (spliced && i == V.layers - 1)
+            TRY(launch_reduce_rows(m->dtype, grad_stream(m, V).f32, V.dx_lp, B, Lv, dv, Lv - n, n, pr.d_deep + (size_t)(i - 1) * n * dv, true, false, unscale, s));
     }
-    {
-        // blocks 1 .. layers-2 (the fused ones): rows 0 .. n (layers - 2) of every image's side block
-        const int fused = (V.layers - 2 < D1 ? V.layers - 2 : D1) * n;
-        if (fused > 0) TRY(launch_reduce_rows(m->dtype, m->vsplice, nullptr, B, used, dv, 0, fused, pr.d_deep, false, false, unscale, s));
-    }
+    // blocks 1 .. layers-2 (the fused ones): rows 0 .. n (layers - 2) of every image's side block
+    const int fused = (V.layers - 2 < D1 ? V.layers - 2 : D1) * n;
+    if (fused > 0) TRY(launch_reduce_rows(m->dtype, m->vsplice, nullptr, B, used, dv, 0, fused, pr.d_deep, false, false, unscale, s));
     // ln_pre backward on the prompt rows only (patch / CLS rows have no trainable ancestor), in place
     LnBwdArgs bp; bp.dy = m->lp_grad ? (const void*)V.dx_lp : (const void*)V.dx; bp.lddy = dv; bp.dy_f32 = !m->lp_grad; bp.x = m->xpre; bp.ldx = dv; bp.row_index = m->vprompt_rows; bp.mean = m->pre_mean; bp.rstd = m->pre_rstd;
     bp.gamma = m->ln_pre_g; bp.dx = V.dx; bp.lddx = dv; bp.rows = B * n; bp.d = dv; bp.by_token = true;
@@ -1795,9 +1799,7 @@ static int prompt_learner_backward_text(mudpt_model* m, hipStream_t s) {
     float *Pm = m->params, *G = m->grads;
     if (D1 <= 0) return MUDPT_OK;
     const int R = D1 * n;
-    // layers >= depth never consume a prompt: rows of d_txt_deep beyond the tower depth stay zero
-    const int used_t = (m->txt.layers - 1 < D1 ? m->txt.layers - 1 : D1) * n;
-    if (used_t < R) HIP_TRY(hipMemsetAsync(m->d_txt_deep + (size_t)used_t * dt, 0, (size_t)(R - used_t) * dt * 4, s));
+    TRY(zero_unused_rows(m->d_txt_deep, used_prompt_rows(m->txt, D1), R, dt, s));
     // txt_deep = deep_prompts + visual_ctx_deep_projections(visual_ctx_deep_prompts)   (mudpt.py:175, clip/model.py:539)
     TRY(launch_add(G + m->off(P_DEEP), m->d_txt_deep, G + m->off(P_DEEP), (size_t)R * dt, s));
     TRY(launch_sgemm(true, false, e, dv, R, 1.f, m->d_txt_deep, e, Pm + m->off(P_VDEEP), dv, 1.f, G + m->off(P_VW), dv, nullptr, s));
@@ -1816,8 +1818,7 @@ static int prompt_learner_backward_vision(mudpt_model* m, hipStream_t s) {
     TRY(launch_sgemm(false, false, n, dt, dv, 1.f, m->d_vprompt0, dv, Pm + m->off(P_EW), dt, 1.f, G + m->off(P_CTX), dt, nullptr, s));
     if (D1 > 0) {
         const int R = D1 * n;
-        const int used_v = (m->vis.layers - 1 < D1 ? m->vis.layers - 1 : D1) * n;
-        if (used_v < R) HIP_TRY(hipMemsetAsync(m->d_vis_deep + (size_t)used_v * dv, 0, (size_t)(R - used_v) * dv * 4, s));
+        TRY(zero_unused_rows(m->d_vis_deep, used_prompt_rows(m->vis, D1), R, dv, s));
         // vis_deep = deep_projections(deep_prompts) + visual_ctx_deep_prompts   (clip/model.py:537, mudpt.py:127)
         TRY(launch_add(G + m->off(P_VDEEP), m->d_vis_deep, G + m->off(P_VDEEP), (size_t)R * dv, s));
         TRY(launch_sgemm(true, false, dv, dt, R, 1.f, m->d_vis_deep, dv, Pm + m->off(P_DEEP), dt, 1.f, G + m->off(P_DW), dt, nullptr, s));
@@ -1838,9 +1839,7 @@ static int umudpt_backward(mudpt_model* m, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, dt = c.t_width, n = c.n_ctx, R = c.depth * n;
     float *Pm = m->params, *G = m->grads;
-    // layers >= depth never consume a prompt: their rows of dG get no gradient from the tower
-    const int used = (1 + (m->vis.layers - 1 < c.depth - 1 ? m->vis.layers - 1 : c.depth - 1)) * n;
-    if (used < R) HIP_TRY(hipMemsetAsync(m->pg_dG + (size_t)used * dv, 0, (size_t)(R - used) * dv * 4, s));
+    TRY(zero_unused_rows(m->pg_dG, n + used_prompt_rows(m->vis, c.depth - 1), R, dv, s));  // row group 0: the input prompt rows
     TRY(pg_backward(c.depth, n, dt, dv, pg_params(Pm + m->off(U_GEN), dt, dv), Pm + m->off(P_CTX), m->pg_dG, m->pg_dX, G + m->off(U_GEN), m->pg_w, s));
     return launch_add(G + m->off(P_CTX), m->pg_dX, G + m->off(P_CTX), (size_t)R * dt, s);  // ctx and deep_prompts lie one behind the other
 }
@@ -1855,9 +1854,7 @@ static int uumudpt_backward_text(mudpt_model* m, hipStream_t s2) {
     if (g.D1 <= 0) return MUDPT_OK;
     float* G = m->grads;
     const int R = g.D1 * g.n;
-    // layers >= depth never consume a prompt: rows of dT beyond the tower depth get no gradient
-    const int used_t = (m->txt.layers - 1 < g.D1 ? m->txt.layers - 1 : g.D1) * g.n;
-    if (used_t < R) HIP_TRY(hipMemsetAsync(m->d_txt_deep + (size_t)used_t * g.e, 0, (size_t)(R - used_t) * g.e * 4, s2));
+    TRY(zero_unused_rows(m->d_txt_deep, used_prompt_rows(m->txt, g.D1), R, g.e, s2));
     TRY(launch_add(G + m->off(P_DEEP), m->d_txt_deep, G + m->off(P_DEEP), (size_t)R * g.e, s2));
     return pg_backward(g.D1, g.n, g.d, g.e, g.P, g.X, m->d_txt_deep, G + m->off(UU_VDEEP), G + m->off(UU_GEN2), m->pg2_w, s2);
 }
