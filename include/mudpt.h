@@ -318,7 +318,8 @@ int mudpt_gemm_form(int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t l
  * with the row stride of A in bytes.  lo_mode 1: A_lo holds T values and a second pass contracts it against the same B (22 bits); lo_mode 2:
  * A_lo holds OCP e4m3 bytes of (v - A) * 2^12 (the first K bytes of each row) and the second pass runs on the MX-scaled fp8 matrix
  * instruction against B8, the e4m3 copy of B ([N, K] bytes at the row stride of B in bytes, values B * 2^shift, b8_scale = 127 - shift =
- * the E8M0 block scale); K % 128 == 0 and dtype fp16 then.  lo_mode 0: no second pass.  epilogue 0 | 1 | 2 | 5 as mudpt_gemm; with
+ * the E8M0 block scale); K % 128 == 0 and dtype fp16 then.  lo_mode 0: no second pass.  epilogue 0 | 1 | 2 | 3 | 5 as mudpt_gemm (4 needs
+ * mudpt_gemm_split_patch's operands; the persistent kernel builds the e4m3 second pass for 0 | 1 | 5 only and refuses 3 at its sizes); with
  * epilogue 1, out1_lo (may be NULL) receives the low half of out1 = QuickGELU(u) in form out1_lo_mode (1 / 2), at the row stride of out1 in bytes. */
 int mudpt_gemm_split(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, const void* A, const void* A_lo, int32_t lo_mode, int32_t lda,
                      const void* B, const void* B8, int32_t b8_scale, int32_t ldb, const float* bias, void* out0, int32_t ldo0, void* out1,
@@ -449,6 +450,12 @@ int mudpt_head_ex(const float* img, const float* txt, const int64_t* labels, flo
  * labels NULL: logits only. */
 int mudpt_pair_head(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
                     int32_t e, float* logits, float* loss, float* row_loss, float* dtxt, void* stream);
+/* mudpt_gemm_split with the patch-embed epilogue's operands (epilogue 4 of mudpt_gemm: patches, seq_len, pos): what the parity mode's vision
+ * tower runs on the split patch rows mudpt_patchify writes.  Every other epilogue as mudpt_gemm_split. */
+int mudpt_gemm_split_patch(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, const void* A, const void* A_lo, int32_t lo_mode, int32_t lda,
+                           const void* B, const void* B8, int32_t b8_scale, int32_t ldb, const float* bias, void* out0, int32_t ldo0, void* out1,
+                           void* out1_lo, int32_t out1_lo_mode, int32_t ldo1, const void* aux, int32_t ldaux, int32_t patches, int32_t seq_len,
+                           const float* pos, int32_t variant, void* stream);
 /* images fp32 [B, 3, S, S] -> patches T [B * (S/p)^2, ldk], inner order (c, py, px), columns 3 p p .. ldk zero (clip/model.py:527-529);
  * patches_lo not NULL: the split form, the remainder in form lo_mode (1 / 2) in rows of 2 ldk bytes. */
 int mudpt_patchify(int32_t dtype, const float* images, void* patches, void* patches_lo, int32_t lo_mode, int32_t B, int32_t image_size, int32_t patch,

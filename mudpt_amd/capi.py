@@ -75,7 +75,9 @@ SIGNATURES = {
                           _i32, _i32, _vp, _i32, _vp]),
     "mudpt_gemm_form": (_i32, [_i32] * 10),
     "mudpt_gemm_split": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
-    "mudpt_e4m3_from_f32": (_i32, [_vp, _vp, _sz, _i32]),
+    "mudpt_gemm_split_patch": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32,
+                                      _i32, _i32, _vp, _i32, _vp]),
+    "mudpt_e4m3_from_f32":(_i32, [_vp, _vp, _sz, _i32]),
     "mudpt_layernorm_fwd_split": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mudpt_layernorm_fwd": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
     "mudpt_layernorm_bwd": (_i32, [_i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,

@@ -2310,6 +2310,17 @@ extern "C" int mudpt_attention_bwd(int32_t dtype, const void* qkv, const void* o
     return launch_attn_bwd(dtype, a, (hipStream_t)stream, o);
 }
 // ---- the launchers' production forms, one thin argument-packing export each (tests/test_kernels_gpu.py, tests/test_movers_gpu.py) ----
+extern "C" int mudpt_gemm_split_patch(int32_t dtype, int32_t epi, int32_t M, int32_t N, int32_t K, const void* A, const void* A_lo, int32_t lo_mode, int32_t lda,
+                                      const void* B, const void* B8, int32_t b8_scale, int32_t ldb, const float* bias, void* out0, int32_t ldo0, void* out1,
+                                      void* out1_lo, int32_t out1_lo_mode, int32_t ldo1, const void* aux, int32_t ldaux, int32_t patches, int32_t seq_len,
+                                      const float* pos, int32_t variant, void* stream) {
+    GemmOpts o;
+    o.variant = variant;
+    GemmArgs a; a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.bias = bias; a.out0 = out0; a.ldo0 = ldo0; a.out1 = out1; a.ldo1 = ldo1;
+    a.aux = aux; a.ldaux = ldaux; a.A_lo = A_lo; a.lo_mode = lo_mode; a.B8 = B8; a.b8_scale = b8_scale; a.out1_lo = out1_lo; a.out1_lo_mode = out1_lo ? out1_lo_mode : (int)LO_F16;
+    a.patches = patches; a.seq_len = seq_len; a.pos = pos;
+    return launch_gemm(dtype, epi, a, (hipStream_t)stream, o);
+}
 extern "C" int mudpt_layernorm_bwd_ex(int32_t dtype, const void* dy, int32_t lddy, int32_t dy_f32, const float* x, int32_t ldx, const int32_t* row_index,
                                       const float* mean, const float* rstd, const float* gamma, const float* dres, const void* dres_lp, int32_t lddres,
                                       float* dx, int32_t lddx, void* dx_lp, int32_t lddx_lp, float* side, int32_t side_row0, int32_t side_n, int32_t side_L,

@@ -100,6 +100,35 @@ def e4m3_spacing(s):
     return torch.ldexp(torch.ones_like(a), torch.frexp(a).exponent - 1 - 3)
 
 
+EPS = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11}  # half ulp relative
+
+
+def check_split_pair(dtype, hi, lo16, lo8, ref):
+    """hi [rows, Hd] in T, lo16 the remainder in T, lo8 its e4m3 codes (uint8), ref float64.  hi + lo against the definition; |lo| <= half an
+    ulp of hi (hi is the T rounding of the kernel's fp32 value, as test_exact_attention_forward asserts); the e4m3 form decodes to the same
+    remainder: e4m3(r 2^12) is within half an e4m3 step of r 2^12 and T(r) within EPS |r| of r, so the two forms differ by at most that sum.
+    The bounds above hold for `hi` alone, so two more pin lo itself (both follow from lo = v - T(v) for the kernel's fp32 value v = ref + err,
+    over N >= 768 elements of continuous data):
+      * lo / ulp is uniform on [-1/2, 1/2]: its mean square is 1/12 (sampling noise ~1 / sqrt(N) of that); a lo that is zero, halved, doubled
+        or saturated misses [1/16, 1/9];
+      * ref - hi = lo + (ref - v), and the kernel's error ref - v does not depend on the rounding remainder, so <lo, ref - hi> / <lo, lo> is
+        1 +- rms(err) / (rms(lo) sqrt(N)): with the error of the order of the remainder (the probabilities enter P.V rounded to T) that is a
+        few per cent at the smallest N.  A sign-flipped lo gives -1, a lo unrelated to the value gives 0: [0.5, 1.5] is asserted."""
+    mant, tiny = (7, 2.0 ** -126) if dtype == "bf16" else (10, 2.0 ** -14)
+    torch.testing.assert_close(hi.double() + lo16.double(), ref, atol=6 * EPS[dtype], rtol=6 * EPS[dtype])
+    ulp = torch.ldexp(torch.ones(()), torch.frexp(hi.float().abs().clamp_min(tiny)).exponent - 1 - mant)
+    assert (lo16.float().abs() <= 0.5 * ulp * (1 + 1e-3)).all()
+    msq = (lo16.double() / ulp.double()).pow(2).mean().item()
+    proj = ((lo16.double() * (ref - hi.double())).sum() / lo16.double().pow(2).sum()).item()
+    print(f"split pair {dtype}: N {hi.numel()}, mean (lo / ulp)^2 {msq:.4f} (1/12 = 0.0833), <lo, ref - hi> / <lo, lo> {proj:.3f}")
+    assert 1 / 16 <= msq <= 1 / 9 and 0.5 <= proj <= 1.5
+    r = lo16.double()
+    assert (r.abs() * 4096 * (1 + 2 * EPS[dtype])).max().item() < 448  # no saturation on these inputs
+    dec = lo8.contiguous().view(torch.float8_e4m3fn).double() / 4096.0
+    bound = 0.5 * e4m3_spacing(r * 4096 * (1 + 2 * EPS[dtype])) / 4096.0 + 2 * EPS[dtype] * r.abs() + 2.0 ** -25  # (2^-25: half a subnormal fp16 step)
+    assert ((dec - r).abs() <= bound).all()
+
+
 PATCH_CASES = [(64, 224, 16, 768), (8, 224, 32, 3072), (16, 336, 14, 640), (5, 32, 8, 192), (3, 28, 14, 640)]  # (B, S, p, ldk) of test_patchify_plain
 PATCH_SPLIT_CASES = [(128, 224, 16, 768), (3, 336, 14, 640), (5, 32, 8, 192), (3, 28, 14, 640), (2, 224, 32, 3072)]
 
@@ -299,16 +328,18 @@ def attention_form_launches():
 
 # ---- GEMM cases of test_gemm_forms_gpu.py, kept here so that test_capi_cpu.py can check, without a GPU, which kernel forms and which regimes of
 # the persistent kernel they reach ----
-class GemmCase(namedtuple("GemmCase", "name form variant M N K epis slices win patch grid order", defaults=(1, None, None, None, None))):
+class GemmCase(namedtuple("GemmCase", "name form variant M N K epis slices win patch grid order lo_mode", defaults=(1, None, None, None, None, 0))):
     """One launch shape of test_gemm_forms_gpu.py: the form (capi.GEMM_FORMS) and split-K slices it must take at 256 compute units under
     `variant` (mudpt_gemm's knob), the epilogues it runs, the (pad, off) of the operand windows it overrides (GEMM_WINDOWS), (P, L) of the
-    patch epilogue, and -- persistent cases -- the grid and tile-order regime it is there for."""
+    patch epilogue, -- persistent cases -- the grid and tile-order regime it is there for, and the form of the split A operand (GEMM_SPLIT_CASES)."""
     __slots__ = ()
 
 
 # (pad, off) in elements, multiples of 16: an operand is the window [rows, width] at column off of a buffer whose row stride is width + pad.
 # Different for every operand, so that a stride or base taken from the wrong one shows.
-GEMM_WINDOWS = {"A": (48, 16), "B": (32, 32), "out0": (48, 32), "out1": (32, 16), "aux": (64, 48)}
+GEMM_WINDOWS = {"A": (48, 16), "B": (32, 32), "out0": (48, 32), "out1": (32, 16), "aux": (64, 48),
+                # the low buffers of a split launch keep the BYTE row stride of their counterpart (A, B, out1): the same pad, another offset
+                "A_lo": (48, 32), "B8": (32, 16), "out1_lo": (32, 32)}
 GEMM_GUARD_ROWS = 32  # rows of NaN (operands) / sentinel (outputs) before and after every window
 _F32, _ST, _RES, _PATCH, _SPLIT = 5, 0, 2, 4, 0x10000  # epilogues (capi.EPI_*) and mudpt_gemm's "split K allowed" bit
 
@@ -352,6 +383,64 @@ GEMM_GELU_CASES = ("t64_k64", "t64deep_k128", "ring4_v6_k64", "t128_v5_k64", "t2
 GEMM_REFUSAL_CASES = _cases("pp_size_ldo0_mod8", "T64x64", 0, 8003, 1008, (64,), (_F32, _ST), win={"out0": (4, 0)})
 
 
+# ---- split-operand cases of test_gemm_split_forms_gpu.py: the second pass (common.h LoMode 1: T remainders against the same B; 2: e4m3
+# remainders against B8) in every form a split operand can take.  K per lo_mode: the e4m3 pass needs K % 128 == 0 ----
+GEMM_SPLIT_FORMS = ("PP", "T256x256", "T128x256", "T256x128", "T64x64", "T128x64_RING4", "T128x128")  # never T64x64_K128 or split K
+GEMM_SPLIT_B8_SCALE = 137     # E8M0 2^10 on the weights x the kernel's 2^-12 on the activations: the e4m3 pass adds (A_lo . B8^T) / 4, exactly
+GEMM_SPLIT_B8_SCALE_ONE = 139  # net factor 1
+
+
+def _split_cases(stem, form, variant, M, N, Ks16, Ks8, epis, **kw):
+    return [GemmCase(f"{stem}_lo{lo}_k{K}", form, variant, M, N, K, epis, lo_mode=lo, **kw) for lo, Ks in ((1, Ks16), (2, Ks8)) for K in Ks]
+
+
+GEMM_SPLIT_CASES = (
+    _split_cases("t64", "T64x64", 0, 131, 80, (64, 192), (128, 384), (_F32, _ST, _RES))
+    + _split_cases("t64_v10", "T64x64", 10, 131, 80, (128,), (128,), (_F32, _ST))  # K = 128 must not go 128-deep with a split operand
+    # the ring: nt = K-tiles of both passes below / at / above its prologue depth of three (lo_mode 1: 2, 4, 6, 8; lo_mode 2: 3, 6, 9)
+    + _split_cases("ring4_v6", "T128x64_RING4", 6, 259, 80, (64, 128, 192, 256), (128, 256, 384), (_F32, _ST, _RES))
+    + _split_cases("t128_v5", "T128x128", 5, 259, 144, (64, 192), (128, 384), (_F32, _ST, _RES))
+    + _split_cases("t128", "T128x128", 0, 4100, 1296, (640,), (640,), (_F32, _RES))  # K > 512, or small_tiles takes the shape
+    + _split_cases("t256_res", "T256x256", 0, 16141, 1040, (64, 192), (128, 384), (_RES,))
+    + _split_cases("t256_v1", "T256x256", 1, 16141, 1040, (64, 192), (128, 384), (_F32, _ST))
+    + _split_cases("t128x256_v2", "T128x256", 2, 16141, 1040, (192,), (128,), (_F32, _ST, _RES))
+    + _split_cases("t256x128_v4", "T256x128", 4, 16141, 1040, (192,), (128,), (_F32, _ST, _RES))
+    # the persistent kernel, at the shapes and (grid, order) regimes of the pp_* cases above.  K-steps per tile: lo_mode 1 2 K / 64 (always
+    # even; K = 128 on one shape so that the first pass ends on either LDS stage), lo_mode 2 K / 64 + K / 128 = 3, 6, 15
+    + _split_cases("pp_all_split", "PP", 0, 8003, 1008, (64, 192), (128, 256, 640), (_F32, _ST), grid="all_split", order="one_group")
+    + _split_cases("pp_one_ntn5", "PP", 0, 8205, 1040, (64, 128, 192), (128, 256, 640), (_F32, _ST), grid="one_per_workgroup", order="one_group")
+    + _split_cases("pp_half_tail", "PP", 0, 13069, 1296, (64, 192), (128, 256, 640), (_F32, _ST), grid="half_tile_tail", order="full_groups")
+    + _split_cases("pp_whole_tail", "PP", 0, 19469, 1040, (64, 192), (128, 256, 640), (_F32, _ST), grid="whole_tile_tail", order="one_group")
+    + _split_cases("pp_leftover_ntn16", "PP", 0, 2061, 4096, (64, 192), (128, 256, 640), (_F32, _ST), grid="one_per_workgroup", order="leftover_group")
+)
+# one case per kernel family that runs again with GEMM_SPLIT_B8_SCALE_ONE
+GEMM_SPLIT_SCALE_CASES = ("t64_lo2_k128", "pp_one_ntn5_lo2_k128")
+# the patch-embed epilogue on a split operand (mudpt_gemm_split_patch): the 256 x 256 tile the benchmark batch runs, and the small tile
+GEMM_SPLIT_PATCH_CASES = (
+    _split_cases("t256_patch", "T256x256", 0, 16170, 1040, (64, 192), (128, 384), (_PATCH,), patch=(98, 103))
+    + _split_cases("t64_patch", "T64x64", 0, 392, 80, (64,), (128,), (_PATCH,), patch=(98, 103))
+)
+# QuickGELU epilogue with a split input and a split output: (form, variant, M, N, K for lo_mode 0 | 1, K for lo_mode 2, all mode pairs?) --
+# one ragged case per form; lo_mode 0 needs K % 128 != 0 on the small tile (or it goes 128-deep)
+GEMM_SPLIT_GELU_CASES = (
+    GemmCase("t64", "T64x64", 0, 131, 80, (64, 128), (1,)), GemmCase("ring4_v6", "T128x64_RING4", 6, 259, 80, (64, 128), (1,)),
+    GemmCase("t128_v5", "T128x128", 5, 259, 144, (64, 128), (1,)), GemmCase("t256_v1", "T256x256", 1, 16141, 1040, (64, 128), (1,)),
+    GemmCase("t128x256_v2", "T128x256", 2, 16141, 1040, (192, 128), (1,)), GemmCase("t256x128_v4", "T256x128", 4, 16141, 1040, (192, 128), (1,)),
+    GemmCase("pp_all_split", "PP", 0, 8003, 1008, (64, 128), (1,), grid="all_split", order="one_group"),
+)
+GEMM_SPLIT_GELU_ALL_PAIRS = ("t64", "pp_all_split")  # (lo_mode, out1_lo_mode) in {0, 1, 2} x {1, 2} there; {1, 2} x {1, 2} on the rest
+
+
+def gemm_split_gelu_case(case, lo_mode):
+    """The launch shape of a GEMM_SPLIT_GELU_CASES entry under the input form lo_mode: its K is (K for lo_mode 0 | 1, K for lo_mode 2)."""
+    return case._replace(K=case.K[1 if lo_mode == 2 else 0], lo_mode=lo_mode)
+
+
+def pp_ksteps(case):
+    """K-steps per tile of gemm_pp_kernel: K / 64 of the first pass, then K / 64 (lo_mode 1) or K / 128 (lo_mode 2) of the second."""
+    return case.K // 64 + {0: 0, 1: case.K // 64, 2: case.K // 128}[case.lo_mode]
+
+
 def gemm_windows(case, windowed=True):
     return dict(GEMM_WINDOWS, **(case.win or {})) if windowed else dict.fromkeys(GEMM_WINDOWS, (0, 0))
 
@@ -359,7 +448,7 @@ def gemm_windows(case, windowed=True):
 def gemm_form_args(case, epi, ncu, windowed=True):
     """mudpt_gemm_form's arguments for epilogue `epi` of a case, with the output strides of its windows."""
     w = gemm_windows(case, windowed)
-    return (epi, case.M, case.N, case.K, case.N + w["out0"][0], case.N + w["out1"][0], case.N + w["aux"][0], 0, case.variant, ncu)
+    return (epi, case.M, case.N, case.K, case.N + w["out0"][0], case.N + w["out1"][0], case.N + w["aux"][0], case.lo_mode, case.variant, ncu)
 
 
 # Mirrors of launch_pp's grid arithmetic and of gemm_pp_kernel's tile order (gemm_pp.hip); GN lives in device code.

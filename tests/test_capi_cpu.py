@@ -292,6 +292,20 @@ def test_gemm_form_table(lib):
     assert lib.mudpt_gemm_form(0, 64, 64, 64, 64, 0, 0, 0, 0, 256) == (capi.GEMM_FORMS.index("T64x64") | 1 << 8)
     for args, _ in GEMM_FORM_REFUSED:
         assert lib.mudpt_gemm_form(*args) == -1, args
+    # a split operand never takes the 128-deep small tile or a split-K form: over the M, N, K of the table, with scratch, under the knobs that lead there
+    never = {capi.GEMM_FORMS.index(f) for f in ("T64x64_K128", "SPLITK_K128", "SPLITK_K64")}
+    shapes = sorted({args[1:4] for args, _ in GEMM_FORM_TABLE})
+    plain = set()
+    for M, N, K in shapes:
+        for knob in (0, 10, 12):
+            for epi in (0, 5):
+                plain.add(lib.mudpt_gemm_form(epi, M, N, K, N, N, N, 0, S16 | knob, 256) & 0xff)
+                for lo_mode in (1, 2):
+                    if lo_mode == 2 and K % 128:
+                        continue
+                    got = lib.mudpt_gemm_form(epi, M, N, K, N, N, N, lo_mode, S16 | knob, 256)
+                    assert got >= 0 and got & 0xff not in never and got >> 8 == 1, (epi, M, N, K, lo_mode, knob, got)
+    assert never <= plain  # the sweep does reach all three without a split operand
 
 
 def test_gemm_gpu_cases_reach_every_form(lib):
@@ -317,3 +331,52 @@ def test_gemm_gpu_cases_reach_every_form(lib):
     assert {c.order for c in pp} == {"one_group", "full_groups", "leftover_group"}
     # K = 64 (one K-step per tile: the prefetch crosses a tile boundary every step) and 128 run on the persistent kernel too
     assert {64, 128} <= {c.K for c in pp}
+
+
+def test_gemm_split_gpu_cases_reach_every_form(lib):
+    """The split-operand cases tests/test_gemm_split_forms_gpu.py runs reach, at 256 compute units, exactly the seven forms a split operand can
+    take, each case with the form it names, under both forms of the low half; the persistent cases reach every grid regime of launch_pp and
+    every tile-order regime under each lo_mode, and the K-step counts per tile the second pass brings: lo_mode 1 doubles the count (always
+    even; the first pass ends on either LDS stage), lo_mode 2 gives K / 64 + K / 128, odd and even."""
+    from tests import helpers as H
+    form = lambda c, epi: lib.mudpt_gemm_form(*H.gemm_form_args(c, epi, 256))  # noqa: E731
+    reached = {1: set(), 2: set()}
+    for c in H.GEMM_SPLIT_CASES + H.GEMM_SPLIT_PATCH_CASES:
+        assert c.lo_mode in (1, 2) and (c.lo_mode == 1 or c.K % 128 == 0), c.name
+        for epi in c.epis:
+            got = form(c, epi)
+            assert got == (capi.GEMM_FORMS.index(c.form) | 1 << 8), (c.name, epi, got)
+            if c in H.GEMM_SPLIT_CASES:
+                reached[c.lo_mode].add(c.form)
+    assert reached[1] == reached[2] == set(H.GEMM_SPLIT_FORMS) == set(capi.GEMM_FORMS) - {"T64x64_K128", "SPLITK_K128", "SPLITK_K64"}
+    names = {c.name for c in H.GEMM_SPLIT_CASES}
+    assert len(names) == len(H.GEMM_SPLIT_CASES) and set(H.GEMM_SPLIT_SCALE_CASES) <= names
+    assert {c.form == "PP" for c in H.GEMM_SPLIT_CASES if c.name in H.GEMM_SPLIT_SCALE_CASES} == {True, False}
+    # the ring's K-tiles of both passes: below, at and above its prologue depth of 3
+    ring = {lo: sorted(H.pp_ksteps(c) for c in H.GEMM_SPLIT_CASES if c.form == "T128x64_RING4" and c.lo_mode == lo) for lo in (1, 2)}
+    assert ring == {1: [2, 4, 6, 8], 2: [3, 6, 9]}
+    for lo in (1, 2):
+        pp = [c for c in H.GEMM_SPLIT_CASES if c.form == "PP" and c.lo_mode == lo]
+        for c in pp:
+            assert (H.pp_grid_regime(c.M, c.N, 256), H.pp_order_regime(c.N)) == (c.grid, c.order), c.name
+        assert {c.grid for c in pp} == {"all_split", "one_per_workgroup", "half_tile_tail", "whole_tile_tail"}
+        assert {c.order for c in pp} == {"one_group", "full_groups", "leftover_group"}
+        steps = {H.pp_ksteps(c) for c in pp}
+        if lo == 1:
+            assert steps == {2, 4, 6} and {c.K // 64 % 2 for c in pp} == {0, 1}
+        else:
+            assert steps == {3, 6, 15} and {n % 2 for n in steps} == {0, 1}
+        # every regime sees both parities where the form has both
+        for grid in ("all_split", "one_per_workgroup", "half_tile_tail", "whole_tile_tail"):
+            assert {H.pp_ksteps(c) % 2 for c in pp if c.grid == grid} == ({0} if lo == 1 else {0, 1}), (lo, grid)
+    # the QuickGELU cases: one per form, each form under every input form it runs with (epilogue 1 reads ldo1)
+    assert [c.form for c in H.GEMM_SPLIT_GELU_CASES] == ["T64x64", "T128x64_RING4", "T128x128", "T256x256", "T128x256", "T256x128", "PP"]
+    for c in H.GEMM_SPLIT_GELU_CASES:
+        for lo in ((0, 1, 2) if c.name in H.GEMM_SPLIT_GELU_ALL_PAIRS else (1, 2)):
+            k = H.gemm_split_gelu_case(c, lo)
+            for windowed in (True, False):
+                got = lib.mudpt_gemm_form(*H.gemm_form_args(k, 1, 256, windowed))
+                assert got == (capi.GEMM_FORMS.index(c.form) | 1 << 8), (c.name, lo, windowed, got)
+    # the patch cases: both tiles under both forms, whole images
+    assert {(c.form, c.lo_mode) for c in H.GEMM_SPLIT_PATCH_CASES} == {(f, lo) for f in ("T256x256", "T64x64") for lo in (1, 2)}
+    assert all(c.M % c.patch[0] == 0 for c in H.GEMM_SPLIT_PATCH_CASES)

@@ -6,7 +6,7 @@ import torch
 
 from oracle import mudpt_oracle as O
 from tests.helpers import (ATTN_CASES, ATTN_LONG_FWD_CASES, ATTN_LONG_FWD_FLAGS, ATTN_SEL_CASES, ATTN_SEL_COMPARE, ATTN_WINDOW_CASES,
-                           ATTN_WINDOW_FULL_FLAG, SENT, P, attn64, attn_bwd_form_flags, attn_window_flags, e4m3_spacing, ok, refused)
+                           ATTN_WINDOW_FULL_FLAG, SENT, P, attn64, attn_bwd_form_flags, attn_window_flags, check_split_pair, ok, refused)
 
 pytestmark = pytest.mark.gpu
 
@@ -745,32 +745,6 @@ def test_layernorm_bwd_token_index_modes(lib, dtype, mode, total, R, d):
     rest = torch.ones(total, dtype=torch.bool)
     rest[idx] = False
     assert (got[rest] == SENT).all() and (got_lp[rest] == SENT).all()
-
-
-def check_split_pair(dtype, hi, lo16, lo8, ref):
-    """hi [rows, Hd] in T, lo16 the remainder in T, lo8 its e4m3 codes (uint8), ref float64.  hi + lo against the definition; |lo| <= half an
-    ulp of hi (hi is the T rounding of the kernel's fp32 value, as test_exact_attention_forward asserts); the e4m3 form decodes to the same
-    remainder: e4m3(r 2^12) is within half an e4m3 step of r 2^12 and T(r) within EPS |r| of r, so the two forms differ by at most that sum.
-    The bounds above hold for `hi` alone, so two more pin lo itself (both follow from lo = v - T(v) for the kernel's fp32 value v = ref + err,
-    over N >= 768 elements of continuous data):
-      * lo / ulp is uniform on [-1/2, 1/2]: its mean square is 1/12 (sampling noise ~1 / sqrt(N) of that); a lo that is zero, halved, doubled
-        or saturated misses [1/16, 1/9];
-      * ref - hi = lo + (ref - v), and the kernel's error ref - v does not depend on the rounding remainder, so <lo, ref - hi> / <lo, lo> is
-        1 +- rms(err) / (rms(lo) sqrt(N)): with the error of the order of the remainder (the probabilities enter P.V rounded to T) that is a
-        few per cent at the smallest N.  A sign-flipped lo gives -1, a lo unrelated to the value gives 0: [0.5, 1.5] is asserted."""
-    mant, tiny = (7, 2.0 ** -126) if dtype == "bf16" else (10, 2.0 ** -14)
-    torch.testing.assert_close(hi.double() + lo16.double(), ref, atol=6 * EPS[dtype], rtol=6 * EPS[dtype])
-    ulp = torch.ldexp(torch.ones(()), torch.frexp(hi.float().abs().clamp_min(tiny)).exponent - 1 - mant)
-    assert (lo16.float().abs() <= 0.5 * ulp * (1 + 1e-3)).all()
-    msq = (lo16.double() / ulp.double()).pow(2).mean().item()
-    proj = ((lo16.double() * (ref - hi.double())).sum() / lo16.double().pow(2).sum()).item()
-    print(f"split pair {dtype}: N {hi.numel()}, mean (lo / ulp)^2 {msq:.4f} (1/12 = 0.0833), <lo, ref - hi> / <lo, lo> {proj:.3f}")
-    assert 1 / 16 <= msq <= 1 / 9 and 0.5 <= proj <= 1.5
-    r = lo16.double()
-    assert (r.abs() * 4096 * (1 + 2 * EPS[dtype])).max().item() < 448  # no saturation on these inputs
-    dec = lo8.contiguous().view(torch.float8_e4m3fn).double() / 4096.0
-    bound = 0.5 * e4m3_spacing(r * 4096 * (1 + 2 * EPS[dtype])) / 4096.0 + 2 * EPS[dtype] * r.abs() + 2.0 ** -25  # (2^-25: half a subnormal fp16 step)
-    assert ((dec - r).abs() <= bound).all()
 
 
 def run_attn_split(lib, dt, tt, qc, B, L, H, flags, ld, pass_ld, lo_mode, single=None):
