@@ -258,10 +258,19 @@ int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch, float* hos
  *   last_single        1 (0 exact)     0 = the last block's attention on all rows instead of the single-query form
  *   attn_two_kernels   0               1 = attention backward as the dQ + dK/dV kernel pair
  *   attn_fused_w1      0               1 = fused attention backward with two 16-row blocks per wave
- *   lp_grad            bf16: 1, else 0 gradient stream of the residual in T (bf16 mode: 0 also returns the forward's update stream to fp32;
+ *   lp_grad            fp16: 0, else 1 gradient stream of the residual in T (bf16 mode: 0 also returns the forward's update stream to fp32;
  *                                      fp16 mode: 1 trades 30 % more gradient error for 0.9 ms)
  *   lp_upd             bf16: 1, else 0 the forward's update stream in T (fp16 mode: would cost 2e-4 of logit error)
+ *   gelu_q8            bf16: 1, else 0 c_fc keeps QuickGELU'(u) in 8 bits for the backward instead of u in T (2.4e-3 on a factor in [-0.1, 1.1]:
+ *                                      bf16's own grade; towers without split operands).  Between steps only: the backward decodes what the
+ *                                      forward stored
  *   txt_split          fp16 / fp32: 1  0 = no split operands in the text tower (fp16 mode; only before the first mudpt_set_weight)
+ *   txt_lo             fp16 / fp32: 1  form of the text tower's low halves: 0 = none, 1 = fp16 pairs (txt_split is its older name)  } MUDPT_F32 above
+ *   vis_lo             fp32: 2, else 0 ... of the vision tower's: 2 = e4m3 remainders on the fp8 matrix pipe (parity mode only)         } and DESIGN.md 2;
+ *   vis_sites          31              bit mask of the sites that split: 1 in_proj, 2 out_proj, 4 c_fc, 8 c_proj, 16 patch embed       } effective from
+ *   txt_sites          31              ... of the text tower                                                                           } the next forward
+ *   vis_exact_attn     0               1 = the vision tower's attention forward in fp32 (parity mode only)                             }
+ *   txt_exact_attn     fp32: 1, else 0 ... the text tower's (parity mode only)                                                         }
  *   txt_trim           1               0 = run the text tower on all ctx_len positions        } read by the next
  *   txt_buckets        3               maximum number of length buckets of the class prompts  } mudpt_set_class_prompts,
  *   txt_bucket_cost    1024            token rows one more bucket must save                   } which must follow

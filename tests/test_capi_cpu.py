@@ -113,6 +113,57 @@ def test_every_launcher_is_called_from_a_test_export():
     assert all(len(reason) > 20 for reason in LAUNCHERS_WITHOUT_AN_EXPORT.values())
 
 
+def model_set_names(source):
+    """The knob names mudpt_model_set compares its argument against: `strcmp(name, "x")` as it stands, `strcmp(k, "x")` behind the tower
+    prefix ("vis_" / "txt_"; only "txt_" where the comparison is guarded by `t == &m->txt`)."""
+    import re
+    body = source[source.index('extern "C" int mudpt_model_set('):]
+    body = re.sub(r"//[^\n]*", "", body[:body.index("unknown knob")])
+    names = set(re.findall(r'strcmp\(name, "(\w+)"\)', body))
+    for txt_only, k in re.findall(r'(t == &m->txt && )?!strcmp\(k, "(\w+)"\)', body):
+        names |= {"txt_" + k} | (set() if txt_only else {"vis_" + k})
+    return names
+
+
+def header_knob_table(header):
+    """The names in the first column of the knob table above mudpt_model_set's declaration."""
+    import re
+    table = header[header.index(" *   knob               default"):header.index("int mudpt_model_set(")]
+    return set(re.findall(r"^ \*   ([a-z][a-z0-9_]*) ", table, flags=re.M)) - {"knob"}
+
+
+def test_every_model_knob_is_documented_and_held_by_a_test():
+    """Every name mudpt_model_set accepts has a row in MODEL_KNOBS (tests/helpers.py) that names the test holding it, or says why none does,
+    and a row in the knob table of include/mudpt.h; neither table lists a name the library does not accept.  A new knob fails here until
+    it has its settings, its test and its line of documentation."""
+    from tests.helpers import KNOB_DEFAULTS, MODEL_KNOBS, knob_settings
+    root = os.path.dirname(capi.HERE)
+    accepted = model_set_names(open(os.path.join(root, "mudpt_amd", "csrc", "model.cpp")).read())
+    assert len(accepted) >= 22 and {"gemm_variant", "gelu_q8", "txt_split", "vis_lo", "txt_exact_attn"} <= accepted, sorted(accepted)
+    assert "vis_split" not in accepted  # "split" is the text tower's older name for "lo" alone
+    documented = header_knob_table(open(capi.HEADER_PATH).read())
+    assert not accepted - set(MODEL_KNOBS), f"knobs without a row in MODEL_KNOBS: {sorted(accepted - set(MODEL_KNOBS))}"
+    assert not set(MODEL_KNOBS) - accepted, f"MODEL_KNOBS rows the library does not accept: {sorted(set(MODEL_KNOBS) - accepted)}"
+    assert not accepted - documented, f"knobs missing from the table in include/mudpt.h: {sorted(accepted - documented)}"
+    assert not documented - accepted, f"rows of the header's table the library does not accept: {sorted(documented - accepted)}"
+    for name, (settings, held_by, why_not) in MODEL_KNOBS.items():
+        assert bool(held_by) != bool(why_not) and (held_by or len(why_not) > 20), name
+        if held_by:  # the test it names exists
+            path, _, test = held_by.partition("::")
+            assert f"\ndef {test}(" in open(os.path.join(root, path)).read(), (name, held_by)
+        for s in settings:  # a setting moves its own knob off the dtype's default, and whatever it moves can be set back
+            assert s.sets[0][0] == name and (s.construct or all(k in KNOB_DEFAULTS[s.dtype] for k, _ in s.sets)), s
+            assert s.sets[0][1] != KNOB_DEFAULTS[s.dtype].get(name, 1 if name == "txt_split" else None), s
+            assert "test_knobs_gpu.py" in held_by, (name, "settings are run by test_knobs_gpu.py")
+    # the settings the GPU module runs: both attention forms, the window, three kernel choices and the streams in both dtypes; the fp16 text tower's split
+    assert {s.sets[0] for s in knob_settings(dtype="bf16")} == {("gemm_variant", 12), ("gemm_variant", 1), ("gemm_variant", 10), ("attn_window", 0),
+                                                                ("attn_two_kernels", 1), ("attn_fused_w1", 1), ("lp_grad", 0), ("lp_upd", 0), ("gelu_q8", 0)}
+    assert {s.sets[0] for s in knob_settings(dtype="fp16")} == {("gemm_variant", 12), ("gemm_variant", 1), ("gemm_variant", 10), ("attn_window", 0),
+                                                                ("attn_two_kernels", 1), ("attn_fused_w1", 1), ("lp_grad", 1), ("lp_upd", 1), ("gelu_q8", 1),
+                                                                ("txt_split", 0), ("txt_lo", 0), ("txt_sites", 5)}
+    assert all(s.lowers == (s.dtype == "fp16" and s.sets[0][0] in ("lp_grad", "lp_upd", "gelu_q8", "txt_split", "txt_lo", "txt_sites")) for s in knob_settings())
+
+
 W = (1 << 8) | (4 << 20)  # the window form: 4 rows from row 1 on
 # (bwd, L, flags, sel) -> form of mudpt_attention_fwd / _bwd / _bwd_sel, as measured on the dispatch this table replaced
 ATTN_FORM_TABLE = [
