@@ -57,6 +57,15 @@
  *                                        all of it: every one is a function of the parameters alone.
  *   mudpt_forward_backward               trainers/uumudpt.py:295-297  forward, F.cross_entropy, backward w.r.t. all 40 tensors
  *   (mudpt_set_class_shard, mudpt_cp_* and mudpt_set_class_token_position refuse the variant.)
+ * A handle made by mudpt_create_frozen runs the zero-shot baselines (trainers/zsclip.py; lpclip/feat_extractor.py): CLIP as it was trained, nothing to learn:
+ *   mudpt_create_frozen / mudpt_set_weight   trainers/zsclip.py:10-29  load_clip_to_cpu: vanilla CLIP, both towers forward only (clip/model.py:443-496,825-838);
+ *                                        "token_embedding.weight" stays on the device
+ *   mudpt_set_text_tokens                trainers/zsclip.py:61-65,108-110  clip.tokenize(template.format(classname)) for every template and class;
+ *                                        clip/model.py:827,836  token_embedding(text) + positional_embedding, text.argmax(dim=-1)
+ *   mudpt_text_features                  trainers/zsclip.py:67-71 (one template: f / |f|), :107-117 (ensemble: normalise, mean over the templates, normalise)
+ *   mudpt_encode_image                   clip/model.py:822 encode_image, lpclip/feat_extractor.py:125  the raw visual(image) features
+ *   mudpt_forward / _ex                  trainers/zsclip.py:74-79  model_inference: logit_scale * normalise(image features) @ text_features.t()
+ *   (mudpt_param_count / _numel are 0; every training, class-prompt, class-shard and mudpt_cp_* entry point refuses the handle.)
  *
  * Conventions: every function returns 0 on success or a MUDPT_ERR_* code; mudpt_last_error() gives
  * the message of the calling thread's last failure.  No exceptions cross the ABI.  A model handle is
@@ -73,6 +82,8 @@
 extern "C" {
 #endif
 
+/* 7 still with mudpt_create_frozen, mudpt_set_text_tokens, mudpt_text_features and mudpt_encode_image: they are additions, no existing
+ * declaration, struct or constant changed, so every caller built against 7 runs unchanged -- the number moves when one would not. */
 #define MUDPT_ABI_VERSION 7
 
 #define MUDPT_OK 0
@@ -142,11 +153,20 @@ typedef struct mudpt_prompt_shape {
 } mudpt_prompt_shape;
 /* mudpt_create for every variant: prompts = NULL for MuDPT / CoCoOp / CoOp (then identical to mudpt_create), required for VPT / MPT. */
 int mudpt_create_ex(const mudpt_config* cfg, const mudpt_prompt_shape* prompts, mudpt_model** out);
+/* Frozen CLIP (trainers/zsclip.py): both towers vanilla and forward only, no trainable tensor.  cfg->variant, n_ctx and depth are not read;
+ * n_cls, max_batch, dtype (all three) and the shape fields are what they are for mudpt_create.  The handle takes mudpt_set_weight (and keeps
+ * "token_embedding.weight" on the device as fp32 [vocab, t_width], vocab = numel / t_width), mudpt_set_text_tokens, mudpt_text_features,
+ * mudpt_encode_image, mudpt_forward / _ex (MUDPT_FWD_REUSE_TEXT accepted, no effect: the text features are always kept), mudpt_text_layout,
+ * mudpt_model_set, mudpt_debug_read ("image_features", "text_features" = the ensembled, normalised table, "text_launches") and mudpt_destroy.
+ * mudpt_param_count / _numel return 0; mudpt_bind_params, mudpt_forward_backward, mudpt_sgd_step, mudpt_set_class_prompts,
+ * mudpt_set_class_token_position, mudpt_set_class_shard, mudpt_cp_* and mudpt_allreduce_grads return MUDPT_ERR_ARG ("... frozen ..."). */
+int mudpt_create_frozen(const mudpt_config* cfg, mudpt_model** out);
 int mudpt_destroy(mudpt_model* m);
 
 /* Frozen weight by OpenAI CLIP state-dict key ("visual.transformer.resblocks.0.attn.in_proj_weight", ...),
  * fp32 HOST data in the checkpoint's own layout; the library converts / transposes to its device layout.
- * Keys the path does not use ("token_embedding.weight", ...) are accepted and ignored. */
+ * Keys the path does not use ("token_embedding.weight", ...) are accepted and ignored; a frozen handle (mudpt_create_frozen) keeps
+ * "token_embedding.weight". */
 int mudpt_set_weight(mudpt_model* m, const char* key, const float* host_data, size_t numel);
 
 /* token_embedding(tokenized "<ctx words> <classname>.") [n_cls, ctx_len, t_width] fp32 HOST and the EOT
@@ -154,6 +174,23 @@ int mudpt_set_weight(mudpt_model* m, const char* key, const float* host_data, si
  * positions 0..max(eot_index) only: under the causal mask (clip/model.py:407-413) later positions reach neither the EOT
  * feature (trainers/mudpt.py:154) nor any gradient. */
 int mudpt_set_class_prompts(mudpt_model* m, const float* embedding, const int32_t* eot_index);
+/* Frozen handles only: the class prompts as token ids, tokens [n_templates, n_cls, ctx_len] int32 HOST = clip.tokenize(template t formatted
+ * with class c); the EOT position of a prompt is the first index of its row's maximum (text.argmax(dim=-1), clip/model.py:836).  Every
+ * template gets its own text layout by the rules of mudpt_set_class_prompts (trim to its longest EOT, length buckets; the knobs txt_trim,
+ * txt_buckets, txt_bucket_cost are read here) and two int32 device tables with the token id and the position of every packed token row; the
+ * embedding is looked up on the device.  Activations are sized for the largest template.  The text features -- normalise(f) for one
+ * template, normalise(mean_t normalise(f_t)) for more, templates in ascending order (bit-reproducible) -- are computed at the next
+ * mudpt_forward / _ex / mudpt_text_features and kept until the next mudpt_set_weight or mudpt_set_text_tokens.  MUDPT_ERR_ARG before any GPU
+ * call: a null pointer, n_templates < 1, an id outside [0, vocab), not a frozen handle; MUDPT_ERR_STATE: "token_embedding.weight" or
+ * "positional_embedding" not set yet.  mudpt_text_layout then reports the token rows summed over the templates, the largest bucket count
+ * of a template and the longest kept length. */
+int mudpt_set_text_tokens(mudpt_model* m, const int32_t* tokens, int32_t n_templates);
+/* Frozen handles only: copies the [n_cls, embed_dim] text features (fp32, rows of norm 1) to feat_dev, computing them first if a weight or
+ * the tokens changed since; asynchronous on `stream`. */
+int mudpt_text_features(mudpt_model* m, float* feat_dev, void* stream);
+/* Frozen handles only: features_dev [batch, embed_dim] fp32 = visual(image), RAW (not normalised), for images_dev [batch, 3, S, S] fp32.
+ * Needs the weights only, not the tokens. */
+int mudpt_encode_image(mudpt_model* m, const float* images_dev, int32_t batch, float* features_dev, void* stream);
 /* CoOp handles only (any other handle: MUDPT_ERR_ARG), before mudpt_set_class_prompts.  position = MUDPT_CLASS_TOKEN_*; name_lens [n_cls]
  * HOST = len(_tokenizer.encode(name)) of every class (trainers/coop.py:80), may be NULL for MUDPT_CLASS_TOKEN_END.  mudpt_set_class_prompts
  * still receives token_embedding("<X ... X> <name>.") in tokenized order and reorders the rows itself; it refuses a class unless
@@ -496,6 +533,15 @@ int mudpt_cocoop_prompts(float* x0, const float* emb_pos, const float* ctx, cons
                          int32_t d, int32_t n, void* stream);
 int mudpt_coop_splice(float* x, const float* ctx, const float* tpos, const int32_t* rows, const int32_t* pos, int32_t C, int32_t n, int32_t d,
                       int32_t csc, void* stream);
+/* Zero-shot CLIP's two kernels (mudpt_amd/csrc/zeroshot.hip).  Refused on the host: a null pointer, a size < 1, d (e) % 4 != 0.
+ *   embed_tokens      out[r, :] = table[tokens_dev[r], :] + pos[positions_dev[r], :], r < rows, d fp32 per row, one add: bit-exact.  The ids
+ *                     are DEVICE data the export cannot read: an id outside [0, vocab) -- or a position outside pos -- READS OUT OF BOUNDS;
+ *                     checking them is the caller's job (mudpt_set_text_tokens checks its own on the host)
+ *   feature_ensemble  one call per template in ascending order over f, acc, out [C, e] (three different tables): v = f / |f| per row; acc = v if
+ *                     `first`, else acc + v; if `last`, out = normalise(acc / n_templates).  n_templates = 1 (first and last): out = v */
+int mudpt_embed_tokens(const float* table, int32_t vocab, const int32_t* tokens_dev, const int32_t* positions_dev, const float* pos, float* out,
+                       int32_t rows, int32_t d, void* stream);
+int mudpt_feature_ensemble(const float* f, float* acc, float* out, int32_t C, int32_t e, int32_t first, int32_t last, int32_t n_templates, void* stream);
 /* UMuDPT's prompt generator in fp32 (mudpt_amd/csrc/promptgen.hip), kernel by kernel:
  *   layernorm_bwd_affine  dx = (dres +) LN'(dy) and dgamma[j] (+)= sum_r dy[r, j] xhat[r, j], dbeta[j] (+)= sum_r dy[r, j] in row order (two runs
  *                         agree bit for bit); x / mean / rstd as mudpt_layernorm_fwd with out_f32 left them

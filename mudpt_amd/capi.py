@@ -44,7 +44,11 @@ SIGNATURES = {
     "mudpt_last_error": (C.c_char_p, []),
     "mudpt_create": (_i32, [C.POINTER(Config), C.POINTER(_vp)]),
     "mudpt_create_ex": (_i32, [C.POINTER(Config), C.POINTER(PromptShape), C.POINTER(_vp)]),
+    "mudpt_create_frozen": (_i32, [C.POINTER(Config), C.POINTER(_vp)]),
     "mudpt_destroy": (_i32, [_vp]),
+    "mudpt_set_text_tokens": (_i32, [_vp, _vp, _i32]),
+    "mudpt_text_features": (_i32, [_vp, _vp, _vp]),
+    "mudpt_encode_image": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "mudpt_set_weight": (_i32, [_vp, C.c_char_p, _vp, _sz]),
     "mudpt_set_class_prompts": (_i32, [_vp, _vp, _vp]),
     "mudpt_set_class_token_position": (_i32, [_vp, _i32, _vp]),
@@ -118,6 +122,8 @@ SIGNATURES = {
     "mudpt_relu_bwd": (_i32, [_vp, _vp, _sz, _vp]),
     "mudpt_cocoop_prompts": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mudpt_coop_splice": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mudpt_embed_tokens": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mudpt_feature_ensemble": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mudpt_layernorm_bwd_affine": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mudpt_pg_attention_fwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mudpt_pg_attention_bwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -246,6 +246,13 @@ int launch_cocoop_dbias(int dtype, const float* dx, const void* dx_lp, float* db
 int launch_coop_splice(float* x, const float* ctx, const float* tpos, const int* rows, const int* pos, int C, int n, int d, bool csc, hipStream_t s);
 // shared: dctx[j] = scale * sum_c dx[rows[c n + j]] (fixed order, coop.hip); CSC: dctx[c][j] = scale * dx[rows[c n + j]]  (fp32 dx or its T copy)
 int launch_coop_dctx(int dtype, const float* dx, const void* dx_lp, const int* rows, float* dctx, int C, int n, int d, bool csc, float scale, hipStream_t s);
+// Zero-shot CLIP (trainers/zsclip.py, zeroshot.hip).  out[r, :] = table[tokens[r], :] + pos[positions[r], :] for `rows` packed token rows of d
+// fp32 (d % 4 == 0): token_embedding + positional_embedding of one prompt template from ids (clip/model.py:827), bit-exact.  tokens / positions
+// are DEVICE tables the launcher cannot read: an id outside [0, vocab) or a position outside pos reads out of bounds.
+int launch_embed_tokens(const float* table, int vocab, const int* tokens, const int* positions, const float* pos, float* out, int rows, int d, hipStream_t s);
+// Prompt ensembling (zsclip.py:107-115), one call per template t in ascending order: v = f / |f| per row; acc = v (first) or acc + v; on the
+// last call out = normalise(acc / n_templates) (one template: out = v).  f, acc, out [C, e] fp32, three different tables, e % 4 == 0.
+int launch_feature_ensemble(const float* f, float* acc, float* out, int C, int e, bool first, bool last, int n_templates, hipStream_t s);
 // y = x / ||x|| per row, inv = 1 / ||x||
 int launch_l2norm(const float* x, float* y, float* inv, int rows, int e, hipStream_t s);
 int launch_relu(float* y, size_t n, hipStream_t s);

@@ -237,6 +237,20 @@ struct mudpt_model {
     bool uumudpt = false;
     float *pg2_T = nullptr, *pg2_ws = nullptr;
     PgWork pg2_w;
+    // Frozen CLIP (mudpt_create_frozen; trainers/zsclip.py): no trainable, both towers vanilla and forward only.  The class prompts arrive as token
+    // ids (mudpt_set_text_tokens), one set per prompt template; every template has its own packed text layout and two device tables (token id,
+    // position) per token row, and the text tower runs once per template from the device-resident embedding table.  txt_n holds the ensembled,
+    // normalised features (text_valid), the only thing a forward needs from the text side
+    bool frozen = false;
+    float* tok_table = nullptr; int vocab = 0;  // "token_embedding.weight" fp32 [vocab, t_width]
+    struct Template {
+        std::vector<Tower::Seg> segs;  // empty = one bucket of n_cls x L
+        int rows = 0, L = 0;           // packed token rows, longest kept length
+        const int *tok = nullptr, *pos = nullptr, *eot_rows = nullptr, *eot_local = nullptr, *perm = nullptr;  // device, inside tmpl_tables
+    };
+    std::vector<Template> tmpl;
+    int* tmpl_tables = nullptr;  // one allocation behind every Template's tables
+    float* ens_acc = nullptr;    // [n_cls, e] running sum of the normalised per-template features
     long text_launches = 0;  // text-tower passes + text-side head launches (mudpt_debug_read "text_launches")
     float *mn_hid = nullptr, *mn_bias = nullptr, *mn_dbias = nullptr, *mn_dhid = nullptr;  // [B, hid], [B, dt], [B, dt], [B, hid]
     float loss_scale = 128.f;  // static, power of two; see mudpt_forward_backward
@@ -563,7 +577,7 @@ extern "C" int mudpt_abi_version(void) { return MUDPT_ABI_VERSION; }
 extern "C" const char* mudpt_last_error(void) { return get_error(); }
 
 // Fills a fresh model; on an error the caller (create_model) destroys it
-static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model* m) {
+static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model* m, bool frozen) {
     ARG_CHECK(c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F16 || c->dtype == MUDPT_F32, "create: dtype must be MUDPT_BF16, MUDPT_F16 or MUDPT_F32");
     ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_UUMUDPT, "create: unknown variant %d", c->variant);
     m->cocoop = c->variant == MUDPT_VARIANT_COCOOP;
@@ -572,9 +586,10 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     m->vpt = c->variant == MUDPT_VARIANT_VPT; m->mpt = c->variant == MUDPT_VARIANT_MPT; m->indep = m->vpt || m->mpt;
     m->uumudpt = c->variant == MUDPT_VARIANT_UUMUDPT;
     m->umudpt = c->variant == MUDPT_VARIANT_UMUDPT || m->uumudpt;
-    const bool vanilla = m->cocoop || m->coop;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
+    m->frozen = frozen;  // mudpt_create_frozen: the caller passed variant MuDPT with n_ctx 0, depth 1 -- no prompt row anywhere
+    const bool vanilla = m->cocoop || m->coop || frozen;  // the vanilla CLIP image encoder, forward only (no prompt rows, no deep prompts)
     ARG_CHECK(vanilla || m->indep || c->depth > 0, "PROMPT_DEPTH should be > 0");  // trainers/mudpt.py:52
-    ARG_CHECK((m->indep || c->n_ctx > 0) && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
+    ARG_CHECK((m->indep || frozen || c->n_ctx > 0) && c->n_cls > 0 && c->max_batch > 0, "create: n_ctx, n_cls, max_batch must be positive");
     ARG_CHECK(c->patch > 0 && c->image_size % c->patch == 0, "create: image_size %d / patch %d unsupported", c->image_size, c->patch);
     ARG_CHECK(c->v_width == c->v_heads * 64 && c->t_width == c->t_heads * 64, "create: head dim must be 64");
     ARG_CHECK(c->v_width % 64 == 0 && c->t_width % 64 == 0 && c->v_width <= 1024 && c->t_width <= 1024, "create: widths must be multiples of 64, <= 1024");
@@ -651,7 +666,8 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     ALLOC(m->cls_rows, B * 4); ALLOC(m->vprompt_rows, (size_t)B * nv * 4);
     ALLOC(m->tpos, (size_t)c->ctx_len * dt * 4); ALLOC(m->ln_fin_g, dt * 4); ALLOC(m->ln_fin_b, dt * 4);
     ALLOC(m->tproj, (size_t)dt * e * 4);
-    ALLOC(m->emb_pos, (size_t)C * c->ctx_len * dt * 4); ALLOC(m->eot_rows, TS * 4); ALLOC(m->eot_local, TS * 4); ALLOC(m->class_perm, C * 4);
+    ALLOC(m->emb_pos, frozen ? 0 : (size_t)C * c->ctx_len * dt * 4);  // frozen: embedded on the device, template by template
+    ALLOC(m->eot_rows, TS * 4); ALLOC(m->eot_local, TS * 4); ALLOC(m->class_perm, C * 4);
     ALLOC(m->txt_sorted, (size_t)C * e * 4); ALLOC(m->dtxt_sorted, (size_t)C * e * 4);
     ALLOC(m->t_ln, (size_t)TS * dt * 4); ALLOC(m->fin_mean, TS * 4); ALLOC(m->fin_rstd, TS * 4); ALLOC(m->dt_ln, (size_t)TS * dt * 4);
     const size_t dn = (size_t)(D1 > 0 ? D1 : 1) * n;
@@ -682,6 +698,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
         ALLOC(m->pg2_T, (size_t)D1 * n * e * 4); ALLOC(m->pg2_ws, ws * 4);
         m->pg2_w = pg_carve(m->pg2_ws, D1, n, dv, nullptr);
     }
+    if (frozen) ALLOC(m->ens_acc, (size_t)C * e * 4);
     ALLOC(m->gemm_scratch, mudpt_model::kScratchElems * 4); ALLOC(m->gemm_scratch2, mudpt_model::kScratchElems * 4);
     HIP_TRY(hipStreamCreateWithFlags(&m->s2, hipStreamNonBlocking));
     for (hipEvent_t* e : {&m->ev_fork, &m->ev_join, &m->ev_fork_b, &m->ev_join_b}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -699,7 +716,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     m->txt.tail_rows = m->eot_rows;
     HIP_TRY(hipMemcpy(m->vprompt_rows, pr.data(), pr.size() * 4, hipMemcpyHostToDevice));
 
-    build_trainables(m);
+    if (!frozen) build_trainables(m);  // a frozen handle has none: mudpt_param_count / _numel report 0
     ALLOC(m->momentum, m->total * 4);
 
     // frozen weights the path needs before it may run
@@ -709,12 +726,13 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
         m->missing.push_back(k);
     expect_block_keys(m, "visual.transformer", c->v_layers);
     expect_block_keys(m, "transformer", c->t_layers);
+    if (frozen) m->missing.push_back("token_embedding.weight");
     return MUDPT_OK;
 }
 
-static int create_model(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out) {
+static int create_model(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out, bool frozen = false) {
     mudpt_model* m = new mudpt_model();
-    if (int rc = create_impl(c, ps, m)) { mudpt_destroy(m); return rc; }
+    if (int rc = create_impl(c, ps, m, frozen)) { mudpt_destroy(m); return rc; }
     *out = m;
     return MUDPT_OK;
 }
@@ -735,8 +753,22 @@ extern "C" int mudpt_create_ex(const mudpt_config* c, const mudpt_prompt_shape* 
     return create_model(c, ps, out);
 }
 
+// Frozen CLIP (trainers/zsclip.py): variant, n_ctx and depth of the caller's config are not read -- the handle is built as a tower pair without
+// a single prompt row, which is what those three fields would describe
+extern "C" int mudpt_create_frozen(const mudpt_config* c, mudpt_model** out) {
+    ARG_CHECK(c && out, "create_frozen: null argument");
+    mudpt_config f = *c;
+    f.variant = MUDPT_VARIANT_MUDPT; f.n_ctx = 0; f.depth = 1;
+    return create_model(&f, nullptr, out, true);
+}
+
+// every entry point that trains, takes embedded class prompts or shards the classes
+#define NOT_FROZEN(m, what) ARG_CHECK(!((m) && (m)->frozen), "%s: a frozen handle (mudpt_create_frozen) has no parameters, class-prompt embeddings or class shards", what)
+
 extern "C" int mudpt_destroy(mudpt_model* m) {
     if (!m) return MUDPT_OK;
+    if (m->tok_table) (void)hipFree(m->tok_table);
+    if (m->tmpl_tables) (void)hipFree(m->tmpl_tables);
     for (void* p : m->allocs) (void)hipFree(p);
     for (Tower* t : {&m->vis, &m->txt})
         for (void* p : t->act_allocs) (void)hipFree(p);
@@ -843,17 +875,27 @@ extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* da
     else if (k == "visual.ln_post.weight") { EXPECT(dv); rc = upload_f32(m->ln_post_g, data, numel); }
     else if (k == "visual.ln_post.bias") { EXPECT(dv); rc = upload_f32(m->ln_post_b, data, numel); }
     else if (k == "visual.proj") { EXPECT(dv * e); rc = upload_f32(m->vproj, data, numel); }
-    else if (k == "positional_embedding") { EXPECT((size_t)c.ctx_len * dt); rc = upload_f32(m->tpos, data, numel); m->prompts_set = false; }
+    else if (k == "positional_embedding") { EXPECT((size_t)c.ctx_len * dt); rc = upload_f32(m->tpos, data, numel); if (!m->frozen) m->prompts_set = false; }  // frozen: added on the device at run time
     else if (k == "ln_final.weight") { EXPECT(dt); rc = upload_f32(m->ln_fin_g, data, numel); }
     else if (k == "ln_final.bias") { EXPECT(dt); rc = upload_f32(m->ln_fin_b, data, numel); }
     else if (k == "text_projection") { EXPECT(dt * e); rc = upload_f32(m->tproj, data, numel); }
     else if (k == "logit_scale") { EXPECT(1); m->scale = std::exp(data[0]); }  // trainers/mudpt.py:181
+    else if (k == "token_embedding.weight" && m->frozen) {  // kept on the device: mudpt_set_text_tokens' prompts are embedded there
+        ARG_CHECK(numel >= dt && numel % dt == 0 && numel / dt <= (size_t)0x7fffffff, "set_weight: %s expects [vocab, %zu], got %zu elements", key, dt, numel);
+        if ((int)(numel / dt) != m->vocab) {  // the ids mudpt_set_text_tokens checked belong to the previous table
+            if (m->tok_table) (void)hipFree(m->tok_table);
+            m->tok_table = nullptr; m->vocab = 0; m->prompts_set = false;
+            HIP_TRY(hipMalloc((void**)&m->tok_table, numel * 4));
+            m->vocab = (int)(numel / dt);
+        }
+        rc = upload_f32(m->tok_table, data, numel);
+    }
     else if (k == "token_embedding.weight" || k == "input_resolution" || k == "context_length" || k == "vocab_size") return MUDPT_OK;
     else { set_error("set_weight: unknown key '%s'", key); return MUDPT_ERR_ARG; }
 #undef EXPECT
     if (rc) return rc;
     m->any_weight_set = true;
-    if (m->vpt) m->text_valid = false;  // VPT keeps its text features across steps: any frozen weight may change them
+    if (m->vpt || m->frozen) m->text_valid = false;  // VPT / a frozen handle keep their text features across calls: any frozen weight may change them
     for (size_t i = 0; i < m->missing.size(); ++i)
         if (m->missing[i] == k) { m->missing.erase(m->missing.begin() + i); break; }
     return MUDPT_OK;
@@ -876,6 +918,7 @@ static int coop_src_row(int position, int n, int nl, int t) {
 
 extern "C" int mudpt_set_class_token_position(mudpt_model* m, int32_t position, const int32_t* name_lens) {
     ARG_CHECK(m, "set_class_token_position: null model");
+    NOT_FROZEN(m, "set_class_token_position");
     ARG_CHECK(m->coop, "set_class_token_position: not a CoOp model (MUDPT_VARIANT_COOP / MUDPT_VARIANT_COOP_CSC)");
     ARG_CHECK(position == MUDPT_CLASS_TOKEN_END || position == MUDPT_CLASS_TOKEN_MIDDLE || position == MUDPT_CLASS_TOKEN_FRONT,
               "set_class_token_position: position %d is not MUDPT_CLASS_TOKEN_END / _MIDDLE / _FRONT", position);
@@ -888,8 +931,67 @@ extern "C" int mudpt_set_class_token_position(mudpt_model* m, int32_t position, 
     return MUDPT_OK;
 }
 
+// Length buckets (MuDPT, many classes): "a photo of a <name>." ends at position 7-9 for most ImageNet names and at 19 for a few; the
+// caller's trim runs EVERY prompt to the longest.  Sorting the prompts by length and cutting the sorted list into <= txt_buckets groups,
+// each run to its own longest member, removes most of the padding (C = 1000 synthetic names: 19 000 -> ~11 000 rows).  Sequences are
+// independent in every kernel of the tower, so the kept rows are bit-identical to the single-bucket run (tests).  A bucket costs a
+// handful of extra launches per block (attention, splice, reductions: ~1 000 rows' worth of time), which the cut search charges.
+// eot [C]: the EOT position of every prompt; Le: the trimmed length of the one-bucket run; n_prompt: prompt rows per sequence (a sequence keeps at
+// least n_prompt + 2 rows).  Returns packed position -> class; *segs stays empty (and *rows untouched) for one bucket in the caller's order.
+static std::vector<int> plan_length_buckets(const mudpt_model* m, const int32_t* eot, size_t C, size_t Le, int n_prompt, int heads, bool allow,
+                                            std::vector<Tower::Seg>* segs, int* rows) {
+    segs->clear();
+    std::vector<int> order(C);  // packed position -> local class
+    for (size_t cc = 0; cc < C; ++cc) order[cc] = (int)cc;
+    auto len_of = [&](int cc) { return std::max(eot[cc] + 1, n_prompt + 2); };
+    if (allow && m->txt_trim && m->txt_buckets > 1 && C * Le >= 2048) {
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return len_of(x) < len_of(y); });
+        std::vector<int> dl, cnt;  // distinct lengths ascending, sequences per length
+        for (int cc : order) {
+            if (dl.empty() || dl.back() != len_of(cc)) { dl.push_back(len_of(cc)); cnt.push_back(0); }
+            ++cnt.back();
+        }
+        const int nd = (int)dl.size(), K = std::min(m->txt_buckets, nd);
+        const long PEN = m->txt_bucket_cost, INF = 1L << 60;
+        std::vector<long> pre(nd + 1, 0);
+        for (int j = 0; j < nd; ++j) pre[j + 1] = pre[j] + cnt[j];
+        // best[b][j]: rows (+ penalties) of covering lengths 0..j-1 with b buckets, the last one ending at length j-1
+        std::vector<std::vector<long>> best(K + 1, std::vector<long>(nd + 1, INF));
+        std::vector<std::vector<int>> from(K + 1, std::vector<int>(nd + 1, 0));
+        best[0][0] = 0;
+        for (int bk = 1; bk <= K; ++bk)
+            for (int j = 1; j <= nd; ++j)
+                for (int i0 = bk - 1; i0 < j; ++i0) {
+                    if (best[bk - 1][i0] >= INF) continue;
+                    const long v = best[bk - 1][i0] + (pre[j] - pre[i0]) * dl[j - 1] + PEN;
+                    if (v < best[bk][j]) { best[bk][j] = v; from[bk][j] = i0; }
+                }
+        int kb = 1;
+        for (int bk = 2; bk <= K; ++bk) if (best[bk][nd] < best[kb][nd]) kb = bk;
+        if (kb > 1) {
+            std::vector<int> cuts;  // bucket boundaries in distinct-length indices
+            for (int bk = kb, j = nd; bk >= 1; --bk) { cuts.push_back(j); j = from[bk][j]; }
+            std::reverse(cuts.begin(), cuts.end());
+            int j0 = 0, row0 = 0;
+            size_t lse0 = 0;
+            for (int j1 : cuts) {
+                Tower::Seg g; g.row0 = row0; g.seq0 = (int)pre[j0]; g.nseq = (int)(pre[j1] - pre[j0]); g.L = dl[j1 - 1]; g.lse0 = lse0;
+                segs->push_back(g);
+                row0 += g.nseq * g.L;
+                lse0 += (size_t)g.nseq * heads * attn_padded_len(g.L);
+                j0 = j1;
+            }
+            *rows = row0;
+        } else {
+            for (size_t cc = 0; cc < C; ++cc) order[cc] = (int)cc;  // one bucket: keep the caller's order
+        }
+    }
+    return order;
+}
+
 extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const int32_t* eot) {
     ARG_CHECK(m && emb && eot, "set_class_prompts: null argument");
+    NOT_FROZEN(m, "set_class_prompts (a frozen handle takes token ids: mudpt_set_text_tokens)");
     for (const std::string& k : m->missing)
         if (k == "positional_embedding") { set_error("set_class_prompts: set 'positional_embedding' first"); return MUDPT_ERR_STATE; }
     const mudpt_config& c = m->cfg;
@@ -941,58 +1043,8 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     }
     m->txt_chunk = (int)chunk;
     if (int rc = alloc_tower_acts(m, m->txt, (int)Le, (int)(m->cocoop ? chunk * C : C))) return rc;
-    // Length buckets (MuDPT, many classes): "a photo of a <name>." ends at position 7-9 for most ImageNet names and at 19 for a few; the
-    // trim above runs EVERY prompt to the longest.  Sorting the prompts by length and cutting the sorted list into <= txt_buckets groups,
-    // each run to its own longest member, removes most of the padding (C = 1000 synthetic names: 19 000 -> ~11 000 rows).  Sequences are
-    // independent in every kernel of the tower, so the kept rows are bit-identical to the single-bucket run (tests).  A bucket costs a
-    // handful of extra launches per block (attention, splice, reductions: ~1 000 rows' worth of time), which the cut search charges.
     Tower& X = m->txt;
-    X.segs.clear();
-    std::vector<int> order(C);  // packed position -> local class
-    for (size_t cc = 0; cc < C; ++cc) order[cc] = (int)cc;
-    auto len_of = [&](int cc) { return std::max(eot[cc] + 1, X.n + 2); };
-    if (!m->cocoop && m->txt_trim && m->txt_buckets > 1 && C * Le >= 2048) {
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return len_of(x) < len_of(y); });
-        std::vector<int> dl, cnt;  // distinct lengths ascending, sequences per length
-        for (int cc : order) {
-            if (dl.empty() || dl.back() != len_of(cc)) { dl.push_back(len_of(cc)); cnt.push_back(0); }
-            ++cnt.back();
-        }
-        const int nd = (int)dl.size(), K = std::min(m->txt_buckets, nd);
-        const long PEN = m->txt_bucket_cost, INF = 1L << 60;
-        std::vector<long> pre(nd + 1, 0);
-        for (int j = 0; j < nd; ++j) pre[j + 1] = pre[j] + cnt[j];
-        // best[b][j]: rows (+ penalties) of covering lengths 0..j-1 with b buckets, the last one ending at length j-1
-        std::vector<std::vector<long>> best(K + 1, std::vector<long>(nd + 1, INF));
-        std::vector<std::vector<int>> from(K + 1, std::vector<int>(nd + 1, 0));
-        best[0][0] = 0;
-        for (int bk = 1; bk <= K; ++bk)
-            for (int j = 1; j <= nd; ++j)
-                for (int i0 = bk - 1; i0 < j; ++i0) {
-                    if (best[bk - 1][i0] >= INF) continue;
-                    const long v = best[bk - 1][i0] + (pre[j] - pre[i0]) * dl[j - 1] + PEN;
-                    if (v < best[bk][j]) { best[bk][j] = v; from[bk][j] = i0; }
-                }
-        int kb = 1;
-        for (int bk = 2; bk <= K; ++bk) if (best[bk][nd] < best[kb][nd]) kb = bk;
-        if (kb > 1) {
-            std::vector<int> cuts;  // bucket boundaries in distinct-length indices
-            for (int bk = kb, j = nd; bk >= 1; --bk) { cuts.push_back(j); j = from[bk][j]; }
-            std::reverse(cuts.begin(), cuts.end());
-            int j0 = 0, row0 = 0;
-            size_t lse0 = 0;
-            for (int j1 : cuts) {
-                Tower::Seg g; g.row0 = row0; g.seq0 = (int)pre[j0]; g.nseq = (int)(pre[j1] - pre[j0]); g.L = dl[j1 - 1]; g.lse0 = lse0;
-                X.segs.push_back(g);
-                row0 += g.nseq * g.L;
-                lse0 += (size_t)g.nseq * X.heads * attn_padded_len(g.L);
-                j0 = j1;
-            }
-            X.rows = row0;
-        } else {
-            for (size_t cc = 0; cc < C; ++cc) order[cc] = (int)cc;  // one bucket: keep the caller's order
-        }
-    }
+    const std::vector<int> order = plan_length_buckets(m, eot, C, Le, X.n, X.heads, !m->cocoop, &X.segs, &X.rows);  // packed position -> local class
     std::vector<float> pos(L * d);
     HIP_TRY(hipMemcpy(pos.data(), m->tpos, pos.size() * 4, hipMemcpyDeviceToHost));
     const size_t reps = chunk;  // CoCoOp: sequence i * C + c for every image i of a chunk (the tables are chunk-local, reused per chunk)
@@ -1042,8 +1094,85 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
     return MUDPT_OK;
 }
 
+// Frozen handles: the class prompts of every template as token ids (trainers/zsclip.py:61-65,108-110).  Host work only until the tables are
+// uploaded: the EOT position of a prompt (clip/model.py:836 text.argmax(dim=-1): the FIRST maximum), each template's layout by the rules of
+// mudpt_set_class_prompts, and per packed token row its id and its position -- what embed_tokens_kernel turns into block 0's input.
+extern "C" int mudpt_set_text_tokens(mudpt_model* m, const int32_t* tokens, int32_t n_templates) {
+    ARG_CHECK(m && tokens, "set_text_tokens: null argument");
+    ARG_CHECK(m->frozen, "set_text_tokens: not a frozen handle (mudpt_create_frozen); the other variants take mudpt_set_class_prompts");
+    ARG_CHECK(n_templates >= 1, "set_text_tokens: n_templates %d must be >= 1", n_templates);
+    bool pos_set = true;
+    for (const std::string& k : m->missing) pos_set = pos_set && k != "positional_embedding";
+    if (!m->tok_table || !pos_set) { set_error("set_text_tokens: set 'token_embedding.weight' and 'positional_embedding' first"); return MUDPT_ERR_STATE; }
+    const mudpt_config& c = m->cfg;
+    const size_t C = (size_t)c.n_cls, L = (size_t)c.ctx_len, T = (size_t)n_templates;
+    for (size_t i = 0; i < T * C * L; ++i)
+        ARG_CHECK(tokens[i] >= 0 && tokens[i] < m->vocab, "set_text_tokens: token id %d (template %zu, class %zu, position %zu) outside the %d rows of the embedding table",
+                  tokens[i], i / (C * L), i / L % C, i % L, m->vocab);
+    Tower& X = m->txt;
+    std::vector<mudpt_model::Template> tm(T);
+    std::vector<int> host;                          // every template's five tables, one behind the other
+    std::vector<size_t> base(T);
+    int Lmax = 0;
+    for (size_t t = 0; t < T; ++t) {
+        const int32_t* tk = tokens + t * C * L;
+        std::vector<int32_t> eot(C);
+        int max_eot = 0;
+        for (size_t cc = 0; cc < C; ++cc) {
+            const int32_t* row = tk + cc * L;
+            eot[cc] = (int32_t)(std::max_element(row, row + L) - row);  // the first of equal maxima
+            max_eot = std::max(max_eot, (int)eot[cc]);
+        }
+        mudpt_model::Template& P = tm[t];
+        const size_t Le = m->txt_trim ? (size_t)std::max(max_eot + 1, 2) : L;
+        int packed = 0;
+        const std::vector<int> order = plan_length_buckets(m, eot.data(), C, Le, 0, X.heads, true, &P.segs, &packed);
+        P.L = (int)Le;
+        P.rows = P.segs.empty() ? (int)(C * Le) : packed;
+        Tower::Seg one; one.nseq = (int)C; one.L = (int)Le;
+        const std::vector<Tower::Seg> segs = P.segs.empty() ? std::vector<Tower::Seg>{one} : P.segs;
+        base[t] = host.size();
+        host.resize(base[t] + 2 * (size_t)P.rows + 3 * C);
+        int *tok = host.data() + base[t], *pos = tok + P.rows, *rows = pos + P.rows, *local = rows + C, *perm = local + C;
+        for (const Tower::Seg& g : segs)
+            for (int j = 0; j < g.nseq; ++j) {
+                const int sq = g.seq0 + j, cc = order[sq], r0 = g.row0 + j * g.L;
+                perm[sq] = cc;
+                rows[sq] = r0 + eot[cc];
+                local[sq] = r0 - g.row0 + eot[cc];
+                for (int l = 0; l < g.L; ++l) { tok[r0 + l] = tk[(size_t)cc * L + l]; pos[r0 + l] = l; }
+            }
+        Lmax = std::max(Lmax, P.L);
+    }
+    if (m->tmpl_tables) (void)hipFree(m->tmpl_tables);
+    m->tmpl_tables = nullptr;
+    m->tmpl.clear();
+    m->prompts_set = false;
+    m->text_valid = false;
+    HIP_TRY(hipMalloc((void**)&m->tmpl_tables, host.size() * 4));
+    HIP_TRY(hipMemcpy(m->tmpl_tables, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    for (size_t t = 0; t < T; ++t) {
+        mudpt_model::Template& P = tm[t];
+        P.tok = m->tmpl_tables + base[t]; P.pos = P.tok + P.rows; P.eot_rows = P.pos + P.rows; P.eot_local = P.eot_rows + C; P.perm = P.eot_local + C;
+    }
+    // one set of activations for every template: n_cls sequences of the longest kept length hold any template's packed rows
+    X.segs.clear();
+    if (int rc = alloc_tower_acts(m, X, Lmax, (int)C)) return rc;
+    m->tmpl = tm;
+    m->prompts_set = true;
+    return MUDPT_OK;
+}
+
 extern "C" int mudpt_text_layout(const mudpt_model* m, int32_t* rows, int32_t* buckets, int32_t* max_len) {
-    ARG_CHECK(m && m->prompts_set, "text_layout: call mudpt_set_class_prompts first");
+    ARG_CHECK(m && m->prompts_set, "text_layout: call mudpt_set_class_prompts (a frozen handle: mudpt_set_text_tokens) first");
+    if (m->frozen) {  // over the templates: token rows summed, the largest bucket count, the longest kept length
+        int r = 0, b = 0, l = 0;
+        for (const mudpt_model::Template& t : m->tmpl) { r += t.rows; b = std::max(b, t.segs.empty() ? 1 : (int)t.segs.size()); l = std::max(l, t.L); }
+        if (rows) *rows = r;
+        if (buckets) *buckets = b;
+        if (max_len) *max_len = l;
+        return MUDPT_OK;
+    }
     const int nseq = m->cocoop ? m->txt_chunk * m->cfg.n_cls : m->ct;
     if (rows) *rows = tower_rows(m->txt, nseq);
     if (buckets) *buckets = m->txt.segs.empty() ? 1 : (int)m->txt.segs.size();
@@ -1064,6 +1193,7 @@ extern "C" int mudpt_param_info(const mudpt_model* m, int i, const char** name, 
     return MUDPT_OK;
 }
 extern "C" int mudpt_bind_params(mudpt_model* m, float* p, float* g) {
+    NOT_FROZEN(m, "bind_params");
     ARG_CHECK(m && p, "bind_params: null argument");
     ARG_CHECK((uintptr_t)p % 16 == 0 && (uintptr_t)g % 16 == 0, "bind_params: buckets must be 16-byte aligned");
     m->params = p;
@@ -1677,6 +1807,79 @@ static int forward_impl(mudpt_model* m, const float* images, int B, hipStream_t 
     return head_forward(m, B, reuse_text, s);
 }
 
+// ---- frozen CLIP (trainers/zsclip.py) ------------------------------------------------------------------------------------
+static int frozen_ready(mudpt_model* m, const char* what, int B, bool need_text) {
+    ARG_CHECK(m, "%s: null model", what);
+    ARG_CHECK(m->frozen, "%s: not a frozen handle (mudpt_create_frozen)", what);
+    for (const std::string& k : m->missing)  // the image side needs the vision tower's weights only
+        if (need_text || k.rfind("visual.", 0) == 0) { set_error("%s: model not ready: %zu frozen weights unset (first needed: %s)", what, m->missing.size(), k.c_str()); return MUDPT_ERR_STATE; }
+    if (need_text && !m->prompts_set) { set_error("%s: model not ready: call mudpt_set_text_tokens", what); return MUDPT_ERR_STATE; }
+    ARG_CHECK(B > 0 && B <= m->cfg.max_batch, "%s: batch %d outside 1..max_batch=%d", what, B, m->cfg.max_batch);
+    return MUDPT_OK;
+}
+
+// The text features of a frozen handle -> m->txt_n [n_cls, e], rows of norm 1.  Templates in ascending order, each: block 0's input from the token
+// ids (zeroshot.hip; no emb_pos copy), the text tower and its head on the EOT rows (clip/model.py:825-838), the bucket scatter back to the
+// caller's class order, the ensemble step (zsclip.py:67-71 one template, :107-117 more).  A template has n_cls >= 1 sequences of >= 2 rows: no
+// launch here has zero rows.  The order is fixed and every kernel's sums are: two builds agree bit for bit.
+static int frozen_text_features(mudpt_model* m, hipStream_t s) {
+    const mudpt_config& c = m->cfg;
+    const int dt = c.t_width, e = c.embed_dim, C = c.n_cls, T = (int)m->tmpl.size();
+    Tower& X = m->txt;
+    for (int t = 0; t < T; ++t) {
+        const mudpt_model::Template& P = m->tmpl[t];
+        X.segs = P.segs; X.rows = P.rows; X.L = P.L; X.Lp = attn_padded_len(P.L); X.tail_rows = P.eot_rows; X.tail_local = P.eot_local;
+        ++m->text_launches;
+        TRY(launch_embed_tokens(m->tok_table, m->vocab, P.tok, P.pos, m->tpos, X.a[0].x_in, P.rows, dt, s));
+        for (int i = 0; i < X.layers; ++i) TRY(block_fwd(m, X, i, C, nullptr, s));
+        const bool packed = P.segs.size() > 1;
+        TRY(tower_head_fwd(m, X, text_head(m), packed ? m->txt_sorted : m->txt_f, C, 0, s));
+        if (packed) TRY(scatter(m->txt_sorted, P.perm, m->txt_f, C, e, 4, s));
+        TRY(launch_feature_ensemble(m->txt_f, m->ens_acc, m->txt_n, C, e, t == 0, t == T - 1, T, s));
+    }
+    m->text_valid = true;
+    return MUDPT_OK;
+}
+
+// model_inference (zsclip.py:74-79): the vanilla vision tower, then the logits-only head against the kept table (the head never
+// re-normalises it: a.txt = null).  Inference: never a split K
+static int frozen_forward(mudpt_model* m, const float* images, int B, float* logits, hipStream_t s) {
+    const mudpt_config& c = m->cfg;
+    if (!m->text_valid) TRY(frozen_text_features(m, s));
+    m->train_fwd = false;
+    TRY(vision_forward(m, images, B, s));
+    HeadArgs h; h.img = m->img_f; h.scale = m->scale; h.logits = m->logits; h.img_n = m->img_n; h.txt_n = m->txt_n;
+    h.img_inv = m->img_inv; h.txt_inv = m->txt_inv; h.B = B; h.C = c.n_cls; h.e = c.embed_dim;
+    if (head_fused_fits(h, false)) {
+        TRY(launch_head_fused_fwd(h, s));
+    } else {
+        TRY(launch_l2norm(m->img_f, m->img_n, m->img_inv, B, c.embed_dim, s));
+        TRY(launch_sgemm(false, true, B, c.n_cls, c.embed_dim, m->scale, m->img_n, c.embed_dim, m->txt_n, c.embed_dim, 0.f, m->logits, c.n_cls, nullptr, s));
+    }
+    HIP_TRY(hipMemcpyAsync(logits, m->logits, (size_t)B * c.n_cls * 4, hipMemcpyDeviceToDevice, s));
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_text_features(mudpt_model* m, float* feat, void* stream) {
+    TRY(frozen_ready(m, "text_features", 1, true));
+    ARG_CHECK(feat, "text_features: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (!m->text_valid) TRY(frozen_text_features(m, s));
+    HIP_TRY(hipMemcpyAsync(feat, m->txt_n, (size_t)m->cfg.n_cls * m->cfg.embed_dim * 4, hipMemcpyDeviceToDevice, s));
+    return MUDPT_OK;
+}
+
+// clip/model.py:822 encode_image, lpclip/feat_extractor.py:125: the raw features, as the vision tower's projection leaves them
+extern "C" int mudpt_encode_image(mudpt_model* m, const float* images, int32_t B, float* features, void* stream) {
+    TRY(frozen_ready(m, "encode_image", B, false));
+    ARG_CHECK(images && features, "encode_image: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    m->train_fwd = false;
+    TRY(vision_forward(m, images, B, s));
+    HIP_TRY(hipMemcpyAsync(features, m->img_f, (size_t)B * m->cfg.embed_dim * 4, hipMemcpyDeviceToDevice, s));
+    return MUDPT_OK;
+}
+
 static int not_sharded(mudpt_model* m, const char* what) {
     if (m->sharded) { set_error("%s: this handle encodes classes %d..%d of %d only (mudpt_set_class_shard): use the mudpt_cp_* phases", what, m->c0, m->c0 + m->ct - 1, m->cfg.n_cls); return MUDPT_ERR_STATE; }
     return MUDPT_OK;
@@ -1687,6 +1890,11 @@ extern "C" int mudpt_forward(mudpt_model* m, const float* images, int32_t B, flo
 }
 
 extern "C" int mudpt_forward_ex(mudpt_model* m, const float* images, int32_t B, float* logits, int32_t flags, void* stream) {
+    if (m && m->frozen) {  // MUDPT_FWD_REUSE_TEXT changes nothing: the text features are kept anyway
+        TRY(frozen_ready(m, "forward", B, true));
+        ARG_CHECK(images && logits, "forward: null argument");
+        return frozen_forward(m, images, B, logits, (hipStream_t)stream);
+    }
     TRY(ready(m, B, false));
     TRY(not_sharded(m, "forward"));
     ARG_CHECK(images && logits, "forward: null argument");
@@ -1881,6 +2089,7 @@ static Learner learner(const mudpt_model* m) {
 // MPT without a vision prompt, mpt.py:224-256): the text tower's backward alone, on the main stream.
 extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const int64_t* labels, int32_t B, float grad_scale,
                                       float* loss, float* logits, void* stream) {
+    NOT_FROZEN(m, "forward_backward");
     TRY(ready(m, B, true));
     ARG_CHECK(images && labels && loss, "forward_backward: null argument");
     hipStream_t s = (hipStream_t)stream;
@@ -1915,6 +2124,7 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
 //   <the usual all-reduce of the gradient bucket>   text-side gradients are partial sums over classes, vision-side ones over images
 extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
     ARG_CHECK(m, "set_class_shard: null model");
+    NOT_FROZEN(m, "set_class_shard");
     if (m->cocoop) { set_error("set_class_shard: CoCoOp's text features depend on the image; shard the batch instead"); return MUDPT_ERR_ARG; }
     if (m->coop) { set_error("set_class_shard: class-parallel CoOp is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
     if (m->indep) { set_error("set_class_shard: class-parallel VPT / MPT is not implemented; shard the batch instead"); return MUDPT_ERR_ARG; }
@@ -1929,20 +2139,21 @@ extern "C" int mudpt_set_class_shard(mudpt_model* m, int32_t c0, int32_t c1) {
 }
 // the class-parallel phases' refusal of every variant but MuDPT (CoCoOp: the phases' own argument checks)
 static int cp_mudpt_only(const mudpt_model* m, const char* what) {
+    NOT_FROZEN(m, what);
     ARG_CHECK(!(m && (m->coop || m->indep || m->umudpt)), "%s: not a MuDPT model (the class-parallel phases run MuDPT only)", what);
     return MUDPT_OK;
 }
 extern "C" int mudpt_cp_buffers(mudpt_model* m, float** feat, float** dfeat, size_t* numel) {
-    ARG_CHECK(m && !m->cocoop, "cp_buffers: not a MuDPT model");
     TRY(cp_mudpt_only(m, "cp_buffers"));
+    ARG_CHECK(m && !m->cocoop, "cp_buffers: not a MuDPT model");
     if (feat) *feat = m->txt_f;
     if (dfeat) *dfeat = m->dtxt;
     if (numel) *numel = (size_t)m->cfg.n_cls * m->cfg.embed_dim;
     return MUDPT_OK;
 }
 extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, int32_t flags, void* stream) {
-    TRY(ready(m, B, false));
     TRY(cp_mudpt_only(m, "cp_forward"));
+    TRY(ready(m, B, false));
     ARG_CHECK(images && !m->cocoop, "cp_forward: null images / not a MuDPT model");
     const bool reuse = (flags & MUDPT_FWD_REUSE_TEXT) != 0;
     if (reuse && !m->text_valid) { set_error("cp_forward: MUDPT_FWD_REUSE_TEXT before any text-tower pass"); return MUDPT_ERR_STATE; }
@@ -1952,8 +2163,8 @@ extern "C" int mudpt_cp_forward(mudpt_model* m, const float* images, int32_t B, 
     return MUDPT_OK;
 }
 extern "C" int mudpt_cp_head(mudpt_model* m, const int64_t* labels, int32_t B, float grad_scale, float* loss, float* logits, int32_t flags, void* stream) {
-    TRY(ready(m, B, labels != nullptr));
     TRY(cp_mudpt_only(m, "cp_head"));
+    TRY(ready(m, B, labels != nullptr));
     ARG_CHECK(!m->cocoop && (labels ? loss != nullptr : logits != nullptr), "cp_head: training needs labels and loss, inference needs logits");
     if (m->cp_stage < 1 || m->cp_B != B) { set_error("cp_head: call mudpt_cp_forward with the same batch first"); return MUDPT_ERR_STATE; }
     hipStream_t s = (hipStream_t)stream;
@@ -1985,6 +2196,7 @@ extern "C" int mudpt_cp_backward(mudpt_model* m, int32_t part, void* stream) {
 }
 
 extern "C" int mudpt_sgd_step(mudpt_model* m, float lr, float momentum, float wd, float dampening, int32_t nesterov, void* stream) {
+    NOT_FROZEN(m, "sgd_step");
     ARG_CHECK(m && m->params && m->grads, "sgd_step: parameters / gradients not bound");
     TRY(launch_sgd(m->params, m->grads, m->momentum, m->total, lr, momentum, wd, dampening, nesterov != 0, m->sgd_first, (hipStream_t)stream));
     m->sgd_first = false;
@@ -2017,6 +2229,7 @@ static nccl_allreduce_fn resolve_allreduce() {
     return fn;
 }
 extern "C" int mudpt_allreduce_grads(mudpt_model* m, void* nccl_comm, void* stream) {
+    NOT_FROZEN(m, "allreduce_grads");
     ARG_CHECK(m && nccl_comm, "allreduce_grads: null model / communicator");
     if (!m->grads) { set_error("allreduce_grads: no gradient bucket bound"); return MUDPT_ERR_STATE; }
     nccl_allreduce_fn fn = resolve_allreduce();
@@ -2138,7 +2351,7 @@ extern "C" int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch,
     if (k.rfind("vis.", 0) == 0) tower(m->vis, k.substr(4), batch);
     else if (k.rfind("txt.", 0) == 0) tower(m->txt, k.substr(4), m->ct);  // this handle's classes
     else if (k == "image_features") { src = m->img_f; n = (size_t)batch * c.embed_dim; }
-    else if (k == "text_features") { src = m->txt_f; n = (size_t)c.n_cls * c.embed_dim; }
+    else if (k == "text_features") { src = m->frozen ? m->txt_n : m->txt_f; n = (size_t)c.n_cls * c.embed_dim; }  // frozen: the ensembled, normalised table
     else if (m->umudpt && !m->uumudpt && (k == "umudpt.G" || k == "umudpt.dG")) { src = k == "umudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
     else if (m->uumudpt && (k == "uumudpt.G" || k == "uumudpt.dG")) { src = k == "uumudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
     else if (m->uumudpt && c.depth > 1 && (k == "uumudpt.T" || k == "uumudpt.dT")) { src = k == "uumudpt.T" ? m->pg2_T : m->d_txt_deep; n = (size_t)(c.depth - 1) * c.n_ctx * c.embed_dim; }
@@ -2438,6 +2651,14 @@ extern "C" int mudpt_cocoop_prompts(float* x0, const float* emb_pos, const float
 extern "C" int mudpt_coop_splice(float* x, const float* ctx, const float* tpos, const int32_t* rows, const int32_t* pos, int32_t C, int32_t n, int32_t d,
                                  int32_t csc, void* stream) {
     return launch_coop_splice(x, ctx, tpos, rows, pos, C, n, d, csc != 0, (hipStream_t)stream);
+}
+// zero-shot CLIP's kernels (zeroshot.hip)
+extern "C" int mudpt_embed_tokens(const float* table, int32_t vocab, const int32_t* tokens_dev, const int32_t* positions_dev, const float* pos, float* out,
+                                  int32_t rows, int32_t d, void* stream) {
+    return launch_embed_tokens(table, vocab, tokens_dev, positions_dev, pos, out, rows, d, (hipStream_t)stream);
+}
+extern "C" int mudpt_feature_ensemble(const float* f, float* acc, float* out, int32_t C, int32_t e, int32_t first, int32_t last, int32_t n_templates, void* stream) {
+    return launch_feature_ensemble(f, acc, out, C, e, first != 0, last != 0, n_templates, (hipStream_t)stream);
 }
 // UMuDPT's prompt generator (promptgen.hip): its three kernels, and the whole block as the model path runs it
 extern "C" int mudpt_layernorm_bwd_affine(const float* x, int32_t ldx, const float* mean, const float* rstd, const float* gamma, const float* dy, int32_t lddy,

@@ -49,7 +49,8 @@ def default_cfg() -> CfgNode:
                   MPT=C(DEEP_TEXT_N_CTX=0, DEEP_VISUAL_N_CTX=0, TEXT_PROMPT_DEPTH=0, VISUAL_PROMPT_DEPTH=0, TEXT_CTX_INIT="a photo of a",
                         PREC="fp16"),  # train.py:106-112
                   UMUDPT=C(N_CTX=2, CTX_INIT="a photo of a", DEEP_PROMPT_DEPTH=8, PREC="fp16"),  # train.py:122-126
-                  UUMUDPT=C(N_CTX=2, CTX_INIT="a photo of a", DEEP_PROMPT_DEPTH=8, PREC="fp16")),  # train.py:129-133
+                  UUMUDPT=C(N_CTX=2, CTX_INIT="a photo of a", DEEP_PROMPT_DEPTH=8, PREC="fp16"),  # train.py:129-133
+                  ZSCLIP=C(PREC="fp16")),  # this package's own node (ZeroshotCLIP / ZeroshotCLIP2): the reference's GPU run is clip.load's fp16 model
     )
 
 

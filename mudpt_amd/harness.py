@@ -12,7 +12,7 @@ import argparse
 
 import torch
 
-from . import cocoop, coop, dassl_lite, parallel, trainer, umudpt, uumudpt, vpt  # noqa: F401  (importing the plugin modules registers MuDPT / CoCoOp / CoOp / VPT, MPT / UMuDPT / UUMuDPT)
+from . import cocoop, coop, dassl_lite, parallel, trainer, umudpt, uumudpt, vpt, zsclip  # noqa: F401  (importing the plugin modules registers MuDPT / CoCoOp / CoOp / VPT, MPT / UMuDPT / UUMuDPT / ZeroshotCLIP, ZeroshotCLIP2)
 
 
 def run(argv=None):
