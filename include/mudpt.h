@@ -260,6 +260,9 @@ int mudpt_cp_backward(mudpt_model* m, int32_t part, void* stream);
 
 /* Static loss scale of the backward pass (default 128): per-sample logit gradients are multiplied by it so the
  * fp16 copies of the token gradients stay normal; the gradients written to the bucket are unscaled again.
+ * Any positive finite value is accepted, a power of two or not; it takes effect at the next step (the class-parallel phases: at the next
+ * mudpt_cp_head).  bf16 handles give the same step bit for bit at every power of two; fp16-typed handles keep their own gradient grade from
+ * 1024 down to 2 and stay inside bf16's at 1, the floor of trainer.data_parallel_step (measured: the table in DESIGN.md 2).
  * The reference's analogue is GradScaler under PREC == "amp" (trainers/mudpt.py:228,243-246). */
 int mudpt_set_loss_scale(mudpt_model* m, float loss_scale);
 

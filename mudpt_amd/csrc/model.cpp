@@ -1918,8 +1918,14 @@ static int head_train(mudpt_model* m, const int64_t* labels, int B, float grad_s
     h.row_loss = m->row_loss; h.dimg = m->dimg; h.dtxt = text_grad ? m->dtxt : nullptr; h.img_n = m->img_n; h.txt_n = m->txt_n; h.img_inv = m->img_inv; h.txt_inv = m->txt_inv;
     // Static loss scaling: the backward pass runs on per-sample gradients times loss_scale (dlogits = (softmax -
     // onehot) * loss_scale, independent of B and of the number of ranks), so the T copies of the token gradients
-    // stay inside fp16's normal range (unscaled they are ~1e-7 at B = 256: flushed).  The four reductions that leave
-    // the towers multiply by `unscale`; everything after them is fp32 and linear.
+    // stay inside fp16's normal range (unscaled they are ~1e-7 at B = 256: flushed).  Every reduction that leaves a
+    // tower multiplies by `unscale` = grad_scale / (B * loss_scale); everything after them (prompt-learner and generator
+    // backwards, meta_net, the bucket) is fp32 and linear.  The sites (tests/test_scales_gpu.py runs each):
+    //   text_backward    launch_reduce_rows per length bucket and deep layer, and again per bucket for layer 0's prompt rows;
+    //                    CoOp: launch_coop_dctx instead (shared or per-class context)
+    //   vision_backward  launch_reduce_rows per deep layer, once over the fused splice (vsplice), once for layer 0's prompt rows
+    //   cocoop_forward_backward  launch_reduce_rows (d ctx) and launch_cocoop_dbias, per chunk of images, with an unscale of its own
+    //   the class-parallel phases  mudpt_cp_backward passes the cp_unscale that the step's mudpt_cp_head stored here
     m->cp_unscale = grad_scale / ((float)B * m->loss_scale);
     h.grad_scale = m->loss_scale * (float)B; h.B = B; h.C = C; h.e = e;
     if (text_grad) ++m->text_launches;  // the text half of the backward (head_dtxt_kernel / its unfused form)

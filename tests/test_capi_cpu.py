@@ -148,9 +148,9 @@ def test_every_model_knob_is_documented_and_held_by_a_test():
     assert not documented - accepted, f"rows of the header's table the library does not accept: {sorted(documented - accepted)}"
     for name, (settings, held_by, why_not) in MODEL_KNOBS.items():
         assert bool(held_by) != bool(why_not) and (held_by or len(why_not) > 20), name
-        if held_by:  # the test it names exists
-            path, _, test = held_by.partition("::")
-            assert f"\ndef {test}(" in open(os.path.join(root, path)).read(), (name, held_by)
+        for held in held_by.split(", ") if held_by else ():  # every test it names exists
+            path, _, test = held.partition("::")
+            assert f"\ndef {test}(" in open(os.path.join(root, path)).read(), (name, held)
         for s in settings:  # a setting moves its own knob off the dtype's default, and whatever it moves can be set back
             assert s.sets[0][0] == name and (s.construct or all(k in KNOB_DEFAULTS[s.dtype] for k, _ in s.sets)), s
             assert s.sets[0][1] != KNOB_DEFAULTS[s.dtype].get(name, 1 if name == "txt_split" else None), s
@@ -161,6 +161,11 @@ def test_every_model_knob_is_documented_and_held_by_a_test():
     assert {s.sets[0] for s in knob_settings(dtype="fp16")} == {("gemm_variant", 12), ("gemm_variant", 1), ("gemm_variant", 10), ("attn_window", 0),
                                                                 ("attn_two_kernels", 1), ("attn_fused_w1", 1), ("lp_grad", 1), ("lp_upd", 1), ("gelu_q8", 1),
                                                                 ("txt_split", 0), ("txt_lo", 0), ("txt_sites", 5)}
+    # the parity mode's own knobs on a dtype "fp32" handle: pairs in the vision tower, its fp32 attention, both (round 3's exact mode), fewer
+    # split sites, the text tower's attention back in fp16
+    assert [s.sets for s in knob_settings(dtype="fp32")] == [(("vis_lo", 1),), (("vis_sites", 12),), (("vis_exact_attn", 1),),
+                                                             (("vis_exact_attn", 1), ("vis_lo", 1)), (("txt_exact_attn", 0),)]
+    assert set(KNOB_DEFAULTS) == {"fp16", "bf16", "fp32"} and all(KNOB_DEFAULTS["fp32"][k] == v for k, v in KNOB_DEFAULTS["fp16"].items() if k != "lp_grad")
     assert all(s.lowers == (s.dtype == "fp16" and s.sets[0][0] in ("lp_grad", "lp_upd", "gelu_q8", "txt_split", "txt_lo", "txt_sites")) for s in knob_settings())
 
 

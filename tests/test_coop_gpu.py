@@ -99,6 +99,41 @@ def test_parity_mode_at_logit_scale_100():
     m.close()
 
 
+@pytest.mark.parametrize("name", [f for f in R.FIXTURES if f.startswith("coop_tiny_")] + ["coop_vitb16_b2_s100"])
+def test_parity_mode_training_step(name):
+    """One training step on a dtype "fp32" handle (what PREC "fp32" selects; every class-token position, shared and per-class contexts, and
+    ViT-B/16 at logit scale 100).  Its forward is the inference forward bit for bit and its loss is the fixture's within the parity mode's
+    logit bound; d ctx passes this suite's own check (the kappa bound, or the CSC rule) with the bf16 constants against both the fixture and
+    the restatement, and inside that twice the figures this fixture measured (test_knobs_gpu.PARITY_STEP_MEASURED)."""
+    from tests.helpers import check_parity_step_grads
+    from tests.test_exact_gpu import LOGIT_ATOL_EXACT
+    from tests.test_knobs_gpu import PARITY_STEP_MEASURED
+    case = R.CoopCase(name)
+    m = build(case, "fp32")
+    m.eval()
+    logits = m(case.images).cpu()
+    m.train()
+    loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
+    torch.cuda.synchronize()
+    assert_training_forward_is_the_inference_forward(logits2, logits, "fp32")
+    slack = 1.0 if case.cfg.v_layers >= 12 else 3.0  # test_exact_gpu.py::test_logits_at_scale_100_within_1e_3: the tiny shape in the default parity mode
+    print(f"{name} parity mode: |loss - reference| {abs(loss.item() - case.loss):.3e} |logit - reference| max {(logits - case.logits).abs().max().item():.3e}")
+    assert abs(loss.item() - case.loss) <= slack * LOGIT_ATOL_EXACT
+    got = m.grads()[R.CTX].detach().cpu()
+    m.close()
+    taps = {}
+    restated = R.forward_backward(case.cfg, case.frozen, case.ctx, case.class_embedding, case.eot, case.name_lens, case.position, case.images, case.labels, taps)[2]
+    for tag, ref in (("fixture", case.dctx), ("restatement", restated)):
+        rms_g, gmax = ref.pow(2).mean().sqrt().item(), ref.abs().max().item()
+        e, er = (got - ref).abs().max().item(), (got - ref).pow(2).mean().sqrt().item()
+        if case.csc:
+            assert er <= GRAD_RMS["bf16"] * rms_g + 1e-12 and e <= 4 * GRAD_RTOL["bf16"] * rms_g + 1e-9, (tag, er / rms_g, e / rms_g)
+        else:
+            bound = DELTA_T["bf16"] * kappa(case, taps["dprompts"])
+            assert er <= bound * rms_g + 1e-12 and e <= 4 * bound * gmax + 1e-9, (tag, er / rms_g, e / gmax, bound)
+    check_parity_step_grads(name, [(R.CTX, got, restated)], PARITY_STEP_MEASURED[name])
+
+
 def test_csc_with_equal_contexts_is_the_shared_context():
     case = R.CoopCase("coop_tiny_middle")
     shared = build(case, "fp16", csc=False)

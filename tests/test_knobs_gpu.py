@@ -24,6 +24,7 @@ from tests import coop_reference as CR
 from tests import helpers as H
 from tests import test_cocoop_gpu as TCC
 from tests import test_coop_gpu as TC
+from tests import test_exact_gpu as TE
 from tests import test_manyclass_gpu as TMC
 from tests import test_model_gpu as TM
 from tests import test_umudpt_gpu as TU
@@ -159,9 +160,11 @@ def fixture_ids(v):
 
 
 # ---- 1. every non-default setting against the oracle ------------------------------------------------------------------------------------
-ORACLE_CASES = ([(name, s) for name in ("mudpt_tiny", "mudpt_vitb16_b4") for s in H.knob_settings()]
+ORACLE_CASES = ([(name, s) for name in ("mudpt_tiny", "mudpt_vitb16_b4") for s in H.knob_settings() if s.dtype != "fp32"]
                 # L = 581 > 224: the two attention-form knobs meet the resident / staged forms
-                + [("mudpt_vitl14_336_b1", s) for s in H.knob_settings(H.ATTN_FORM_KNOBS)])
+                + [("mudpt_vitl14_336_b1", s) for s in H.knob_settings(H.ATTN_FORM_KNOBS)]
+                # the parity mode's own knobs at the logit scale its bound is stated at
+                + [(name, s) for name in ("mudpt_tiny_s100", "mudpt_vitb16_b4_s100") for s in H.knob_settings(dtype="fp32")])
 
 
 # What the settings that lower an fp16 handle's grade measure on an MI355X against the oracle (O.forward_backward on the CPU, as in
@@ -179,6 +182,78 @@ LOWERED_MEASURED = {
 }
 
 
+# What the parity mode's own knobs measure on an MI355X against the oracle at logit scale 100, the worse of mudpt_tiny_s100 and
+# mudpt_vitb16_b4_s100: setting -> (worst tensor's max gradient error / its rms, worst tensor's rms gradient error / its rms, smallest
+# cosine).  The default parity handle measures the "default" row; all of them are expected near LOWERED_MEASURED["lp_grad"] (the backward
+# is the fp16 mode's with lp_grad = 1, whatever the forward's operands).  The test bounds each by TWICE its row inside the bf16 constants.
+PARITY_KNOBS_MEASURED = {  # (the ViT-B/16 fixture is the worse one in every row; logits: 3.8e-4, 3.0e-4, 7.8e-5, 1.2e-5, 3.4e-3 there)
+    "vis_lo1-fp32": (2.44e-2, 3.03e-3, 0.999995),
+    "vis_sites12-fp32": (2.83e-2, 3.43e-3, 0.999994),
+    "vis_exact_attn1-fp32": (2.87e-2, 3.51e-3, 0.999994),
+    "vis_exact_attn1-vis_lo1-fp32": (2.86e-2, 3.50e-3, 0.999994),
+    "txt_exact_attn0-fp32": (3.45e-2, 3.28e-3, 0.999995),
+}
+
+
+def parity_logit_bound(c, setting):
+    """The bound test_exact_gpu.py's ablation holds the row with these knobs to (ViT-B/16 at logit scale 100); on the 3-layer tiny shape
+    times the slack test_logits_at_scale_100_within_1e_3 gives it: 3 while the vision attention runs in fp16 (7 tokens: it averages over
+    nothing), TINY_SLACK once vis_exact_attn = 1."""
+    bound = next(b for _, knobs, b in TE.ABLATION if knobs == dict(setting.sets))
+    if c.cfg.v_layers >= 12:
+        return bound
+    return bound * (TE.TINY_SLACK if dict(setting.sets).get("vis_exact_attn") else 3.0)
+
+
+def check_parity_setting(name, setting):
+    """test_setting_matches_the_oracle on a dtype "fp32" handle: logits and loss against the fixture inside the ablation's bound for the
+    row; every gradient tensor against the oracle with the bf16 constants as the hard bound (the mode runs lp_grad = 1) and, inside them,
+    twice PARITY_KNOBS_MEASURED's row; the fp16 cosine floor.  (ViT-L/14@336, where vis_exact_attn = 1 feeds the staged or resident backward
+    at L = 581, is left to the ablation's logits: one handle's weight ingestion alone takes 15 s.)"""
+    c = load(name)
+    got = run(name, "fp32", setting.sets)
+    logit_tol = parity_logit_bound(c, setting)
+    dl = (got.logits - c.logits).abs().max().item()
+    print(f"{name} {setting.id}: |loss - reference| {abs(got.loss - c.loss):.3e} |logit - reference| max {dl:.3e} (bound {logit_tol:.2e})")
+    assert abs(got.loss - c.loss) <= logit_tol and dl <= logit_tol
+    grad_max, grad_rms, cos_floor = 4 * GRAD_RTOL["bf16"], GRAD_RMS["bf16"], GRAD_COS["fp16"]
+    measured = PARITY_KNOBS_MEASURED[setting.id]
+    grad_max, grad_rms = min(grad_max, 2 * measured[0]), min(grad_rms, 2 * measured[1])
+    ref, worst = oracle_grads(name), [0.0, 0.0, 1.0]
+    for k in O.TRAINABLE_ORDER:
+        r, g = ref[k], got.grads[k]
+        rms = r.pow(2).mean().sqrt().item()
+        err = (g - r).abs().max().item()
+        rel_rms = (g - r).pow(2).mean().sqrt().item() / max(rms, 1e-30)
+        cos = torch.nn.functional.cosine_similarity(g.flatten(), r.flatten(), dim=0).item()
+        worst = [max(worst[0], err / max(rms, 1e-30)), max(worst[1], rel_rms), min(worst[2], cos)]
+        print(f"  {k}: rms {rms:.3e} max err {err / max(rms, 1e-30):.3e} x rms (bound {grad_max:.2e}) rms err {rel_rms:.3e} x rms (bound {grad_rms:.2e}) cos {cos:.6f}")
+        assert err <= grad_max * rms + 1e-9, (k, err, rms)
+        assert rel_rms <= grad_rms or rms == 0, (k, rel_rms)
+        assert cos > cos_floor, (k, cos)
+    print(f"{name} {setting.id}: worst tensor max {worst[0]:.2e} rms {worst[1]:.2e} cos {worst[2]:.6f}")
+
+
+# What one training step of a parity-mode handle (dtype "fp32") measures on an MI355X against the variant's restatement, the worst tensor:
+# fixture -> (max gradient error / rms, rms gradient error / rms, smallest cosine).  The variants' suites (test_parity_mode_training_step in
+# test_coop_gpu.py, test_vpt_gpu.py, test_umudpt_gpu.py, test_uumudpt_gpu.py; the CoCoOp half of test_exact_gpu.py) hold each fixture to TWICE
+# its row inside the bf16 constants (helpers.check_parity_step_grads).  Expected near LOWERED_MEASURED["lp_grad"]: the same backward.
+# The ViT-B/16 rows at logit scale 100 with a larger RMS error are sums of nearly cancelling per-class terms (CoOp's shared context, MPT's
+# text prompts, CoCoOp: the kappa of tests/test_cocoop_gpu.py; the softmax is more peaked at scale 100), the same relative error on every
+# tensor of the fixture; UUMuDPT's larger maximum is the tail of 1.7 M-element generator weights at an RMS error of 2.8e-3.  No row points at
+# a wrong copy: that gives O(1).  (A cosine that prints as 1.000000 is recorded as 0.999999.)
+PARITY_STEP_MEASURED = {
+    "coop_tiny_end": (1.03e-2, 2.11e-3, 0.999998), "coop_tiny_middle": (6.63e-3, 1.49e-3, 0.999999), "coop_tiny_front": (6.34e-3, 1.31e-3, 0.999999),
+    "coop_tiny_end_csc": (7.55e-3, 9.14e-4, 0.999999), "coop_tiny_middle_csc": (6.17e-3, 8.97e-4, 0.999999), "coop_tiny_front_csc": (7.70e-3, 9.45e-4, 0.999999),
+    "coop_vitb16_b2_s100": (2.82e-2, 5.23e-3, 0.999986),
+    "vpt_tiny": (3.85e-3, 8.67e-4, 0.999999), "mpt_tiny": (5.20e-3, 1.30e-3, 0.999999), "mpt_tiny_textonly": (4.03e-3, 9.98e-4, 0.999999),
+    "vpt_vitb16_b2_s100": (7.89e-3, 1.05e-3, 0.999999), "mpt_vitb16_b2_s100": (2.74e-2, 5.10e-3, 0.999987),
+    "umudpt_tiny": (9.58e-3, 1.43e-3, 0.999999), "umudpt_vitb16_b2_s100": (1.98e-2, 2.88e-3, 0.999996),
+    "uumudpt_tiny": (1.83e-2, 1.49e-3, 0.999999), "uumudpt_vitb16_b2_s100": (4.94e-2, 3.12e-3, 0.999995),
+    "cocoop_tiny_s100": (1.30e-2, 2.25e-3, 0.999998), "cocoop_vitb16_b2_s100": (5.71e-2, 6.95e-3, 0.999976),
+}
+
+
 @pytest.mark.parametrize("name,setting", ORACLE_CASES, ids=fixture_ids)
 def test_setting_matches_the_oracle(name, setting):
     """One step under the setting, then the checks of test_loss_and_grads_match_reference with the dtype's own constants: loss and logits
@@ -190,6 +265,8 @@ def test_setting_matches_the_oracle(name, setting):
     fewer split operands in the text tower) have the bf16 constants as their hard bound: bf16 mode runs with all of them on at a 16 x
     coarser T, and a wiring error gives O(1) errors either way.  Inside it, each is held to twice what it measures against the oracle
     (LOWERED_MEASURED, with the header's figure for the trade beside it).  Every figure is printed against the oracle for the record."""
+    if setting.dtype == "fp32":
+        return check_parity_setting(name, setting)
     c, dtype = load(name), setting.dtype
     got = run(name, dtype, setting.sets, setting.construct)
     grade = "bf16" if setting.lowers else dtype
@@ -223,14 +300,22 @@ def test_setting_matches_the_oracle(name, setting):
 BACKWARD_ONLY = ("attn_window", "attn_two_kernels", "attn_fused_w1", "gelu_q8", "lp_grad")  # lp_grad: with lp_upd pinned (MODEL_KNOBS' bf16 row)
 
 
-@pytest.mark.parametrize("name,setting", [(n, s) for n in ("mudpt_tiny", "mudpt_vitb16_b4") for s in H.knob_settings(BACKWARD_ONLY)], ids=fixture_ids)
+# the same five on a parity-mode handle, each moved off that mode's default
+PARITY_BACKWARD_ONLY = [H.KnobSetting("fp32", ((k, 1 - KNOB_DEFAULTS["fp32"][k]),)) for k in BACKWARD_ONLY]
+
+
+@pytest.mark.parametrize("name,setting", [(n, s) for n in ("mudpt_tiny", "mudpt_vitb16_b4") for s in H.knob_settings(BACKWARD_ONLY) + PARITY_BACKWARD_ONLY], ids=fixture_ids)
 def test_backward_only_knob_leaves_the_forward_alone(name, setting):
     """The attention backward's forms and window, the 8-bit QuickGELU' codes (c_fc's second output; QuickGELU(u) itself is written as before)
     and the gradient stream's type are read by the backward alone: logits and loss of the step equal the default's bit for bit.  The two
     that change the backward's arithmetic do move the gradients -- a knob the step ignores would pass everything else here."""
     base, got = run(name, setting.dtype), run(name, setting.dtype, setting.sets)
     assert torch.equal(got.logits, base.logits) and got.loss == base.loss, (got.logits - base.logits).abs().max().item()
-    if setting.sets[0][0] in ("gelu_q8", "lp_grad"):
+    if setting.dtype == "fp32" and setting.sets[0][0] == "gelu_q8":
+        # both towers of the parity mode run split operands, and a tower with split operands keeps u in T whatever the knob says (model.cpp:
+        # "gelu_q8 && t.split == LO_NONE"): the whole step is the default's
+        assert_same_step(got, base, f"{name} fp32 gelu_q8 1 vs 0")
+    elif setting.sets[0][0] in ("gelu_q8", "lp_grad"):
         assert any(not torch.equal(got.grads[k], g) for k, g in base.grads.items())
 
 
@@ -241,8 +326,10 @@ WINDOW_FIXTURES = ["mudpt_tiny", "mudpt_vitb16_b4",  # L = 201: BWD_TWO
                    "seeded_tiny_n12", "seeded_tiny_n16"]  # the last prompt row opens a 16-row block: vision tower, text tower
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("name", WINDOW_FIXTURES)
+WINDOW_CASES = [(n, dt) for n in WINDOW_FIXTURES for dt in DTYPES] + [(n, "fp32") for n in ("mudpt_tiny", "coop_tiny_middle", "seeded_tiny_n16")]
+
+
+@pytest.mark.parametrize("name,dtype", WINDOW_CASES)
 def test_attention_window_changes_nothing(name, dtype):
     """kernels.h: the windowed attention backward computes "the same sums in the same order as without the window" on its rows and writes no
     other row of dqkv; block_bwd reads the prompt rows alone.  With attn_two_kernels = 1 the windowed and the full call run the same form
@@ -326,6 +413,34 @@ def test_step_leaves_nothing_behind(name, dtype, first):
     finally:
         m.set_params(c.params)
     assert_same_step(got, _FRESH[name, dtype], f"{name} {dtype} after a {first} step")
+
+
+PARITY_LEFTOVER_FIXTURES = ["mudpt_tiny", "coop_tiny_end", "cocoop_tiny", "vpt_tiny", "mpt_tiny", "umudpt_tiny", "uumudpt_tiny"]
+
+
+@pytest.mark.parametrize("name", PARITY_LEFTOVER_FIXTURES)
+def test_parity_handle_leaves_nothing_behind(name):
+    """test_step_leaves_nothing_behind on a dtype "fp32" handle, one fixture per variant, with vis_exact_attn flipped 0 -> 1 -> 0 between the
+    steps: another seed's step and eval forward under the default, the same under vis_exact_attn = 1 (the vision tower's backward then reads
+    the fp16 qkv copy and the lse that attention_exact.hip wrote, not the fp16 kernel's), the knob back at 0, the fixture's parameters, the
+    fixture's step on its first B - 1 images.  That step equals the same step on a freshly built fp32 handle bit for bit: a stale qkv_lp or
+    lse of the other kernel, or of the larger batch, shows here."""
+    c, dtype = load(name), "fp32"
+    B = len(c.labels)
+    images, labels = c.images[:B - 1], c.labels[:B - 1]
+    fresh = build(name, dtype)
+    want = step(fresh, images, labels)
+    fresh.close()
+    m = handle(name, dtype)
+    try:
+        dirty(m, c, B, B - 1)
+        with knobs_set(m, dtype, (("vis_exact_attn", 1),)):
+            dirty(m, c, B, B - 1)
+        m.set_params(c.params)
+        got = step(m, images, labels)
+    finally:
+        m.set_params(c.params)
+    assert_same_step(got, want, f"{name} fp32 after steps under vis_exact_attn 0, 1")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -138,20 +138,74 @@ def test_parity_mode_at_logit_scale_100():
     m.close()
 
 
+@pytest.mark.parametrize("name", ["umudpt_tiny", "umudpt_vitb16_b2_s100"])
+def test_parity_mode_training_step(name):
+    """One training step on a dtype "fp32" handle, in the pieces of test_logits_loss_grads_taps_match_reference: the forward is the inference
+    forward bit for bit and the loss the fixture's within the parity mode's logit bound; (a) what the towers leave and (c) every tensor
+    against the fixture with the bf16 constants (the mode runs lp_grad = 1); (b) the generators' own fp32 backward keeps its fp32 bound;
+    inside (a) / (c), every tensor against the restatement within twice what this fixture measured (test_knobs_gpu.PARITY_STEP_MEASURED)."""
+    from tests.helpers import check_parity_step_grads
+    from tests.test_exact_gpu import LOGIT_ATOL_EXACT
+    from tests.test_knobs_gpu import PARITY_STEP_MEASURED
+    case = load(name)
+    B, c = len(case.labels), case.cfg
+    m = build(case, "fp32")
+    m.eval()
+    logits = m(case.images).cpu()
+    m.train()
+    loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
+    torch.cuda.synchronize()
+    assert_training_forward_is_the_inference_forward(logits2, logits, "fp32")
+    slack = 1.0 if c.v_layers >= 12 else 3.0  # test_exact_gpu.py::test_logits_at_scale_100_within_1e_3: the tiny shape in the default parity mode
+    print(f"{name} parity mode: |loss - reference| {abs(loss.item() - case.loss):.3e} |logit - reference| max {(logits - case.logits).abs().max().item():.3e}")
+    assert abs(loss.item() - case.loss) <= slack * LOGIT_ATOL_EXACT
+    got = {k: v.detach().cpu().clone() for k, v in m.grads().items()}
+    tag = f"{name} fp32"
+    _, _, ref_grads, ref_dG = restated(case)
+    dG = m.debug_read("umudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
+    m.close()
+    check_tower_grad(dG, ref_dG, "bf16", f"{tag} (a) dG")
+    for k in (R.CTX, R.DEEP):
+        if got[k].numel():
+            check_tower_grad(got[k], ref_grads[k], "bf16", f"{tag} (a) {k}")
+    scale = dG.pow(2).mean().sqrt().item()  # (b)
+    atol, rtol = 3e-5 * math.sqrt(4 * c.t_width) * scale, 1e-5
+    _, _, g64 = R.generator_backward(case.params, R.prompt_tables(case.params), dG)
+    worst = max(((got[k].double() - r).abs() / (atol + rtol * r.abs())).max().item() for k, r in g64.items())
+    print(f"{tag} (b): worst generator gradient at {worst:.3f} of the fp32 bound")
+    assert worst <= 1.0
+    for k in case.keys:  # (c)
+        if got[k].numel() == 0:
+            continue
+        if k in case.grads:
+            if case.grads[k].abs().max().item() == 0:
+                assert torch.count_nonzero(got[k]) == 0, k
+                continue
+            check_tower_grad(got[k], case.grads[k], "bf16", f"{tag} (c) {k}")
+        else:
+            rows, vals, rms = case.grad_samples[k]
+            if rms == 0:
+                assert torch.count_nonzero(got[k]) == 0, k
+                continue
+            check_tower_grad(got[k][rows], vals, "bf16", f"{tag} (c) {k} [16 rows]", rms=rms)
+    check_parity_step_grads(name, [(k, got[k], ref_grads[k]) for k in case.keys], PARITY_STEP_MEASURED[name])
+
+
 def test_unconsumed_layers_get_exactly_zero():
     """depth 5 over 3-layer towers: the vision tower never splices G[3], G[4], so those rows of dG are exactly zero; the generator's
     attention stays inside one layer, so dX of those layers -- and with the text tower's own zero the gradient of deep_prompts[2:] -- is
     exactly zero too, while every weight gradient still matches (the parametrised test above)."""
     case = load("umudpt_tiny_d5")
-    m = build(case, "fp16")
-    m.forward_backward(case.images, case.labels)
-    c = case.cfg
-    dG = m.debug_read("umudpt.dG", len(case.labels)).view(c.depth, c.n_ctx, c.v_width)
-    assert torch.count_nonzero(dG[3:]) == 0 and torch.count_nonzero(dG[:3]) > 0
-    g = m.grads()[R.DEEP].cpu()
-    assert torch.count_nonzero(g[2:]) == 0 and torch.count_nonzero(g[:2]) > 0
-    assert torch.count_nonzero(restated(case)[2][R.DEEP][2:]) == 0
-    m.close()
+    for dtype in ("fp16", "fp32"):  # the parity mode's handle too: its backward reads other copies of the forward's buffers
+        m = build(case, dtype)
+        m.forward_backward(case.images, case.labels)
+        c = case.cfg
+        dG = m.debug_read("umudpt.dG", len(case.labels)).view(c.depth, c.n_ctx, c.v_width)
+        assert torch.count_nonzero(dG[3:]) == 0 and torch.count_nonzero(dG[:3]) > 0, dtype
+        g = m.grads()[R.DEEP].cpu()
+        assert torch.count_nonzero(g[2:]) == 0 and torch.count_nonzero(g[:2]) > 0, dtype
+        assert torch.count_nonzero(restated(case)[2][R.DEEP][2:]) == 0
+        m.close()
 
 
 def test_depth_one_lists_an_empty_deep_prompts():

@@ -162,24 +162,78 @@ def test_parity_mode_at_logit_scale_100():
     m.close()
 
 
+@pytest.mark.parametrize("name", ["uumudpt_tiny", "uumudpt_vitb16_b2_s100"])
+def test_parity_mode_training_step(name):
+    """One training step on a dtype "fp32" handle, in the pieces of test_logits_loss_grads_taps_match_reference: the forward is the inference
+    forward bit for bit and the loss the fixture's within the parity mode's logit bound; (a) what the towers leave and (c) every tensor
+    against the fixture with the bf16 constants (the mode runs lp_grad = 1); (b) the generators' own fp32 backward keeps its fp32 bound;
+    inside (a) / (c), every tensor against the restatement within twice what this fixture measured (test_knobs_gpu.PARITY_STEP_MEASURED)."""
+    from tests.helpers import check_parity_step_grads
+    from tests.test_exact_gpu import LOGIT_ATOL_EXACT
+    from tests.test_knobs_gpu import PARITY_STEP_MEASURED
+    case = load(name)
+    B, c = len(case.labels), case.cfg
+    m = build(case, "fp32")
+    m.eval()
+    logits = m(case.images).cpu()
+    m.train()
+    loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
+    torch.cuda.synchronize()
+    assert_training_forward_is_the_inference_forward(logits2, logits, "fp32")
+    slack = 1.0 if c.v_layers >= 12 else 3.0  # test_exact_gpu.py::test_logits_at_scale_100_within_1e_3: the tiny shape in the default parity mode
+    print(f"{name} parity mode: |loss - reference| {abs(loss.item() - case.loss):.3e} |logit - reference| max {(logits - case.logits).abs().max().item():.3e}")
+    assert abs(loss.item() - case.loss) <= slack * LOGIT_ATOL_EXACT
+    got = {k: v.detach().cpu().clone() for k, v in m.grads().items()}
+    tag = f"{name} fp32"
+    _, _, ref_grads, ref_dG, ref_dT = restated(case)
+    dG = m.debug_read("uumudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
+    dT = m.debug_read("uumudpt.dT", B).view(c.depth - 1, c.n_ctx, c.embed_dim) if c.depth > 1 else None
+    m.close()
+    check_tower_grad(dG, ref_dG, "bf16", f"{tag} (a) dG")
+    if dT is not None:
+        check_tower_grad(dT, ref_dT, "bf16", f"{tag} (a) dT")
+    for k in (R.CTX, R.DEEP, R.VCTX, R.VDEEP):
+        if got[k].numel():
+            check_tower_grad(got[k], ref_grads[k], "bf16", f"{tag} (a) {k}")
+    generator_bound(got, case, R.GEN1, R.prompt_tables(case.params), dG, c.t_width, f"{tag} Gen1")  # (b)
+    if dT is not None:
+        generator_bound(got, case, R.GEN2, case.params[R.VDEEP], dT, c.v_width, f"{tag} Gen2")
+    for k in case.keys:  # (c)
+        if got[k].numel() == 0:
+            continue
+        if k in case.grads:
+            if case.grads[k].abs().max().item() == 0:
+                assert torch.count_nonzero(got[k]) == 0, k
+                continue
+            check_tower_grad(got[k], case.grads[k], "bf16", f"{tag} (c) {k}")
+        else:
+            rows, vals, rms = case.grad_samples[k]
+            if rms == 0:
+                assert torch.count_nonzero(got[k]) == 0, k
+                continue
+            check_tower_grad(got[k][rows], vals, "bf16", f"{tag} (c) {k} [16 rows]", rms=rms)
+    check_parity_step_grads(name, [(k, got[k], ref_grads[k]) for k in case.keys], PARITY_STEP_MEASURED[name])
+
+
 def test_unconsumed_layers_get_exactly_zero():
     """depth 5 over 3-layer towers: the vision tower never splices G[3], G[4], the text tower never deep_prompts[2:] + T[2:], so those rows of dG
     and dT are exactly zero; either generator's attention stays inside one layer, so its dX of those layers is exactly zero too, and with it
     the gradients of deep_prompts[2:] and visual_ctx_deep_prompts[2:] -- each the sum of a tower's zero and a generator's zero."""
     case = load("uumudpt_tiny_d5")
-    m = build(case, "fp16")
-    m.forward_backward(case.images, case.labels)
-    c, B = case.cfg, len(case.labels)
-    dG = m.debug_read("uumudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
-    dT = m.debug_read("uumudpt.dT", B).view(c.depth - 1, c.n_ctx, c.embed_dim)
-    assert torch.count_nonzero(dG[3:]) == 0 and torch.count_nonzero(dG[:3]) > 0
-    assert torch.count_nonzero(dT[2:]) == 0 and torch.count_nonzero(dT[:2]) > 0
-    ref = restated(case)[2]
-    for k in (R.DEEP, R.VDEEP):
-        g = m.grads()[k].cpu()
-        assert torch.count_nonzero(g[2:]) == 0 and torch.count_nonzero(g[:2]) > 0, k
-        assert torch.count_nonzero(ref[k][2:]) == 0
-    m.close()
+    for dtype in ("fp16", "fp32"):  # the parity mode's handle too: its backward reads other copies of the forward's buffers
+        m = build(case, dtype)
+        m.forward_backward(case.images, case.labels)
+        c, B = case.cfg, len(case.labels)
+        dG = m.debug_read("uumudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
+        dT = m.debug_read("uumudpt.dT", B).view(c.depth - 1, c.n_ctx, c.embed_dim)
+        assert torch.count_nonzero(dG[3:]) == 0 and torch.count_nonzero(dG[:3]) > 0, dtype
+        assert torch.count_nonzero(dT[2:]) == 0 and torch.count_nonzero(dT[:2]) > 0, dtype
+        ref = restated(case)[2]
+        for k in (R.DEEP, R.VDEEP):
+            g = m.grads()[k].cpu()
+            assert torch.count_nonzero(g[2:]) == 0 and torch.count_nonzero(g[:2]) > 0, (k, dtype)
+            assert torch.count_nonzero(ref[k][2:]) == 0
+        m.close()
 
 
 def test_depth_one_lists_empty_tensors_and_idles_gen2():

@@ -79,6 +79,33 @@ def test_parity_mode_at_logit_scale_100(name):
     m.close()
 
 
+@pytest.mark.parametrize("name", ["vpt_tiny", "mpt_tiny", "mpt_tiny_textonly", "vpt_vitb16_b2_s100", "mpt_vitb16_b2_s100"])
+def test_parity_mode_training_step(name):
+    """One training step on a dtype "fp32" handle: the forward is the inference forward bit for bit, the loss is the fixture's within the
+    parity mode's logit bound, every gradient passes check_grads with the bf16 constants against the fixture and the restatement, and
+    inside that twice the figures this fixture measured (test_knobs_gpu.PARITY_STEP_MEASURED)."""
+    from tests.helpers import check_parity_step_grads
+    from tests.test_exact_gpu import LOGIT_ATOL_EXACT
+    from tests.test_knobs_gpu import PARITY_STEP_MEASURED
+    case = R.VptCase(name)
+    m = build(case, "fp32")
+    m.eval()
+    logits = m(case.images).cpu()
+    m.train()
+    loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
+    torch.cuda.synchronize()
+    assert_training_forward_is_the_inference_forward(logits2, logits, "fp32")
+    slack = 1.0 if case.cfg.v_layers >= 12 else 3.0  # test_exact_gpu.py::test_logits_at_scale_100_within_1e_3: the tiny shape in the default parity mode
+    print(f"{name} parity mode: |loss - reference| {abs(loss.item() - case.loss):.3e} |logit - reference| max {(logits - case.logits).abs().max().item():.3e}")
+    assert abs(loss.item() - case.loss) <= slack * LOGIT_ATOL_EXACT
+    got = {k: v.detach().cpu().clone() for k, v in m.grads().items()}
+    m.close()
+    restated = R.forward_backward(case.cfg, case.frozen, case.params, case.trainer, case.shape, case.class_embedding, case.eot, case.images, case.labels)[2]
+    check_grads(got, case.grads, "bf16", f"{name} fp32 vs fixture")
+    check_grads(got, restated, "bf16", f"{name} fp32 vs restatement")
+    check_parity_step_grads(name, [(k, got[k], restated[k]) for k in case.keys], PARITY_STEP_MEASURED[name])
+
+
 def test_vpt_text_features_are_computed_once():
     """VPT's text tower has nothing to learn: after the first pass no step and no eval forward launches a text-tower pass or a text-side
     head kernel, and the logits are those of a handle that recomputes them."""
