@@ -49,6 +49,12 @@ class ModelShape:
                           ctx_len=sd["positional_embedding"].shape[0], embed_dim=sd["text_projection"].shape[1],
                           n_ctx=n_ctx, depth=depth)
 
+    @staticmethod
+    def from_config(cfg, n_ctx: int, depth: int) -> "ModelShape":
+        """The backbone dimensions of ``cfg`` -- any object with this class's backbone fields -- with the prompt config given here: a
+        variant decides its own n_ctx / depth."""
+        return ModelShape(**{f: getattr(cfg, f) for f in ModelShape.__dataclass_fields__ if f not in ("n_ctx", "depth")}, n_ctx=n_ctx, depth=depth)
+
 
 def umudpt_init_tensors(n_ctx: int, depth: int, d_t: int, d_v: int, ctx_rows: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """Initial values of UMuDPT's 20 trainables, drawn as the reference draws them (trainers/umudpt.py:96-124): the same torch modules

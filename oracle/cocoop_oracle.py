@@ -4,8 +4,8 @@ A from-scratch fp32 restatement, in plain torch CPU ops, of what the reference c
 
   * ``trainers/cocoop.py:141-165``  PromptLearner.forward (meta_net bias, ctx shift, construct_prompts) -> :func:`prompts_for`
   * ``clip/model.py:478-496``       VisionTransformer.forward (the vanilla ViT: ``clip.load(..., cfg=None)``,
-                                    ``trainers/cocoop.py:38``)                                            -> :func:`vision_tower`
-  * ``trainers/cocoop.py:51-64``    TextEncoder.forward                                                  -> :func:`text_tower`
+                                    ``trainers/cocoop.py:38``)                                            -> ``mudpt_oracle.vision_tower``, no rows
+  * ``trainers/cocoop.py:51-64``    TextEncoder.forward                                                  -> ``mudpt_oracle.text_tower``
   * ``trainers/cocoop.py:178-198``  CustomCLIP.forward (per-image text features, logits, CE in training)  -> :func:`forward`
   * ``trainers/cocoop.py:258-261``  loss.backward() w.r.t. the ``prompt_learner`` parameters (:222-226)   -> :func:`forward_backward`
 
@@ -19,7 +19,6 @@ import math
 from typing import Dict, List, Optional, Tuple
 
 import torch
-import torch.nn.functional as F
 
 from . import mudpt_oracle as O
 
@@ -65,19 +64,6 @@ def flatten(tensors: Dict[str, Tensor]) -> Tensor:
     return torch.cat([tensors[k].reshape(-1) for k in TRAINABLE_ORDER])
 
 
-def vision_tower(cfg: O.Config, sd: Dict[str, Tensor], images: Tensor) -> Tensor:
-    """clip/model.py:478-496 (img_prompt False): conv-as-GEMM, CLS + positional embedding, ln_pre, blocks, ln_post(CLS) @ proj."""
-    B = images.shape[0]
-    w = sd["visual.conv1.weight"].reshape(cfg.v_width, -1)
-    x = O.patchify(images.float(), cfg.patch) @ w.t()
-    cls = sd["visual.class_embedding"].expand(B, 1, -1)
-    x = torch.cat([cls, x], dim=1) + sd["visual.positional_embedding"]
-    x = O.layer_norm(x, sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"])
-    for i in range(cfg.v_layers):
-        x = O.block(x, sd, f"visual.transformer.resblocks.{i}.", cfg.v_heads, None)
-    return O.layer_norm(x[:, 0], sd["visual.ln_post.weight"], sd["visual.ln_post.bias"]) @ sd["visual.proj"]
-
-
 def meta_net(params: Dict[str, Tensor], im_features: Tensor) -> Tensor:
     """trainers/cocoop.py:103-107,145."""
     P = "prompt_learner.meta_net."
@@ -94,30 +80,18 @@ def prompts_for(cfg: O.Config, params: Dict[str, Tensor], class_embedding: Tenso
                       class_embedding[:, 1 + n:].unsqueeze(0).expand(B, -1, -1, -1)], dim=2)
 
 
-def text_tower(cfg: O.Config, sd: Dict[str, Tensor], prompts: Tensor, eot: Tensor) -> Tensor:
-    """trainers/cocoop.py:51-64 on [S, ctx_len, d_t] prompts: + positional embedding, causal blocks, ln_final, EOT row @ projection."""
-    x = prompts + sd["positional_embedding"]
-    S, L, _ = x.shape
-    mask = O.causal_mask(L)
-    for i in range(cfg.t_layers):
-        x = O.block(x, sd, f"transformer.resblocks.{i}.", cfg.t_heads, mask)
-    x = O.layer_norm(x, sd["ln_final.weight"], sd["ln_final.bias"])
-    return x[torch.arange(S), eot] @ sd["text_projection"]
-
-
 def forward(cfg: O.Config, sd: Dict[str, Tensor], params: Dict[str, Tensor], class_embedding: Tensor, eot: Tensor,
             images: Tensor, taps: Dict[str, Tensor] = None) -> Tensor:
-    """trainers/cocoop.py:178-195 -> logits [B, C].  taps (tests): receives the text-tower input "prompts" [B * C, ctx_len, d_t] with its
-    gradient retained, i.e. the per-(image, class) terms whose sums are the ctx / meta_net gradients."""
+    """trainers/cocoop.py:178-195 -> logits [B, C]: the vanilla ViT (no prompt rows), then the text tower once per (image, class) prompt.
+    taps (tests): receives the text-tower input "prompts" [B * C, ctx_len, d_t] with its gradient retained, i.e. the per-(image, class)
+    terms whose sums are the ctx / meta_net gradients."""
     B, C = images.shape[0], class_embedding.shape[0]
-    img = vision_tower(cfg, sd, images)
-    img = img / img.norm(dim=-1, keepdim=True)
+    img = O.unit(O.vision_tower(cfg, sd, images))
     prompts = prompts_for(cfg, params, class_embedding, img).reshape(B * C, cfg.ctx_len, cfg.t_width)
     if taps is not None and prompts.requires_grad:
         prompts.retain_grad()
         taps["prompts"] = prompts
-    txt = text_tower(cfg, sd, prompts, eot.repeat(B)).reshape(B, C, -1)
-    txt = txt / txt.norm(dim=-1, keepdim=True)
+    txt = O.unit(O.text_tower(cfg, sd, prompts, eot.repeat(B)).reshape(B, C, -1))
     return sd["logit_scale"].exp() * torch.einsum("be,bce->bc", img, txt)
 
 
@@ -125,14 +99,9 @@ def forward_backward(cfg: O.Config, sd: Dict[str, Tensor], params: Dict[str, Ten
                      images: Tensor, labels: Tensor, taps: Dict[str, Tensor] = None):
     """trainers/cocoop.py:196-197 + :258-261: mean cross-entropy and its gradient w.r.t. the 5 trainables.
     taps (tests): "dprompts" [B, C, ctx_len, d_t] = gradient w.r.t. every (image, class) prompt (the terms the gradients sum over)."""
-    leaf = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
-    inner = {} if taps is not None else None
-    logits = forward(cfg, sd, leaf, class_embedding, eot, images, inner)
-    loss = F.cross_entropy(logits, labels.long())
-    if taps is None:
-        grads = torch.autograd.grad(loss, [leaf[k] for k in TRAINABLE_ORDER])
-    else:
-        loss.backward()
-        grads = [leaf[k].grad for k in TRAINABLE_ORDER]
-        taps["dprompts"] = inner["prompts"].grad.detach().reshape(images.shape[0], class_embedding.shape[0], cfg.ctx_len, cfg.t_width)
-    return loss.detach(), logits.detach(), dict(zip(TRAINABLE_ORDER, grads))
+    inner = None if taps is None else {}
+    out = O.loss_and_grads(lambda leaf: forward(cfg, sd, leaf, class_embedding, eot, images, inner), params, labels, TRAINABLE_ORDER, inner,
+                           keep=() if taps is None else ("prompts",))
+    if taps is not None:
+        taps["dprompts"] = out[3].reshape(images.shape[0], class_embedding.shape[0], cfg.ctx_len, cfg.t_width)
+    return out[:3]

@@ -4,11 +4,15 @@ This file is a from-scratch fp32 restatement, in plain torch CPU ops, of the ari
 the reference performs in
 
   * ``trainers/mudpt.py:117-130``  MuDPTPromptLearner.forward   -> :func:`prompt_learner`
-  * ``clip/model.py:526-553``      VisionTransformer_MuDPT.forward -> :func:`vision_tower`
+  * ``clip/model.py:526-553``      VisionTransformer_MuDPT.forward -> :func:`vision_tower`  (fed by :func:`forward`)
   * ``clip/model.py:275-301``      ResidualAttentionBlock_MuDPT.forward -> :func:`block`
   * ``trainers/mudpt.py:142-156``  TextEncoder.forward          -> :func:`text_tower`
   * ``trainers/mudpt.py:170-184``  CustomCLIP.forward           -> :func:`forward`
   * ``trainers/mudpt.py:249-251``  cross-entropy + backward     -> :func:`forward_backward`
+
+:func:`vision_tower` and :func:`text_tower` are the ONLY restatement of the two transformers: the other variants' restatements
+(``oracle/cocoop_oracle.py``, ``tests/*_reference.py``) build their prompt rows and call them, and share :func:`cosine_logits` and
+:func:`loss_and_grads`.
 
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import
 it.  The product path (``mudpt_amd``) never does and fails loudly when its HIP library is missing.
@@ -315,71 +319,101 @@ def prompt_learner(cfg: Config, params: Dict[str, Tensor], class_embedding: Tens
     return prompts, shared, params[P + "deep_prompts"], t2v
 
 
-def vision_tower(cfg: Config, sd: Dict[str, Tensor], params: Dict[str, Tensor], images: Tensor,
-                 shared: Tensor, t2v: Tensor, taps: Optional[dict] = None):
-    """clip/model.py:526-553.  Returns (image_features [B, e], v->t text prompts [D-1, n, e])."""
-    V = "image_encoder."
+def vision_tower(cfg: Config, sd: Dict[str, Tensor], images: Tensor, rows: Optional[Tensor] = None, deep: Optional[Tensor] = None,
+                 taps: Optional[dict] = None, block=block, patch_embed=None) -> Tensor:
+    """The ViT of every variant (clip/model.py:478-496 vanilla, :526-553 MuDPT, :574-597 UMuDPT, :443-496 VPT) -> image features [B, e].
+
+    ``rows [n, d_v]``: the input prompt rows, already summed by the caller, appended after the positional embedding (they get none) and
+    before ln_pre.  ``deep [D1, n, d_v]``: block i replaces the LAST n rows by deep[i - 1] while 1 <= i <= D1 (clip/model.py:279,290-297);
+    block 0 never splices and the blocks past D1 keep propagating the rows.  taps: "visual.ln_pre", "vis.x_in.<i>" = the input of block i
+    after its splice, and :func:`block`'s outputs.  ``block`` / ``patch_embed(patches, w)``: a rounding model of the block and of the
+    patch GEMM in their place (tests/precision_ablation.py)."""
     B = images.shape[0]
-    n = cfg.n_ctx
     w = sd["visual.conv1.weight"].reshape(cfg.v_width, -1)
-    x = patchify(images.float(), cfg.patch) @ w.t()
+    x = patchify(images.float(), cfg.patch)
+    x = x @ w.t() if patch_embed is None else patch_embed(x, w)
     cls = sd["visual.class_embedding"].expand(B, 1, -1)
     x = torch.cat([cls, x], dim=1) + sd["visual.positional_embedding"]
-    vp = (params[V + "visual_ctx"] + shared).unsqueeze(0).expand(B, -1, -1)  # no pos-emb on prompt rows
-    x = torch.cat([x, vp], dim=1)
-    deep = t2v + params[V + "visual_ctx_deep_prompts"]
-    v2t = (params[V + "visual_ctx_deep_prompts"] @ params[V + "visual_ctx_deep_projections.weight"].t()
-           + params[V + "visual_ctx_deep_projections.bias"])
+    if rows is not None:
+        x = torch.cat([x, rows.unsqueeze(0).expand(B, -1, -1)], dim=1)
     x = layer_norm(x, sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"])
     if taps is not None:
         taps["visual.ln_pre"] = x
     L = x.shape[1]
     for i in range(cfg.v_layers):
-        # clip/model.py:279,290-297: layer i >= 1 replaces the LAST n rows by deep[i-1] while i-1 < D-1
-        if i >= 1 and (i - 1) < deep.shape[0]:
-            x = torch.cat([x[:, :L - n], deep[i - 1].unsqueeze(0).expand(B, -1, -1)], dim=1)
+        if deep is not None and 1 <= i <= deep.shape[0]:
+            x = torch.cat([x[:, :L - deep.shape[1]], deep[i - 1].unsqueeze(0).expand(B, -1, -1)], dim=1)
+        if taps is not None:
+            taps[f"vis.x_in.{i}"] = x
         x = block(x, sd, f"visual.transformer.resblocks.{i}.", cfg.v_heads, None, taps)
-    f = layer_norm(x[:, 0], sd["visual.ln_post.weight"], sd["visual.ln_post.bias"]) @ sd["visual.proj"]
-    return f, v2t
+    return layer_norm(x[:, 0], sd["visual.ln_post.weight"], sd["visual.ln_post.bias"]) @ sd["visual.proj"]
 
 
-def text_tower(cfg: Config, sd: Dict[str, Tensor], prompts: Tensor, eot: Tensor, deep: Tensor,
-               taps: Optional[dict] = None) -> Tensor:
-    """trainers/mudpt.py:142-156 with the text branch of clip/model.py:281-289."""
-    n = cfg.n_ctx
-    x = prompts + sd["positional_embedding"]
-    C, L, _ = x.shape
+def text_tower(cfg: Config, sd: Dict[str, Tensor], prompts: Tensor, eot: Tensor, deep: Optional[Tensor] = None,
+               taps: Optional[dict] = None, block=block) -> Tensor:
+    """The causal text transformer of every variant (clip/model.py:825-838, trainers/mudpt.py:142-156 with the text branch of
+    clip/model.py:281-289) on prompts [S, L, d_t] that the caller has built -> text features [S, e] at the rows ``eot``; L may stop
+    short of ctx_len behind the last EOT row (causal: the rows in front do not change).
+
+    ``deep [D1, n, d_t]``: block i replaces rows 1..n by deep[i - 1] while 1 <= i <= D1, without a positional embedding (appendix A.6).
+    taps: "txt.x_in.<i>" = the input of block i after its splice, and :func:`block`'s outputs."""
+    S, L, _ = prompts.shape
+    x = prompts + sd["positional_embedding"][:L]
     mask = causal_mask(L)
     for i in range(cfg.t_layers):
-        if i >= 1 and (i - 1) < deep.shape[0]:  # rows 1..n replaced, no pos-emb (appendix A.6)
-            x = torch.cat([x[:, :1], deep[i - 1].unsqueeze(0).expand(C, -1, -1), x[:, 1 + n:]], dim=1)
+        if deep is not None and 1 <= i <= deep.shape[0]:
+            x = torch.cat([x[:, :1], deep[i - 1].unsqueeze(0).expand(S, -1, -1), x[:, 1 + deep.shape[1]:]], dim=1)
+        if taps is not None:
+            taps[f"txt.x_in.{i}"] = x
         x = block(x, sd, f"transformer.resblocks.{i}.", cfg.t_heads, mask, taps)
     x = layer_norm(x, sd["ln_final.weight"], sd["ln_final.bias"])
-    return x[torch.arange(C), eot] @ sd["text_projection"]
+    return x[torch.arange(S), eot] @ sd["text_projection"]
+
+
+def unit(f: Tensor) -> Tensor:
+    return f / f.norm(dim=-1, keepdim=True)
+
+
+def cosine_logits(sd: Dict[str, Tensor], img: Tensor, txt: Tensor) -> Tensor:
+    """trainers/mudpt.py:178-182: exp(logit_scale) times the cosine of image features [B, e] and text features [C, e] -> [B, C]."""
+    return sd["logit_scale"].exp() * unit(img) @ unit(txt).t()
+
+
+def loss_and_grads(forward, params: Dict[str, Tensor], labels: Tensor, order: Optional[List[str]] = None, taps: Optional[dict] = None, keep=()):
+    """Mean cross-entropy of ``forward(leaves)`` (logits [B, C] from leaf copies of ``params``) and its gradient w.r.t. the tensors named
+    by ``order`` (default: all of ``params``), zeros where a tensor is not used -> (loss, logits, {key: grad}), followed by the gradient
+    of each intermediate ``taps[k]`` for k in ``keep`` (``forward`` fills ``taps``)."""
+    leaf = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
+    logits = forward(leaf)
+    for k in keep:
+        taps[k].retain_grad()
+    loss = F.cross_entropy(logits, labels.long())
+    loss.backward()
+    grad = lambda t: t.grad.detach() if t.grad is not None else torch.zeros_like(t)  # noqa: E731
+    return (loss.detach(), logits.detach(), {k: grad(leaf[k]) for k in (order or leaf)}, *(grad(taps[k]) for k in keep))
 
 
 def forward(cfg: Config, sd: Dict[str, Tensor], params: Dict[str, Tensor], class_embedding: Tensor,
             eot: Tensor, images: Tensor, taps: Optional[dict] = None) -> Tensor:
-    """trainers/mudpt.py:170-184 CustomCLIP.forward -> logits [B, C] fp32."""
+    """trainers/mudpt.py:170-184 CustomCLIP.forward -> logits [B, C] fp32.  The vision tower's prompt rows are visual_ctx + the projected
+    text ctx and its deep rows visual_ctx_deep_prompts + the projected text deep prompts (clip/model.py:530-541); the text tower's deep
+    rows are deep_prompts + the projected vision deep prompts (trainers/mudpt.py:172-176)."""
+    V = "image_encoder.visual_ctx"
     prompts, shared, text_deep, t2v = prompt_learner(cfg, params, class_embedding)
-    img_f, v2t = vision_tower(cfg, sd, params, images, shared, t2v, taps)
+    rows = params[V] + shared
+    deep = t2v + params[V + "_deep_prompts"]
+    v2t = params[V + "_deep_prompts"] @ params[V + "_deep_projections.weight"].t() + params[V + "_deep_projections.bias"]
+    img_f = vision_tower(cfg, sd, images, rows, deep, taps)
     txt_f = text_tower(cfg, sd, prompts, eot, text_deep + v2t, taps)
     if taps is not None:
         taps["image_features"], taps["text_features"] = img_f, txt_f
-    img_f = img_f / img_f.norm(dim=-1, keepdim=True)
-    txt_f = txt_f / txt_f.norm(dim=-1, keepdim=True)
-    return sd["logit_scale"].exp() * img_f @ txt_f.t()
+    return cosine_logits(sd, img_f, txt_f)
 
 
 def forward_backward(cfg: Config, sd: Dict[str, Tensor], params: Dict[str, Tensor],
                      class_embedding: Tensor, eot: Tensor, images: Tensor, labels: Tensor):
     """trainers/mudpt.py:249-251: mean cross-entropy and its gradient w.r.t. the 10 trainables."""
-    leaf = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
-    logits = forward(cfg, sd, leaf, class_embedding, eot, images)
-    loss = F.cross_entropy(logits, labels.long())
-    grads = torch.autograd.grad(loss, [leaf[k] for k in TRAINABLE_ORDER], allow_unused=True)
-    grads = {k: (g if g is not None else torch.zeros_like(leaf[k])) for k, g in zip(TRAINABLE_ORDER, grads)}
-    return loss.detach(), logits.detach(), grads
+    return loss_and_grads(lambda leaf: forward(cfg, sd, leaf, class_embedding, eot, images), params, labels, TRAINABLE_ORDER)
 
 
 def sgd_step(param: Tensor, grad: Tensor, buf: Optional[Tensor], lr: float, momentum: float = 0.9,

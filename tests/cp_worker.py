@@ -25,8 +25,7 @@ def main():
     img, lab = c.images[rank * per:(rank + 1) * per], c.labels[rank * per:(rank + 1) * per]
     from mudpt_amd.model import CustomCLIP, ModelShape
     cfg = c.cfg
-    shape = ModelShape(cfg.image_size, cfg.patch, cfg.v_width, cfg.v_layers, cfg.v_heads, cfg.t_width, cfg.t_layers, cfg.t_heads,
-                       cfg.ctx_len, cfg.embed_dim, cfg.n_ctx, cfg.depth)
+    shape = ModelShape.from_config(cfg, cfg.n_ctx, cfg.depth)
     m = CustomCLIP(shape, c.frozen, c.tokens, max_batch=per, dtype=dtype, class_shard=parallel.class_range(len(c.tokens), rank, world))
     m.set_params(c.params)
     loss, logits = m.forward_backward(img, lab, grad_scale=1.0 / world, return_logits=True)

@@ -12,37 +12,62 @@ from oracle import mudpt_oracle as O
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-class GoldenCase:
+class FixtureCase:
+    """One tests/golden/<name>.npz fixture of any variant, with everything the file holds as a recipe rebuilt: the frozen weights and the
+    images from their seeds (the images held to the stored checksum), the tokenized class prompts with their EOT rows and token embeddings,
+    labels, the reference's logits and loss, and the sampled block inputs ``taps`` = {"<vis|txt>.<i>": ([seq, rows, d], rows)}.  A variant's
+    loader subclasses it and adds its own fields; ``keys`` (its trainables in order) lets :meth:`load_grads` read the gradients."""
+
+    def __init__(self, name: str):
+        z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+        self.name, self.z = name, z
+        self.cfg = O.Config(**ast.literal_eval(str(z["config"])))
+        self.seeds = tuple(int(v) for v in z["seeds"])  # (frozen weights, trainables, images); the zero-shot fixtures have no trainables
+        self.frozen = O.make_frozen_state(self.cfg, self.seeds[0])
+        if "logit_scale" in z.files:  # the *_s100 fixtures: exp(logit_scale) = 100, what pretrained CLIP checkpoints hold (clip/model.py:919)
+            self.frozen["logit_scale"] = torch.tensor(float(z["logit_scale"]))
+        if "classnames" in z.files:
+            self.classnames = [str(v) for v in z["classnames"]]
+        if "tokenized_prompts" in z.files:
+            self.tokens = torch.from_numpy(z["tokenized_prompts"]).long()
+            self.eot = self.tokens.argmax(dim=-1)  # trainers/mudpt.py:154
+            self.class_embedding = self.frozen["token_embedding.weight"][self.tokens]
+        if "ctx_token_ids" in z.files:
+            self.ctx_token_ids = [int(v) for v in z["ctx_token_ids"]]
+        self.labels = torch.from_numpy(z["labels"])
+        g = torch.Generator().manual_seed(self.seeds[-1])
+        self.images = torch.randn(len(self.labels), 3, self.cfg.image_size, self.cfg.image_size, generator=g)
+        if "images_checksum" in z.files:  # the seeded images are the ones the fixture was generated from
+            img = self.images.double()
+            np.testing.assert_allclose([img.sum().item(), img.abs().sum().item()], z["images_checksum"], rtol=1e-12)
+        self.logits = torch.from_numpy(z["logits"])
+        if "loss" in z.files:
+            self.loss = float(z["loss"])
+        self.taps = {k[4:]: (torch.from_numpy(z[k]), [int(r) for r in z[k + ".rows"]]) for k in z.files if k.startswith("tap.") and k + ".rows" in z.files}
+
+    def load_grads(self):
+        """grads: the full gradients; grad_samples: (rows, values [16, cols], rms of the whole tensor) of the ones stored as sampled rows."""
+        z = self.z
+        self.grads = {k: torch.from_numpy(z["grad." + k]) for k in self.keys if "grad." + k in z.files}
+        self.grad_samples = {k: ([int(r) for r in z["grad_rows." + k + ".idx"]], torch.from_numpy(z["grad_rows." + k]), float(z["grad_rms." + k]))
+                             for k in self.keys if "grad_rows." + k in z.files}
+
+
+class GoldenCase(FixtureCase):
     """name "mudpt_*": trainers/mudpt.py fixtures; "cocoop_*": trainers/cocoop.py fixtures (5 trainables, cocoop_oracle)."""
 
     def __init__(self, name: str):
+        super().__init__(name)
         self.cocoop = name.startswith("cocoop")
-        z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
-        self.z = z
-        self.cfg = O.Config(**ast.literal_eval(str(z["config"])))
-        fs, ts, is_ = (int(v) for v in z["seeds"])
-        self.frozen = O.make_frozen_state(self.cfg, fs)
-        if "logit_scale" in z.files:  # the *_s100 fixtures: exp(logit_scale) = 100, what pretrained CLIP checkpoints hold (clip/model.py:919)
-            self.frozen["logit_scale"] = torch.tensor(float(z["logit_scale"]))
-        self.tokens = torch.from_numpy(z["tokenized_prompts"]).long()
-        self.eot = self.tokens.argmax(dim=-1)  # trainers/mudpt.py:154
-        self.class_embedding = self.frozen["token_embedding.weight"][self.tokens]
         if self.cocoop:
-            from oracle import cocoop_oracle as CO
-            self.params = CO.make_trainable_state(self.cfg, ts, self.frozen, [int(v) for v in z["ctx_token_ids"]])
+            from oracle import cocoop_oracle as variant
         else:
-            self.params = O.make_trainable_state(self.cfg, ts, self.frozen, [int(v) for v in z["ctx_token_ids"]])
-        self.labels = torch.from_numpy(z["labels"])
-        g = torch.Generator().manual_seed(is_)
-        B = len(self.labels)
-        self.images = torch.randn(B, 3, self.cfg.image_size, self.cfg.image_size, generator=g)
-        self.logits = torch.from_numpy(z["logits"])
-        self.loss = float(z["loss"])
+            variant = O
+        self.params = variant.make_trainable_state(self.cfg, self.seeds[1], self.frozen, self.ctx_token_ids)
 
     def check_recipe(self):
-        """The seeded recipe reproduced the tensors the fixture was generated from."""
-        img = self.images.double()
-        np.testing.assert_allclose([img.sum().item(), img.abs().sum().item()], self.z["images_checksum"], rtol=1e-12)
+        """The seeded recipe reproduced the tensors the fixture was generated from (the images: FixtureCase)."""
+        assert "images_checksum" in self.z.files
         f = self.frozen
         if "frozen_checksum" not in self.z.files:
             return
@@ -91,6 +116,78 @@ GRAD_RTOL = {"fp16": 2e-2, "bf16": 1.5e-1}  # relative to each gradient tensor's
 # bf16 <= 3.8e-2 over the four fixtures; the bounds leave a factor 2.3 / 1.6.
 GRAD_RMS = {"fp16": 6e-3, "bf16": 6e-2}
 GRAD_COS = {"fp16": 0.9995, "bf16": 0.99}  # direction: cosine similarity of a whole gradient tensor with the oracle's
+
+
+# ---- the steps the variants' parity suites share ---------------------------------------------------------------------------------------------
+def check_logits(logits, case, dtype, tag, slack=None, rms_bound=LOGIT_RMS, atol=LOGIT_ATOL):
+    """A handle's logits against the fixture's: rms and maximum within slack x the mode's bounds; slack defaults to TINY_SLACK on the 3-layer
+    shape.  Returns the slack (the suites hold the loss to slack * LOGIT_ATOL)."""
+    d = logits.detach().cpu() - case.logits
+    err, rms = d.abs().max().item(), d.pow(2).mean().sqrt().item()
+    slack = (TINY_SLACK if case.cfg.v_layers < 12 else 1.0) if slack is None else slack
+    print(f"{tag}: |logit - reference| max {err:.3e} rms {rms:.3e}")
+    assert rms <= slack * rms_bound[dtype] and err <= slack * atol[dtype], (tag, err, rms)
+    return slack
+
+
+def check_sampled_taps(m, case, dtype):
+    """The fixture's sampled block inputs (FixtureCase.taps: the rows a block splices, after its splice) against the handle's x_in buffers."""
+    B = len(case.labels)
+    for key, (ref, rows) in case.taps.items():
+        tower, i = key.split(".")
+        x = m.debug_read(f"{tower}.x_in.{i}", B)
+        d = case.cfg.v_width if tower == "vis" else case.cfg.t_width
+        x = x.view(-1, x.numel() // (d * (B if tower == "vis" else len(case.classnames))), d)[:, rows]
+        tol = (2e-3 if dtype == "fp16" else 3e-2) * (1 + ref.abs().max().item())
+        assert (x - ref).abs().max().item() <= tol, (key, (x - ref).abs().max().item())
+
+
+def check_parity_mode_at_scale_100(m, case):
+    """The body of the suites' test_parity_mode_at_logit_scale_100: a dtype "fp32" handle's eval logits within 1e-3 of the fixture's; closes m."""
+    m.eval()
+    logits = m(case.images).cpu()
+    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
+    print(f"{case.name} parity mode: |logit - reference| max {err:.3e} rms {rms:.3e}")
+    assert err <= 1e-3
+    m.close()
+
+
+def check_grad(g, r, dtype, tag, rms=None, rms_err=True, cos=False):
+    """One gradient tensor against its reference: the largest error within 4 GRAD_RTOL x the reference's rms and (rms_err) the rms of the
+    error within GRAD_RMS x it; cos: the cosine above GRAD_COS as well.  rms: of the whole tensor, where g and r are sampled rows of it."""
+    g, r = g.detach().float().cpu(), r.float()
+    rms = r.pow(2).mean().sqrt().item() if rms is None else rms
+    err, rel_rms = (g - r).abs().max().item(), (g - r).pow(2).mean().sqrt().item() / max(rms, 1e-30)
+    c = torch.nn.functional.cosine_similarity(g.flatten(), r.flatten(), dim=0).item() if cos else None
+    print(f"{tag}: rms {rms:.3e} max err / rms {err / max(rms, 1e-30):.3e} rms err {rel_rms:.3e}" + (f" cos {c:.6f}" if cos else ""))
+    assert err <= GRAD_RTOL[dtype] * rms * 4 + 1e-9, (tag, err, rms)
+    assert not rms_err or rel_rms <= GRAD_RMS[dtype], (tag, rel_rms)
+    assert not cos or c > GRAD_COS[dtype], (tag, c)
+
+
+def check_grads(got, ref, dtype, tag, **kw):
+    """check_grad of every tensor of ref."""
+    for k, r in ref.items():
+        check_grad(got[k], r, dtype, f"{tag} {k}", **kw)
+
+
+def check_fixture_grads(got, case, dtype, tag, factor=1.0):
+    """Every trainable against factor x the fixture's stored gradient (the reference's own autograd): the full tensor, or its sampled rows
+    with the stored rms of the whole; exactly zero where the reference's is."""
+    for k in case.keys:
+        if got[k].numel() == 0:
+            continue
+        if k in case.grads:
+            if case.grads[k].abs().max().item() == 0:
+                assert torch.count_nonzero(got[k]) == 0, k
+            else:
+                check_grad(got[k], case.grads[k] * factor, dtype, f"{tag} {k}")
+        else:
+            rows, vals, rms = case.grad_samples[k]
+            if rms == 0:
+                assert torch.count_nonzero(got[k]) == 0, k
+            else:
+                check_grad(got[k][rows], vals * factor, dtype, f"{tag} {k} [16 rows]", rms=rms * factor)
 
 
 # ---- the parity mode's training step (dtype "fp32": an fp16-typed backward with lp_grad = 1) in the variants' suites ---------------------------

@@ -97,38 +97,18 @@ def block(x, sd, prefix, heads, mask, md):
 def forward(case, vis, txt, layer_from=0):
     """logits with rounding models vis / txt (dicts site -> mode); layers below layer_from of the VISION tower run the f16 model."""
     cfg, sd, params = case.cfg, case.frozen, case.params
-    prompts, shared, text_deep, t2v = O.prompt_learner(cfg, params, case.class_embedding)
-    V = "image_encoder."
-    B, n = case.images.shape[0], cfg.n_ctx
-    w = sd["visual.conv1.weight"].reshape(cfg.v_width, -1)
-    x = linear(O.patchify(case.images.float(), cfg.patch), w, 0.0, vis.get("patch", "f32"))
-    x = torch.cat([sd["visual.class_embedding"].expand(B, 1, -1), x], dim=1) + sd["visual.positional_embedding"]
-    x = torch.cat([x, (params[V + "visual_ctx"] + shared).unsqueeze(0).expand(B, -1, -1)], dim=1)
-    deep = t2v + params[V + "visual_ctx_deep_prompts"]
-    v2t = params[V + "visual_ctx_deep_prompts"] @ params[V + "visual_ctx_deep_projections.weight"].t() + params[V + "visual_ctx_deep_projections.bias"]
-    x = O.layer_norm(x, sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"])
-    L = x.shape[1]
     f16 = {s: "f16" for s in SITES}
-    for i in range(cfg.v_layers):
-        if i >= 1 and (i - 1) < deep.shape[0]:
-            x = torch.cat([x[:, :L - n], deep[i - 1].unsqueeze(0).expand(B, -1, -1)], dim=1)
-        x = block(x, sd, f"visual.transformer.resblocks.{i}.", cfg.v_heads, None, vis if i >= layer_from else f16)
-    img_f = O.layer_norm(x[:, 0], sd["visual.ln_post.weight"], sd["visual.ln_post.bias"]) @ sd["visual.proj"]
-    # text tower on the positions the library runs (up to the last EOT; causal: identical rows)
-    Le = int(case.eot.max()) + 1
-    x = (prompts + sd["positional_embedding"])[:, :Le]
-    C = x.shape[0]
-    mask = O.causal_mask(Le)
-    tdeep = text_deep + v2t
-    for i in range(cfg.t_layers):
-        if i >= 1 and (i - 1) < tdeep.shape[0]:
-            x = torch.cat([x[:, :1], tdeep[i - 1].unsqueeze(0).expand(C, -1, -1), x[:, 1 + n:]], dim=1)
-        x = block(x, sd, f"transformer.resblocks.{i}.", cfg.t_heads, mask, txt)
-    x = O.layer_norm(x, sd["ln_final.weight"], sd["ln_final.bias"])
-    txt_f = x[torch.arange(C), case.eot] @ sd["text_projection"]
-    img_f = img_f / img_f.norm(dim=-1, keepdim=True)
-    txt_f = txt_f / txt_f.norm(dim=-1, keepdim=True)
-    return sd["logit_scale"].exp() * img_f @ txt_f.t()
+    layer = lambda prefix: int(prefix.split(".")[-2])  # noqa: E731  ("...resblocks.<i>.")
+    vis_block = lambda x, sd, prefix, heads, mask, taps: block(x, sd, prefix, heads, mask, vis if layer(prefix) >= layer_from else f16)  # noqa: E731
+    txt_block = lambda x, sd, prefix, heads, mask, taps: block(x, sd, prefix, heads, mask, txt)  # noqa: E731
+    V = "image_encoder.visual_ctx"
+    prompts, shared, text_deep, t2v = O.prompt_learner(cfg, params, case.class_embedding)
+    v2t = params[V + "_deep_prompts"] @ params[V + "_deep_projections.weight"].t() + params[V + "_deep_projections.bias"]
+    img_f = O.vision_tower(cfg, sd, case.images, params[V] + shared, t2v + params[V + "_deep_prompts"], block=vis_block,
+                           patch_embed=lambda x, w: linear(x, w, 0.0, vis.get("patch", "f32")))
+    Le = int(case.eot.max()) + 1  # the text tower on the positions the library runs (up to the last EOT)
+    txt_f = O.text_tower(cfg, sd, prompts[:, :Le], case.eot, text_deep + v2t, block=txt_block)
+    return O.cosine_logits(sd, img_f, txt_f)
 
 
 def modes(base, **over):

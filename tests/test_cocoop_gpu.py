@@ -5,7 +5,7 @@ import torch
 
 from oracle import cocoop_oracle as CO
 from oracle import mudpt_oracle as O
-from tests.helpers import GoldenCase, assert_training_forward_is_the_inference_forward
+from tests.helpers import GoldenCase, assert_training_forward_is_the_inference_forward, check_logits
 
 pytestmark = pytest.mark.gpu
 
@@ -39,8 +39,7 @@ def cancellation_factors(cfg, dprompts):
 
 def build(cfg, frozen, tokens, params, dtype, max_batch, knobs=None):
     from mudpt_amd.model import CustomCLIP, ModelShape
-    shape = ModelShape(cfg.image_size, cfg.patch, cfg.v_width, cfg.v_layers, cfg.v_heads, cfg.t_width, cfg.t_layers, cfg.t_heads,
-                       cfg.ctx_len, cfg.embed_dim, cfg.n_ctx, 1)
+    shape = ModelShape.from_config(cfg, cfg.n_ctx, 1)
     m = CustomCLIP(shape, frozen, tokens, max_batch=max_batch, dtype=dtype, variant="cocoop", knobs=knobs)
     assert m.param_names == CO.TRAINABLE_ORDER  # the reference's prompt_learner.* names, flat-bucket order
     m.set_params(params)
@@ -59,10 +58,7 @@ def test_logits_loss_grads_match_reference(case, dtype):
     m = build(case.cfg, case.frozen, case.tokens, case.params, dtype, len(case.labels))
     m.eval()
     logits = m(case.images).cpu()  # eval mode: logits (trainers/cocoop.py:198)
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    print(f"{dtype}: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    slack = TINY_SLACK if case.cfg.v_layers < 12 else 1.0
-    assert rms <= slack * LOGIT_RMS[dtype] and err <= slack * LOGIT_ATOL[dtype]
+    slack = check_logits(logits, case, dtype, dtype, TINY_SLACK if case.cfg.v_layers < 12 else 1.0, LOGIT_RMS, LOGIT_ATOL)
     m.train()
     loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)  # training mode: CE inside forward (:196-197)
     torch.cuda.synchronize()

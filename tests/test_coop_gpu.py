@@ -8,7 +8,7 @@ import torch
 
 from oracle import mudpt_oracle as O
 from tests import coop_reference as R
-from tests.helpers import assert_training_forward_is_the_inference_forward
+from tests.helpers import assert_training_forward_is_the_inference_forward, check_logits, check_parity_mode_at_scale_100
 
 pytestmark = pytest.mark.gpu
 
@@ -33,8 +33,7 @@ PARITY = [f for f in R.FIXTURES if not f.endswith("_s100")]
 
 def shape_of(cfg):
     from mudpt_amd.model import ModelShape
-    return ModelShape(cfg.image_size, cfg.patch, cfg.v_width, cfg.v_layers, cfg.v_heads, cfg.t_width, cfg.t_layers, cfg.t_heads,
-                      cfg.ctx_len, cfg.embed_dim, cfg.n_ctx, 1)
+    return ModelShape.from_config(cfg, cfg.n_ctx, 1)
 
 
 def build(case, dtype, ctx=None, csc=None, tokens=None, name_lens=None, max_batch=None, knobs=None):
@@ -64,10 +63,7 @@ def test_logits_loss_grads_match_reference(case, dtype):
     m = build(case, dtype)
     m.eval()
     logits = m(case.images).cpu()
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    slack = slack_of(case.cfg)
-    print(f"{case.name} {dtype}: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    assert rms <= slack * LOGIT_RMS[dtype] and err <= slack * LOGIT_ATOL[dtype]
+    slack = check_logits(logits, case, dtype, f"{case.name} {dtype}", slack_of(case.cfg), LOGIT_RMS, LOGIT_ATOL)
     m.train()
     loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
     torch.cuda.synchronize()
@@ -91,12 +87,7 @@ def test_logits_loss_grads_match_reference(case, dtype):
 
 def test_parity_mode_at_logit_scale_100():
     case = R.CoopCase("coop_vitb16_b2_s100")
-    m = build(case, "fp32")
-    m.eval()
-    err = (m(case.images).cpu() - case.logits).abs().max().item()
-    print(f"parity mode, scale 100: max |dlogit| {err:.3e}")
-    assert err <= 1e-3
-    m.close()
+    check_parity_mode_at_scale_100(build(case, "fp32"), case)
 
 
 @pytest.mark.parametrize("name", [f for f in R.FIXTURES if f.startswith("coop_tiny_")] + ["coop_vitb16_b2_s100"])

@@ -17,8 +17,7 @@ pytestmark = pytest.mark.gpu
 
 def build(cfg, frozen, tokens, params, dtype, max_batch):
     from mudpt_amd.model import CustomCLIP, ModelShape
-    shape = ModelShape(cfg.image_size, cfg.patch, cfg.v_width, cfg.v_layers, cfg.v_heads, cfg.t_width, cfg.t_layers, cfg.t_heads,
-                       cfg.ctx_len, cfg.embed_dim, cfg.n_ctx, cfg.depth)
+    shape = ModelShape.from_config(cfg, cfg.n_ctx, cfg.depth)
     m = CustomCLIP(shape, frozen, tokens, max_batch=max_batch, dtype=dtype)
     m.set_params(params)
     return m

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import mudpt_oracle as O
-from tests.helpers import GRAD_COS, GRAD_RMS, GRAD_RTOL, LOGIT_ATOL, LOGIT_RMS, TINY_SLACK, GoldenCase  # noqa: F401  (the bounds: the variants' suites import them from here)
+from tests.helpers import GRAD_COS, GRAD_RMS, GRAD_RTOL, LOGIT_ATOL, LOGIT_RMS, TINY_SLACK, GoldenCase, check_logits  # noqa: F401  (the bounds: the variants' suites import them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -12,8 +12,7 @@ pytestmark = pytest.mark.gpu
 def build(case: GoldenCase, dtype: str, max_batch=None, knobs=None):
     from mudpt_amd.model import CustomCLIP, ModelShape
     c = case.cfg
-    shape = ModelShape(c.image_size, c.patch, c.v_width, c.v_layers, c.v_heads, c.t_width, c.t_layers, c.t_heads, c.ctx_len,
-                       c.embed_dim, c.n_ctx, c.depth)
+    shape = ModelShape.from_config(c, c.n_ctx, c.depth)
     m = CustomCLIP(shape, case.frozen, case.tokens, max_batch=max_batch or len(case.labels), dtype=dtype, knobs=knobs)
     m.set_params(case.params)
     return m
@@ -27,13 +26,7 @@ def case(request):
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 def test_logits_match_reference(case, dtype):
     m = build(case, dtype)
-    logits = m(case.images).cpu()
-    err = (logits - case.logits).abs().max().item()
-    rms = (logits - case.logits).pow(2).mean().sqrt().item()
-    print(f"{dtype}: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    slack = TINY_SLACK if case.cfg.v_layers < 12 else 1.0
-    assert rms <= slack * LOGIT_RMS[dtype], rms
-    assert err <= slack * LOGIT_ATOL[dtype], err
+    check_logits(m(case.images), case, dtype, dtype)
     m.close()
 
 
@@ -109,8 +102,7 @@ def test_unused_deep_prompts_get_zero_grad():
     cfg = dataclasses.replace(case.cfg, depth=6)  # 3 layers -> only deep[0], deep[1] are used
     params = O.make_trainable_state(cfg, 5, case.frozen, [int(v) for v in case.z["ctx_token_ids"]])
     from mudpt_amd.model import CustomCLIP, ModelShape
-    shape = ModelShape(cfg.image_size, cfg.patch, cfg.v_width, cfg.v_layers, cfg.v_heads, cfg.t_width, cfg.t_layers, cfg.t_heads,
-                       cfg.ctx_len, cfg.embed_dim, cfg.n_ctx, cfg.depth)
+    shape = ModelShape.from_config(cfg, cfg.n_ctx, cfg.depth)
     m = CustomCLIP(shape, case.frozen, case.tokens, max_batch=3, dtype="fp16")
     m.set_params(params)
     loss = m.forward_backward(case.images, case.labels)

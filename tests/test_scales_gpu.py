@@ -27,8 +27,7 @@ from tests import test_exact_gpu as TE
 from tests import test_knobs_gpu as TK
 from tests import test_umudpt_gpu as TU
 from tests import test_uumudpt_gpu as TUU
-from tests import test_vpt_gpu as TV
-from tests.helpers import GRAD_COS, GRAD_RMS, GRAD_RTOL
+from tests.helpers import GRAD_COS, GRAD_RMS, GRAD_RTOL, check_fixture_grads, check_grad, check_grads
 from tests.test_knobs_gpu import Step, assert_same_step
 
 pytestmark = pytest.mark.gpu
@@ -187,27 +186,15 @@ def check_against_reference(name, grade, grads, factor, tag):
             bound = TC.DELTA_T[grade] * _coop_kappa(c)
             assert er <= bound * rms_g + 1e-12 and e <= 4 * bound * gmax + 1e-9, (tag, er / rms_g, e / gmax, bound)
     elif fx.startswith(("vpt_", "mpt_")):
-        TV.check_grads(grads, {k: r * factor for k, r in c.grads.items()}, grade, tag)
+        check_grads(grads, {k: r * factor for k, r in c.grads.items()}, grade, tag)
     elif fx.startswith(("umudpt_", "uumudpt_")):  # pieces (a) and (c) of the suites' parity test; (b) does not depend on the towers' type
         mod = TU if fx.startswith("umudpt_") else TUU
         restated = mod.restated(c)[2]
         tables = (TU.R.CTX, TU.R.DEEP) if mod is TU else (TUU.R.CTX, TUU.R.DEEP, TUU.R.VCTX, TUU.R.VDEEP)
-        for k in c.keys:
-            if grads[k].numel() == 0:
-                continue
-            if k in tables:
-                mod.check_tower_grad(grads[k], restated[k] * factor, grade, f"{tag} (a) {k}")
-            if k in c.grads:
-                if c.grads[k].abs().max().item() == 0:
-                    assert torch.count_nonzero(grads[k]) == 0, k
-                else:
-                    mod.check_tower_grad(grads[k], c.grads[k] * factor, grade, f"{tag} (c) {k}")
-            else:
-                rows, vals, rms = c.grad_samples[k]
-                if rms == 0:
-                    assert torch.count_nonzero(grads[k]) == 0, k
-                else:
-                    mod.check_tower_grad(grads[k][rows], vals * factor, grade, f"{tag} (c) {k} [16 rows]", rms=rms * factor)
+        for k in tables:
+            if grads[k].numel():
+                check_grad(grads[k], restated[k] * factor, grade, f"{tag} (a) {k}")
+        check_fixture_grads(grads, c, grade, f"{tag} (c)", factor)
     else:  # test_cocoop_gpu.py::test_logits_loss_grads_match_reference
         kappa = _cocoop_kappa(fx, c)
         for k in CO.TRAINABLE_ORDER:

@@ -16,8 +16,9 @@ import pytest
 import torch
 
 from tests import umudpt_reference as R
-from tests.helpers import assert_training_forward_is_the_inference_forward
-from tests.test_model_gpu import GRAD_RMS, GRAD_RTOL, LOGIT_ATOL, LOGIT_RMS, TINY_SLACK
+from tests.helpers import (assert_training_forward_is_the_inference_forward, check_fixture_grads, check_grad, check_logits,
+                           check_parity_mode_at_scale_100, check_sampled_taps)
+from tests.test_model_gpu import LOGIT_ATOL, TINY_SLACK
 
 pytestmark = pytest.mark.gpu
 PARITY = [f for f in R.FIXTURES if not f.endswith("_s100")]
@@ -25,9 +26,7 @@ PARITY = [f for f in R.FIXTURES if not f.endswith("_s100")]
 
 def build(case, dtype, max_batch=None, knobs=None, params=None):
     from mudpt_amd.model import CustomCLIP, ModelShape
-    c = case.cfg
-    shape = ModelShape(c.image_size, c.patch, c.v_width, c.v_layers, c.v_heads, c.t_width, c.t_layers, c.t_heads, c.ctx_len, c.embed_dim,
-                       c.n_ctx, c.depth)
+    shape = ModelShape.from_config(case.cfg, case.cfg.n_ctx, case.cfg.depth)
     m = CustomCLIP(shape, case.frozen, case.tokens, ctx_token_ids=case.ctx_token_ids, max_batch=max_batch or len(case.labels), dtype=dtype,
                    variant="umudpt", knobs=knobs, seed=case.seeds[1])
     assert m.param_names == case.keys and m.ctx_key == R.CTX
@@ -51,19 +50,6 @@ def restated(case):
     return _REF[case.name]
 
 
-def grad_errors(g, r, rms=None):
-    g, r = g.detach().float().cpu(), r.float()
-    rms = r.pow(2).mean().sqrt().item() if rms is None else rms
-    return rms, (g - r).abs().max().item(), (g - r).pow(2).mean().sqrt().item() / max(rms, 1e-30)
-
-
-def check_tower_grad(g, r, dtype, tag, rms=None):
-    rms, err, rel_rms = grad_errors(g, r, rms)
-    print(f"{tag}: rms {rms:.3e} max err / rms {err / max(rms, 1e-30):.3e} rms err {rel_rms:.3e}")
-    assert err <= GRAD_RTOL[dtype] * rms * 4 + 1e-9, (tag, err, rms)
-    assert rel_rms <= GRAD_RMS[dtype], (tag, rel_rms)
-
-
 @pytest.fixture(scope="module", params=PARITY)
 def case(request):
     return load(request.param)
@@ -75,17 +61,8 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
     m = build(case, dtype)
     m.eval()
     logits = m(case.images).cpu()
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    slack = TINY_SLACK if case.cfg.v_layers < 12 else 1.0
-    print(f"{case.name} {dtype}: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    assert rms <= slack * LOGIT_RMS[dtype] and err <= slack * LOGIT_ATOL[dtype]
-    for key, (ref, rows) in case.taps.items():  # the spliced rows of the sampled block inputs
-        tower, i = key.split(".")
-        x = m.debug_read(f"{tower}.x_in.{i}", B)
-        d = case.cfg.v_width if tower == "vis" else case.cfg.t_width
-        x = x.view(-1, x.numel() // (d * (B if tower == "vis" else len(case.classnames))), d)[:, rows]
-        tol = (2e-3 if dtype == "fp16" else 3e-2) * (1 + ref.abs().max().item())
-        assert (x - ref).abs().max().item() <= tol, (key, (x - ref).abs().max().item())
+    slack = check_logits(logits, case, dtype, f"{case.name} {dtype}")
+    check_sampled_taps(m, case, dtype)  # the spliced rows of the sampled block inputs
     m.train()
     loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
     torch.cuda.synchronize()
@@ -101,10 +78,10 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
     assert (G - G_ref).abs().max().item() <= 3e-5 * math.sqrt(4 * c.t_width) + 1e-5 * G_ref.abs().max().item()
     # (a) the prompt tables' gradients and dG: the towers' rounding, MuDPT's constants
     dG = m.debug_read("umudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
-    check_tower_grad(dG, ref_dG, dtype, f"{case.name} {dtype} (a) dG")
+    check_grad(dG, ref_dG, dtype, f"{case.name} {dtype} (a) dG")
     for k in (R.CTX, R.DEEP):
         if got[k].numel():
-            check_tower_grad(got[k], ref_grads[k], dtype, f"{case.name} {dtype} (a) {k}")
+            check_grad(got[k], ref_grads[k], dtype, f"{case.name} {dtype} (a) {k}")
     # (b) the generator's own backward in fp32, fed the library's dG
     scale = dG.pow(2).mean().sqrt().item()
     atol, rtol = 3e-5 * math.sqrt(4 * c.t_width) * scale, 1e-5
@@ -116,26 +93,13 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
     print(f"{case.name} {dtype} (b): dG rms {scale:.3e}; worst generator gradient {worst[1]} at {worst[0]:.3f} of the fp32 bound")
     assert worst[0] <= 1.0, worst
     # (c) all 20 against the fixture (the reference's own autograd)
-    for k in case.keys:
-        if got[k].numel() == 0:
-            continue
-        if k in case.grads:
-            check_tower_grad(got[k], case.grads[k], dtype, f"{case.name} {dtype} (c) {k}")
-        else:
-            rows, vals, rms = case.grad_samples[k]
-            check_tower_grad(got[k][rows], vals, dtype, f"{case.name} {dtype} (c) {k} [16 rows]", rms=rms)
+    check_fixture_grads(got, case, dtype, f"{case.name} {dtype} (c)")
     m.close()
 
 
 def test_parity_mode_at_logit_scale_100():
     case = load("umudpt_vitb16_b2_s100")
-    m = build(case, "fp32")
-    m.eval()
-    logits = m(case.images).cpu()
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    print(f"{case.name} parity mode: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    assert err <= 1e-3
-    m.close()
+    check_parity_mode_at_scale_100(build(case, "fp32"), case)
 
 
 @pytest.mark.parametrize("name", ["umudpt_tiny", "umudpt_vitb16_b2_s100"])
@@ -164,30 +128,17 @@ def test_parity_mode_training_step(name):
     _, _, ref_grads, ref_dG = restated(case)
     dG = m.debug_read("umudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
     m.close()
-    check_tower_grad(dG, ref_dG, "bf16", f"{tag} (a) dG")
+    check_grad(dG, ref_dG, "bf16", f"{tag} (a) dG")
     for k in (R.CTX, R.DEEP):
         if got[k].numel():
-            check_tower_grad(got[k], ref_grads[k], "bf16", f"{tag} (a) {k}")
+            check_grad(got[k], ref_grads[k], "bf16", f"{tag} (a) {k}")
     scale = dG.pow(2).mean().sqrt().item()  # (b)
     atol, rtol = 3e-5 * math.sqrt(4 * c.t_width) * scale, 1e-5
     _, _, g64 = R.generator_backward(case.params, R.prompt_tables(case.params), dG)
     worst = max(((got[k].double() - r).abs() / (atol + rtol * r.abs())).max().item() for k, r in g64.items())
     print(f"{tag} (b): worst generator gradient at {worst:.3f} of the fp32 bound")
     assert worst <= 1.0
-    for k in case.keys:  # (c)
-        if got[k].numel() == 0:
-            continue
-        if k in case.grads:
-            if case.grads[k].abs().max().item() == 0:
-                assert torch.count_nonzero(got[k]) == 0, k
-                continue
-            check_tower_grad(got[k], case.grads[k], "bf16", f"{tag} (c) {k}")
-        else:
-            rows, vals, rms = case.grad_samples[k]
-            if rms == 0:
-                assert torch.count_nonzero(got[k]) == 0, k
-                continue
-            check_tower_grad(got[k][rows], vals, "bf16", f"{tag} (c) {k} [16 rows]", rms=rms)
+    check_fixture_grads(got, case, "bf16", f"{tag} (c)")
     check_parity_step_grads(name, [(k, got[k], ref_grads[k]) for k in case.keys], PARITY_STEP_MEASURED[name])
 
 
@@ -223,8 +174,7 @@ def test_init_is_the_references_draw():
     """The module's own initial values (seed = the fixture's) carry the checksums of the reference's freshly constructed prompt learner."""
     case = load("umudpt_tiny")
     from mudpt_amd.model import CustomCLIP, ModelShape
-    c = case.cfg
-    shape = ModelShape(c.image_size, c.patch, c.v_width, c.v_layers, c.v_heads, c.t_width, c.t_layers, c.t_heads, c.ctx_len, c.embed_dim, c.n_ctx, c.depth)
+    shape = ModelShape.from_config(case.cfg, case.cfg.n_ctx, case.cfg.depth)
     m = CustomCLIP(shape, case.frozen, case.tokens, ctx_token_ids=case.ctx_token_ids, max_batch=3, dtype="fp16", variant="umudpt", seed=case.seeds[1])
     for k, v in m.state_dict().items():
         got = [v.double().sum().item(), v.double().abs().sum().item()]

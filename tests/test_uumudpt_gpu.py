@@ -17,8 +17,9 @@ import pytest
 import torch
 
 from tests import uumudpt_reference as R
-from tests.helpers import assert_training_forward_is_the_inference_forward
-from tests.test_model_gpu import GRAD_RMS, GRAD_RTOL, LOGIT_ATOL, LOGIT_RMS, TINY_SLACK
+from tests.helpers import (assert_training_forward_is_the_inference_forward, check_fixture_grads, check_grad, check_logits,
+                           check_parity_mode_at_scale_100, check_sampled_taps)
+from tests.test_model_gpu import LOGIT_ATOL, TINY_SLACK
 
 pytestmark = pytest.mark.gpu
 PARITY = [f for f in R.FIXTURES if not f.endswith("_s100")]
@@ -26,9 +27,7 @@ PARITY = [f for f in R.FIXTURES if not f.endswith("_s100")]
 
 def build(case, dtype, max_batch=None, knobs=None, params=None):
     from mudpt_amd.model import CustomCLIP, ModelShape
-    c = case.cfg
-    shape = ModelShape(c.image_size, c.patch, c.v_width, c.v_layers, c.v_heads, c.t_width, c.t_layers, c.t_heads, c.ctx_len, c.embed_dim,
-                       c.n_ctx, c.depth)
+    shape = ModelShape.from_config(case.cfg, case.cfg.n_ctx, case.cfg.depth)
     m = CustomCLIP(shape, case.frozen, case.tokens, ctx_token_ids=case.ctx_token_ids, max_batch=max_batch or len(case.labels), dtype=dtype,
                    variant="uumudpt", knobs=knobs, seed=case.seeds[1])
     assert m.param_names == case.keys and m.ctx_key == R.CTX
@@ -50,19 +49,6 @@ def restated(case):
     if case.name not in _REF:
         _REF[case.name] = R.forward_backward(case.cfg, case.frozen, case.params, case.class_embedding, case.eot, case.images, case.labels)
     return _REF[case.name]
-
-
-def grad_errors(g, r, rms=None):
-    g, r = g.detach().float().cpu(), r.float()
-    rms = r.pow(2).mean().sqrt().item() if rms is None else rms
-    return rms, (g - r).abs().max().item(), (g - r).pow(2).mean().sqrt().item() / max(rms, 1e-30)
-
-
-def check_tower_grad(g, r, dtype, tag, rms=None):
-    rms, err, rel_rms = grad_errors(g, r, rms)
-    print(f"{tag}: rms {rms:.3e} max err / rms {err / max(rms, 1e-30):.3e} rms err {rel_rms:.3e}")
-    assert err <= GRAD_RTOL[dtype] * rms * 4 + 1e-9, (tag, err, rms)
-    assert rel_rms <= GRAD_RMS[dtype], (tag, rel_rms)
 
 
 def generator_bound(got, case, names, X, d_out, width, tag):
@@ -89,17 +75,8 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
     m = build(case, dtype)
     m.eval()
     logits = m(case.images).cpu()
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    slack = TINY_SLACK if case.cfg.v_layers < 12 else 1.0
-    print(f"{case.name} {dtype}: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    assert rms <= slack * LOGIT_RMS[dtype] and err <= slack * LOGIT_ATOL[dtype]
-    for key, (ref, rows) in case.taps.items():  # the spliced rows of the sampled block inputs
-        tower, i = key.split(".")
-        x = m.debug_read(f"{tower}.x_in.{i}", B)
-        d = case.cfg.v_width if tower == "vis" else case.cfg.t_width
-        x = x.view(-1, x.numel() // (d * (B if tower == "vis" else len(case.classnames))), d)[:, rows]
-        tol = (2e-3 if dtype == "fp16" else 3e-2) * (1 + ref.abs().max().item())
-        assert (x - ref).abs().max().item() <= tol, (key, (x - ref).abs().max().item())
+    slack = check_logits(logits, case, dtype, f"{case.name} {dtype}")
+    check_sampled_taps(m, case, dtype)  # the spliced rows of the sampled block inputs
     m.train()
     loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
     torch.cuda.synchronize()
@@ -117,16 +94,16 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
     assert (G - G_ref).abs().max().item() <= 3e-5 * math.sqrt(4 * c.t_width) + 1e-5 * G_ref.abs().max().item()
     # (a) the gradients the towers leave: their rounding, MuDPT's constants
     dG = m.debug_read("uumudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
-    check_tower_grad(dG, ref_dG, dtype, f"{tag} (a) dG")
+    check_grad(dG, ref_dG, dtype, f"{tag} (a) dG")
     dT = None
     if c.depth > 1:
         T = m.debug_read("uumudpt.T", B).view(c.depth - 1, c.n_ctx, c.embed_dim)
         assert (T - T_ref).abs().max().item() <= 3e-5 * math.sqrt(4 * c.v_width) + 1e-5 * T_ref.abs().max().item()
         dT = m.debug_read("uumudpt.dT", B).view(c.depth - 1, c.n_ctx, c.embed_dim)
-        check_tower_grad(dT, ref_dT, dtype, f"{tag} (a) dT")
+        check_grad(dT, ref_dT, dtype, f"{tag} (a) dT")
     for k in (R.CTX, R.DEEP, R.VCTX, R.VDEEP):
         if got[k].numel():
-            check_tower_grad(got[k], ref_grads[k], dtype, f"{tag} (a) {k}")
+            check_grad(got[k], ref_grads[k], dtype, f"{tag} (a) {k}")
     # (b) each generator's own backward in fp32, fed the library's dG / dT
     generator_bound(got, case, R.GEN1, R.prompt_tables(case.params), dG, c.t_width, f"{tag} Gen1")
     if c.depth > 1:
@@ -134,32 +111,13 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
     else:  # Gen2 idles: its gradients are the zeroed bucket's zeros, as the reference's are
         assert all(torch.count_nonzero(got[k]) == 0 for k, _ in R.generator_keys(R.GEN2, c.v_width, c.embed_dim))
     # (c) all 40 against the fixture (the reference's own autograd)
-    for k in case.keys:
-        if got[k].numel() == 0:
-            continue
-        if k in case.grads:
-            if case.grads[k].abs().max().item() == 0:
-                assert torch.count_nonzero(got[k]) == 0, k
-                continue
-            check_tower_grad(got[k], case.grads[k], dtype, f"{tag} (c) {k}")
-        else:
-            rows, vals, rms = case.grad_samples[k]
-            if rms == 0:
-                assert torch.count_nonzero(got[k]) == 0, k
-                continue
-            check_tower_grad(got[k][rows], vals, dtype, f"{tag} (c) {k} [16 rows]", rms=rms)
+    check_fixture_grads(got, case, dtype, f"{tag} (c)")
     m.close()
 
 
 def test_parity_mode_at_logit_scale_100():
     case = load("uumudpt_vitb16_b2_s100")
-    m = build(case, "fp32")
-    m.eval()
-    logits = m(case.images).cpu()
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    print(f"{case.name} parity mode: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    assert err <= 1e-3
-    m.close()
+    check_parity_mode_at_scale_100(build(case, "fp32"), case)
 
 
 @pytest.mark.parametrize("name", ["uumudpt_tiny", "uumudpt_vitb16_b2_s100"])
@@ -189,29 +147,16 @@ def test_parity_mode_training_step(name):
     dG = m.debug_read("uumudpt.dG", B).view(c.depth, c.n_ctx, c.v_width)
     dT = m.debug_read("uumudpt.dT", B).view(c.depth - 1, c.n_ctx, c.embed_dim) if c.depth > 1 else None
     m.close()
-    check_tower_grad(dG, ref_dG, "bf16", f"{tag} (a) dG")
+    check_grad(dG, ref_dG, "bf16", f"{tag} (a) dG")
     if dT is not None:
-        check_tower_grad(dT, ref_dT, "bf16", f"{tag} (a) dT")
+        check_grad(dT, ref_dT, "bf16", f"{tag} (a) dT")
     for k in (R.CTX, R.DEEP, R.VCTX, R.VDEEP):
         if got[k].numel():
-            check_tower_grad(got[k], ref_grads[k], "bf16", f"{tag} (a) {k}")
+            check_grad(got[k], ref_grads[k], "bf16", f"{tag} (a) {k}")
     generator_bound(got, case, R.GEN1, R.prompt_tables(case.params), dG, c.t_width, f"{tag} Gen1")  # (b)
     if dT is not None:
         generator_bound(got, case, R.GEN2, case.params[R.VDEEP], dT, c.v_width, f"{tag} Gen2")
-    for k in case.keys:  # (c)
-        if got[k].numel() == 0:
-            continue
-        if k in case.grads:
-            if case.grads[k].abs().max().item() == 0:
-                assert torch.count_nonzero(got[k]) == 0, k
-                continue
-            check_tower_grad(got[k], case.grads[k], "bf16", f"{tag} (c) {k}")
-        else:
-            rows, vals, rms = case.grad_samples[k]
-            if rms == 0:
-                assert torch.count_nonzero(got[k]) == 0, k
-                continue
-            check_tower_grad(got[k][rows], vals, "bf16", f"{tag} (c) {k} [16 rows]", rms=rms)
+    check_fixture_grads(got, case, "bf16", f"{tag} (c)")
     check_parity_step_grads(name, [(k, got[k], ref_grads[k]) for k in case.keys], PARITY_STEP_MEASURED[name])
 
 
@@ -256,8 +201,7 @@ def test_init_is_the_references_draw():
     behind its own seed point."""
     case = load("uumudpt_tiny")
     from mudpt_amd.model import CustomCLIP, ModelShape
-    c = case.cfg
-    shape = ModelShape(c.image_size, c.patch, c.v_width, c.v_layers, c.v_heads, c.t_width, c.t_layers, c.t_heads, c.ctx_len, c.embed_dim, c.n_ctx, c.depth)
+    shape = ModelShape.from_config(case.cfg, case.cfg.n_ctx, case.cfg.depth)
     m = CustomCLIP(shape, case.frozen, case.tokens, ctx_token_ids=case.ctx_token_ids, max_batch=3, dtype="fp16", variant="uumudpt", seed=case.seeds[1])
     for k, v in m.state_dict().items():
         got = [v.double().sum().item(), v.double().abs().sum().item()]

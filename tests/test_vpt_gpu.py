@@ -7,8 +7,9 @@ import torch
 
 from oracle import mudpt_oracle as O
 from tests import vpt_reference as R
-from tests.helpers import assert_training_forward_is_the_inference_forward
-from tests.test_model_gpu import GRAD_RMS, GRAD_RTOL, LOGIT_ATOL, LOGIT_RMS, TINY_SLACK
+from tests.helpers import (assert_training_forward_is_the_inference_forward, check_grads, check_logits, check_parity_mode_at_scale_100,
+                           check_sampled_taps)
+from tests.test_model_gpu import LOGIT_ATOL
 
 pytestmark = pytest.mark.gpu
 PARITY = [f for f in R.FIXTURES if not f.endswith("_s100")]
@@ -16,8 +17,7 @@ PARITY = [f for f in R.FIXTURES if not f.endswith("_s100")]
 
 def build(case, dtype, max_batch=None, knobs=None, params=None):
     from mudpt_amd.model import CustomCLIP, ModelShape
-    c = case.cfg
-    shape = ModelShape(c.image_size, c.patch, c.v_width, c.v_layers, c.v_heads, c.t_width, c.t_layers, c.t_heads, c.ctx_len, c.embed_dim, 4, 1)
+    shape = ModelShape.from_config(case.cfg, 4, 1)
     m = CustomCLIP(shape, case.frozen, case.tokens, ctx_token_ids=case.ctx_token_ids or None, max_batch=max_batch or len(case.labels),
                    dtype=dtype, variant=case.variant, knobs=knobs, prompt_shape=case.shape)
     assert m.param_names == case.keys
@@ -25,16 +25,6 @@ def build(case, dtype, max_batch=None, knobs=None, params=None):
         assert torch.equal(m.state_dict()[R.TEXT_CTX].cpu(), case.params[R.TEXT_CTX])
     m.set_params(case.params if params is None else params)
     return m
-
-
-def check_grads(got, ref, dtype, tag):
-    for k, r in ref.items():
-        g = got[k].detach().float().cpu()
-        rms = r.pow(2).mean().sqrt().item()
-        err, rel_rms = (g - r).abs().max().item(), (g - r).pow(2).mean().sqrt().item() / max(rms, 1e-30)
-        print(f"{tag} {k}: rms {rms:.3e} max err / rms {err / max(rms, 1e-30):.3e} rms err {rel_rms:.3e}")
-        assert err <= GRAD_RTOL[dtype] * rms * 4 + 1e-9, (k, err, rms)
-        assert rel_rms <= GRAD_RMS[dtype], (k, rel_rms)
 
 
 @pytest.fixture(scope="module", params=PARITY)
@@ -47,17 +37,8 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
     m = build(case, dtype)
     m.eval()
     logits = m(case.images).cpu()
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    slack = TINY_SLACK if case.cfg.v_layers < 12 else 1.0
-    print(f"{case.name} {dtype}: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    assert rms <= slack * LOGIT_RMS[dtype] and err <= slack * LOGIT_ATOL[dtype]
-    for key, (ref, rows) in case.taps.items():  # the spliced rows of the sampled block inputs
-        tower, i = key.split(".")
-        x = m.debug_read(f"{tower}.x_in.{i}", len(case.labels))
-        d = case.cfg.v_width if tower == "vis" else case.cfg.t_width
-        x = x.view(-1, x.numel() // (d * (len(case.labels) if tower == "vis" else len(case.classnames))), d)[:, rows]
-        tol = (2e-3 if dtype == "fp16" else 3e-2) * (1 + ref.abs().max().item())
-        assert (x - ref).abs().max().item() <= tol, (key, (x - ref).abs().max().item())
+    slack = check_logits(logits, case, dtype, f"{case.name} {dtype}")
+    check_sampled_taps(m, case, dtype)  # the spliced rows of the sampled block inputs
     m.train()
     loss, logits2 = m.forward_backward(case.images, case.labels, return_logits=True)
     torch.cuda.synchronize()
@@ -70,13 +51,7 @@ def test_logits_loss_grads_taps_match_reference(case, dtype):
 @pytest.mark.parametrize("name", ["vpt_vitb16_b2_s100", "mpt_vitb16_b2_s100"])
 def test_parity_mode_at_logit_scale_100(name):
     case = R.VptCase(name)
-    m = build(case, "fp32")
-    m.eval()
-    logits = m(case.images).cpu()
-    err, rms = (logits - case.logits).abs().max().item(), (logits - case.logits).pow(2).mean().sqrt().item()
-    print(f"{name} parity mode: |logit - reference| max {err:.3e} rms {rms:.3e}")
-    assert err <= 1e-3
-    m.close()
+    check_parity_mode_at_scale_100(build(case, "fp32"), case)
 
 
 @pytest.mark.parametrize("name", ["vpt_tiny", "mpt_tiny", "mpt_tiny_textonly", "vpt_vitb16_b2_s100", "mpt_vitb16_b2_s100"])

@@ -1,7 +1,7 @@
 """Test-local restatement of the UMuDPT path (trainers/umudpt.py:79-230) in plain torch CPU, and the loader of the umudpt_* fixtures.
 
 The towers are MuDPT's (``ResidualAttentionBlock_UMuDPT``, clip/model.py:304-351, is ``ResidualAttentionBlock_MuDPT`` line for line), so the
-blocks are the unchanged ``oracle.mudpt_oracle.block``; only the front end that makes the prompt tables differs
+towers are ``oracle.mudpt_oracle``'s; only the front end that makes the prompt tables differs
 (``UMuDPTPromptLearner.forward``, umudpt.py:161-178): X = cat(ctx[None], deep_prompts) [depth, n_ctx, d_t] goes through ln_pre, ONE pre-LN
 transformer block whose attention runs over the n_ctx rows of one layer (the permute(1, 0, 2) makes the layers the batch), ln_post and
 visual_proj; G[0] are the vision tower's input prompt rows, G[1:] its deep prompts (``VisionTransformer_UMuDPT``, clip/model.py:556-597),
@@ -10,18 +10,15 @@ float64).  Pinned by the fixtures of tests/golden/gen_golden_umudpt.py, which ra
 """
 from __future__ import annotations
 
-import ast
 import math
-import os
 from typing import Dict, List, Optional, Tuple
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 from oracle import mudpt_oracle as O
+from tests.helpers import GOLDEN, FixtureCase  # noqa: F401
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = ["umudpt_tiny", "umudpt_tiny_d1", "umudpt_tiny_d5", "umudpt_vitb16_b2", "umudpt_vitb16_b2_s100"]
 P = "umudpt_prompt_learner."
 CTX, DEEP = P + "ctx", P + "deep_prompts"
@@ -100,65 +97,28 @@ def prompt_tables(params: Dict[str, torch.Tensor]) -> torch.Tensor:
     return torch.cat([params[CTX].unsqueeze(0), params[DEEP]], dim=0)  # umudpt.py:170
 
 
-def vision_tower(cfg: O.Config, sd, G: torch.Tensor, images, taps: Optional[Dict] = None) -> torch.Tensor:
-    """VisionTransformer_UMuDPT.forward (clip/model.py:574-597): G[0] appended after the positional embedding, blocks 1 <= i replace the
-    last n_ctx rows by G[i] while i < depth -> image features [B, e]."""
-    B, n = images.shape[0], cfg.n_ctx
-    w = sd["visual.conv1.weight"].reshape(cfg.v_width, -1)
-    x = O.patchify(images.float(), cfg.patch) @ w.t()
-    x = torch.cat([sd["visual.class_embedding"].expand(B, 1, -1), x], dim=1) + sd["visual.positional_embedding"]
-    x = torch.cat([x, G[0].unsqueeze(0).expand(B, -1, -1)], dim=1)
-    x = O.layer_norm(x, sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"])
-    L = x.shape[1]
-    for i in range(cfg.v_layers):
-        if 1 <= i < G.shape[0]:
-            x = torch.cat([x[:, :L - n], G[i].unsqueeze(0).expand(B, -1, -1)], dim=1)
-        if taps is not None:
-            taps[f"vis.x_in.{i}"] = x
-        x = O.block(x, sd, f"visual.transformer.resblocks.{i}.", cfg.v_heads, None)
-    return O.layer_norm(x[:, 0], sd["visual.ln_post.weight"], sd["visual.ln_post.bias"]) @ sd["visual.proj"]
-
-
-def text_tower(cfg: O.Config, sd, params, class_embedding, eot, taps: Optional[Dict] = None) -> torch.Tensor:
-    """construct_prompts + TextEncoder.forward (umudpt.py:141-168,190-204): ctx at rows 1..n_ctx, blocks 1 <= i < depth replace them by
-    deep_prompts[i - 1] -> text features [C, e]."""
-    n, C = cfg.n_ctx, class_embedding.shape[0]
-    prompts = torch.cat([class_embedding[:, :1], params[CTX].unsqueeze(0).expand(C, -1, -1), class_embedding[:, 1 + n:]], dim=1)
-    x = prompts + sd["positional_embedding"]
-    mask = O.causal_mask(x.shape[1])
-    deep = params[DEEP]
-    for i in range(cfg.t_layers):
-        if i >= 1 and i - 1 < deep.shape[0]:
-            x = torch.cat([x[:, :1], deep[i - 1].unsqueeze(0).expand(C, -1, -1), x[:, 1 + n:]], dim=1)
-        if taps is not None:
-            taps[f"txt.x_in.{i}"] = x
-        x = O.block(x, sd, f"transformer.resblocks.{i}.", cfg.t_heads, mask)
-    x = O.layer_norm(x, sd["ln_final.weight"], sd["ln_final.bias"])
-    return x[torch.arange(C), eot] @ sd["text_projection"]
+def text_prompts(ctx: torch.Tensor, class_embedding: torch.Tensor) -> torch.Tensor:
+    """construct_prompts (umudpt.py:141-168): ctx at rows 1..n_ctx of every class prompt."""
+    C = class_embedding.shape[0]
+    return torch.cat([class_embedding[:, :1], ctx.unsqueeze(0).expand(C, -1, -1), class_embedding[:, 1 + ctx.shape[0]:]], dim=1)
 
 
 def forward(cfg, sd, params, class_embedding, eot, images, taps=None) -> torch.Tensor:
-    """CustomCLIP.forward (umudpt.py:217-230) -> logits [B, C].  taps["G"]: the generator's output (kept in the graph)."""
+    """CustomCLIP.forward (umudpt.py:217-230) -> logits [B, C]: G[0] are the vision tower's input rows and G[1:] its deep rows
+    (clip/model.py:574-597), the text tower takes ctx and deep_prompts as they are (umudpt.py:190-204).  taps["G"]: the generator's output
+    (kept in the graph)."""
     G = generator(params, prompt_tables(params))
     if taps is not None:
         taps["G"] = G
-    img = vision_tower(cfg, sd, G, images, taps)
-    txt = text_tower(cfg, sd, params, class_embedding, eot, taps)
-    img = img / img.norm(dim=-1, keepdim=True)
-    txt = txt / txt.norm(dim=-1, keepdim=True)
-    return sd["logit_scale"].exp() * img @ txt.t()
+    img = O.vision_tower(cfg, sd, images, G[0], G[1:], taps)
+    txt = O.text_tower(cfg, sd, text_prompts(params[CTX], class_embedding), eot, params[DEEP], taps)
+    return O.cosine_logits(sd, img, txt)
 
 
 def forward_backward(cfg, sd, params, class_embedding, eot, images, labels):
     """F.cross_entropy (umudpt.py:292-294) and the gradient of all 20 tensors -> (loss, logits, {key: grad}, dG)."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
     taps = {}
-    logits = forward(cfg, sd, leaves, class_embedding, eot, images, taps)
-    taps["G"].retain_grad()
-    loss = F.cross_entropy(logits, labels.long())
-    loss.backward()
-    grads = {k: (v.grad.detach() if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logits.detach(), grads, taps["G"].grad.detach()
+    return O.loss_and_grads(lambda leaves: forward(cfg, sd, leaves, class_embedding, eot, images, taps), params, labels, taps=taps, keep=("G",))
 
 
 def sample_rows(key: str, rows: int, seed: int) -> List[int]:
@@ -167,33 +127,15 @@ def sample_rows(key: str, rows: int, seed: int) -> List[int]:
     return sorted(int(v) for v in torch.randperm(rows, generator=g)[:SAMPLE_ROWS])
 
 
-class UmudptCase:
-    """One tests/golden/umudpt_*.npz fixture with its frozen weights and its 20 tensors rebuilt from the seeded recipe."""
+class UmudptCase(FixtureCase):
+    """One tests/golden/umudpt_*.npz fixture with its 20 tensors rebuilt from the seeded recipe (cfg.n_ctx / cfg.depth: TRAINER.UMUDPT.N_CTX /
+    DEEP_PROMPT_DEPTH).  tests.uumudpt_reference's loader swaps in its own two recipe functions."""
+    seeded_params, trainable_keys = staticmethod(seeded_params), staticmethod(trainable_keys)
 
     def __init__(self, name: str):
-        z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
-        self.name, self.z = name, z
-        self.cfg = O.Config(**ast.literal_eval(str(z["config"])))  # n_ctx / depth: TRAINER.UMUDPT.N_CTX / DEEP_PROMPT_DEPTH
-        fs, ts, is_ = (int(v) for v in z["seeds"])
-        self.seeds = (fs, ts, is_)
-        self.frozen = O.make_frozen_state(self.cfg, fs)
-        self.frozen["logit_scale"] = torch.tensor(float(z["logit_scale"]))
-        self.classnames = [str(v) for v in z["classnames"]]
-        self.tokens = torch.from_numpy(z["tokenized_prompts"]).long()
-        self.eot = self.tokens.argmax(dim=-1)
-        self.class_embedding = self.frozen["token_embedding.weight"][self.tokens]
-        self.ctx_token_ids = [int(v) for v in z["ctx_token_ids"]]
+        super().__init__(name)
         self.ctx_init = self.frozen["token_embedding.weight"][self.ctx_token_ids]  # the reference's CTX_INIT rows (umudpt.py:96-103)
-        self.params = seeded_params(self.cfg, ts, self.ctx_init)
-        self.keys = [k for k, _ in trainable_keys(self.cfg)]
-        self.labels = torch.from_numpy(z["labels"])
-        g = torch.Generator().manual_seed(is_)
-        self.images = torch.randn(len(self.labels), 3, self.cfg.image_size, self.cfg.image_size, generator=g)
-        self.logits = torch.from_numpy(z["logits"])
-        self.loss = float(z["loss"])
-        # full gradients, or (rows, values [16, cols], rms of the whole tensor) for the sampled ones
-        self.grads = {k: torch.from_numpy(z["grad." + k]) for k in self.keys if "grad." + k in z.files}
-        self.grad_samples = {k: ([int(r) for r in z["grad_rows." + k + ".idx"]], torch.from_numpy(z["grad_rows." + k]), float(z["grad_rms." + k]))
-                             for k in self.keys if "grad_rows." + k in z.files}
-        self.init_checksums = {k: [float(v) for v in z["init_checksum." + k]] for k in self.keys}
-        self.taps = {k[4:]: (torch.from_numpy(z[k]), [int(r) for r in z[k + ".rows"]]) for k in z.files if k.startswith("tap.") and not k.endswith(".rows")}
+        self.params = self.seeded_params(self.cfg, self.seeds[1], self.ctx_init)
+        self.keys = [k for k, _ in self.trainable_keys(self.cfg)]
+        self.load_grads()
+        self.init_checksums = {k: [float(v) for v in self.z["init_checksum." + k]] for k in self.keys}

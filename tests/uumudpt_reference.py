@@ -6,7 +6,7 @@ UUMuDPT is UMuDPT with the coupling in both directions.  Gen1, the prompt learne
 ``visual_ctx_deep_prompts`` [D - 1, n, d_v] and Gen2, the same pipeline (LayerNorm -> one pre-LN block -> LayerNorm -> Linear) at width d_v
 with d_v / 64 heads and output width e: T [D - 1, n, e] = Gen2(visual_ctx_deep_prompts).  Vision input prompt rows G[0] + visual_ctx, vision
 deep prompts G[1:] + visual_ctx_deep_prompts, text deep prompts deep_prompts + T (uumudpt.py:224: needs e == d_t), text input rows ctx.  The
-blocks are MuDPT's (``ResidualAttentionBlock_UUMuDPT``), so both towers are tests/umudpt_reference's, fed the sums.
+blocks are MuDPT's (``ResidualAttentionBlock_UUMuDPT``), so both towers are ``oracle.mudpt_oracle``'s, fed the sums.
 
 Both generators ARE :func:`tests.umudpt_reference.generator` / ``generator_backward``: :func:`gen_params` renames one generator's 18 tensors
 to the keys those functions read; nothing of them is restated here.  Pinned by the fixtures of tests/golden/gen_golden_uumudpt.py, which ran the
@@ -14,14 +14,10 @@ reference's own modules (tests/test_uumudpt_cpu.py).
 """
 from __future__ import annotations
 
-import ast
 import math
-import os
 from typing import Dict, List, Optional, Tuple
 
-import numpy as np
 import torch
-import torch.nn.functional as F
 
 from oracle import mudpt_oracle as O
 from tests import umudpt_reference as U
@@ -122,56 +118,23 @@ def forward(cfg, sd, params, class_embedding, eot, images, taps=None) -> torch.T
     if taps is not None:
         taps["G"], taps["T"] = G, T
     vis = torch.cat([G[:1] + params[VCTX].unsqueeze(0), G[1:] + params[VDEEP]], dim=0)  # clip/model.py:638-643
-    img = U.vision_tower(cfg, sd, vis, images, taps)
-    txt = U.text_tower(cfg, sd, {U.CTX: params[CTX], U.DEEP: params[DEEP] + T}, class_embedding, eot, taps)  # uumudpt.py:224
-    img = img / img.norm(dim=-1, keepdim=True)
-    txt = txt / txt.norm(dim=-1, keepdim=True)
-    return sd["logit_scale"].exp() * img @ txt.t()
+    img = O.vision_tower(cfg, sd, images, vis[0], vis[1:], taps)
+    txt = O.text_tower(cfg, sd, U.text_prompts(params[CTX], class_embedding), eot, params[DEEP] + T, taps)  # uumudpt.py:224
+    return O.cosine_logits(sd, img, txt)
 
 
 def forward_backward(cfg, sd, params, class_embedding, eot, images, labels):
     """F.cross_entropy (uumudpt.py:298-299) and the gradient of all 40 tensors -> (loss, logits, {key: grad}, dG, dT)."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
     taps = {}
-    logits = forward(cfg, sd, leaves, class_embedding, eot, images, taps)
-    taps["G"].retain_grad()
-    taps["T"].retain_grad()
-    loss = F.cross_entropy(logits, labels.long())
-    loss.backward()
-    grads = {k: (v.grad.detach() if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    dT = taps["T"].grad
-    return loss.detach(), logits.detach(), grads, taps["G"].grad.detach(), torch.zeros_like(taps["T"]) if dT is None else dT.detach()
+    return O.loss_and_grads(lambda leaves: forward(cfg, sd, leaves, class_embedding, eot, images, taps), params, labels, taps=taps, keep=("G", "T"))
 
 
-class UumudptCase:
-    """One tests/golden/uumudpt_*.npz fixture with its frozen weights and its 40 tensors rebuilt from the seeded recipe."""
+class UumudptCase(U.UmudptCase):
+    """One tests/golden/uumudpt_*.npz fixture with its 40 tensors rebuilt from the seeded recipe (cfg.n_ctx / cfg.depth: TRAINER.UUMUDPT.N_CTX /
+    DEEP_PROMPT_DEPTH; ctx_init: uumudpt.py:97-104)."""
+    seeded_params, trainable_keys = staticmethod(seeded_params), staticmethod(trainable_keys)
 
     def __init__(self, name: str):
-        z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
-        self.name, self.z = name, z
-        self.cfg = O.Config(**ast.literal_eval(str(z["config"])))  # n_ctx / depth: TRAINER.UUMUDPT.N_CTX / DEEP_PROMPT_DEPTH
-        fs, ts, is_ = (int(v) for v in z["seeds"])
-        self.seeds = (fs, ts, is_)
-        self.frozen = O.make_frozen_state(self.cfg, fs)
-        self.frozen["logit_scale"] = torch.tensor(float(z["logit_scale"]))
-        self.classnames = [str(v) for v in z["classnames"]]
-        self.tokens = torch.from_numpy(z["tokenized_prompts"]).long()
-        self.eot = self.tokens.argmax(dim=-1)
-        self.class_embedding = self.frozen["token_embedding.weight"][self.tokens]
-        self.ctx_token_ids = [int(v) for v in z["ctx_token_ids"]]
-        self.ctx_init = self.frozen["token_embedding.weight"][self.ctx_token_ids]  # the reference's CTX_INIT rows (uumudpt.py:97-104)
-        self.params = seeded_params(self.cfg, ts, self.ctx_init)
-        self.keys = [k for k, _ in trainable_keys(self.cfg)]
-        self.labels = torch.from_numpy(z["labels"])
-        g = torch.Generator().manual_seed(is_)
-        self.images = torch.randn(len(self.labels), 3, self.cfg.image_size, self.cfg.image_size, generator=g)
-        self.logits = torch.from_numpy(z["logits"])
-        self.loss = float(z["loss"])
-        # full gradients, or (rows, values [16, cols], rms of the whole tensor) for the sampled ones
-        self.grads = {k: torch.from_numpy(z["grad." + k]) for k in self.keys if "grad." + k in z.files}
-        self.grad_samples = {k: ([int(r) for r in z["grad_rows." + k + ".idx"]], torch.from_numpy(z["grad_rows." + k]), float(z["grad_rms." + k]))
-                             for k in self.keys if "grad_rows." + k in z.files}
-        self.init_checksums = {k: [float(v) for v in z["init_checksum." + k]] for k in self.keys}
-        self.sample_above = int(z["sample_above"])
-        self.missing_keys = [str(v) for v in z["clip_missing_keys"]]  # what CLIP.load_state_dict reported for the frozen state dict
-        self.taps = {k[4:]: (torch.from_numpy(z[k]), [int(r) for r in z[k + ".rows"]]) for k in z.files if k.startswith("tap.") and not k.endswith(".rows")}
+        super().__init__(name)
+        self.sample_above = int(self.z["sample_above"])
+        self.missing_keys = [str(v) for v in self.z["clip_missing_keys"]]  # what CLIP.load_state_dict reported for the frozen state dict
