@@ -83,7 +83,9 @@ extern "C" {
 #endif
 
 /* 7 still with mudpt_create_frozen, mudpt_set_text_tokens, mudpt_text_features and mudpt_encode_image: they are additions, no existing
- * declaration, struct or constant changed, so every caller built against 7 runs unchanged -- the number moves when one would not. */
+ * declaration, struct or constant changed, so every caller built against 7 runs unchanged -- the number moves when one would not.
+ * mudpt_amd/capi.py binds from this file: it parses every declaration (int / int32_t / int64_t / float / size_t, const char*, any other pointer
+ * or array; a type outside that raises at import) and every integer #define MUDPT_*, so names, types and order are stated here only. */
 #define MUDPT_ABI_VERSION 7
 
 #define MUDPT_OK 0

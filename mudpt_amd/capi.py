@@ -4,21 +4,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
+from operator import itemgetter
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MUDPT_LIB") or os.path.join(HERE, "lib", "libmudpt_hip.so")  # MUDPT_LIB: A/B runs of two builds on one box
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "mudpt.h")
 
-BF16, F16, F32 = 0, 1, 2  # F32: the parity mode (include/mudpt.h MUDPT_F32)
-VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARIANT_MPT, VARIANT_UMUDPT, VARIANT_UUMUDPT = 0, 1, 2, 3, 4, 5, 6, 7
-CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = 0, 1, 2  # TRAINER.COOP.CLASS_TOKEN_POSITION "end" / "middle" / "front"
-ABI_VERSION = 7
-EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = range(6)
-# mudpt_attention_form's codes (include/mudpt.h MUDPT_ATTN_*), by name
-ATTN_FORMS = ("FWD_PAIR", "FWD_PERSISTENT", "FWD_RESIDENT", "FWD_STAGED", "BWD_TWO", "BWD_FUSED_W2", "BWD_FUSED_W1", "BWD_SWEEP", "BWD_RESIDENT",
-              "BWD_STAGED")
-# mudpt_gemm_form's codes (include/mudpt.h MUDPT_GEMM_*), by name
-GEMM_FORMS = ("PP", "T256x256", "T128x256", "T256x128", "T64x64_K128", "T64x64", "T128x64_RING4", "T128x128", "SPLITK_K128", "SPLITK_K64")
+EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BWD, EPI_PATCH, EPI_STORE_F32 = range(6)  # kernels.h Epilogue: not a #define of the header
 
 
 class MudptError(RuntimeError):
@@ -36,112 +28,64 @@ class PromptShape(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("t_n_ctx", "t_depth", "v_n_ctx", "v_depth")]
 
 
-_vp, _i32, _f32, _sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "size_t": C.c_size_t}
+_RETURNS = {"int": C.c_int32, "size_t": C.c_size_t, "const char*": C.c_char_p}
 
-# name -> (restype, argtypes); must list every function include/mudpt.h declares (tests check that)
-SIGNATURES = {
-    "mudpt_abi_version": (_i32, []),
-    "mudpt_last_error": (C.c_char_p, []),
-    "mudpt_create": (_i32, [C.POINTER(Config), C.POINTER(_vp)]),
-    "mudpt_create_ex": (_i32, [C.POINTER(Config), C.POINTER(PromptShape), C.POINTER(_vp)]),
-    "mudpt_create_frozen": (_i32, [C.POINTER(Config), C.POINTER(_vp)]),
-    "mudpt_destroy": (_i32, [_vp]),
-    "mudpt_set_text_tokens": (_i32, [_vp, _vp, _i32]),
-    "mudpt_text_features": (_i32, [_vp, _vp, _vp]),
-    "mudpt_encode_image": (_i32, [_vp, _vp, _i32, _vp, _vp]),
-    "mudpt_set_weight": (_i32, [_vp, C.c_char_p, _vp, _sz]),
-    "mudpt_set_class_prompts": (_i32, [_vp, _vp, _vp]),
-    "mudpt_set_class_token_position": (_i32, [_vp, _i32, _vp]),
-    "mudpt_param_count": (_i32, [_vp]),
-    "mudpt_param_numel": (_sz, [_vp]),
-    "mudpt_param_info": (_i32, [_vp, _i32, C.POINTER(C.c_char_p), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i32),
-                                C.POINTER(C.c_int64 * 3)]),
-    "mudpt_bind_params": (_i32, [_vp, _vp, _vp]),
-    "mudpt_forward": (_i32, [_vp, _vp, _i32, _vp, _vp]),
-    "mudpt_forward_ex": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
-    "mudpt_forward_backward": (_i32, [_vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp]),
-    "mudpt_sgd_step": (_i32, [_vp, _f32, _f32, _f32, _f32, _i32, _vp]),
-    "mudpt_sgd_reset": (_i32, [_vp]),
-    "mudpt_allreduce_grads": (_i32, [_vp, _vp, _vp]),
-    "mudpt_text_layout": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
-    "mudpt_set_class_shard": (_i32, [_vp, _i32, _i32]),
-    "mudpt_cp_buffers": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
-    "mudpt_cp_forward": (_i32, [_vp, _vp, _i32, _i32, _vp]),
-    "mudpt_cp_head": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp, _i32, _vp]),
-    "mudpt_cp_backward": (_i32, [_vp, _i32, _vp]),
-    "mudpt_debug_read": (_i32, [_vp, C.c_char_p, _i32, _vp, _sz, C.POINTER(_sz)]),
-    "mudpt_set_loss_scale": (_i32, [_vp, _f32]),
-    "mudpt_model_set": (_i32, [_vp, C.c_char_p, _i32]),
-    "mudpt_profile_enable": (_i32, [_vp, _i32]),
-    "mudpt_profile_read": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "mudpt_profile_read_classes": (_i32, [_vp, C.POINTER(C.c_double * 5), C.POINTER(C.c_double * 5), C.POINTER(C.c_int64 * 5), C.POINTER(C.c_double)]),
-    "mudpt_gemm": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
-                          _i32, _i32, _vp, _i32, _vp]),
-    "mudpt_gemm_form": (_i32, [_i32] * 10),
-    "mudpt_gemm_split": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
-    "mudpt_gemm_split_patch": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32,
-                                      _i32, _i32, _vp, _i32, _vp]),
-    "mudpt_e4m3_from_f32":(_i32, [_vp, _vp, _sz, _i32]),
-    "mudpt_layernorm_fwd_split": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_layernorm_fwd": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
-    "mudpt_layernorm_bwd": (_i32, [_i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
-                                   _i32, _i32, _i32, _vp]),
-    "mudpt_attention_padded_len": (_i32, [_i32]),
-    "mudpt_attention_fwd": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_attention_form": (_i32, [_i32, _i32, _i32, _i32]),
-    "mudpt_attention_fwd_exact": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_attention_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_attention_fwd_single": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_attention_bwd_single": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_layernorm_fwd_fused": (_i32, [_i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32,
-                                         _vp, _vp, _i32, _i32, _vp]),
-    "mudpt_head": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "mudpt_reduce_rows": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _vp]),
-    "mudpt_cocoop_dbias": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
-    "mudpt_coop_dctx": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
-    "mudpt_sgemm": (_i32, [_i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i32, _f32, _vp, _i32, _vp, _vp]),
-    "mudpt_layernorm_bwd_ex": (_i32, [_i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
-                                      _vp, _i32, _i32, _i32, _sz, _i32, _i32, _i32, _vp]),
-    "mudpt_layernorm_fwd_ex": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
-                                      _vp, _vp, _i32, _i32, _vp]),
-    "mudpt_attention_fwd_split": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_attention_fwd_single_split": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_attention_bwd_sel": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_head_ex": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_i32), _vp]),
-    "mudpt_pair_head": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "mudpt_patchify": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_set_rows": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "mudpt_gather_rows": (_i32, [_vp, _sz, _vp, _vp, _sz, _i32, _i32, _vp]),
-    "mudpt_scatter_rows": (_i32, [_vp, _sz, _vp, _vp, _sz, _i32, _i32, _vp]),
-    "mudpt_add_rows": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp]),
-    "mudpt_linear_bwd": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mudpt_colsum": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp]),
-    "mudpt_add": (_i32, [_vp, _vp, _vp, _sz, _vp]),
-    "mudpt_cast": (_i32, [_i32, _vp, _vp, _sz, _vp]),
-    "mudpt_relu": (_i32, [_vp, _sz, _vp]),
-    "mudpt_relu_bwd": (_i32, [_vp, _vp, _sz, _vp]),
-    "mudpt_cocoop_prompts": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_coop_splice": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_embed_tokens": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
-    "mudpt_feature_ensemble": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_layernorm_bwd_affine": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "mudpt_pg_attention_fwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_pg_attention_bwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "mudpt_quickgelu_fwd": (_i32, [_vp, _vp, _sz, _vp]),
-    "mudpt_quickgelu_bwd": (_i32, [_vp, _vp, _vp, _sz, _vp]),
-    "mudpt_promptgen_workspace": (_sz, [_i32, _i32, _i32, _i32]),
-    "mudpt_promptgen_param_numel": (_sz, [_i32, _i32]),
-    "mudpt_promptgen_forward": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mudpt_promptgen_backward": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-}
+
+def parse_header(text):
+    """name -> (restype, [(parameter name, ctype)]) of every `ret mudpt_name(params);` of a header, in the vocabulary include/mudpt.h uses:
+    the scalars above, `const char*` (c_char_p) and any other pointer, `T**` or `T name[n]` (c_void_p: ctypes takes byref(x) there).  A type
+    outside it raises with the declaration's name; nothing is guessed."""
+    text = re.sub(r"^[ \t]*#.*$", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S), flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t]*?\**)\s*\b(mudpt_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise MudptError(f"{name}: return type '{ret}' is outside the binding's vocabulary")
+        args = []
+        for p in (q.strip() for q in params.split(",") if params.strip() != "void"):
+            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)\s*(\w+)\s*(\[\d*\])?", p)
+            base, stars, pname, array = m.groups() if m else (None, "", None, None)
+            if stars or array:
+                ctype = C.c_char_p if (base, stars, array) == ("char", "*", None) else C.c_void_p
+            elif base in _SCALARS:
+                ctype = _SCALARS[base]
+            else:
+                raise MudptError(f"{name}: parameter '{p}' is outside the binding's vocabulary")
+            args.append((pname, ctype))
+        out[name] = (_RETURNS[ret], args)
+    missed = sorted(set(re.findall(r"\b(mudpt_[a-z0-9_]+)\s*\(", text)) - set(out))
+    if missed:
+        raise MudptError(f"{', '.join(missed)}: declared in a form that was not read")
+    return out
+
+
+def parse_defines(text, prefix):
+    """{NAME: value} of every `#define <prefix>NAME <integer>` of a header."""
+    return {n: int(v) for n, v in re.findall(rf"^[ \t]*#define\s+{prefix}(\w+)\s+(-?\d+)\b", text, flags=re.M)}
+
+
+_HEADER = open(HEADER_PATH).read()
+DECLARATIONS = parse_header(_HEADER)  # include/mudpt.h is the only statement of names, types and order
+SIGNATURES = {name: (res, [t for _, t in params]) for name, (res, params) in DECLARATIONS.items()}  # name -> (restype, argtypes)
+_DEFINES = parse_defines(_HEADER, "MUDPT_")
+# spelled out, so that a #define that is gone fails here, at import, with its name (KeyError)
+ABI_VERSION = _DEFINES["ABI_VERSION"]
+BF16, F16, F32 = itemgetter("BF16", "F16", "F32")(_DEFINES)  # F32: the parity mode
+VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARIANT_MPT, VARIANT_UMUDPT, VARIANT_UUMUDPT = itemgetter(
+    "VARIANT_MUDPT", "VARIANT_COCOOP", "VARIANT_COOP", "VARIANT_COOP_CSC", "VARIANT_VPT", "VARIANT_MPT", "VARIANT_UMUDPT", "VARIANT_UUMUDPT")(_DEFINES)
+CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = itemgetter("CLASS_TOKEN_END", "CLASS_TOKEN_MIDDLE", "CLASS_TOKEN_FRONT")(_DEFINES)  # TRAINER.COOP.CLASS_TOKEN_POSITION
+CP_VISION, CP_TEXT = itemgetter("CP_VISION", "CP_TEXT")(_DEFINES)  # mudpt_cp_backward parts
+FWD_REUSE_TEXT, FWD_TRAINING = itemgetter("FWD_REUSE_TEXT", "FWD_TRAINING")(_DEFINES)  # mudpt_forward_ex / mudpt_cp_forward flags
+# the codes of mudpt_attention_form / mudpt_gemm_form (MUDPT_ATTN_* / MUDPT_GEMM_*): the names after the prefix, ordered by value
+ATTN_FORMS, GEMM_FORMS = (tuple(n[len(pre):] for n in sorted(_DEFINES, key=_DEFINES.get) if n.startswith(pre)) for pre in ("ATTN_", "GEMM_"))
 
 _lib = None
 
 
-def declared_functions(header: str = HEADER_PATH):
+def declared_functions():
     """Function names declared in include/mudpt.h."""
-    text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(mudpt_[a-z0-9_]+)\s*\(", text)))
+    return sorted(SIGNATURES)
 
 
 def load():
@@ -173,8 +117,22 @@ def check(rc: int, what: str = ""):
         raise MudptError(f"mudpt {what}: {kind}: {msg}")
 
 
-CP_VISION, CP_TEXT = 1, 2  # mudpt_cp_backward parts
-FWD_REUSE_TEXT, FWD_TRAINING = 1, 2  # mudpt_forward_ex / mudpt_cp_forward flags
+def call(name, **kw):
+    """Call export `name` with the header's parameter names and return its code, unchecked.  A torch tensor passes its data_ptr(); None or
+    an omitted pointer is null (`stream`: the null stream), an omitted scalar 0."""
+    params = DECLARATIONS[name][1]
+    unknown = sorted(set(kw) - {n for n, _ in params})
+    if unknown:
+        raise TypeError(f"{name} has no parameter {', '.join(unknown)}")
+    args = []
+    for n, t in params:
+        v, pointer = kw.get(n), t in (C.c_void_p, C.c_char_p)
+        if hasattr(v, "data_ptr"):
+            if not pointer:
+                raise TypeError(f"{name}: a tensor for the scalar parameter {n}")
+            v = v.data_ptr()
+        args.append(0 if v is None and not pointer else v)
+    return getattr(load(), name)(*args)
 
 
 class _DeviceMemory:

@@ -130,7 +130,7 @@ class Launches:
         B, L, H, Lp = self.B, self.L, self.H, self.Lp
         obuf, out = guarded((B, L, H * 64), self.tt, SENT)
         lbuf, lse = guarded((B, H, Lp), torch.float32, SENT)
-        ok(self.lib, self.lib.mudpt_attention_fwd(self.dt, P(self.qkv), P(out), P(lse), B, L, H, flags, None))
+        ok(self.lib, capi.call("mudpt_attention_fwd", dtype=self.dt, qkv=self.qkv, out=out, lse=lse, B=B, L=L, H=H, causal=flags))
         assert_guards(obuf, out, SENT, f"{form} out")
         assert_guards(lbuf, lse, SENT, f"{form} lse")
         assert not out.isnan().any(), f"{form}: out has unwritten or poisoned elements"
@@ -145,7 +145,7 @@ class Launches:
         o.copy_(out)
         dbuf, dqkv = guarded((B, L, 3 * H * 64), self.tt, SENT)
         ebuf, delta = guarded((B, H, Lp), torch.float32, SENT)
-        ok(self.lib, self.lib.mudpt_attention_bwd(self.dt, P(self.qkv), P(o), P(self.dout), P(lse), P(delta), P(dqkv), B, L, H, flags, None))
+        ok(self.lib, capi.call("mudpt_attention_bwd", dtype=self.dt, qkv=self.qkv, out=o, dout=self.dout, lse=lse, delta=delta, dqkv=dqkv, B=B, L=L, H=H, causal=flags))
         assert_guards(dbuf, dqkv, SENT, f"{form} dqkv")
         assert_guards(ebuf, delta, SENT, f"{form} delta")
         assert not dqkv.isnan().any(), f"{form}: dqkv has unwritten or poisoned elements"
@@ -326,7 +326,7 @@ def test_attention_single_query_edges_guarded(lib, dtype, B, L, H, causal, posit
     sel = (rows * L + pos).to(torch.int32).cuda()
     obuf, out_sel = guarded((B, Hd), tt, SENT)
     lbuf, lse_sel = guarded((B, H), torch.float32, SENT)
-    ok(lib, lib.mudpt_attention_fwd_single(dt, P(qc), P(q_sel), P(sel), P(out_sel), P(lse_sel), B, L, H, int(causal), None))
+    ok(lib, capi.call("mudpt_attention_fwd_single", dtype=dt, qkv=qc, q_sel=q_sel, sel_rows=sel, out_sel=out_sel, lse_sel=lse_sel, B=B, L=L, H=H, causal=int(causal)))
     assert_guards(obuf, out_sel, SENT, "out_sel")
     assert_guards(lbuf, lse_sel, SENT, "lse_sel")
     torch.testing.assert_close(out_sel.cpu().double(), ref_out[rows, pos], atol=6 * EPS[dtype], rtol=6 * EPS[dtype])

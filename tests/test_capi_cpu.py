@@ -1,6 +1,7 @@
 """No-GPU checks of the C-ABI library: it loads, and exports every function include/mudpt.h declares."""
 import ctypes as C
 import os
+import re
 
 import pytest
 
@@ -15,12 +16,46 @@ def lib():
 
 
 def test_header_functions_are_exported_and_bound(lib):
+    """capi.py binds from include/mudpt.h itself: every declaration is exported by the library and bound with the header's types and order."""
     declared = capi.declared_functions()
-    assert len(declared) >= 20
+    loose = re.findall(r"\b(mudpt_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", open(capi.HEADER_PATH).read(), flags=re.S))  # an independent, looser scan
+    assert len(declared) >= 20 and declared == sorted(set(loose)), "a declaration the parser did not read"
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/mudpt.h but not exported"
-        assert name in capi.SIGNATURES, f"{name} has no ctypes signature in mudpt_amd/capi.py"
-    assert sorted(capi.SIGNATURES) == declared
+        fn, (res, params) = getattr(lib, name), capi.DECLARATIONS[name]
+        assert fn.restype is res and list(fn.argtypes) == [t for _, t in params] == capi.SIGNATURES[name][1], name
+
+
+def test_header_parser_vocabulary():
+    """One declaration per type the header may use -> its ctypes; comments and preprocessor lines are no declarations; an unknown type raises."""
+    text = """/* int mudpt_in_a_comment(int x); */
+    #define MUDPT_NOT_A_FUNCTION(x) 1
+    typedef struct mudpt_model mudpt_model;
+    int mudpt_a(void);
+    const char* mudpt_b(int i, int32_t j, int64_t k, float f, size_t n);
+    size_t mudpt_c(const mudpt_model* m, const char* key, const char** name, mudpt_model** out,
+                   int64_t shape[3], const float* x, uint8_t* bytes, void* stream);"""
+    i32, vp = C.c_int32, C.c_void_p
+    assert capi.parse_header(text) == {
+        "mudpt_a": (i32, []), "mudpt_b": (C.c_char_p, [("i", i32), ("j", i32), ("k", C.c_int64), ("f", C.c_float), ("n", C.c_size_t)]),
+        "mudpt_c": (C.c_size_t, [("m", vp), ("key", C.c_char_p), ("name", vp), ("out", vp), ("shape", vp), ("x", vp), ("bytes", vp), ("stream", vp)])}
+    for declaration, word in (("int mudpt_x(double v);", "double v"), ("int mudpt_x(unsigned n);", "unsigned n"), ("double mudpt_x(void);", "double"),
+                              ("int mudpt_x(mudpt_config cfg);", "mudpt_config cfg"), ("int mudpt_x(const unsigned char* p);", "unsigned char"),
+                              ("int mudpt_ok(void);\nint mudpt_x(void (*cb)(int));", "not read")):  # a form the parser cannot consume is no silent gap
+        with pytest.raises(capi.MudptError, match="mudpt_x.*" + word):
+            capi.parse_header(declaration)
+    assert capi.parse_defines("#define MUDPT_X_B 1  /* one */\n#define MUDPT_X_A 0\n#define MUDPT_Y 7\n", "MUDPT_X_") == {"B": 1, "A": 0}
+    assert (capi.BF16, capi.F16, capi.F32, capi.VARIANT_UUMUDPT, capi.CLASS_TOKEN_FRONT, capi.CP_TEXT, capi.FWD_TRAINING) == (0, 1, 2, 7, 2, 2, 2)
+    assert capi.ATTN_FORMS[:2] == ("FWD_PAIR", "FWD_PERSISTENT") and capi.GEMM_FORMS[::9] == ("PP", "SPLITK_K64") and len(capi.ATTN_FORMS) == len(capi.GEMM_FORMS) == 10
+
+
+def test_call_by_name_refuses_an_unknown_keyword(lib):
+    import torch
+    for kw, word in (({"Lp": 33}, "Lp"), ({"L": torch.zeros(1)}, "L")):  # a keyword the export does not have; a tensor for a scalar parameter
+        with pytest.raises(TypeError, match="mudpt_attention_padded_len.*" + word):
+            capi.call("mudpt_attention_padded_len", **kw)
+    assert (capi.call("mudpt_attention_padded_len", L=33), capi.call("mudpt_attention_padded_len")) == (64, lib.mudpt_attention_padded_len(0))  # omitted scalar: 0
+    assert capi.call("mudpt_create") == 1 and b"null" in lib.mudpt_last_error()  # omitted pointers are null
 
 
 def test_abi_version(lib):
@@ -60,9 +95,7 @@ def test_product_does_not_import_the_oracle():
 def test_host_e4m3_conversion_matches_torch():
     """mudpt_e4m3_from_f32 (the conversion mudpt_set_weight applies to the frozen weights for the e4m3 second pass of the parity mode's
     vision tower) is OCP e4m3fn with round-to-nearest-even and saturation at +-448: bit for bit torch's float8_e4m3fn on in-range values."""
-    import ctypes as C
     import torch
-    from mudpt_amd import capi
     lib = capi.load()
     g = torch.Generator().manual_seed(0)
     x = torch.cat([torch.randn(20000, generator=g) * s for s in (1e-3, 0.02, 0.5, 4.0, 100.0)] +
@@ -94,7 +127,6 @@ def test_every_launcher_is_called_from_a_test_export():
     """Every `int launch_*` kernels.h declares must be called from one of the single-kernel exports of model.cpp (the surface the float64 parity
     tests of tests/test_kernels_gpu.py, test_exact_gpu.py and test_movers_gpu.py drive), or stand in the allowlist above with its reason.  A new
     launcher that only the whole-model tests reach fails here."""
-    import re
     csrc = os.path.join(os.path.dirname(capi.HERE), "mudpt_amd", "csrc")
     header = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "kernels.h")).read())
     launchers = sorted(set(re.findall(r"^\s*int\s+(launch_[a-z0-9_]+)\s*\(", header, flags=re.M)))
@@ -116,7 +148,6 @@ def test_every_launcher_is_called_from_a_test_export():
 def model_set_names(source):
     """The knob names mudpt_model_set compares its argument against: `strcmp(name, "x")` as it stands, `strcmp(k, "x")` behind the tower
     prefix ("vis_" / "txt_"; only "txt_" where the comparison is guarded by `t == &m->txt`)."""
-    import re
     body = source[source.index('extern "C" int mudpt_model_set('):]
     body = re.sub(r"//[^\n]*", "", body[:body.index("unknown knob")])
     names = set(re.findall(r'strcmp\(name, "(\w+)"\)', body))
@@ -127,7 +158,6 @@ def model_set_names(source):
 
 def header_knob_table(header):
     """The names in the first column of the knob table above mudpt_model_set's declaration."""
-    import re
     table = header[header.index(" *   knob               default"):header.index("int mudpt_model_set(")]
     return set(re.findall(r"^ \*   ([a-z][a-z0-9_]*) ", table, flags=re.M)) - {"knob"}
 

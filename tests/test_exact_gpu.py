@@ -12,7 +12,7 @@ import os
 import pytest
 import torch
 
-from tests.helpers import GoldenCase
+from tests.helpers import GoldenCase, ok
 from tests.test_model_gpu import build
 
 pytestmark = pytest.mark.gpu
@@ -260,10 +260,8 @@ def test_split_operand_gemm(lo_mode, M, N, K, epi):
     out0 = torch.zeros(M, N, device="cuda", dtype=torch.float32 if out_f32 else torch.float16)
     out1 = torch.zeros(M, N, device="cuda", dtype=torch.float16) if epi == 1 else None
     out1_lo = (torch.zeros(M, N, device="cuda", dtype=torch.float16) if lo_mode == 1 else torch.zeros(M, 2 * N, device="cuda", dtype=torch.uint8)) if epi == 1 else None
-    rc = lib.mudpt_gemm_split(1, epi, M, N, K, P(hi_d), P(lo_d), lo_mode, K, P(W_d), P(W8_d), s8, K, P(bias_d), P(out0), N, P(out1), P(out1_lo), lo_mode, N,
-                              P(aux), N, 0, None)
-    assert rc == 0, lib.mudpt_last_error().decode()
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_gemm_split", dtype=1, epilogue=epi, M=M, N=N, K=K, A=hi_d, A_lo=lo_d, lo_mode=lo_mode, lda=K, B=W_d, B8=W8_d, b8_scale=s8, ldb=K, bias=bias_d,
+                      out0=out0, ldo0=N, out1=out1, out1_lo=out1_lo, out1_lo_mode=lo_mode, ldo1=N, aux=aux, ldaux=N))
     # what the two passes contract: hi . W + lo . (W or its e4m3 copy)
     Wd = W.double()
     ref = hi.double() @ Wd.t() + (a_eff - hi.double()) @ (w8_eff if lo_mode == 2 else Wd).t() + bias.double()
@@ -305,8 +303,7 @@ def test_layernorm_writes_split_operands(lo_mode):
     gamma, beta = (1 + 0.1 * torch.randn(d, generator=g)).cuda(), (0.05 * torch.randn(d, generator=g)).cuda()
     out = torch.zeros(rows, d, device="cuda", dtype=torch.float16)
     lo = torch.zeros(rows, d, device="cuda", dtype=torch.float16) if lo_mode == 1 else torch.zeros(rows, 2 * d, device="cuda", dtype=torch.uint8)
-    assert lib.mudpt_layernorm_fwd_split(1, P(x), d, P(gamma), P(beta), P(out), P(lo), lo_mode, d, rows, d, None) == 0, lib.mudpt_last_error().decode()
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_fwd_split", dtype=1, x=x, ldx=d, gamma=gamma, beta=beta, out=out, out_lo=lo, lo_mode=lo_mode, ldo=d, rows=rows, d=d))
     y = torch.nn.functional.layer_norm(x.double(), (d,), gamma.double(), beta.double(), 1e-5).cpu()
     lo_v = lo.double().cpu() if lo_mode == 1 else lo[:, :d].cpu().view(torch.float8_e4m3fn).float().double() / 4096.0
     err = (out.double().cpu() + lo_v - y).abs().max().item()

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from mudpt_amd import capi
-from tests.helpers import (GEMM_FORM_CASES, GEMM_GELU_CASES, GEMM_GUARD_ROWS, GEMM_REFUSAL_CASES, SENT, P, gemm_form_args, gemm_windows, ok,
+from tests.helpers import (GEMM_FORM_CASES, GEMM_GELU_CASES, GEMM_GUARD_ROWS, GEMM_REFUSAL_CASES, SENT, gemm_form_args, gemm_windows, ok,
                            pp_case_for, refused)
 
 pytestmark = pytest.mark.gpu
@@ -100,9 +100,9 @@ def run_windowed(lib, dtype, epi, case, ops, variant=None, windows=True, q8=Fals
     got = lib.mudpt_gemm_form(epi, M, N, K, out0.stride(0), ldo1, ldaux, 0, variant, device_cus())
     want = capi.GEMM_FORMS.index(case.form) | case.slices << 8
     assert got == want, f"{case.name} epilogue {epi}: form {capi.GEMM_FORMS[got & 0xff] if got >= 0 else got} x {got >> 8}, the case is there for {case.form} x {case.slices}"
-    ok(lib, lib.mudpt_gemm(dt, epi, M, N, K, P(A), A.stride(0), P(B), B.stride(0), P(bias), P(out0), out0.stride(0), P(out1),
-                           out1.stride(0) if out1 is not None else 0, P(aux), aux.stride(0) if aux is not None else 0, patches, seq_len, P(pos),
-                           variant | (Q8 if q8 else 0), None))
+    ok(lib, capi.call("mudpt_gemm", dtype=dt, epilogue=epi, M=M, N=N, K=K, A=A, lda=A.stride(0), B=B, ldb=B.stride(0), bias=bias, out0=out0, ldo0=out0.stride(0), out1=out1,
+                      ldo1=out1.stride(0) if out1 is not None else 0, aux=aux, ldaux=aux.stride(0) if aux is not None else 0, patches=patches, seq_len=seq_len, pos=pos,
+                      variant=variant | (Q8 if q8 else 0)))
     assert_outside_untouched(buf0, out_rows, N, w["out0"], sent0, written)
     if buf1 is not None:
         assert_outside_untouched(buf1, M, N, w["out1"], SENT)
@@ -212,6 +212,6 @@ def test_gemm_output_stride_the_persistent_kernel_cannot_take(lib, dtype):
     for pads in ((4, 0), (0, 4)):  # lda = K + 4, then ldb = K + 4
         A = torch.zeros(M, K + pads[0], device="cuda", dtype=tt)
         B = torch.zeros(N, K + pads[1], device="cuda", dtype=tt)
-        refused(lib, lib.mudpt_gemm(DT[dtype][0], capi.EPI_STORE_F32, M, N, K, P(A), A.stride(0), P(B), B.stride(0), None, P(out), N, None, 0, None, 0, 0, 0,
-                                    None, 0, None), "bad lda/ldb")
+        refused(lib, capi.call("mudpt_gemm", dtype=DT[dtype][0], epilogue=capi.EPI_STORE_F32, M=M, N=N, K=K, A=A, lda=A.stride(0), B=B, ldb=B.stride(0), out0=out, ldo0=N),
+                "bad lda/ldb")
         assert bool((out == SENT).all())

@@ -16,7 +16,7 @@ import torch
 
 from mudpt_amd import capi
 from tests.helpers import (EPS, GEMM_GUARD_ROWS, GEMM_SPLIT_B8_SCALE, GEMM_SPLIT_B8_SCALE_ONE, GEMM_SPLIT_CASES, GEMM_SPLIT_GELU_ALL_PAIRS,
-                           GEMM_SPLIT_GELU_CASES, GEMM_SPLIT_PATCH_CASES, GEMM_SPLIT_SCALE_CASES, SENT, P, check_split_pair, gemm_split_gelu_case,
+                           GEMM_SPLIT_GELU_CASES, GEMM_SPLIT_PATCH_CASES, GEMM_SPLIT_SCALE_CASES, SENT, check_split_pair, gemm_split_gelu_case,
                            gemm_windows, ok, refused)
 from tests.test_gemm_forms_gpu import DT, assert_outside_untouched, device_cus, exact_operands, lib, on_this_device, windowed  # noqa: F401  (lib: the fixture)
 
@@ -84,12 +84,10 @@ def run_split(lib, dtype, epi, case, ops, b8_scale=GEMM_SPLIT_B8_SCALE, windows=
     got = lib.mudpt_gemm_form(epi, M, N, K, out0.stride(0), ldo1, ldaux, lo, case.variant, device_cus())
     want = capi.GEMM_FORMS.index(case.form) | 1 << 8
     assert got == want, f"{case.name} epilogue {epi}: form {capi.GEMM_FORMS[got & 0xff] if got >= 0 else got}, the case is there for {case.form}"
-    args = (dt, epi, M, N, K, P(A), P(A_lo), lo, A.stride(0), P(B), P(B8), b8_scale, B.stride(0), P(bias), P(out0), out0.stride(0), P(out1), P(out1_lo),
-            out1_lo_mode, out1.stride(0) if out1 is not None else 0, P(aux), aux.stride(0) if aux is not None else 0)
-    if epi == capi.EPI_PATCH:
-        ok(lib, lib.mudpt_gemm_split_patch(*args, patches, seq_len, P(pos), case.variant, None))
-    else:
-        ok(lib, lib.mudpt_gemm_split(*args, case.variant, None))
+    patch = dict(patches=patches, seq_len=seq_len, pos=pos) if epi == capi.EPI_PATCH else {}
+    ok(lib, capi.call("mudpt_gemm_split_patch" if patch else "mudpt_gemm_split", dtype=dt, epilogue=epi, M=M, N=N, K=K, A=A, A_lo=A_lo, lo_mode=lo, lda=A.stride(0), B=B,
+                      B8=B8, b8_scale=b8_scale, ldb=B.stride(0), bias=bias, out0=out0, ldo0=out0.stride(0), out1=out1, out1_lo=out1_lo, out1_lo_mode=out1_lo_mode,
+                      ldo1=out1.stride(0) if out1 is not None else 0, aux=aux, ldaux=aux.stride(0) if aux is not None else 0, variant=case.variant, **patch))
     assert_outside_untouched(buf0, out_rows, N, w["out0"], SENT, written)
     if buf1 is not None:
         assert_outside_untouched(buf1, M, N, w["out1"], SENT)
@@ -252,8 +250,8 @@ def test_split_gemm_refusals(lib):
     out = torch.full((M, N), SENT, device="cuda", dtype=torch.float32)
 
     def call(word, dt=1, k=K, a=A, a_lo=lo8, lo_mode=2, b8=B8, scale=127):
-        refused(lib, lib.mudpt_gemm_split(dt, capi.EPI_STORE_F32, M, N, k, P(a), P(a_lo), lo_mode, K, P(B), P(b8), scale, K, None, P(out), N, None, None, 0, 0,
-                                          None, 0, 0, None), word)
+        refused(lib, capi.call("mudpt_gemm_split", dtype=dt, epilogue=capi.EPI_STORE_F32, M=M, N=N, K=k, A=a, A_lo=a_lo, lo_mode=lo_mode, lda=K, B=B, B8=b8, b8_scale=scale, ldb=K,
+                               out0=out, ldo0=N), word)
         assert bool((out == SENT).all())
 
     call("fp16 operands only", dt=0, a=Ab)          # lo_mode 2 with bf16
@@ -268,8 +266,8 @@ def test_split_gemm_refusals(lib):
     call("bad lo_mode 3", lo_mode=3)
     # K = 192 itself, with operands that wide
     A192, lo192, B192, B8192 = (torch.zeros(64, w, device="cuda", dtype=t) for w, t in ((192, torch.float16), (384, torch.uint8), (192, torch.float16), (384, torch.uint8)))
-    refused(lib, lib.mudpt_gemm_split(1, capi.EPI_STORE_F32, M, N, 192, P(A192), P(lo192), 2, 192, P(B192), P(B8192), 127, 192, None, P(out), N, None, None, 0, 0,
-                                      None, 0, 0, None), "K % 128")
+    refused(lib, capi.call("mudpt_gemm_split", dtype=1, epilogue=capi.EPI_STORE_F32, M=M, N=N, K=192, A=A192, A_lo=lo192, lo_mode=2, lda=192, B=B192, B8=B8192, b8_scale=127,
+                           ldb=192, out0=out, ldo0=N), "K % 128")
     assert bool((out == SENT).all())
     # at a persistent-kernel shape the e4m3 second pass is built for the forward epilogues only
     M, N = 8003, 1008
@@ -278,6 +276,6 @@ def test_split_gemm_refusals(lib):
     B, B8 = torch.zeros(N, K, device="cuda", dtype=torch.float16), torch.zeros(N, 2 * K, device="cuda", dtype=torch.uint8)
     aux = torch.zeros(M, N, device="cuda", dtype=torch.float16)
     out = torch.full((M, N), SENT, device="cuda", dtype=torch.float16)
-    refused(lib, lib.mudpt_gemm_split(1, capi.EPI_GELU_BWD, M, N, K, P(A), P(lo8), 2, K, P(B), P(B8), 127, K, None, P(out), N, None, None, 0, 0, P(aux), N, 0, None),
-            "not built with the e4m3 second pass")
+    refused(lib, capi.call("mudpt_gemm_split", dtype=1, epilogue=capi.EPI_GELU_BWD, M=M, N=N, K=K, A=A, A_lo=lo8, lo_mode=2, lda=K, B=B, B8=B8, b8_scale=127, ldb=K, out0=out, ldo0=N,
+                           aux=aux, ldaux=N), "not built with the e4m3 second pass")
     assert bool((out == SENT).all())

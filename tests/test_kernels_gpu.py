@@ -4,6 +4,7 @@ import ctypes as C
 import pytest
 import torch
 
+from mudpt_amd import capi
 from oracle import mudpt_oracle as O
 from tests.helpers import (ATTN_CASES, ATTN_LONG_FWD_CASES, ATTN_LONG_FWD_FLAGS, ATTN_SEL_CASES, ATTN_SEL_COMPARE, ATTN_WINDOW_CASES,
                            ATTN_WINDOW_FULL_FLAG, SENT, P, attn64, attn_bwd_form_flags, attn_window_flags, check_split_pair, ok, refused)
@@ -16,7 +17,6 @@ EPS = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11}  # half ulp relative
 
 @pytest.fixture(scope="module")
 def lib():
-    from mudpt_amd import capi
     assert torch.cuda.is_available(), "GPU tests need the MI355X"
     return capi.load()
 
@@ -24,10 +24,9 @@ def lib():
 def gemm(lib, dt, epi, A, B, bias=None, out0=None, out1=None, aux=None, patches=0, seq_len=0, pos=None, variant=0):
     M, K = A.shape
     N = B.shape[0]
-    ok(lib, lib.mudpt_gemm(dt, epi, M, N, K, P(A), A.stride(0), P(B), B.stride(0), P(bias), P(out0), out0.stride(0),
-                           P(out1), out1.stride(0) if out1 is not None else 0, P(aux), aux.stride(0) if aux is not None else 0,
-                           patches, seq_len, P(pos), variant, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_gemm", dtype=dt, epilogue=epi, M=M, N=N, K=K, A=A, lda=A.stride(0), B=B, ldb=B.stride(0), bias=bias, out0=out0, ldo0=out0.stride(0),
+                      out1=out1, ldo1=out1.stride(0) if out1 is not None else 0, aux=aux, ldaux=aux.stride(0) if aux is not None else 0,
+                      patches=patches, seq_len=seq_len, pos=pos, variant=variant))
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
@@ -206,7 +205,7 @@ def test_gemm_patch_epilogue(lib, dtype):
 def test_gemm_rejects_bad_shapes(lib):
     A = torch.zeros(64, 96, device="cuda", dtype=torch.bfloat16)
     out = torch.zeros(64, 64, device="cuda", dtype=torch.bfloat16)
-    rc = lib.mudpt_gemm(0, 0, 64, 64, 96, P(A), 96, P(A), 96, None, P(out), 64, None, 0, None, 0, 0, 0, None, 0, None)
+    rc = capi.call("mudpt_gemm", dtype=0, epilogue=0, M=64, N=64, K=96, A=A, lda=96, B=A, ldb=96, out0=out, ldo0=64)
     assert rc == 1 and b"multiple of 64" in lib.mudpt_last_error()
 
 
@@ -222,12 +221,10 @@ def test_layernorm_fwd_bwd(lib, dtype, rows, d):
     out = torch.empty(rows, d, device="cuda", dtype=tt)
     mean, rstd = torch.empty(rows, device="cuda"), torch.empty(rows, device="cuda")
     xc, gc, bc = x.cuda(), gamma.cuda(), beta.cuda()  # keep device tensors alive across the async launches
-    ok(lib, lib.mudpt_layernorm_fwd(dt, P(xc), d, None, P(gc), P(bc), P(out), d, 0, P(mean), P(rstd), rows, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_fwd", dtype=dt, x=xc, ldx=d, gamma=gc, beta=bc, out=out, ldo=d, out_f32=0, mean=mean, rstd=rstd, rows=rows, d=d))
     torch.testing.assert_close(out.cpu().float(), y.detach(), atol=4 * EPS[dtype], rtol=4 * EPS[dtype])
     o32 = torch.empty(rows, d, device="cuda")
-    ok(lib, lib.mudpt_layernorm_fwd(dt, P(xc), d, None, P(gc), P(bc), P(o32), d, 1, None, None, rows, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_fwd", dtype=dt, x=xc, ldx=d, gamma=gc, beta=bc, out=o32, ldo=d, out_f32=1, rows=rows, d=d))
     torch.testing.assert_close(o32.cpu(), y.detach(), atol=2e-5, rtol=1e-5)
     # backward: dx = dres + LN'(dy), dy in T
     dy = torch.randn(rows, d, generator=g).to(tt)
@@ -236,9 +233,8 @@ def test_layernorm_fwd_bwd(lib, dtype, rows, d):
     dx = torch.empty(rows, d, device="cuda")
     dx_lp = torch.empty(rows, d, device="cuda", dtype=tt)
     dyc, drc = dy.cuda(), dres.cuda()
-    ok(lib, lib.mudpt_layernorm_bwd(dt, P(dyc), d, 0, P(xc), d, None, P(mean), P(rstd), P(gc), P(drc), d, P(dx), d,
-                                    P(dx_lp), d, rows, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_bwd", dtype=dt, dy=dyc, lddy=d, dy_f32=0, x=xc, ldx=d, mean=mean, rstd=rstd, gamma=gc, dres=drc, lddres=d, dx=dx, lddx=d,
+                      dx_lp=dx_lp, lddx_lp=d, rows=rows, d=d))
     torch.testing.assert_close(dx.cpu(), dx_ref + dres, atol=2e-5, rtol=2e-5)
     torch.testing.assert_close(dx_lp.cpu().float(), dx_ref + dres, atol=4 * EPS[dtype] * 4, rtol=4 * EPS[dtype])
 
@@ -269,17 +265,15 @@ def test_layernorm_fused_add_and_prompt_splice(lib, dtype, add_kind):
     xout = torch.full((rows, d), float("nan"), device="cuda")
     out = torch.empty(rows, d, device="cuda", dtype=tt)
     mean, rstd = torch.empty(rows, device="cuda"), torch.empty(rows, device="cuda")
-    ok(lib, lib.mudpt_layernorm_fwd_fused(dt, P(xc), d, P(a32), P(alp), d, P(oc), row0, n, L, P(xout), d, P(gc), P(bc), P(out), d, 0,
-                                          P(mean), P(rstd), rows, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_fwd_fused", dtype=dt, x=xc, ldx=d, add=a32, add_lp=alp, ldadd=d, ov_rows=oc, ov_row0=row0, ov_n=n, ov_L=L, xout=xout, ldxout=d,
+                      gamma=gc, beta=bc, out=out, ldo=d, out_f32=0, mean=mean, rstd=rstd, rows=rows, d=d))
     assert torch.equal(xout.cpu(), v)                      # the saved block input: exact
     torch.testing.assert_close(out.cpu().float(), y, atol=4 * EPS[dtype], rtol=4 * EPS[dtype])
     torch.testing.assert_close(mean.cpu(), v.mean(-1), atol=1e-5, rtol=1e-5)
     torch.testing.assert_close(rstd.cpu(), (v.var(-1, unbiased=False) + 1e-5).rsqrt(), atol=1e-5, rtol=2e-5)
     # fp32 output and no splice: every row is x + add
     o32 = torch.empty(rows, d, device="cuda")
-    ok(lib, lib.mudpt_layernorm_fwd_fused(dt, P(xc), d, P(a32), P(alp), d, None, 0, 0, 1, None, 0, P(gc), P(bc), P(o32), d, 1, None, None, rows, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_fwd_fused", dtype=dt, x=xc, ldx=d, add=a32, add_lp=alp, ldadd=d, ov_L=1, gamma=gc, beta=bc, out=o32, ldo=d, out_f32=1, rows=rows, d=d))
     v2 = x + (add if add_kind == "f32" else add_t.float() if add_kind == "lp" else 0)
     torch.testing.assert_close(o32.cpu(), O.layer_norm(v2, gamma, beta), atol=2e-5, rtol=1e-5)
 
@@ -412,13 +406,12 @@ def test_layernorm_gather_scatter(lib):
     y = O.layer_norm(xr, gamma, beta)
     out, mean, rstd = torch.empty(rows, d, device="cuda"), torch.empty(rows, device="cuda"), torch.empty(rows, device="cuda")
     xc, ic, gc, bc = x.cuda(), idx.cuda(), gamma.cuda(), beta.cuda()
-    ok(lib, lib.mudpt_layernorm_fwd(0, P(xc), d, P(ic), P(gc), P(bc), P(out), d, 1, P(mean), P(rstd), rows, d, None))
+    ok(lib, capi.call("mudpt_layernorm_fwd", dtype=0, x=xc, ldx=d, row_index=ic, gamma=gc, beta=bc, out=out, ldo=d, out_f32=1, mean=mean, rstd=rstd, rows=rows, d=d))
     dy = torch.randn(rows, d, generator=g)
     (dref,) = torch.autograd.grad(y, xr, dy)
     dx = torch.zeros(total, d, device="cuda")
     dyc = dy.cuda()
-    ok(lib, lib.mudpt_layernorm_bwd(0, P(dyc), d, 1, P(xc), d, P(ic), P(mean), P(rstd), P(gc), None, 0, P(dx), d, None, 0, rows, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_bwd", dtype=0, dy=dyc, lddy=d, dy_f32=1, x=xc, ldx=d, row_index=ic, mean=mean, rstd=rstd, gamma=gc, dx=dx, lddx=d, rows=rows, d=d))
     torch.testing.assert_close(out.cpu(), y.detach(), atol=2e-5, rtol=1e-5)
     full = torch.zeros(total, d)
     full[idx.long()] = dref
@@ -440,8 +433,7 @@ def test_attention_fwd_bwd(lib, dtype, B, L, H, causal):
     qc = qkv.cuda()
     out = torch.empty(B, L, H * 64, device="cuda", dtype=tt)
     lse = torch.empty(B, H, Lp, device="cuda")
-    ok(lib, lib.mudpt_attention_fwd(dt, P(qc), P(out), P(lse), B, L, H, int(causal), None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_fwd", dtype=dt, qkv=qc, out=out, lse=lse, B=B, L=L, H=H, causal=int(causal)))
     torch.testing.assert_close(out.cpu().float(), ref.detach(), atol=6 * EPS[dtype], rtol=6 * EPS[dtype])
     # LSE against the definition
     q, k, _ = q32.detach().split(H * 64, dim=-1)
@@ -452,28 +444,24 @@ def test_attention_fwd_bwd(lib, dtype, B, L, H, causal):
     dqkv = torch.zeros(B, L, 3 * H * 64, device="cuda", dtype=tt)
     delta = torch.empty(B, H, Lp, device="cuda")
     doc = dout.cuda()
-    ok(lib, lib.mudpt_attention_bwd(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(dqkv), B, L, H, int(causal), None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_bwd", dtype=dt, qkv=qc, out=out, dout=doc, lse=lse, delta=delta, dqkv=dqkv, B=B, L=L, H=H, causal=int(causal)))
     scale = dref.abs().max().item()
     torch.testing.assert_close(dqkv.cpu().float(), dref, atol=12 * EPS[dtype] * scale, rtol=8 * EPS[dtype])
     # Every form (fixed summation order, no atomics) is bit for bit the same run to run.  The two-kernel form (bit 1), the fused single
     # pass (bit 3: Q, K, V, dO resident once) and the fused pass with two blocks per wave (bit 2) do the same per-block arithmetic in the
     # same order, compiled separately (fma contraction may differ): the same gradients to T-precision rounding.
     again = torch.zeros_like(dqkv)
-    ok(lib, lib.mudpt_attention_bwd(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(again), B, L, H, int(causal), None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_bwd", dtype=dt, qkv=qc, out=out, dout=doc, lse=lse, delta=delta, dqkv=again, B=B, L=L, H=H, causal=int(causal)))
     assert torch.equal(again, dqkv)
     # bit 4: the single-sweep kernel (non-causal, L <= 224): S / dP / exp computed once, dS rounded to T crosses LDS for dQ -- the same
     # rounding point as the other forms (they round dS to T for the dQ product too)
     for form in attn_bwd_form_flags(L, causal):
         other = torch.full_like(dqkv, float("nan"))
-        ok(lib, lib.mudpt_attention_bwd(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(other), B, L, H, int(causal) | form, None))
-        torch.cuda.synchronize()
+        ok(lib, capi.call("mudpt_attention_bwd", dtype=dt, qkv=qc, out=out, dout=doc, lse=lse, delta=delta, dqkv=other, B=B, L=L, H=H, causal=int(causal) | form))
         torch.testing.assert_close(other.cpu().float(), dref, atol=12 * EPS[dtype] * scale, rtol=8 * EPS[dtype])
         torch.testing.assert_close(other.float(), dqkv.float(), atol=2 * EPS[dtype] * scale, rtol=2 * EPS[dtype])
         twice = torch.zeros_like(dqkv)
-        ok(lib, lib.mudpt_attention_bwd(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(twice), B, L, H, int(causal) | form, None))
-        torch.cuda.synchronize()
+        ok(lib, capi.call("mudpt_attention_bwd", dtype=dt, qkv=qc, out=out, dout=doc, lse=lse, delta=delta, dqkv=twice, B=B, L=L, H=H, causal=int(causal) | form))
         assert torch.equal(twice, other), form
 
 
@@ -494,8 +482,7 @@ def test_attention_long_forward_forms(lib, dtype, B, L, H, causal, gain):
     for flag in ATTN_LONG_FWD_FLAGS:
         out = torch.full((B, L, H * 64), float("nan"), device="cuda", dtype=tt)
         lse = torch.full((B, H, Lp), float("nan"), device="cuda")
-        ok(lib, lib.mudpt_attention_fwd(dt, P(qc), P(out), P(lse), B, L, H, int(causal) | flag, None))
-        torch.cuda.synchronize()
+        ok(lib, capi.call("mudpt_attention_fwd", dtype=dt, qkv=qc, out=out, lse=lse, B=B, L=L, H=H, causal=int(causal) | flag))
         outs.append(out.cpu().float()); lses.append(lse.cpu())
     ref = O.attention(qkv.float(), H, O.causal_mask(L) if causal else None)
     for out in outs:
@@ -526,8 +513,7 @@ def test_attention_single_query(lib, dtype, B, L, H, causal):
     qc, sc = qkv.cuda(), sel.cuda()
     q_sel = qkv[torch.arange(B), pos, :H * 64].contiguous().cuda()
     out_sel, lse_sel = torch.empty(B, H * 64, device="cuda", dtype=tt), torch.empty(B, H, device="cuda")
-    ok(lib, lib.mudpt_attention_fwd_single(dt, P(qc), P(q_sel), P(sc), P(out_sel), P(lse_sel), B, L, H, int(causal), None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_fwd_single", dtype=dt, qkv=qc, q_sel=q_sel, sel_rows=sc, out_sel=out_sel, lse_sel=lse_sel, B=B, L=L, H=H, causal=int(causal)))
     torch.testing.assert_close(out_sel.cpu().float(), ref_sel.detach(), atol=6 * EPS[dtype], rtol=6 * EPS[dtype])
     qh, kh = q32.detach()[..., :H * 64].view(B, L, H, 64), q32.detach()[..., H * 64:2 * H * 64].view(B, L, H, 64)
     sco = torch.einsum("bhd,blhd->bhl", qh[torch.arange(B), pos], kh) / 8
@@ -537,16 +523,15 @@ def test_attention_single_query(lib, dtype, B, L, H, causal):
     dqkv = torch.full((B, L, 3 * H * 64), 7.0, device="cuda", dtype=tt)  # the q third must stay untouched
     dq_sel = torch.empty(B, H * 64, device="cuda", dtype=tt)
     dc = dsel.cuda()
-    ok(lib, lib.mudpt_attention_bwd_single(dt, P(qc), P(q_sel), P(sc), P(out_sel), P(dc), P(lse_sel), P(dqkv), P(dq_sel), B, L, H, int(causal), None))
-    torch.cuda.synchronize()
+    bwd_args = dict(dtype=dt, qkv=qc, q_sel=q_sel, sel_rows=sc, out_sel=out_sel, dout_sel=dc, lse_sel=lse_sel, B=B, L=L, H=H, causal=int(causal))
+    ok(lib, capi.call("mudpt_attention_bwd_single", dqkv=dqkv, dq_sel=dq_sel, **bwd_args))
     scale = dref.abs().max().item()
     tol = dict(atol=12 * EPS[dtype] * scale, rtol=8 * EPS[dtype])
     torch.testing.assert_close(dq_sel.cpu().float(), dref[torch.arange(B), pos, :H * 64], **tol)
     torch.testing.assert_close(dqkv.cpu().float()[..., H * 64:], dref[..., H * 64:], **tol)
     assert (dqkv[..., :H * 64] == 7.0).all()
     again, dq2 = torch.zeros_like(dqkv), torch.empty_like(dq_sel)
-    ok(lib, lib.mudpt_attention_bwd_single(dt, P(qc), P(q_sel), P(sc), P(out_sel), P(dc), P(lse_sel), P(again), P(dq2), B, L, H, int(causal), None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_bwd_single", dqkv=again, dq_sel=dq2, **bwd_args))
     assert torch.equal(again[..., H * 64:], dqkv[..., H * 64:]) and torch.equal(dq2, dq_sel)
 
 
@@ -562,15 +547,13 @@ def test_attention_backward_window_form(lib, B, L, H, causal, row0, n):
     dout = torch.randn(B, L, H * 64, generator=g).to(tt).cuda()
     Lp = lib.mudpt_attention_padded_len(L)
     out, lse, delta = torch.empty(B, L, H * 64, device="cuda", dtype=tt), torch.zeros(B, H, Lp, device="cuda"), torch.zeros(B, H, Lp, device="cuda")
-    ok(lib, lib.mudpt_attention_fwd(dt, P(qkv), P(out), P(lse), B, L, H, int(causal), None))
+    ok(lib, capi.call("mudpt_attention_fwd", dtype=dt, qkv=qkv, out=out, lse=lse, B=B, L=L, H=H, causal=int(causal)))
     full = torch.empty_like(qkv)
-    ok(lib, lib.mudpt_attention_bwd(dt, P(qkv), P(out), P(dout), P(lse), P(delta), P(full), B, L, H, int(causal) | ATTN_WINDOW_FULL_FLAG, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_bwd", dtype=dt, qkv=qkv, out=out, dout=dout, lse=lse, delta=delta, dqkv=full, B=B, L=L, H=H, causal=int(causal) | ATTN_WINDOW_FULL_FLAG))
     delta_full = delta.clone()
     win = torch.full_like(qkv, 3.0)
     delta.zero_()
-    ok(lib, lib.mudpt_attention_bwd(dt, P(qkv), P(out), P(dout), P(lse), P(delta), P(win), B, L, H, int(causal) | attn_window_flags(row0, n), None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_bwd", dtype=dt, qkv=qkv, out=out, dout=dout, lse=lse, delta=delta, dqkv=win, B=B, L=L, H=H, causal=int(causal) | attn_window_flags(row0, n)))
     assert torch.equal(win[:, row0:row0 + n], full[:, row0:row0 + n])
     assert torch.equal(delta[..., :L], delta_full[..., :L])  # delta of every query feeds the dK / dV pass
     gran = 128 if L > 224 else 16
@@ -592,8 +575,7 @@ def test_attention_softmax_extremes(lib):
     out = torch.empty(B, L, 64, device="cuda", dtype=torch.float16)
     lse = torch.empty(B, H, 224, device="cuda")
     qc = qkv.cuda()
-    ok(lib, lib.mudpt_attention_fwd(1, P(qc), P(out), P(lse), B, L, H, 0, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_attention_fwd", dtype=1, qkv=qc, out=out, lse=lse, B=B, L=L, H=H))
     assert torch.isfinite(out).all() and torch.isfinite(lse[:, :, :L]).all()
     torch.testing.assert_close(out.cpu().float(), ref, atol=4e-3, rtol=4e-3)
 
@@ -696,9 +678,9 @@ def test_layernorm_bwd_fused_splice_backward(lib, dtype, kind, nseq, L, d, row0,
     dx = torch.full((rows + 1, d), SENT, device="cuda")
     dx_lp = torch.full((rows + 1, d), SENT, device="cuda", dtype=tt)
     xc, gc, dyc, drc, mc, rc_ = x.cuda(), gamma.cuda(), dy.cuda(), dres.cuda(), mean.cuda(), rstd.cuda()
-    ok(lib, lib.mudpt_layernorm_bwd_ex(dt, P(dyc), d, int(kind == "dy_f32"), P(xc), d, None, P(mc), P(rc_), P(gc), None if kind == "dres_lp" else P(drc),
-                                       P(drc) if kind == "dres_lp" else None, d, P(dx), d, P(dx_lp), d, P(side), row0, n, L, side_ldb, 0, rows, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_bwd_ex", dtype=dt, dy=dyc, lddy=d, dy_f32=int(kind == "dy_f32"), x=xc, ldx=d, mean=mc, rstd=rc_, gamma=gc,
+                      dres=None if kind == "dres_lp" else drc, dres_lp=drc if kind == "dres_lp" else None, lddres=d, dx=dx, lddx=d, dx_lp=dx_lp, lddx_lp=d,
+                      side=side, side_row0=row0, side_n=n, side_L=L, side_ldb=side_ldb, index_mode=0, rows=rows, d=d))
     got, got_lp, sv = dx.cpu(), dx_lp.cpu(), side.cpu()
     assert (got[rows:] == SENT).all() and (got_lp[rows:] == SENT).all()
     got, got_lp = got[:rows].view(nseq, L, d), got_lp[:rows].view(nseq, L, d)
@@ -736,9 +718,8 @@ def test_layernorm_bwd_token_index_modes(lib, dtype, mode, total, R, d):
     dx = torch.full((total, d), SENT, device="cuda")
     dx_lp = torch.full((total, d), SENT, device="cuda", dtype=tt)
     xc, gc, dyc, drc, mc, rc_, ic = x.cuda(), gamma.cuda(), dy.cuda(), dres.cuda(), mean.cuda(), rstd.cuda(), idx.to(torch.int32).cuda()
-    ok(lib, lib.mudpt_layernorm_bwd_ex(dt, P(dyc), d, int(not lp), P(xc), d, P(ic), P(mc), P(rc_), P(gc), None if lp else P(drc), P(drc) if lp else None, d,
-                                       P(dx), d, P(dx_lp), d, None, 0, 0, 1, 0, mode, R, d, None))
-    torch.cuda.synchronize()
+    ok(lib, capi.call("mudpt_layernorm_bwd_ex", dtype=dt, dy=dyc, lddy=d, dy_f32=int(not lp), x=xc, ldx=d, row_index=ic, mean=mc, rstd=rc_, gamma=gc,
+                      dres=None if lp else drc, dres_lp=drc if lp else None, lddres=d, dx=dx, lddx=d, dx_lp=dx_lp, lddx_lp=d, side_L=1, index_mode=mode, rows=R, d=d))
     got, got_lp = dx.cpu(), dx_lp.cpu()
     torch.testing.assert_close(got[idx].double(), want, atol=2e-5, rtol=2e-5)
     torch.testing.assert_close(got_lp[idx].double(), want, atol=16 * EPS[dtype], rtol=4 * EPS[dtype])
@@ -755,11 +736,11 @@ def run_attn_split(lib, dt, tt, qc, B, L, H, flags, ld, pass_ld, lo_mode, single
     if single:
         q_sel, sel = single
         lse = torch.full((B, H), float("nan"), device="cuda")
-        ok(lib, lib.mudpt_attention_fwd_single_split(dt, P(qc), P(q_sel), P(sel), P(out), P(lo), lo_mode, ld, P(lse), B, L, H, flags, None))
+        ok(lib, capi.call("mudpt_attention_fwd_single_split", dtype=dt, qkv=qc, q_sel=q_sel, sel_rows=sel, out_sel=out, out_lo=lo, lo_mode=lo_mode, ld_out=ld, lse_sel=lse,
+                          B=B, L=L, H=H, causal=flags))
     else:
         lse = torch.full((B, H, lib.mudpt_attention_padded_len(L)), float("nan"), device="cuda")
-        ok(lib, lib.mudpt_attention_fwd_split(dt, P(qc), P(out), P(lo), lo_mode, pass_ld, P(lse), B, L, H, flags, None))
-    torch.cuda.synchronize()
+        ok(lib, capi.call("mudpt_attention_fwd_split", dtype=dt, qkv=qc, out=out, out_lo=lo, lo_mode=lo_mode, ld_out=pass_ld, lse=lse, B=B, L=L, H=H, causal=flags))
     return out.cpu(), None if lo is None else lo.cpu(), lse.cpu()
 
 
@@ -837,21 +818,19 @@ def test_attention_bwd_sel_rows(lib, dtype, L, H, causal):
     Lp = lib.mudpt_attention_padded_len(L)
     qc, doc, sel = qkv.cuda(), dout.cuda(), (torch.arange(B) * L + pos).to(torch.int32).cuda()
     out, lse = torch.empty(B, L, Hd, device="cuda", dtype=tt), torch.zeros(B, H, Lp, device="cuda")
-    ok(lib, lib.mudpt_attention_fwd(dt, P(qc), P(out), P(lse), B, L, H, int(causal), None))
+    ok(lib, capi.call("mudpt_attention_fwd", dtype=dt, qkv=qc, out=out, lse=lse, B=B, L=L, H=H, causal=int(causal)))
     delta = torch.zeros(B, H, Lp, device="cuda")
     res = []
     for _ in range(2):
         dqkv = torch.full((B, L, 3 * Hd), float("nan"), device="cuda", dtype=tt)
-        ok(lib, lib.mudpt_attention_bwd_sel(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(dqkv), P(sel), B, L, H, int(causal), None))
-        torch.cuda.synchronize()
+        ok(lib, capi.call("mudpt_attention_bwd_sel", dtype=dt, qkv=qc, out=out, dout=doc, lse=lse, delta=delta, dqkv=dqkv, sel_rows=sel, B=B, L=L, H=H, causal=int(causal)))
         res.append(dqkv.cpu())
     assert torch.equal(res[0].view(torch.int16), res[1].view(torch.int16))
     scale = dref.abs().max().item()
     torch.testing.assert_close(res[0].double(), dref, atol=12 * EPS[dtype] * scale, rtol=8 * EPS[dtype])
     for flag, same in ATTN_SEL_COMPARE:
         gen = torch.full((B, L, 3 * Hd), float("nan"), device="cuda", dtype=tt)
-        ok(lib, lib.mudpt_attention_bwd(dt, P(qc), P(out), P(doc), P(lse), P(delta), P(gen), B, L, H, int(causal) | flag, None))
-        torch.cuda.synchronize()
+        ok(lib, capi.call("mudpt_attention_bwd", dtype=dt, qkv=qc, out=out, dout=doc, lse=lse, delta=delta, dqkv=gen, B=B, L=L, H=H, causal=int(causal) | flag))
         if same:
             assert torch.equal(res[0], gen.cpu())
         else:
@@ -1113,40 +1092,35 @@ def test_layernorm_launchers_refuse_bad_arguments(lib):
     x, g, st = torch.randn(2 * rows, d, device="cuda"), torch.ones(d, device="cuda"), torch.ones(2 * rows, device="cuda")
     h = torch.full((2 * rows, d), SENT, device="cuda", dtype=torch.float16)
     dx, side, idx = f(2 * rows, d), f(2 * rows, d), torch.arange(rows, dtype=torch.int32, device="cuda")
-    bwd = lambda **k: lib.mudpt_layernorm_bwd_ex(1, P(h), k.get("lddy", d), 0, P(x), k.get("ldx", d), P(idx) if k.get("idx") else None, P(st), P(st), P(g),  # noqa: E731
-                                                 P(x) if k.get("dres") else None, P(h) if k.get("dres_lp") else None, k.get("lddres", d), P(dx), k.get("lddx", d),
-                                                 P(h) if k.get("dx_lp") else None, k.get("lddx_lp", d), P(side) if k.get("side") else None, k.get("row0", 0),
-                                                 k.get("n", 0), k.get("L", 1), k.get("ldb", 0), k.get("mode", 0), rows, d, None)
-    refused(lib, bwd(dres=1, dres_lp=1), "exclusive")                       # both residual gradients
-    refused(lib, bwd(dres=1, lddres=d - 4), "dres stride")                 # a stride shorter than the row
-    refused(lib, bwd(dres_lp=1, lddres=d - 4), "dres stride")              # ... of the T stream as well
-    refused(lib, bwd(dx_lp=1, lddx_lp=d - 4), "dx_lp stride")
+    bwd_args = dict(dtype=1, dy=h, lddy=d, x=x, ldx=d, mean=st, rstd=st, gamma=g, lddres=d, dx=dx, lddx=d, lddx_lp=d, side_L=1, rows=rows, d=d)
+    bwd = lambda **k: capi.call("mudpt_layernorm_bwd_ex", **{**bwd_args, **k})  # noqa: E731
+    refused(lib, bwd(dres=x, dres_lp=h), "exclusive")                       # both residual gradients
+    refused(lib, bwd(dres=x, lddres=d - 4), "dres stride")                 # a stride shorter than the row
+    refused(lib, bwd(dres_lp=h, lddres=d - 4), "dres stride")              # ... of the T stream as well
+    refused(lib, bwd(dx_lp=h, lddx_lp=d - 4), "dx_lp stride")
     refused(lib, bwd(ldx=d - 4), "shorter than d")
     refused(lib, bwd(lddy=d - 4), "shorter than d")
     refused(lib, bwd(lddx=d - 4), "shorter than d")
-    refused(lib, bwd(side=1, row0=2, n=3, L=4, ldb=3 * d), "splice rows")   # rows 2..4 of a 4-row sequence
-    refused(lib, bwd(side=1, row0=1, n=2, L=4, ldb=d), "splice rows")       # two rows do not fit a side stride of d
-    refused(lib, bwd(side=1, row0=1, n=2, L=4, ldb=2 * d, idx=1), "identity row map")
-    refused(lib, bwd(mode=3), "index_mode")
+    refused(lib, bwd(side=side, side_row0=2, side_n=3, side_L=4, side_ldb=3 * d), "splice rows")   # rows 2..4 of a 4-row sequence
+    refused(lib, bwd(side=side, side_row0=1, side_n=2, side_L=4, side_ldb=d), "splice rows")       # two rows do not fit a side stride of d
+    refused(lib, bwd(side=side, side_row0=1, side_n=2, side_L=4, side_ldb=2 * d, row_index=idx), "identity row map")
+    refused(lib, bwd(index_mode=3), "index_mode")
     assert (dx == SENT).all() and (side == SENT).all() and (h == SENT).all()
     out, xo = f(2 * rows, d), f(2 * rows, d)
-    fwd = lambda **k: lib.mudpt_layernorm_fwd_fused(1, P(x), d, P(x) if k.get("add") else None, None, k.get("ldadd", d), P(x) if k.get("ov") else None,  # noqa: E731
-                                                    k.get("row0", 0), k.get("n", 0), k.get("L", 1), P(xo) if k.get("xout") else None, k.get("ldxout", d), P(g), P(g),
-                                                    P(out), d, 1, None, None, rows, d, None)
-    refused(lib, fwd(add=1, ldadd=d - 4), "addend stride")
-    refused(lib, fwd(xout=1, ldxout=d - 4), "xout stride")
-    refused(lib, fwd(ov=1, row0=0, n=1, L=0), "splice rows")               # ov_L = 0: r % ov_L
-    refused(lib, fwd(ov=1, row0=3, n=2, L=4), "splice rows")               # rows 3..4 of a 4-row sequence
+    fwd_args = dict(dtype=1, x=x, ldx=d, ldadd=d, ov_L=1, ldxout=d, gamma=g, beta=g, out=out, ldo=d, out_f32=1, rows=rows, d=d)
+    fwd = lambda name="mudpt_layernorm_fwd_fused", **k: capi.call(name, **{**fwd_args, **k})  # noqa: E731
+    refused(lib, fwd(add=x, ldadd=d - 4), "addend stride")
+    refused(lib, fwd(xout=xo, ldxout=d - 4), "xout stride")
+    refused(lib, fwd(ov_rows=x, ov_row0=0, ov_n=1, ov_L=0), "splice rows")  # ov_L = 0: r % ov_L
+    refused(lib, fwd(ov_rows=x, ov_row0=3, ov_n=2, ov_L=4), "splice rows")  # rows 3..4 of a 4-row sequence
     # the row map next to a fused operand (out is indexed by r, x / add / xout by row_index[r]) and a split output that is not T
     lo = torch.full((2 * rows, 2 * d), SENT, device="cuda")
-    ex = lambda **k: lib.mudpt_layernorm_fwd_ex(1, P(x), d, P(idx) if k.get("idx") else None, P(x) if k.get("add") else None, None, d,  # noqa: E731
-                                                P(x) if k.get("ov") else None, 0, k.get("ov", 0), 4, P(xo) if k.get("xout") else None, d, P(g), P(g), P(out),
-                                                P(lo) if k.get("lo") else None, k.get("lo", 1), d, k.get("f32", 0), None, None, rows, d, None)
-    refused(lib, ex(idx=1, add=1), "identity row map")
-    refused(lib, ex(idx=1, xout=1), "identity row map")
-    refused(lib, ex(idx=1, ov=2), "identity row map")
-    refused(lib, ex(lo=1, f32=1), "out_lo needs a T output")
-    refused(lib, ex(lo=3), "out_lo needs a T output")
+    ex = lambda **k: fwd("mudpt_layernorm_fwd_ex", **{"ov_L": 4, "lo_mode": 1, "out_f32": 0, **k})  # noqa: E731
+    refused(lib, ex(row_index=idx, add=x), "identity row map")
+    refused(lib, ex(row_index=idx, xout=xo), "identity row map")
+    refused(lib, ex(row_index=idx, ov_rows=x, ov_row0=0, ov_n=2, ov_L=4), "identity row map")
+    refused(lib, ex(out_lo=lo, lo_mode=1, out_f32=1), "out_lo needs a T output")
+    refused(lib, ex(out_lo=lo, lo_mode=3), "out_lo needs a T output")
     assert (out == SENT).all() and (xo == SENT).all() and (lo == SENT).all()
 
 
@@ -1156,16 +1130,17 @@ def test_attention_forward_refuses_a_bad_split_output(lib):
     out = torch.full((B * L, H * 64 + 64), SENT, device="cuda", dtype=torch.float16)
     lo = torch.full((B * L, 2 * (H * 64 + 64)), 0x5A, device="cuda", dtype=torch.uint8)
     lse = torch.full((B, H, 64), SENT, device="cuda")
-    refused(lib, lib.mudpt_attention_fwd_split(1, P(qkv), P(out), P(lo), 1, H * 64 - 8, P(lse), B, L, H, 0, None), "ld_out")   # rows would overlap
-    refused(lib, lib.mudpt_attention_fwd_split(1, P(qkv), P(out), P(lo), 1, H * 64 + 4, P(lse), B, L, H, 0, None), "ld_out")   # 8-byte rows: not 16-byte aligned
-    refused(lib, lib.mudpt_attention_fwd_split(1, P(qkv), P(out), P(lo), 3, H * 64, P(lse), B, L, H, 0, None), "lo_mode")
-    refused(lib, lib.mudpt_attention_fwd_split(1, P(qkv), P(out), P(lo), 0, H * 64, P(lse), B, L, H, 0, None), "lo_mode")
-    sel = (torch.arange(B, dtype=torch.int32) * L).cuda()
-    q_sel = qkv[:, 0, :H * 64].contiguous()
-    refused(lib, lib.mudpt_attention_fwd_single_split(1, P(qkv), P(q_sel), P(sel), P(out), P(lo), 0, H * 64, P(lse), B, L, H, 0, None), "lo_mode")
-    refused(lib, lib.mudpt_attention_fwd_single_split(1, P(qkv), P(q_sel), P(sel), P(out), P(lo), 1, H * 64 - 8, P(lse), B, L, H, 0, None), "single query")
+    fwd = lambda **k: capi.call("mudpt_attention_fwd_split", dtype=1, qkv=qkv, out=out, out_lo=lo, lse=lse, B=B, L=L, H=H, **k)  # noqa: E731
+    refused(lib, fwd(lo_mode=1, ld_out=H * 64 - 8), "ld_out")   # rows would overlap
+    refused(lib, fwd(lo_mode=1, ld_out=H * 64 + 4), "ld_out")   # 8-byte rows: not 16-byte aligned
+    refused(lib, fwd(lo_mode=3, ld_out=H * 64), "lo_mode")
+    refused(lib, fwd(lo_mode=0, ld_out=H * 64), "lo_mode")
+    sel, q_sel = (torch.arange(B, dtype=torch.int32) * L).cuda(), qkv[:, 0, :H * 64].contiguous()
+    single = lambda **k: capi.call("mudpt_attention_fwd_single_split", dtype=1, qkv=qkv, q_sel=q_sel, sel_rows=sel, out_sel=out, out_lo=lo, lse_sel=lse, B=B, L=L, H=H, **k)  # noqa: E731
+    refused(lib, single(lo_mode=0, ld_out=H * 64), "lo_mode")
+    refused(lib, single(lo_mode=1, ld_out=H * 64 - 8), "single query")
     dq = torch.full((B, L, 3 * H * 64), SENT, device="cuda", dtype=torch.float16)
-    refused(lib, lib.mudpt_attention_bwd_sel(1, P(qkv), P(out), P(qkv), P(lse), P(lse), P(dq), None, B, L, H, 0, None), "sel_rows")
+    refused(lib, capi.call("mudpt_attention_bwd_sel", dtype=1, qkv=qkv, out=out, dout=qkv, lse=lse, delta=lse, dqkv=dq, B=B, L=L, H=H), "sel_rows")
     assert (out == SENT).all() and (lo == 0x5A).all() and (lse == SENT).all() and (dq == SENT).all()
 
 
@@ -1247,12 +1222,12 @@ def test_remaining_launchers_refuse_bad_arguments(lib):
     o, lse, delta = torch.randn(B, La, Hd, device="cuda").half(), torch.zeros(B, H, 64, device="cuda"), f(B, H, 64)
     dq = torch.full((B, La, 3 * Hd), SENT, device="cuda", dtype=torch.float16)
     sel = (torch.arange(B, dtype=torch.int32) * La).cuda()
-    bw = lambda dt=1, B_=B, L_=La: lib.mudpt_attention_bwd(dt, P(qkv), P(o), P(o), P(lse), P(delta), P(dq), B_, L_, H, 0, None)  # noqa: E731
-    bs = lambda dt=1, B_=B, L_=La: lib.mudpt_attention_bwd_sel(dt, P(qkv), P(o), P(o), P(lse), P(delta), P(dq), P(sel), B_, L_, H, 0, None)  # noqa: E731
-    for call in (bw, bs):
-        refused(lib, call(B_=0), "attention: bad arguments")
-        refused(lib, call(L_=0), "attention: bad arguments")
-        refused(lib, call(dt=9), "unknown dtype")
+    bwd_args = dict(dtype=1, qkv=qkv, out=o, dout=o, lse=lse, delta=delta, dqkv=dq, B=B, L=La, H=H)
+    for name, form in (("mudpt_attention_bwd", {}), ("mudpt_attention_bwd_sel", {"sel_rows": sel})):
+        call = lambda **k: capi.call(name, **{**bwd_args, **form, **k})  # noqa: E731
+        refused(lib, call(B=0), "attention: bad arguments")
+        refused(lib, call(L=0), "attention: bad arguments")
+        refused(lib, call(dtype=9), "unknown dtype")
     q_sel, dq_sel, lse_sel = qkv[:, 0, :Hd].contiguous(), torch.full((B, Hd), SENT, device="cuda", dtype=torch.float16), torch.zeros(B, H, device="cuda")
     b1 = lambda dt=1, B_=B: lib.mudpt_attention_bwd_single(dt, P(qkv), P(q_sel), P(sel), P(q_sel), P(q_sel), P(lse_sel), P(dq), P(dq_sel), B_, La, H, 0, None)  # noqa: E731
     refused(lib, b1(B_=0), "single query")

@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+from mudpt_amd import capi
 from oracle import mudpt_oracle as O
 from tests import umudpt_reference as R
 from tests.helpers import SENT, P, ok, refused
@@ -16,7 +17,6 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def lib():
-    from mudpt_amd import capi
     return capi.load()
 
 
@@ -27,7 +27,7 @@ def bits(t):
 def ln_fwd(lib, x, gamma, beta):
     rows, d = x.shape
     y, mean, rstd = torch.empty(rows, d, device="cuda"), torch.empty(rows, device="cuda"), torch.empty(rows, device="cuda")
-    ok(lib, lib.mudpt_layernorm_fwd(1, P(x), d, None, P(gamma), P(beta), P(y), d, 1, P(mean), P(rstd), rows, d, None))
+    ok(lib, capi.call("mudpt_layernorm_fwd", dtype=1, x=x, ldx=d, gamma=gamma, beta=beta, out=y, ldo=d, out_f32=1, mean=mean, rstd=rstd, rows=rows, d=d))
     return y, mean, rstd
 
 

@@ -1,5 +1,4 @@
 """Attention micro-benchmark through the C ABI (GPU box): vision shape B=256, L=201, H=12 and text 11 x 77 x 8."""
-import ctypes as C
 import os
 import sys
 
@@ -10,7 +9,6 @@ from mudpt_amd import capi
 
 def main():
     lib = capi.load()
-    P = lambda t: C.c_void_p(t.data_ptr())
     if "--long" in sys.argv:  # BASELINE configs[4]: ViT-L/14@336, B 128, L 581, H 16 (the tiled kernels)
         B, L, H = 128, 581, 16
         Lp = lib.mudpt_attention_padded_len(L)
@@ -19,9 +17,10 @@ def main():
         out = torch.empty(B, L, H * 64, device="cuda", dtype=torch.bfloat16)
         dqkv, lse, delta = torch.empty_like(qkv), torch.zeros(B, H, Lp, device="cuda"), torch.zeros(B, H, Lp, device="cuda")
         fl = 4.0 * B * H * L * L * 64
-        for nm, fn, mult in (("fwd", lambda: lib.mudpt_attention_fwd(0, P(qkv), P(out), P(lse), B, L, H, 0, None), 1.0),
-                             ("fwd 16-block tiled", lambda: lib.mudpt_attention_fwd(0, P(qkv), P(out), P(lse), B, L, H, 2, None), 1.0),
-                             ("bwd (dQ kernel + dK/dV kernel)", lambda: lib.mudpt_attention_bwd(0, P(qkv), P(out), P(dout), P(lse), P(delta), P(dqkv), B, L, H, 0, None), 3.5)):
+        run_fwd = lambda flags: capi.call("mudpt_attention_fwd", dtype=0, qkv=qkv, out=out, lse=lse, B=B, L=L, H=H, causal=flags)  # noqa: E731
+        for nm, fn, mult in (("fwd", lambda: run_fwd(0), 1.0), ("fwd 16-block tiled", lambda: run_fwd(2), 1.0),
+                             ("bwd (dQ kernel + dK/dV kernel)",
+                              lambda: capi.call("mudpt_attention_bwd", dtype=0, qkv=qkv, out=out, dout=dout, lse=lse, delta=delta, dqkv=dqkv, B=B, L=L, H=H), 3.5)):
             assert fn() == 0
             torch.cuda.synchronize()
             best = 1e9
@@ -45,10 +44,10 @@ def main():
         delta = torch.zeros(B, H, Lp, device="cuda")
 
         def fwd(form=0):
-            assert lib.mudpt_attention_fwd(0, P(qkv), P(out), P(lse), B, L, H, causal | form, None) == 0
+            assert capi.call("mudpt_attention_fwd", dtype=0, qkv=qkv, out=out, lse=lse, B=B, L=L, H=H, causal=causal | form) == 0
 
         def bwd(form=0):
-            assert lib.mudpt_attention_bwd(0, P(qkv), P(out), P(dout), P(lse), P(delta), P(dqkv), B, L, H, causal | form, None) == 0
+            assert capi.call("mudpt_attention_bwd", dtype=0, qkv=qkv, out=out, dout=dout, lse=lse, delta=delta, dqkv=dqkv, B=B, L=L, H=H, causal=causal | form) == 0
         res = []
         for fn in (fwd, lambda: bwd(8), lambda: bwd(2), lambda: bwd(4), lambda: bwd(0 if causal else 16)):
             fn()

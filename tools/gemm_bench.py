@@ -3,7 +3,6 @@
     python tools/gemm_bench.py [--dtype bf16] [--variants 0,1] [--rounds 5]
 Variants are selected with mudpt_gemm's variant argument and interleaved in one process (A/B rule)."""
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -54,7 +53,6 @@ def main():
     lib = capi.load()
     dt, tt = (0, torch.bfloat16) if a.dtype == "bf16" else (1, torch.float16)
     variants = [int(v) for v in a.variants.split(",")]
-    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     total = {v: 0.0 for v in variants}
     for name, M, N, K, epi in shapes:
         if (a.only and a.only not in name) or (a.epi >= 0 and epi != a.epi):
@@ -68,8 +66,8 @@ def main():
         aux = torch.randn(M, N, device="cuda").to(torch.float32 if epi == 2 else tt) if epi in (2, 3) else None
 
         def run(v=0):
-            rc = lib.mudpt_gemm(dt, epi, M, N, K, P(A), K, P(B), K, P(bias) if epi != 3 else None, P(out0), N, P(out1), N if out1 is not None else 0,
-                                P(aux), N if aux is not None else 0, 0, 0, None, v, None)
+            rc = capi.call("mudpt_gemm", dtype=dt, epilogue=epi, M=M, N=N, K=K, A=A, lda=K, B=B, ldb=K, bias=bias if epi != 3 else None, out0=out0, ldo0=N, out1=out1,
+                           ldo1=N if out1 is not None else 0, aux=aux, ldaux=N if aux is not None else 0, variant=v)
             assert rc == 0, lib.mudpt_last_error()
         best = {v: 1e9 for v in variants}
         for r in range(a.rounds):
