@@ -14,6 +14,8 @@
  *   mudpt_allreduce_grads                trainers/mudpt.py:230-233 nn.DataParallel's gradient reduce (here: one RCCL all-reduce)
  *   mudpt_set_class_shard / mudpt_cp_*   trainers/mudpt.py:142-156,178-182 the same step with the class prompts divided over the ranks
  *   mudpt_gemm / _layernorm_* / _attention_*   the ATen ops under clip/model.py:164-175,257-301 (unit parity)
+ *   mudpt_augment / _check / _form       configs/trainers/MuDPT/vit_b16_bz4_ep10_nctx2_depth9.yaml:9-13 INPUT.TRANSFORMS, INTERPOLATION "bicubic" (Dassl's transform pipeline on
+ *                                        the loader's CPU workers) and trainers/mudpt.py:263-268 parse_batch_train's host -> device copy
  * With mudpt_config.variant = MUDPT_VARIANT_COCOOP the same entry points run the CoCoOp path (trainers/cocoop.py):
  *   mudpt_create / mudpt_set_weight      trainers/cocoop.py:22-40  load_clip_to_cpu: vanilla CLIP (clip/model.py:443-496 ViT)
  *   mudpt_set_class_prompts              trainers/cocoop.py:113-122 token_prefix / token_suffix, tokenized_prompts
@@ -82,7 +84,7 @@
 extern "C" {
 #endif
 
-/* 7 still with mudpt_create_frozen, mudpt_set_text_tokens, mudpt_text_features and mudpt_encode_image: they are additions, no existing
+/* 7 still with mudpt_create_frozen, mudpt_set_text_tokens, mudpt_text_features, mudpt_encode_image and the mudpt_augment* three: they are additions, no existing
  * declaration, struct or constant changed, so every caller built against 7 runs unchanged -- the number moves when one would not.
  * mudpt_amd/capi.py binds from this file: it parses every declaration (int / int32_t / int64_t / float / size_t, const char*, any other pointer
  * or array; a type outside that raises at import) and every integer #define MUDPT_*, so names, types and order are stated here only. */
@@ -334,6 +336,44 @@ int mudpt_profile_read(mudpt_model* m, double* gemm_ms, double* gemm_flop, int64
  * executed by all GEMM and attention launches of both towers. */
 #define MUDPT_PROF_CLASSES 5
 int mudpt_profile_read_classes(mudpt_model* m, double* ms, double* work, int64_t* launches, double* executed_flop);
+
+/* ---- the input pipeline on the device (stateless: no model handle; additions, so MUDPT_ABI_VERSION stays) ---------------------------
+ * What they replace: Dassl's training transform of every shipped yaml -- INPUT.TRANSFORMS ("random_resized_crop", "random_flip",
+ * "normalize") with INTERPOLATION "bicubic", run per image and step in Pillow on the loader's CPU workers (torchvision RandomResizedCrop's
+ * F.resized_crop = img.crop(box).resize((S, S), BICUBIC), hflip, ToTensor, Normalize) -- and the [B, 3, S, S] fp32 host -> device copy of
+ * parse_batch_train (trainers/mudpt.py:263-268).  Images are decoded ONCE into a flat uint8 HWC store in device memory; per step the host
+ * draws a few integers per sample and one launch writes the batch mudpt_forward_backward takes.  The evaluation transform
+ * (Resize(S) on the short side + CenterCrop(S)) is an instance of the same operation.
+ *
+ * params row n = (image, flip, x_lo, x_len, x_out, x_off, y_lo, y_len, y_out, y_off), int32.  Per axis (in_len, out_len, out_off, lo from
+ * the row; o in [0, size)), all in fp64, Pillow's ImagingResample rule by rule:
+ *   scale = in_len / out_len; fs = max(scale, 1); support = 2 fs; center = (o + out_off + 0.5) scale;
+ *   taps t in [max(0, (int)(center - support + 0.5)), min(in_len, (int)(center + support + 0.5)));
+ *   raw weight f((t - center + 0.5) / fs), f the cubic with a = -0.5; divided by their sum (added in ascending t);
+ *   fixed point k_t = (int)(w 2^22 + (w < 0 ? -0.5 : 0.5)); tap t reads source index lo + t;
+ *   a pass: acc = 2^21 + sum k_t byte_t in int32, result byte = clamp(acc >> 22, 0, 255).
+ * The horizontal pass runs first and is rounded to bytes, the vertical pass runs on those bytes; flip writes column size - 1 - o; byte b of
+ * channel c becomes (float(b) / 255.0f - mean[c]) / std[c] in IEEE fp32 (ToTensor + Normalize); out[n, c, y, x] planar.
+ *   training  (crop box i, j, h, w):  x_lo = j, x_len = w, x_out = size, x_off = 0; y likewise with i, h
+ *   evaluation: x_lo = 0, x_len = W, x_out = Wr, x_off = round((Wr - size) / 2), Wr = size on the short side, int(size long / short) on the other
+ * (Pillow 12.2.0 itself was seen to run vertical-then-horizontal on sources 8 pixels wide and >= 900 rows high; this library never does.)
+ *
+ * mudpt_augment: pixels_dev the store; images_dev [n_images, 3] = byte offset, height, width of each image; params_dev [batch, 10];
+ * mean_std_host six HOST floats (mean[3], std[3]), read before the call returns; out_dev [batch, 3, size, size] fp32.  Asynchronous on `stream`.
+ * MUDPT_ERR_ARG before any GPU call: a null pointer, batch < 0, size < 1; batch == 0 launches nothing.  The kernel TRUSTS both tables. */
+int mudpt_augment(const uint8_t* pixels_dev, const int64_t* images_dev, int32_t n_images, const int32_t* params_dev, int32_t batch, int32_t size,
+                  const float* mean_std_host, float* out_dev, void* stream);
+/* HOST only: validates HOST copies of the two tables before they are uploaded.  images: heights and widths >= 1, offsets >= 0 and ascending
+ * with room for 3 H W bytes each; params: image in [0, n_images), flip 0 | 1, x_len / x_out / y_len / y_out >= 1, lo >= 0 and lo + len
+ * inside the image, out_off >= 0 and out_off + size <= out_len.  MUDPT_ERR_ARG with a message that names the table, the row and the column. */
+int mudpt_augment_check(const int64_t* images_host, int32_t n_images, const int32_t* params_host, int32_t batch, int32_t size);
+/* HOST arithmetic only: the kernel form one sample takes (every form writes the same bytes), as form | R << 8; -1 for a length < 1.
+ * TABLE while the tables and R rows' worth of source rows fit the workgroup's 40 000 bytes of LDS, for the largest R of 16, 8, 4, 2, 1:
+ *   3072 + 8 size + 4 size kx + 128 + 64 ky + rows(R) 3 ceil4(size),  kx / ky = 2 ceil(support) + 1,
+ *   rows(R) = (int)((R - 1) scale_y + 2 support_y + 1) + 2;   DIRECT otherwise (R = 0). */
+#define MUDPT_AUGMENT_TABLE 0  /* augment_kernel: weight tables and the horizontal pass in LDS, 16-byte stores */
+#define MUDPT_AUGMENT_DIRECT 1 /* the same kernel, a thread per output pixel, every weight recomputed where it is used */
+int mudpt_augment_form(int32_t x_len, int32_t x_out, int32_t y_len, int32_t y_out, int32_t size);
 
 /* ---- single kernels, exported for parity tests (all pointers device memory) ---------------------------- */
 /* epilogues: 0 store T | 1 bias+QuickGELU (out0 = u, out1 = gelu(u)) | 2 f32 out0 = aux + acc + bias |

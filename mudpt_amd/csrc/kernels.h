@@ -260,6 +260,12 @@ int launch_relu_bwd(float* dy, const float* y, size_t n, hipStream_t s);
 // Fused SGD (torch.optim.SGD semantics) over the flat bucket.
 int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay,
                float dampening, bool nesterov, bool first_step, hipStream_t s);
+// The input pipeline on the device (augment.hip; the arguments and the operation: include/mudpt.h at mudpt_augment).  images / params are
+// DEVICE tables the launcher cannot read (mudpt_augment_check validates a host copy); mean_std_host is read before the launch returns.
+int launch_augment(const uint8_t* pixels, const int64_t* images, int n_images, const int32_t* params, int batch, int size, const float* mean_std_host,
+                   float* out, hipStream_t s);
+// host arithmetic: MUDPT_AUGMENT_TABLE | R << 8 or MUDPT_AUGMENT_DIRECT for one sample's two axes, -1 for lengths < 1
+int augment_form(int x_len, int x_out, int y_len, int y_out, int size);
 
 // ------------------------------------------------------------------------------------------------
 // UMuDPT's prompt generator (promptgen.hip; trainers/umudpt.py:56-76,161-178): fp32 end to end, TRAINABLE weights

@@ -2706,3 +2706,41 @@ extern "C" int mudpt_promptgen_backward(int32_t depth, int32_t n_ctx, int32_t d_
     if (int r = promptgen_workspace_ok("promptgen_backward", depth, n_ctx, d_t, d_v, workspace, workspace_numel)) return r;
     return pg_backward(depth, n_ctx, d_t, d_v, pg_params(params, d_t, d_v), X, dG, dX, grads, pg_carve(workspace, depth, n_ctx, d_t, nullptr), (hipStream_t)stream);
 }
+
+// ---- the input pipeline on the device (augment.hip): stateless, no model handle.  Defined in this section so that the launcher-coverage
+// check of tests/test_capi_cpu.py finds launch_augment behind an export; include/mudpt.h documents the three in a section of their own ----
+extern "C" int mudpt_augment(const uint8_t* pixels_dev, const int64_t* images_dev, int32_t n_images, const int32_t* params_dev, int32_t batch, int32_t size,
+                             const float* mean_std_host, float* out_dev, void* stream) {
+    return launch_augment(pixels_dev, images_dev, n_images, params_dev, batch, size, mean_std_host, out_dev, (hipStream_t)stream);
+}
+extern "C" int mudpt_augment_check(const int64_t* images_host, int32_t n_images, const int32_t* params_host, int32_t batch, int32_t size) {
+    ARG_CHECK(images_host && params_host, "augment_check: null argument");
+    ARG_CHECK(n_images >= 0 && batch >= 0 && size >= 1, "augment_check: n_images %d, batch %d, size %d", n_images, batch, size);
+    int64_t end = 0;  // first byte past the previous image
+    for (int32_t i = 0; i < n_images; ++i) {
+        const int64_t off = images_host[3 * i], H = images_host[3 * i + 1], W = images_host[3 * i + 2];
+        ARG_CHECK(H >= 1 && H <= INT32_MAX, "augment_check: images row %d, column height = %lld: must be in [1, 2^31)", i, (long long)H);
+        ARG_CHECK(W >= 1 && W <= INT32_MAX, "augment_check: images row %d, column width = %lld: must be in [1, 2^31)", i, (long long)W);
+        ARG_CHECK(off >= end, "augment_check: images row %d, column offset = %lld: overlaps the image before it, which ends at byte %lld", i, (long long)off,
+                  (long long)end);
+        end = off + 3 * H * W;
+    }
+    static const char* const col[10] = {"image", "flip", "x_lo", "x_len", "x_out", "x_off", "y_lo", "y_len", "y_out", "y_off"};
+    for (int32_t n = 0; n < batch; ++n) {
+        const int32_t* p = params_host + (size_t)n * 10;
+        ARG_CHECK(p[0] >= 0 && p[0] < n_images, "augment_check: params row %d, column %s = %d: outside [0, %d)", n, col[0], p[0], n_images);
+        ARG_CHECK(p[1] == 0 || p[1] == 1, "augment_check: params row %d, column %s = %d: must be 0 or 1", n, col[1], p[1]);
+        for (int a = 0; a < 2; ++a) {  // x: columns 2 .. 5 against the width, y: 6 .. 9 against the height
+            const int32_t* q = p + 2 + 4 * a;
+            const int64_t extent = images_host[3 * p[0] + (a == 0 ? 2 : 1)];
+            ARG_CHECK(q[0] >= 0, "augment_check: params row %d, column %s = %d: must be >= 0", n, col[2 + 4 * a], q[0]);
+            ARG_CHECK(q[1] >= 1 && (int64_t)q[0] + q[1] <= extent, "augment_check: params row %d, column %s = %d: needs 1 <= len and lo + len <= %lld", n,
+                      col[3 + 4 * a], q[1], (long long)extent);
+            ARG_CHECK(q[2] >= size, "augment_check: params row %d, column %s = %d: the output length must be >= size (%d)", n, col[4 + 4 * a], q[2], size);
+            ARG_CHECK(q[3] >= 0 && (int64_t)q[3] + size <= q[2], "augment_check: params row %d, column %s = %d: needs 0 <= off and off + size (%d) <= out_len (%d)", n,
+                      col[5 + 4 * a], q[3], size, q[2]);
+        }
+    }
+    return MUDPT_OK;
+}
+extern "C" int mudpt_augment_form(int32_t x_len, int32_t x_out, int32_t y_len, int32_t y_out, int32_t size) { return augment_form(x_len, x_out, y_len, y_out, size); }

@@ -152,6 +152,15 @@ class SyntheticDataManager:
         self.train_loader_x = make(cfg.DATASET.NUM_TRAIN, cfg.DATALOADER.TRAIN_X.BATCH_SIZE)
         self.test_loader = make(cfg.DATASET.NUM_TEST, min(cfg.DATALOADER.TEST.BATCH_SIZE, cfg.DATASET.NUM_TEST))
         self.num_classes = len(classnames)
+        self._cfg = cfg
+
+    def uint8_store(self, device, max_bytes=None):
+        """The opt-in device-resident path (trainer.install_loader, MUDPT_DEVICE_DATA=1): NUM_TRAIN seeded uint8 images of varied sizes around
+        INPUT.SIZE in a DeviceImageStore, standing in for a decoded training set."""
+        from .augment import DeviceImageStore
+        from .synth import synthetic_uint8_images
+        S = self._cfg.INPUT.SIZE[0]
+        return DeviceImageStore.from_arrays(*synthetic_uint8_images(self._cfg.DATASET.NUM_TRAIN, self.num_classes, self._cfg.SEED, S, S + S // 2), device=device, max_bytes=max_bytes)
 
 
 class TrainerX:

@@ -108,3 +108,17 @@ def random_clip_state(shape: ModelShape, seed: int = 0, fp16_weights: bool = Tru
             sd[k] = t.half().float() if fp16_weights else t
     sd["logit_scale"] = torch.tensor(math.log(1 / 0.07))
     return sd
+
+
+def synthetic_uint8_images(n: int, n_classes: int, seed: int = 0, lo: int = 32, hi: int = 64):
+    """n seeded HWC uint8 "photographs" with heights and widths drawn from [lo, hi] and uniform labels: what a decoded few-shot training set
+    looks like to DeviceImageStore.from_arrays (mudpt_amd/augment.py), without files.  Smooth colour ramps under noise, so that a resample
+    has structure to get wrong."""
+    g = torch.Generator().manual_seed(seed)
+    sizes = torch.randint(lo, hi + 1, (n, 2), generator=g)
+    labels = torch.randint(0, n_classes, (n,), generator=g)
+    images = []
+    for h, w in sizes.tolist():
+        ramp = torch.arange(h)[:, None, None] * torch.tensor([3, 1, 2]) + torch.arange(w)[None, :, None] * torch.tensor([1, 2, 3])
+        images.append(((ramp + torch.randint(0, 64, (h, w, 3), generator=g)) % 256).to(torch.uint8))
+    return images, labels

@@ -120,17 +120,61 @@ def data_parallel_step(trainer, batch, with_acc: bool = False):
     return loss_summary
 
 
+DEVICE_DATA_TRANSFORMS = {"random_resized_crop", "random_flip", "normalize"}  # INPUT.TRANSFORMS of every yaml the reference ships
+
+
+def device_data_loader(trainer, loader, local: int):
+    """The opt-in device-resident input path (mudpt_amd/augment.py; MUDPT_DEVICE_DATA=1 or trainer.device_store): a DeviceAugmentLoader over
+    a DeviceImageStore -- trainer.device_store if one was handed over, else the training set decoded once from the ``impath`` / ``label``
+    items of Dassl's data_source, else dassl_lite's synthetic uint8 set.  None, after a one-line note, when the configuration is not the one
+    the kernel reproduces (exactly the three transforms above with INTERPOLATION "bicubic"), when no image list is found, or when the store
+    would take more than a quarter of the free device memory: install_loader then goes on as without the opt-in."""
+    from .augment import CLIP_MEAN, CLIP_STD, DeviceAugmentLoader, DeviceImageStore, StoreTooLarge
+    inp = trainer.cfg.INPUT
+    transforms, interpolation = set(getattr(inp, "TRANSFORMS", ()) or ()), getattr(inp, "INTERPOLATION", None)
+    if transforms != DEVICE_DATA_TRANSFORMS or interpolation != "bicubic":
+        print(f"Device-resident data refused: INPUT.TRANSFORMS {sorted(transforms)} / INTERPOLATION {interpolation!r} is not "
+              f"{sorted(DEVICE_DATA_TRANSFORMS)} / 'bicubic'; using the host loader")
+        return None
+    device = f"cuda:{local}"
+    budget = torch.cuda.mem_get_info(device)[0] // 4
+    store = getattr(trainer, "device_store", None)
+    if store is None:
+        source = getattr(getattr(loader, "dataset", None), "data_source", None)
+        try:
+            if source is not None and len(source) > 0 and all(hasattr(item, "impath") and hasattr(item, "label") for item in source):
+                store = DeviceImageStore.from_paths([item.impath for item in source], [item.label for item in source], device=device, max_bytes=budget)
+            elif hasattr(getattr(trainer, "dm", None), "uint8_store"):
+                store = trainer.dm.uint8_store(device, max_bytes=budget)
+            else:
+                print("Device-resident data refused: the training set exposes no impath / label items; using the host loader")
+                return None
+        except StoreTooLarge as too_large:
+            print(f"Device-resident data refused: {too_large}, a quarter of the free device memory; using the host loader")
+            return None
+    trainer.device_store = store
+    print(f"Device-resident data: {len(store)} images, {store.nbytes / 2 ** 20:.1f} MiB of uint8 on {device}; crop, flip and normalize run in one HIP launch per step")
+    return DeviceAugmentLoader(store, trainer.cfg.DATALOADER.TRAIN_X.BATCH_SIZE, inp.SIZE[0], getattr(inp, "PIXEL_MEAN", CLIP_MEAN), getattr(inp, "PIXEL_STD", CLIP_STD),
+                               getattr(inp, "RRC_SCALE", (0.08, 1.0)), seed=trainer.cfg.SEED)
+
+
 def install_loader(trainer, local: int):
     """Rank-aware, prefetched training loader (called at the end of build_model).  world > 1: ``train_loader_x`` is rebuilt over the same
     dataset with its batch sampler wrapped in parallel.ShardedBatchSampler, so each rank loads and decodes 1/world of every global
     batch (the reference's nn.DataParallel scatters ONE loaded batch, trainers/mudpt.py:230-233; here nothing is loaded N times);
     loaders that cannot be rebuilt (list-like synthetic ones) keep the slice-after-load fallback (parallel.shard_batch).  Then the
-    DevicePrefetcher overlaps the next batch's host -> device copy with the current step."""
+    DevicePrefetcher overlaps the next batch's host -> device copy with the current step.  With the opt-in of device_data_loader the
+    images never leave the device and its loader takes the place of both."""
     from .prefetch import DevicePrefetcher
     loader = getattr(trainer, "train_loader_x", None)
     trainer._loader_sharded = False
     if loader is None or isinstance(loader, DevicePrefetcher):
         return
+    if os.environ.get("MUDPT_DEVICE_DATA") == "1" or getattr(trainer, "device_store", None) is not None:
+        device_loader = device_data_loader(trainer, loader, local)
+        if device_loader is not None:
+            trainer.train_loader_x = device_loader
+            return
     if parallel.world_size() > 1:
         sharded = parallel.shard_loader(loader)  # unchanged if the loader is rank-aware already (MUDPT_DATA_SHARDED=1, DistributedSampler)
         if sharded is not None:
