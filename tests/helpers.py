@@ -714,3 +714,154 @@ def pp_case_for(case, ncu):
         if pp_grid_regime(M, case.N, ncu) == case.grid:
             return case._replace(M=M)
     return None
+
+
+# ---- LayerNorm: inputs, float64 reference and derived bounds of test_layernorm_cpu.py / test_layernorm_gpu.py -----------------------------
+LN_EPS = 1e-5
+LN_U = 2.0 ** -24  # unit roundoff of fp32
+LN_REGIMES = ("plain", "offset", "eps_dominates", "var_near_eps", "constant", "outliers", "zero")
+LN_ROWS_PER_REGIME = 5  # 35 rows: the last block of four waves is partial
+# one lane, a few lanes, a partly filled last 64-lane slab at k = 1, 2, 3, the full register file
+LN_WIDTHS = (4, 68, 260, 516, 772, 1020, 1024)
+# pad (elements) of every row stride in the strided launches: all different, so that a stride taken from the wrong operand shows
+LN_PADS = {"x": 4, "out": 8, "add": 12, "xout": 16, "dy": 20, "dres": 24, "dx": 28, "dx_lp": 32}
+LN_NO_PADS = dict.fromkeys(LN_PADS, 0)
+
+
+def ln_regimes(rows_per_regime, d, generator):
+    """[7 rows_per_regime, d] fp32: the row groups of LN_REGIMES stacked, so that one launch covers them all.
+      plain          randn * 2 + 0.5: the data of every older LayerNorm test (eps moves the result by 5e-6 here)
+      offset         randn * 0.05 + 300: |mean| / std = 6000, a one-pass variance cancels to garbage
+      eps_dominates  randn * 1e-3 + 0.25: variance 1e-6, a tenth of eps
+      var_near_eps   randn * 3e-3 - 1: variance 9e-6
+      constant       rows of 0.1 alternating with rows of -7.3: variance exactly 0, a mean that summing in fp32 does not reproduce exactly
+      outliers       randn with column 3 = 2000 and column d - 1 = -900
+      zero           all zeros: y = beta, rstd = 1 / sqrt(eps)"""
+    n = rows_per_regime
+    r = lambda: torch.randn(n, d, generator=generator)  # noqa: E731
+    const = torch.empty(n, d)
+    const[0::2], const[1::2] = 0.1, -7.3
+    outl = r()
+    outl[:, 3] = 2000.0
+    outl[:, d - 1] = -900.0
+    return torch.cat([r() * 2 + 0.5, r() * 0.05 + 300, r() * 1e-3 + 0.25, r() * 3e-3 - 1, const, outl, torch.zeros(n, d)])
+
+
+def ln_groups(rows_per_regime=LN_ROWS_PER_REGIME):
+    """Regime number (index into LN_REGIMES) of every row of ln_regimes."""
+    return torch.arange(len(LN_REGIMES) * rows_per_regime) // rows_per_regime
+
+
+def ln_operands(rows, d, generator):
+    """gamma, beta, dy, dres as elsewhere in the suite."""
+    gamma, beta = 1 + 0.1 * torch.randn(d, generator=generator), 0.1 * torch.randn(d, generator=generator)
+    return gamma, beta, torch.randn(rows, d, generator=generator), torch.randn(rows, d, generator=generator)
+
+
+LnRef = namedtuple("LnRef", "x mean rstd xhat y amax")
+LnBwdRef = namedtuple("LnBwdRef", "dx dgamma dbeta gmax")
+
+
+def ln64(x, gamma, beta, eps=LN_EPS):
+    """LayerNorm from the definition in float64 (biased variance) on the fp32 values given; mean / rstd / amax as [rows, 1]."""
+    x, gamma, beta = x.double(), gamma.double(), beta.double()
+    mean = x.mean(-1, keepdim=True)
+    rstd = ((x - mean).pow(2).mean(-1, keepdim=True) + eps).rsqrt()
+    xhat = (x - mean) * rstd
+    return LnRef(x, mean, rstd, xhat, xhat * gamma + beta, x.abs().amax(-1, keepdim=True))
+
+
+def ln_bwd64(ref, gamma, dy, dres=None):
+    """Gradients of ln64 in float64 from the definition: dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ dres, exactly), g = dy gamma;
+    dgamma = sum_r dy xhat, dbeta = sum_r dy; gmax = max |g| of every row.  The kernels are GIVEN mean and rstd in fp32 (ln_stats32).  dx is
+    held to the definition all the same: ln_bwd_bounds carries that rounding, 16 u amax rstd on xhat.  dgamma's bound has no such term --
+    half an ulp of a mean of 300 moves xhat by 3e-4 in the offset regime, the same way in every column, 15 to 80 times the bound measured on
+    a faithful fp32 restatement -- so dgamma is the same sum in float64 over the operands the kernel reads: xhat = (x - fp32(mean)) fp32(rstd)."""
+    dy = dy.double()
+    g = dy * gamma.double()
+    dx = ref.rstd * (g - g.mean(-1, keepdim=True) - ref.xhat * (g * ref.xhat).mean(-1, keepdim=True))
+    if dres is not None:
+        dx = dx + dres.double()
+    mean32, rstd32 = ln_stats32(ref)
+    xhat_given = (ref.x - mean32.double().unsqueeze(-1)) * rstd32.double().unsqueeze(-1)
+    return LnBwdRef(dx, (dy * xhat_given).sum(0), dy.sum(0), g.abs().amax(-1, keepdim=True))
+
+
+def ln_stats32(ref):
+    """mean, rstd [rows] of ln64 rounded to fp32: the backward's inputs, so that a backward test does not depend on the forward kernel."""
+    return ref.mean.squeeze(-1).float(), ref.rstd.squeeze(-1).float()
+
+
+def ln_bounds(ref, gamma, dtype=None, lo_mode=0, hi=None):
+    """Bounds on |result - ln64| of a correct fp32 two-pass LayerNorm, derived (never fitted to a kernel).  u = 2^-24, amax = max |x| of the row:
+      mean   16 u amax: d terms of at most amax summed in a tree of depth <= 10 + 6 (lane, then wave), each level rounding once
+      rstd   relative 16 u + (16 u amax rstd)^2 / 2.  The first term covers the sum of squares, the division, the add of eps and the
+             hardware rsqrt (1 ulp).  The second is what an error dm of the centre does to a small variance: sum (x - m - dm)^2 / d =
+             var + dm^2, so rstd changes by dm^2 rstd^2 / 2 relative
+      y      fp32: 2e-5 (1 + |y|) + 16 u amax rstd max |gamma|: the project's constant, and the error of the mean carried through
+             (x - mean) rstd gamma
+             T (dtype "bf16" | "fp16"): + EPS[dtype] |y|, half an ulp of T = correct rounding (the older tests allowed 4 EPS: truncation
+             passed), + 2^-25 in fp16 (half a subnormal step)
+             split pair hi + lo (lo_mode 1 | 2) instead: the fp32 bound + EPS^2 |y| (lo in T: half an ulp of T relative to a remainder of
+             at most half an ulp of hi; 2^-22 in fp16) or + 2^-4 EPS |y| (e4m3: 3 mantissa bits; 2^-15 in fp16).  e4m3 saturates at
+             448 / 4096: where half an ulp of `hi` exceeds that (bf16, |y| >= 32) the excess is added"""
+    mean = 16 * LN_U * ref.amax
+    e = mean * ref.rstd
+    rstd = ref.rstd * (16 * LN_U + 0.5 * e * e)
+    y = 2e-5 * (1 + ref.y.abs()) + e * gamma.double().abs().max()
+    if dtype is not None and lo_mode == 0:
+        y = y + EPS[dtype] * ref.y.abs() + (2.0 ** -25 if dtype == "fp16" else 0.0)
+    elif lo_mode == 1:
+        y = y + EPS[dtype] ** 2 * ref.y.abs()
+    elif lo_mode == 2:
+        mant, tiny = (7, 2.0 ** -126) if dtype == "bf16" else (10, 2.0 ** -14)
+        half_ulp = torch.ldexp(torch.ones(()), torch.frexp(hi.float().abs().clamp_min(tiny)).exponent - 2 - mant).double()
+        y = y + 2.0 ** -4 * EPS[dtype] * ref.y.abs() + (half_ulp - 448.0 / 4096.0).clamp_min(0)
+    return {"mean": mean, "rstd": rstd, "y": y}
+
+
+def ln_bwd_bounds(ref, bref, dy, dtype=None):
+    """Bounds on |result - ln_bwd64| of a correct fp32 backward that is given mean / rstd rounded to fp32.  G = max |dy gamma| of the row,
+    e = 16 u amax rstd (the error of xhat that the rounding of the centre leaves):
+      dx      2e-5 (rstd G + |dx|) + rstd G e (1 + |xhat|): the project's constant on the size of the terms, and e through
+              g - mean(g) - xhat mean(g xhat) (once in xhat itself, once in the mean that xhat enters)
+      dx_lp   + EPS[dtype] |dx| (correct rounding to T)
+      dgamma  4e-6 sqrt(rows) x the largest |dy xhat| term of the column (test_ln_bwd_affine's bound for unit-variance terms, scaled);
+      dbeta   4e-6 sqrt(rows) x the largest |dy| of the column"""
+    e = 16 * LN_U * ref.amax * ref.rstd
+    dx = 2e-5 * (ref.rstd * bref.gmax + bref.dx.abs()) + ref.rstd * bref.gmax * e * (1 + ref.xhat.abs())
+    if dtype is not None:
+        dx = dx + EPS[dtype] * bref.dx.abs()
+    s = 4e-6 * dy.shape[0] ** 0.5
+    return {"dx": dx, "dgamma": s * (dy.double() * ref.xhat).abs().amax(0), "dbeta": s * dy.double().abs().amax(0)}
+
+
+def ln_ratios(got, want, bound, groups=None):
+    """Worst |got - want| / bound of every regime ([len(LN_REGIMES)], or one number without groups): 0 / 0 counts as 0, a NaN or an
+    infinity in `got` as infinite."""
+    got = got.detach().double().cpu()
+    if got.dim() < want.dim():
+        got = got.unsqueeze(-1)
+    err = (got - want).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.expand_as(err))
+    ratio = torch.where(torch.isfinite(got), ratio, torch.full_like(ratio, float("inf")))
+    if groups is None:
+        return ratio.max()
+    ratio = ratio.reshape(len(groups), -1).amax(-1)
+    return torch.stack([ratio[groups == i].max() if (groups == i).any() else torch.zeros(()) for i in range(len(LN_REGIMES))])
+
+
+def ln_check(tag, what, got, want, bound, groups=None, limit=1.0, record=None):
+    """Assert ln_ratios <= limit; print the ratios first; record[(what, regime)] keeps the worst ratio seen."""
+    r = ln_ratios(got, want, bound, groups)
+    if groups is None:
+        print(f"{tag} {what}: worst error / bound {r.item():.3f}")
+        if record is not None:
+            record[(what, "all")] = max(record.get((what, "all"), 0.0), r.item())
+    else:
+        print(f"{tag} {what}: worst error / bound " + " ".join(f"{n} {v:.3f}" for n, v in zip(LN_REGIMES, r.tolist())))
+        if record is not None:
+            for n, v in zip(LN_REGIMES, r.tolist()):
+                record[(what, n)] = max(record.get((what, n), 0.0), v)
+    assert (r <= limit).all(), (tag, what, r.tolist())
+    return r
