@@ -68,6 +68,8 @@
  *   mudpt_encode_image                   clip/model.py:822 encode_image, lpclip/feat_extractor.py:125  the raw visual(image) features
  *   mudpt_forward / _ex                  trainers/zsclip.py:74-79  model_inference: logit_scale * normalise(image features) @ text_features.t()
  *   (mudpt_param_count / _numel are 0; every training, class-prompt, class-shard and mudpt_cp_* entry point refuses the handle.)
+ * The linear probe (lpclip/linear_probe.py:64, sklearn's LogisticRegression(solver="lbfgs")) needs no handle: its objective is evaluated by the
+ * stateless mudpt_probe_* kernels at the end of this file, and mudpt_amd/lpclip.py + mudpt_amd/lbfgs.py drive them.
  *
  * Conventions: every function returns 0 on success or a MUDPT_ERR_* code; mudpt_last_error() gives
  * the message of the calling thread's last failure.  No exceptions cross the ABI.  A model handle is
@@ -610,6 +612,24 @@ int mudpt_promptgen_forward(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d
                             size_t workspace_numel, void* stream);
 int mudpt_promptgen_backward(int32_t depth, int32_t n_ctx, int32_t d_t, int32_t d_v, const float* params, const float* X, const float* dG, float* dX,
                              float* grads, float* workspace, size_t workspace_numel, void* stream);
+/* The linear probe's kernels (mudpt_amd/csrc/probe.hip; lpclip/linear_probe.py's LogisticRegression(solver="lbfgs")), exact fp32 on the matrix cores
+ * (v_mfma_f32_32x32x2_f32), 128 x 128 x 32 tiles staged through LDS; any sizes >= 1 and any strides >= the row length.  Scalars travel as float.
+ *   probe_gemm_nt     C [M, N] = A [M, K] . B [N, K]^T (+ bias[N], may be NULL): the logits Z = X W^T + b
+ *   probe_gemm_tn     C [M, N] = A [Kd, M]^T . B [Kd, N] (+ beta W [M, N], may be NULL), db [M] (may be NULL) = column sums of A: dW = P^T X + beta W and
+ *                     db = P^T 1 in one pass.  The depth is cut into slices of whole 32-deep steps (slices = 0: the library's choice for the device,
+ *                     otherwise the wish, both as mudpt_probe_gemm_tn_slices reports), the partial sums go to scratch (slices * (M N + M) floats) and are
+ *                     added in ascending order by a second kernel: no float atomics, two runs give the same bits.  C must not alias A, B or W.
+ *   probe_gemm_tn_slices  HOST arithmetic only: the slice count for a wish (<= 0: two workgroups per compute unit of ncu, at least two steps a slice); -1 for sizes < 1
+ *   probe_rows        Z [rows, n_cls] in place: logits -> P = (softmax - onehot(labels)) / rows; row_loss [rows] = logsumexp(z) - z[label] (computed as
+ *                     log1p(sum of the other exponentials) + (max - z[label])); loss_sum[0] (a device double) = their sum in a fixed order.
+ *                     labels int32 [rows] in [0, n_cls) are DEVICE data the kernel TRUSTS: the caller checks them on the host
+ *   probe_argmax      pred[r] (int32) = the lowest index of the maximum of row r, as numpy.argmax; labels / count (both or neither, int32): count[0] = matches */
+int mudpt_probe_gemm_nt(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const float* B, int32_t ldb, const float* bias, float* C, int32_t ldc, void* stream);
+int mudpt_probe_gemm_tn(int32_t M, int32_t N, int32_t Kd, const float* A, int32_t lda, const float* B, int32_t ldb, float beta, const float* W, int32_t ldw, float* C,
+                        int32_t ldc, float* db, float* scratch, size_t scratch_numel, int32_t slices, void* stream);
+int mudpt_probe_gemm_tn_slices(int32_t M, int32_t N, int32_t Kd, int32_t slices, int32_t ncu);
+int mudpt_probe_rows(float* Z, int32_t ldz, const int32_t* labels, int32_t rows, int32_t n_cls, float* row_loss, double* loss_sum, void* stream);
+int mudpt_probe_argmax(const float* Z, int32_t ldz, int32_t rows, int32_t n_cls, int32_t* pred, const int32_t* labels, int32_t* count, void* stream);
 
 #ifdef __cplusplus
 }

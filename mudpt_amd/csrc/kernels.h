@@ -268,6 +268,24 @@ int launch_augment(const uint8_t* pixels, const int64_t* images, int n_images, c
 int augment_form(int x_len, int x_out, int y_len, int y_out, int size);
 
 // ------------------------------------------------------------------------------------------------
+// The linear probe (probe.hip; lpclip/linear_probe.py): one evaluation of the multinomial logistic objective in exact fp32 on the matrix cores
+// ------------------------------------------------------------------------------------------------
+// C [M, N] = A [M, K] . B [N, K]^T (+ bias[N]): both operands k-contiguous, any M, N, K and strides, 128 x 128 x 32 tiles through LDS
+int launch_probe_gemm_nt(int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc, hipStream_t s);
+// C [M, N] = A [Kd, M]^T . B [Kd, N] (+ beta W), db [M] (may be null) = column sums of A.  The depth Kd is cut into `slices` runs of whole K-steps
+// (0: probe_tn_slices' choice for this device), one workgroup per tile and slice writes its partial sums to scratch (slices * (M N + M) floats),
+// and a second kernel adds them in ascending order: no atomics, two runs give the same bits.  C must not alias A, B or W.
+int launch_probe_gemm_tn(int M, int N, int Kd, const float* A, int lda, const float* B, int ldb, float beta, const float* W, int ldw, float* C, int ldc, float* db,
+                         float* scratch, size_t scratch_numel, int slices, hipStream_t s);
+// host arithmetic: the slices launch_probe_gemm_tn runs for a wish of `want` (<= 0: two workgroups per compute unit, at least two K-steps per slice); -1: bad sizes
+int probe_tn_slices(int M, int N, int Kd, int want, int ncu);
+// Z [rows, n_cls] (row stride ldz) in place: logits -> P = (softmax - onehot(labels)) / rows; row_loss [rows] = logsumexp - z[label];
+// loss_sum[0] = their sum, added in double in a fixed order.  labels [rows] int32 in [0, n_cls) are TRUSTED.
+int launch_probe_rows(float* Z, int ldz, const int* labels, int rows, int n_cls, float* row_loss, double* loss_sum, hipStream_t s);
+// pred[r] = lowest index of the maximum of row r (numpy.argmax); labels / count (both or neither): count[0] = rows with pred == label
+int launch_probe_argmax(const float* Z, int ldz, int rows, int n_cls, int* pred, const int* labels, int* count, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // UMuDPT's prompt generator (promptgen.hip; trainers/umudpt.py:56-76,161-178): fp32 end to end, TRAINABLE weights
 // ------------------------------------------------------------------------------------------------
 // LayerNorm backward that also produces the affine gradients: dx = (dres +) LN'(dy), dgamma[j] (+)= sum_r dy[r][j] xhat[r][j],

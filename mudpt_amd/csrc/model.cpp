@@ -2666,6 +2666,22 @@ extern "C" int mudpt_embed_tokens(const float* table, int32_t vocab, const int32
 extern "C" int mudpt_feature_ensemble(const float* f, float* acc, float* out, int32_t C, int32_t e, int32_t first, int32_t last, int32_t n_templates, void* stream) {
     return launch_feature_ensemble(f, acc, out, C, e, first != 0, last != 0, n_templates, (hipStream_t)stream);
 }
+// the linear probe's kernels (probe.hip)
+extern "C" int mudpt_probe_gemm_nt(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const float* B, int32_t ldb, const float* bias, float* C, int32_t ldc,
+                                   void* stream) {
+    return launch_probe_gemm_nt(M, N, K, A, lda, B, ldb, bias, C, ldc, (hipStream_t)stream);
+}
+extern "C" int mudpt_probe_gemm_tn(int32_t M, int32_t N, int32_t Kd, const float* A, int32_t lda, const float* B, int32_t ldb, float beta, const float* W, int32_t ldw,
+                                   float* C, int32_t ldc, float* db, float* scratch, size_t scratch_numel, int32_t slices, void* stream) {
+    return launch_probe_gemm_tn(M, N, Kd, A, lda, B, ldb, beta, W, ldw, C, ldc, db, scratch, scratch_numel, slices, (hipStream_t)stream);
+}
+extern "C" int mudpt_probe_gemm_tn_slices(int32_t M, int32_t N, int32_t Kd, int32_t slices, int32_t ncu) { return probe_tn_slices(M, N, Kd, slices, ncu); }
+extern "C" int mudpt_probe_rows(float* Z, int32_t ldz, const int32_t* labels, int32_t rows, int32_t n_cls, float* row_loss, double* loss_sum, void* stream) {
+    return launch_probe_rows(Z, ldz, labels, rows, n_cls, row_loss, loss_sum, (hipStream_t)stream);
+}
+extern "C" int mudpt_probe_argmax(const float* Z, int32_t ldz, int32_t rows, int32_t n_cls, int32_t* pred, const int32_t* labels, int32_t* count, void* stream) {
+    return launch_probe_argmax(Z, ldz, rows, n_cls, pred, labels, count, (hipStream_t)stream);
+}
 // UMuDPT's prompt generator (promptgen.hip): its three kernels, and the whole block as the model path runs it
 extern "C" int mudpt_layernorm_bwd_affine(const float* x, int32_t ldx, const float* mean, const float* rstd, const float* gamma, const float* dy, int32_t lddy,
                                           const float* dres, int32_t lddres, float* dx, int32_t lddx, float* dgamma, float* dbeta, int32_t accumulate,
