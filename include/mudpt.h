@@ -70,6 +70,8 @@
  *   (mudpt_param_count / _numel are 0; every training, class-prompt, class-shard and mudpt_cp_* entry point refuses the handle.)
  * The linear probe (lpclip/linear_probe.py:64, sklearn's LogisticRegression(solver="lbfgs")) needs no handle: its objective is evaluated by the
  * stateless mudpt_probe_* kernels at the end of this file, and mudpt_amd/lpclip.py + mudpt_amd/lbfgs.py drive them.
+ * The test pass's evaluator (Dassl's evaluation/evaluator.py Classification, the end of every script's trainer.test()) needs none either: the
+ * stateless mudpt_eval_* four at the end of this file count on the device, and mudpt_amd/evaluator.py drives them.
  *
  * Conventions: every function returns 0 on success or a MUDPT_ERR_* code; mudpt_last_error() gives
  * the message of the calling thread's last failure.  No exceptions cross the ABI.  A model handle is
@@ -630,6 +632,28 @@ int mudpt_probe_gemm_tn(int32_t M, int32_t N, int32_t Kd, const float* A, int32_
 int mudpt_probe_gemm_tn_slices(int32_t M, int32_t N, int32_t Kd, int32_t slices, int32_t ncu);
 int mudpt_probe_rows(float* Z, int32_t ldz, const int32_t* labels, int32_t rows, int32_t n_cls, float* row_loss, double* loss_sum, void* stream);
 int mudpt_probe_argmax(const float* Z, int32_t ldz, int32_t rows, int32_t n_cls, int32_t* pred, const int32_t* labels, int32_t* count, void* stream);
+/* The test pass's evaluator (mudpt_amd/csrc/evaluate.hip; Dassl's Classification evaluator: accuracy, macro-F1, per-class results, confusion matrix).
+ * Stateless additions without a model handle, so MUDPT_ABI_VERSION stays.  The state is ONE int32 device buffer of mudpt_eval_state_numel elements:
+ *   [total, correct, invalid, reserved] [support: C] [predicted: C] [hit: C] [cmat: C x C, row = label, column = prediction; only when with_cmat]
+ *   eval_state_numel  HOST arithmetic only: 4 + 3 C (+ C^2 with_cmat); 0 for n_cls < 1, or with_cmat and C^2 >= 2^31
+ *   eval_reset        zeroes the state
+ *   eval_accumulate   logits [rows, n_cls] fp32 (row stride ldz >= n_cls), labels [rows] int64, both DEVICE data.  The prediction p of a row is what
+ *                     torch.max(logits, 1)[1] gives on the CPU for the same values: the lowest index of the maximum; the index of the first NaN if the
+ *                     row holds one; +0 == -0; a row of -inf gives 0 (NOT probe_argmax's rule, which skips NaN).  Every logit is read once (16-byte
+ *                     loads when the base is 16-byte aligned and ldz % 4 == 0).  A label y outside [0, n_cls) adds one to invalid and nothing else
+ *                     (it never indexes anything); a valid row adds one to total, support[y], predicted[p], to correct and hit[y] when p == y, and
+ *                     to cmat[y][p] when with_cmat.  Integer atomics only: two runs give the same bits.  pred (int32 [rows], may be NULL) receives
+ *                     p, -1 for an invalid row.  Nothing is reset: consecutive launches on one stream add up.
+ *   eval_finalize     one launch; results (6 DEVICE doubles) = total, correct, invalid, n_supported = classes with support > 0,
+ *                     macro_f1 = 100 x mean over those classes of 2 hit / (support + predicted)  (sklearn's f1_score(average="macro",
+ *                     labels=np.unique(y_true))), perclass_accuracy = mean over them of 100 x hit / support; double sums in a fixed order, zeros
+ *                     (never NaN) for an empty state.  It reads the first 4 + 3 C elements only.
+ * MUDPT_ERR_ARG before any GPU call, no output touched: a null pointer (pred excepted), rows < 1, n_cls < 1, ldz < n_cls, with_cmat and n_cls^2 >= 2^31. */
+size_t mudpt_eval_state_numel(int32_t n_cls, int32_t with_cmat);
+int mudpt_eval_reset(int32_t* state, int32_t n_cls, int32_t with_cmat, void* stream);
+int mudpt_eval_accumulate(const float* logits, int32_t ldz, const int64_t* labels, int32_t rows, int32_t n_cls, int32_t* state, int32_t with_cmat, int32_t* pred,
+                          void* stream);
+int mudpt_eval_finalize(const int32_t* state, int32_t n_cls, double* results, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@ It replaces, for the transforms every shipped yaml uses (INPUT.TRANSFORMS random
 (DESIGN.md 5).  The kernel reproduces Pillow's 8-bit bicubic arithmetic, so the bytes are the ones the reference's pipeline feeds the
 model; which crops are drawn follows torchvision's RandomResizedCrop.get_params in distribution, from this module's own seeded stream.
 
-Opt-in (trainer.install_loader: MUDPT_DEVICE_DATA=1 or trainer.device_store); nothing here runs otherwise.
+Opt-in (trainer.install_loader: MUDPT_DEVICE_DATA=1 or trainer.device_store); nothing here runs otherwise.  The test pass has its own
+switch (trainer.install_test_loader: MUDPT_DEVICE_TEST=1 or trainer.device_test_store -> DeviceEvalLoader, the evaluation transform).
 """
 from __future__ import annotations
 
@@ -167,6 +168,39 @@ def center_crop_params(store, indices, size: int) -> torch.Tensor:
         wr, hr = (size, int(size * h / w)) if w <= h else (int(size * w / h), size)
         rows.append([i, 0, 0, w, wr, int(round((wr - size) / 2.0)), 0, h, hr, int(round((hr - size) / 2.0))])
     return torch.tensor(rows, dtype=torch.int32).reshape(-1, 10)
+
+
+class DeviceEvalLoader:
+    """The test loader over a DeviceImageStore: every image once, in index order, no drop_last, under the evaluation transform
+    (center_crop_params).  The rows of the WHOLE store are computed, held to check_params and uploaded once, here; a batch is then a slice
+    of those device rows into store.launch plus a slice of store.labels -- no host copy and no sync per batch.  Yields
+    {"img", "label", "_mudpt_sharded": True} with device tensors produced on the current stream.  Every rank evaluates the whole
+    store, as the reference's test() does.  A "cpu" store holds the same rows for host arithmetic (``params``, ``batch_ranges``);
+    iterating needs the GPU."""
+
+    def __init__(self, store, batch_size: int, size: int, mean=CLIP_MEAN, std=CLIP_STD):
+        self.store, self.batch_size, self.size, self.mean, self.std = store, int(batch_size), int(size), tuple(mean), tuple(std)
+        if self.batch_size < 1:
+            raise ValueError(f"a test batch of {batch_size} images")
+        if len(store) == 0:
+            raise ValueError("a store of 0 images gives no test batch")
+        self.params = center_crop_params(store, range(len(store)), self.size).contiguous()  # host
+        check_params(store.table, self.params, self.size)
+        self.params_dev = self.params.to(store.device)
+
+    def __len__(self):
+        return -(-len(self.store) // self.batch_size)
+
+    def batch_ranges(self):
+        """[(first, past-the-last)] store index of every batch: the last one may be short."""
+        n = len(self.store)
+        return [(lo, min(lo + self.batch_size, n)) for lo in range(0, n, self.batch_size)]
+
+    def __iter__(self):
+        if self.store.device.type != "cuda":
+            raise capi.MudptError("DeviceEvalLoader runs a HIP kernel per batch: the store must live on a GPU (there is no CPU form)")
+        for lo, hi in self.batch_ranges():
+            yield {"img": self.store.launch(self.params_dev[lo:hi], self.size, self.mean, self.std), "label": self.store.labels[lo:hi], "_mudpt_sharded": True}
 
 
 class DeviceAugmentLoader:

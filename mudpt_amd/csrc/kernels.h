@@ -286,6 +286,18 @@ int launch_probe_rows(float* Z, int ldz, const int* labels, int rows, int n_cls,
 int launch_probe_argmax(const float* Z, int ldz, int rows, int n_cls, int* pred, const int* labels, int* count, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// The test pass's evaluator (evaluate.hip; Dassl's Classification evaluator): integer counts in one int32 state buffer, laid out
+// [total, correct, invalid, reserved] [support: C] [predicted: C] [hit: C] [cmat: C x C, row = label, column = prediction; with_cmat only]
+// ------------------------------------------------------------------------------------------------
+size_t eval_state_numel(int n_cls, int with_cmat);  // host arithmetic; 0 for n_cls < 1 or a matrix of 2^31 cells or more
+int launch_eval_reset(int* state, int n_cls, int with_cmat, hipStream_t s);
+// the prediction of a row is torch.max(logits, 1)[1] on the CPU (lowest index of the maximum, the first NaN if there is one) -- NOT
+// probe_row_argmax's rule; a label outside [0, n_cls) only counts as invalid; nothing is reset, launches add up.  pred may be null.
+int launch_eval_accumulate(const float* logits, int ldz, const int64_t* labels, int rows, int n_cls, int* state, int with_cmat, int* pred, hipStream_t s);
+// results [6] (device doubles) = total, correct, invalid, classes with support, macro-F1 and mean per-class accuracy in percent over those classes
+int launch_eval_finalize(const int* state, int n_cls, double* results, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // UMuDPT's prompt generator (promptgen.hip; trainers/umudpt.py:56-76,161-178): fp32 end to end, TRAINABLE weights
 // ------------------------------------------------------------------------------------------------
 // LayerNorm backward that also produces the affine gradients: dx = (dres +) LN'(dy), dgamma[j] (+)= sum_r dy[r][j] xhat[r][j],

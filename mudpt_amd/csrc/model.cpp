@@ -2682,6 +2682,16 @@ extern "C" int mudpt_probe_rows(float* Z, int32_t ldz, const int32_t* labels, in
 extern "C" int mudpt_probe_argmax(const float* Z, int32_t ldz, int32_t rows, int32_t n_cls, int32_t* pred, const int32_t* labels, int32_t* count, void* stream) {
     return launch_probe_argmax(Z, ldz, rows, n_cls, pred, labels, count, (hipStream_t)stream);
 }
+// the test pass's evaluator (evaluate.hip): stateless, no model handle
+extern "C" size_t mudpt_eval_state_numel(int32_t n_cls, int32_t with_cmat) { return eval_state_numel(n_cls, with_cmat); }
+extern "C" int mudpt_eval_reset(int32_t* state, int32_t n_cls, int32_t with_cmat, void* stream) { return launch_eval_reset(state, n_cls, with_cmat, (hipStream_t)stream); }
+extern "C" int mudpt_eval_accumulate(const float* logits, int32_t ldz, const int64_t* labels, int32_t rows, int32_t n_cls, int32_t* state, int32_t with_cmat,
+                                     int32_t* pred, void* stream) {
+    return launch_eval_accumulate(logits, ldz, labels, rows, n_cls, state, with_cmat, pred, (hipStream_t)stream);
+}
+extern "C" int mudpt_eval_finalize(const int32_t* state, int32_t n_cls, double* results, void* stream) {
+    return launch_eval_finalize(state, n_cls, results, (hipStream_t)stream);
+}
 // UMuDPT's prompt generator (promptgen.hip): its three kernels, and the whole block as the model path runs it
 extern "C" int mudpt_layernorm_bwd_affine(const float* x, int32_t ldx, const float* mean, const float* rstd, const float* gamma, const float* dy, int32_t lddy,
                                           const float* dres, int32_t lddres, float* dx, int32_t lddx, float* dgamma, float* dbeta, int32_t accumulate,

@@ -41,6 +41,7 @@ def default_cfg() -> CfgNode:
         OPTIM=C(NAME="sgd", LR=0.0025, MAX_EPOCH=10, LR_SCHEDULER="cosine", WARMUP_EPOCH=1, WARMUP_TYPE="constant",
                 WARMUP_CONS_LR=1e-5, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, SGD_DAMPNING=0.0, SGD_NESTEROV=False),
         TRAIN=C(PRINT_FREQ=5),
+        TEST=C(EVALUATOR="Classification", PER_CLASS_RESULT=False, COMPUTE_CMAT=False),  # Dassl's defaults (dassl/config/defaults.py)
         TRAINER=C(NAME="MuDPT", MUDPT=C(N_CTX=2, CTX_INIT="a photo of a", DEEP_PROMPT_DEPTH=8, PREC="fp16"),
                   COCOOP=C(N_CTX=4, CTX_INIT="a photo of a", PREC="fp16"),  # train.py:92-95 + configs/trainers/CoCoOp/*.yaml
                   COOP=C(N_CTX=16, CTX_INIT="", PREC="fp16", CSC=False, CLASS_TOKEN_POSITION="end"),  # train.py:83-88
@@ -162,6 +163,27 @@ class SyntheticDataManager:
         S = self._cfg.INPUT.SIZE[0]
         return DeviceImageStore.from_arrays(*synthetic_uint8_images(self._cfg.DATASET.NUM_TRAIN, self.num_classes, self._cfg.SEED, S, S + S // 2), device=device, max_bytes=max_bytes)
 
+    def uint8_test_store(self, device, max_bytes=None):
+        """The opt-in device-resident test pass (trainer.install_test_loader, MUDPT_DEVICE_TEST=1): NUM_TEST seeded uint8 images of varied
+        sizes around INPUT.SIZE, standing in for a decoded test set (another seed than the training store's)."""
+        from .augment import DeviceImageStore
+        from .synth import synthetic_uint8_images
+        S = self._cfg.INPUT.SIZE[0]
+        return DeviceImageStore.from_arrays(*synthetic_uint8_images(self._cfg.DATASET.NUM_TEST, self.num_classes, self._cfg.SEED + 1, S, S + S // 2), device=device,
+                                            max_bytes=max_bytes)
+
+
+def build_evaluator(cfg, **kwargs):
+    """Dassl's build_evaluator for its one classification evaluator: TEST.EVALUATOR "Classification" (Dassl's default) and
+    "DeviceClassification" (the name registered with real Dassl) both give mudpt_amd.evaluator.DeviceClassification, which computes
+    Classification's numbers."""
+    from .evaluator import DeviceClassification
+    test = getattr(cfg, "TEST", None)
+    name = getattr(test, "EVALUATOR", "Classification")
+    if name not in ("Classification", "DeviceClassification"):
+        raise KeyError(f"dassl_lite only provides the Classification evaluator, not {name!r}")
+    return DeviceClassification(cfg, **kwargs)
+
 
 class TrainerX:
     """The slice of dassl.engine.TrainerX / SimpleTrainer / TrainerBase the plugin uses."""
@@ -176,6 +198,7 @@ class TrainerX:
         self.output_dir = cfg.OUTPUT_DIR
         self.build_data_loader()
         self.build_model()
+        self.evaluator = build_evaluator(cfg, lab2cname=self.lab2cname)  # SimpleTrainer.__init__: after the data loader, which names the classes
 
     # -- hooks subclasses override ---------------------------------------------------------------------------
     def check_cfg(self, cfg):
@@ -254,13 +277,10 @@ class TrainerX:
 
     @torch.no_grad()
     def test(self, split=None):
+        """SimpleTrainer.test(): reset, process per batch, evaluate; the accuracy is returned (Dassl returns the first result)."""
         self.set_model_mode("eval")
-        correct = total = 0
+        self.evaluator.reset()
         for batch in self.test_loader:
             x, y = self.parse_batch_test(batch)
-            pred = self.model_inference(x).argmax(dim=1)
-            correct += int((pred == y).sum())
-            total += int(y.numel())
-        acc = 100.0 * correct / max(total, 1)
-        print(f"=> result\n* total: {total}\n* correct: {correct}\n* accuracy: {acc:.1f}%")
-        return acc
+            self.evaluator.process(self.model_inference(x), y)
+        return list(self.evaluator.evaluate().values())[0]

@@ -24,7 +24,7 @@ except ImportError:  # Dassl is not installed in the build image nor on the GPU 
     from .dassl_lite import TRAINER_REGISTRY, TrainerX, build_optimizer, build_lr_scheduler, load_checkpoint, load_pretrained_weights
     HAVE_DASSL = False
 
-from . import parallel, synth
+from . import evaluator, parallel, synth  # noqa: F401 -- evaluator: with Dassl, registers DeviceClassification in its EVALUATOR_REGISTRY
 from .model import CustomCLIP, ModelShape
 
 PREC_TO_DTYPE = {"fp16": "fp16", "fp32": "fp32", "amp": "bf16"}
@@ -180,6 +180,53 @@ def install_loader(trainer, local: int):
         if sharded is not None:
             loader, trainer._loader_sharded = sharded, True
     trainer.train_loader_x = DevicePrefetcher(loader, device=f"cuda:{local}", shard=not trainer._loader_sharded)
+
+
+def device_test_loader(trainer, loader, local: int):
+    """The opt-in device-resident test pass (MUDPT_DEVICE_TEST=1 or trainer.device_test_store; its own switch, MUDPT_DEVICE_DATA does not
+    take it): a DeviceEvalLoader over a DeviceImageStore -- trainer.device_test_store if one was handed over, else the test set decoded once
+    from the ``impath`` / ``label`` items of Dassl's data_source, else dassl_lite's synthetic uint8 test set.  Dassl's test transform is
+    Resize(max(INPUT.SIZE)) + CenterCrop(INPUT.SIZE) + ToTensor and, if INPUT.TRANSFORMS names it, normalize, with INTERPOLATION: the
+    kernel reproduces it for a square size, "normalize" and "bicubic".  None, after a one-line note, under the conditions
+    device_data_loader refuses: another transform, no image list, a store over a quarter of the free device memory."""
+    from .augment import CLIP_MEAN, CLIP_STD, DeviceEvalLoader, DeviceImageStore, StoreTooLarge
+    inp = trainer.cfg.INPUT
+    transforms, interpolation, size = set(getattr(inp, "TRANSFORMS", ()) or ()), getattr(inp, "INTERPOLATION", None), tuple(inp.SIZE)
+    if "normalize" not in transforms or interpolation != "bicubic" or len(set(size)) != 1:
+        print(f"Device-resident test data refused: INPUT.SIZE {size} / TRANSFORMS {sorted(transforms)} / INTERPOLATION {interpolation!r} is not "
+              "a square size with 'normalize' / 'bicubic'; using the host loader")
+        return None
+    device = f"cuda:{local}"
+    budget = torch.cuda.mem_get_info(device)[0] // 4
+    store = getattr(trainer, "device_test_store", None)
+    if store is None:
+        source = getattr(getattr(loader, "dataset", None), "data_source", None)
+        try:
+            if source is not None and len(source) > 0 and all(hasattr(item, "impath") and hasattr(item, "label") for item in source):
+                store = DeviceImageStore.from_paths([item.impath for item in source], [item.label for item in source], device=device, max_bytes=budget)
+            elif hasattr(getattr(trainer, "dm", None), "uint8_test_store"):
+                store = trainer.dm.uint8_test_store(device, max_bytes=budget)
+            else:
+                print("Device-resident test data refused: the test set exposes no impath / label items; using the host loader")
+                return None
+        except StoreTooLarge as too_large:
+            print(f"Device-resident test data refused: {too_large}, a quarter of the free device memory; using the host loader")
+            return None
+    trainer.device_test_store = store
+    print(f"Device-resident test data: {len(store)} images, {store.nbytes / 2 ** 20:.1f} MiB of uint8 on {device}; resize, center crop and normalize run in one HIP launch per batch")
+    return DeviceEvalLoader(store, trainer.cfg.DATALOADER.TEST.BATCH_SIZE, size[0], getattr(inp, "PIXEL_MEAN", CLIP_MEAN), getattr(inp, "PIXEL_STD", CLIP_STD))
+
+
+def install_test_loader(trainer, local: int):
+    """Under the opt-in of device_test_loader, ``test_loader`` becomes the DeviceEvalLoader; otherwise nothing changes."""
+    from .augment import DeviceEvalLoader
+    loader = getattr(trainer, "test_loader", None)
+    if loader is None or isinstance(loader, DeviceEvalLoader):
+        return
+    if os.environ.get("MUDPT_DEVICE_TEST") == "1" or getattr(trainer, "device_test_store", None) is not None:
+        device_loader = device_test_loader(trainer, loader, local)
+        if device_loader is not None:
+            trainer.test_loader = device_loader
 
 
 def parse_batch(trainer, batch):
@@ -359,6 +406,11 @@ class PromptTrainer(TrainerX):
         if parallel.world_size() > 1:
             parallel.broadcast_params(self.model.flat_params)
         install_loader(self, local)  # rank-aware (world > 1) and prefetched training loader
+        self._local = local
+
+    def test(self, split=None):
+        install_test_loader(self, self._local)  # the opt-in may be taken after construction (trainer.device_test_store)
+        return super().test(split=split)
 
     def forward_backward(self, batch):
         return data_parallel_step(self, batch, with_acc=self.WITH_ACC)

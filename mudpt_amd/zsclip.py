@@ -19,7 +19,7 @@ from torch import nn
 
 from . import capi, synth
 from .model import ModelShape
-from .trainer import TRAINER_REGISTRY, TrainerX, load_clip_state_dict, precision_to_dtype, tokenize_prompts, warn_if_fp16_misses_the_bound
+from .trainer import TRAINER_REGISTRY, TrainerX, install_test_loader, load_clip_state_dict, precision_to_dtype, tokenize_prompts, warn_if_fp16_misses_the_bound
 
 # trainers/zsclip.py:32-48: the per-dataset prompt, keyed by cfg.DATASET.NAME
 CUSTOM_TEMPLATES = {
@@ -205,6 +205,10 @@ class ZeroshotCLIP(TrainerX):
 
     def model_inference(self, image):
         return self.model(image)
+
+    def test(self, split=None):
+        install_test_loader(self, self.model.device.index or 0)  # the opt-in device-resident test pass (MUDPT_DEVICE_TEST=1 / device_test_store)
+        return super().test(split=split)
 
 
 @TRAINER_REGISTRY.register()
