@@ -68,6 +68,9 @@
  *   mudpt_encode_image                   clip/model.py:822 encode_image, lpclip/feat_extractor.py:125  the raw visual(image) features
  *   mudpt_forward / _ex                  trainers/zsclip.py:74-79  model_inference: logit_scale * normalise(image features) @ text_features.t()
  *   (mudpt_param_count / _numel are 0; every training, class-prompt, class-shard and mudpt_cp_* entry point refuses the handle.)
+ * Frozen, CoOp and CoCoOp handles also run the test pass from cached image features:
+ *   mudpt_forward_features               trainers/zsclip.py:74-79, coop.py:212-223, cocoop.py:178-188 behind their clip_model.visual(image)
+ *   mudpt_image_features                 lpclip/feat_extractor.py:125-137  the features of the last inference forward, for {dir}/{dataset}/{split}.npz
  * The linear probe (lpclip/linear_probe.py:64, sklearn's LogisticRegression(solver="lbfgs")) needs no handle: its objective is evaluated by the
  * stateless mudpt_probe_* kernels at the end of this file, and mudpt_amd/lpclip.py + mudpt_amd/lbfgs.py drive them.
  * The test pass's evaluator (Dassl's evaluation/evaluator.py Classification, the end of every script's trainer.test()) needs none either: the
@@ -229,6 +232,24 @@ int mudpt_forward(mudpt_model* m, const float* images_dev, int32_t batch, float*
  * an inference forward never does, so the logits of an image do not depend on the size of the test batch it arrives in. */
 #define MUDPT_FWD_TRAINING 2
 int mudpt_forward_ex(mudpt_model* m, const float* images_dev, int32_t batch, float* logits_dev, int32_t flags, void* stream);
+
+/* The test pass from cached image features (additions: MUDPT_ABI_VERSION stays).  trainers/zsclip.py:74-79 (ZeroshotCLIP / ZeroshotCLIP2),
+ * trainers/coop.py:212-223 (CoOp) and trainers/cocoop.py:178-188 (CoCoOp) all begin with the frozen, prompt-free clip_model.visual(image) and
+ * read nothing else of the image: per image that call is a constant, and lpclip/feat_extractor.py:125-137 names the file that holds it
+ * ({dir}/{dataset}/{split}.npz).  mudpt_forward_features is mudpt_forward_ex with that call replaced by its result: features_dev
+ * [batch, embed_dim] fp32, RAW (not normalised) -- what mudpt_encode_image and mudpt_image_features return -- is copied to where the
+ * vision tower leaves its output, and everything behind it runs through the same code: a frozen handle computes its text features if a
+ * weight or the tokens changed and runs the logits-only head (it needs no "visual.*" weight for this, nor does mudpt_text_features); CoOp runs the text tower, unless
+ * MUDPT_FWD_REUSE_TEXT, and the head; CoCoOp normalises, runs meta_net, the per-image prompts, the chunked text tower and the pair head.
+ * Logits of forwarded features equal the logits of the image forward they came from bit for bit, under any chunking of the batch.
+ * MUDPT_ERR_ARG, nothing launched and the handle as it was: MuDPT, VPT, MPT, UMuDPT, UUMuDPT (their trainable prompts run inside the vision
+ * tower, so their image features are no constant), a null pointer, batch outside 1..max_batch; MUDPT_ERR_STATE as mudpt_forward_ex. */
+int mudpt_forward_features(mudpt_model* m, const float* features_dev, int32_t batch, float* logits_dev, int32_t flags, void* stream);
+/* The raw visual(image) features [batch, embed_dim] of the last INFERENCE forward (mudpt_forward / _ex, mudpt_forward_features,
+ * mudpt_encode_image) of a frozen, CoOp or CoCoOp handle, device to device, asynchronous on `stream`: what lpclip/feat_extractor.py:125
+ * appends per batch, taken from a test pass that ran anyway.  MUDPT_ERR_STATE: no such forward since the handle was created or since a
+ * training step, or it had another batch size; MUDPT_ERR_ARG: the five variants mudpt_forward_features refuses, a null pointer. */
+int mudpt_image_features(mudpt_model* m, int32_t batch, float* features_dev, void* stream);
 
 /* One training step's forward + backward: loss_dev[0] = mean cross-entropy over the batch, gradients of
  * (grad_scale * loss) written to the bound gradient bucket.  logits_dev may be NULL.  grad_scale = 1/world

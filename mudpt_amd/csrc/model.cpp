@@ -169,6 +169,7 @@ struct mudpt_model {
     std::vector<std::string> missing;  // weight keys not yet set
     bool prompts_set = false;
     bool text_valid = false;  // txt_f holds the text features of the currently bound parameter values' last forward
+    int feat_B = 0;           // img_f holds the raw features of the last INFERENCE forward, of this many images (mudpt_image_features); 0: of none
 
     Tower vis, txt;
     // vision stem / head
@@ -1588,6 +1589,19 @@ static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_
     return tower_head_fwd(m, m->vis, vision_head(m), m->img_f, B, 0, s);
 }
 
+// What a forward is given for its image side: the images, for the vision tower, or -- mudpt_forward_features -- the raw [B, e] features that
+// tower would leave in m->img_f.  Everything behind m->img_f is one code path for both
+struct ImageSide {
+    const float *images = nullptr, *features = nullptr;
+    ImageSide(const float* images_) : images(images_) {}
+    static ImageSide cached(const float* features_) { ImageSide in(nullptr); in.features = features_; return in; }
+};
+static int image_side_forward(mudpt_model* m, const ImageSide& in, int B, hipStream_t s) {
+    if (!in.features) return vision_forward(m, in.images, B, s);
+    HIP_TRY(hipMemcpyAsync(m->img_f, in.features, (size_t)B * m->cfg.embed_dim * 4, hipMemcpyDeviceToDevice, s));
+    return MUDPT_OK;
+}
+
 // ---- CoCoOp (trainers/cocoop.py) ------------------------------------------------------------------------------------
 // text tower over the prompts of images [i0, i0 + nb): prompts (:148-165) + positional embedding (:52), 12 causal blocks, ln_final on
 // the EOT rows, text_projection -> rows i0 * C .. of m->txt_f
@@ -1612,11 +1626,11 @@ static HeadArgs cocoop_head_args(mudpt_model* m, int i0, int nb, int B) {
 
 // image features of the frozen vanilla ViT, normalised (:183), and meta_net: linear1 -> ReLU -> linear2 (:103-107, fp32) -> the
 // per-image context shift m->mn_bias [B, dt]
-static int cocoop_image_side(mudpt_model* m, const float* images, int B, hipStream_t s) {
+static int cocoop_image_side(mudpt_model* m, const ImageSide& in, int B, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     const int dt = c.t_width, e = c.embed_dim, hd = m->hid;
     float* Pm = m->params;
-    TRY(vision_forward(m, images, B, s));
+    TRY(image_side_forward(m, in, B, s));
     TRY(launch_l2norm(m->img_f, m->img_n, m->img_inv, B, e, s));
     TRY(launch_sgemm(false, true, B, hd, e, 1.f, m->img_n, e, Pm + m->off(Q_W1), e, 0.f, m->mn_hid, hd, Pm + m->off(Q_B1), s));
     TRY(launch_relu(m->mn_hid, (size_t)B * hd, s));
@@ -1626,8 +1640,8 @@ static int cocoop_image_side(mudpt_model* m, const float* images, int B, hipStre
 
 // forward (:178-198): image features -> meta_net bias per image (:141-146) -> the text tower over the (image, class) prompts, a chunk
 // of images per pass (the reference loops image by image, :187-194) -> logits [B, C].
-static int cocoop_forward(mudpt_model* m, const float* images, int B, hipStream_t s) {
-    TRY(cocoop_image_side(m, images, B, s));
+static int cocoop_forward(mudpt_model* m, const ImageSide& in, int B, hipStream_t s) {
+    TRY(cocoop_image_side(m, in, B, s));
     for (int i0 = 0; i0 < B; i0 += m->txt_chunk) {
         const int nb = B - i0 < m->txt_chunk ? B - i0 : m->txt_chunk;
         TRY(cocoop_text_chunk(m, i0, nb, s));
@@ -1769,7 +1783,7 @@ static Learner learner(const mudpt_model* m);
 // persistent GEMMs, memory-bound LayerNorms) instead of serialising behind them.  With reuse_text (inference with unchanged
 // parameters: the reference recomputes the text tower for every test batch, trainers/mudpt.py:170-184) the text
 // features of the previous call are kept.
-static int towers_forward(mudpt_model* m, const float* images, int B, hipStream_t s, bool reuse_text) {
+static int towers_forward(mudpt_model* m, const ImageSide& in, int B, hipStream_t s, bool reuse_text) {
     const Learner L = learner(m);
     if (L.fwd) TRY(L.fwd(m, s));
     if (!reuse_text) {
@@ -1780,7 +1794,7 @@ static int towers_forward(mudpt_model* m, const float* images, int B, hipStream_
         HIP_TRY(hipEventRecord(m->ev_join, m->s2));
         if (L.fwd_vision) TRY(L.fwd_vision(m, s));
     }
-    TRY(vision_forward(m, images, B, s));  // clip/model.py:526-553
+    TRY(image_side_forward(m, in, B, s));  // clip/model.py:526-553
     if (!reuse_text) HIP_TRY(hipStreamWaitEvent(s, m->ev_join, 0));
     return MUDPT_OK;
 }
@@ -1800,19 +1814,19 @@ static int head_forward(mudpt_model* m, int B, bool reuse_text, hipStream_t s) {
     return MUDPT_OK;
 }
 
-static int forward_impl(mudpt_model* m, const float* images, int B, hipStream_t s, bool reuse_text = false, bool skip_head = false) {
-    if (m->cocoop) return cocoop_forward(m, images, B, s);
-    TRY(towers_forward(m, images, B, s, reuse_text));
+static int forward_impl(mudpt_model* m, const ImageSide& in, int B, hipStream_t s, bool reuse_text = false, bool skip_head = false) {
+    if (m->cocoop) return cocoop_forward(m, in, B, s);
+    TRY(towers_forward(m, in, B, s, reuse_text));
     if (skip_head) return MUDPT_OK;  // the training step runs the fused forward + cross-entropy + backward head itself
     return head_forward(m, B, reuse_text, s);
 }
 
 // ---- frozen CLIP (trainers/zsclip.py) ------------------------------------------------------------------------------------
-static int frozen_ready(mudpt_model* m, const char* what, int B, bool need_text) {
+static int frozen_ready(mudpt_model* m, const char* what, int B, bool need_text, bool need_vision = true) {
     ARG_CHECK(m, "%s: null model", what);
     ARG_CHECK(m->frozen, "%s: not a frozen handle (mudpt_create_frozen)", what);
-    for (const std::string& k : m->missing)  // the image side needs the vision tower's weights only
-        if (need_text || k.rfind("visual.", 0) == 0) { set_error("%s: model not ready: %zu frozen weights unset (first needed: %s)", what, m->missing.size(), k.c_str()); return MUDPT_ERR_STATE; }
+    for (const std::string& k : m->missing)  // the image side needs the vision tower's weights only, a forward from cached features none of them
+        if (k.rfind("visual.", 0) == 0 ? need_vision : need_text) { set_error("%s: model not ready: %zu frozen weights unset (first needed: %s)", what, m->missing.size(), k.c_str()); return MUDPT_ERR_STATE; }
     if (need_text && !m->prompts_set) { set_error("%s: model not ready: call mudpt_set_text_tokens", what); return MUDPT_ERR_STATE; }
     ARG_CHECK(B > 0 && B <= m->cfg.max_batch, "%s: batch %d outside 1..max_batch=%d", what, B, m->cfg.max_batch);
     return MUDPT_OK;
@@ -1843,11 +1857,11 @@ static int frozen_text_features(mudpt_model* m, hipStream_t s) {
 
 // model_inference (zsclip.py:74-79): the vanilla vision tower, then the logits-only head against the kept table (the head never
 // re-normalises it: a.txt = null).  Inference: never a split K
-static int frozen_forward(mudpt_model* m, const float* images, int B, float* logits, hipStream_t s) {
+static int frozen_forward(mudpt_model* m, const ImageSide& in, int B, float* logits, hipStream_t s) {
     const mudpt_config& c = m->cfg;
     if (!m->text_valid) TRY(frozen_text_features(m, s));
     m->train_fwd = false;
-    TRY(vision_forward(m, images, B, s));
+    TRY(image_side_forward(m, in, B, s));
     HeadArgs h; h.img = m->img_f; h.scale = m->scale; h.logits = m->logits; h.img_n = m->img_n; h.txt_n = m->txt_n;
     h.img_inv = m->img_inv; h.txt_inv = m->txt_inv; h.B = B; h.C = c.n_cls; h.e = c.embed_dim;
     if (head_fused_fits(h, false)) {
@@ -1861,7 +1875,7 @@ static int frozen_forward(mudpt_model* m, const float* images, int B, float* log
 }
 
 extern "C" int mudpt_text_features(mudpt_model* m, float* feat, void* stream) {
-    TRY(frozen_ready(m, "text_features", 1, true));
+    TRY(frozen_ready(m, "text_features", 1, true, false));  // the text side alone: a handle that serves cached image features has no visual.* weights
     ARG_CHECK(feat, "text_features: null argument");
     hipStream_t s = (hipStream_t)stream;
     if (!m->text_valid) TRY(frozen_text_features(m, s));
@@ -1875,8 +1889,10 @@ extern "C" int mudpt_encode_image(mudpt_model* m, const float* images, int32_t B
     ARG_CHECK(images && features, "encode_image: null argument");
     hipStream_t s = (hipStream_t)stream;
     m->train_fwd = false;
+    m->feat_B = 0;
     TRY(vision_forward(m, images, B, s));
     HIP_TRY(hipMemcpyAsync(features, m->img_f, (size_t)B * m->cfg.embed_dim * 4, hipMemcpyDeviceToDevice, s));
+    m->feat_B = B;
     return MUDPT_OK;
 }
 
@@ -1889,22 +1905,64 @@ extern "C" int mudpt_forward(mudpt_model* m, const float* images, int32_t B, flo
     return mudpt_forward_ex(m, images, B, logits, 0, stream);
 }
 
-extern "C" int mudpt_forward_ex(mudpt_model* m, const float* images, int32_t B, float* logits, int32_t flags, void* stream) {
+static const char* variant_name(const mudpt_model* m) {
+    return m->frozen ? "frozen CLIP" : m->cocoop ? "CoCoOp" : m->coop ? "CoOp" : m->vpt ? "VPT" : m->mpt ? "MPT" : m->uumudpt ? "UUMuDPT" : m->umudpt ? "UMuDPT" : "MuDPT";
+}
+// The handles whose visual(image) is a constant of the image: the frozen, prompt-free tower of trainers/zsclip.py:74-79, coop.py:212-223 and
+// cocoop.py:178-188.  The other five splice trainable prompts into the vision tower (MPT: it may; its handle is refused whole)
+static int features_are_constant(const mudpt_model* m, const char* what) {
+    ARG_CHECK(m, "%s: null model", what);
+    ARG_CHECK(m->frozen || m->coop || m->cocoop, "%s: refused for %s: its trainable prompts run inside the vision tower, so its image features are no constant "
+              "of the image and cannot be cached; run mudpt_forward on the images", what, variant_name(m));
+    return MUDPT_OK;
+}
+
+// One inference forward (mudpt_forward_ex: what = "forward", from the images; mudpt_forward_features: from the features): every check, then
+// the launches.  A call that fails a check has launched nothing and changed nothing
+static int inference_forward(mudpt_model* m, const ImageSide& in, int32_t B, float* logits, int32_t flags, void* stream, const char* what) {
+    const bool cached = in.features != nullptr;
+    hipStream_t s = (hipStream_t)stream;
     if (m && m->frozen) {  // MUDPT_FWD_REUSE_TEXT changes nothing: the text features are kept anyway
-        TRY(frozen_ready(m, "forward", B, true));
-        ARG_CHECK(images && logits, "forward: null argument");
-        return frozen_forward(m, images, B, logits, (hipStream_t)stream);
+        TRY(frozen_ready(m, what, B, true, !cached));
+        ARG_CHECK((in.images || in.features) && logits, "%s: null argument", what);
+        m->feat_B = 0;
+        TRY(frozen_forward(m, in, B, logits, s));
+        m->feat_B = B;
+        return MUDPT_OK;
     }
     TRY(ready(m, B, false));
-    TRY(not_sharded(m, "forward"));
-    ARG_CHECK(images && logits, "forward: null argument");
-    hipStream_t s = (hipStream_t)stream;
+    TRY(not_sharded(m, what));
+    ARG_CHECK((in.images || in.features) && logits, "%s: null argument", what);
     // CoCoOp's text features depend on the image; VPT's on nothing trainable: once computed they stay (until mudpt_set_weight / _set_class_prompts)
     const bool reuse = ((flags & MUDPT_FWD_REUSE_TEXT) != 0 || (m->vpt && m->text_valid)) && !m->cocoop;
-    if (reuse && !m->text_valid) { set_error("forward: MUDPT_FWD_REUSE_TEXT before any text-tower pass"); return MUDPT_ERR_STATE; }
+    if (reuse && !m->text_valid) { set_error("%s: MUDPT_FWD_REUSE_TEXT before any text-tower pass", what); return MUDPT_ERR_STATE; }
     m->train_fwd = false;
-    TRY(forward_impl(m, images, B, s, reuse));
+    m->feat_B = 0;
+    TRY(forward_impl(m, in, B, s, reuse));
     HIP_TRY(hipMemcpyAsync(logits, m->logits, (size_t)B * m->cfg.n_cls * 4, hipMemcpyDeviceToDevice, s));
+    m->feat_B = B;
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_forward_ex(mudpt_model* m, const float* images, int32_t B, float* logits, int32_t flags, void* stream) {
+    return inference_forward(m, ImageSide(images), B, logits, flags, stream, "forward");
+}
+
+// model_inference behind clip_model.visual(image) (trainers/zsclip.py:76-79, coop.py:214-223, cocoop.py:182-198): the forward above from the
+// features lpclip/feat_extractor.py:125 saves
+extern "C" int mudpt_forward_features(mudpt_model* m, const float* features, int32_t B, float* logits, int32_t flags, void* stream) {
+    TRY(features_are_constant(m, "forward_features"));
+    ARG_CHECK(features, "forward_features: null argument");
+    return inference_forward(m, ImageSide::cached(features), B, logits, flags, stream, "forward_features");
+}
+
+// lpclip/feat_extractor.py:125: visual(image) of the batch the last inference forward ran on
+extern "C" int mudpt_image_features(mudpt_model* m, int32_t B, float* features, void* stream) {
+    TRY(features_are_constant(m, "image_features"));
+    ARG_CHECK(features, "image_features: null argument");
+    if (m->feat_B == 0) { set_error("image_features: no inference forward since the handle was created or since its last training step"); return MUDPT_ERR_STATE; }
+    if (m->feat_B != B) { set_error("image_features: the last inference forward ran on %d images, not %d", m->feat_B, B); return MUDPT_ERR_STATE; }
+    HIP_TRY(hipMemcpyAsync(features, m->img_f, (size_t)B * m->cfg.embed_dim * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MUDPT_OK;
 }
 
@@ -2100,6 +2158,7 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
     ARG_CHECK(images && labels && loss, "forward_backward: null argument");
     hipStream_t s = (hipStream_t)stream;
     m->train_fwd = true;
+    m->feat_B = 0;  // a training forward may split K: its features are not the ones a test pass caches
     if (m->cocoop) return cocoop_forward_backward(m, images, labels, B, grad_scale, loss, logits, s);
     TRY(not_sharded(m, "forward_backward"));
     const Learner L = learner(m);

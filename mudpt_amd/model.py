@@ -110,6 +110,21 @@ def uumudpt_init_tensors(n_ctx: int, depth: int, d_t: int, d_v: int, embed_dim: 
     return out
 
 
+def check_features(feat: torch.Tensor, embed_dim: int, max_batch: int):
+    """The library is told only B: features of another width would make the copy read out of bounds."""
+    assert feat.dim() == 2 and feat.shape[1] == embed_dim, f"features must be [B, {embed_dim}], got {tuple(feat.shape)}"
+    assert 0 < feat.shape[0] <= max_batch, f"batch {feat.shape[0]} outside 1..max_batch={max_batch}"
+
+
+def read_image_features(model, batch: Optional[int] = None) -> torch.Tensor:
+    """``mudpt_image_features`` of a CustomCLIP / FrozenCLIP: the raw features [B, embed_dim] of its last inference forward; B as the model's
+    last forward had it unless ``batch`` says which one the caller expects (bad state if the library's last one had another)."""
+    batch = int(getattr(model, "_last_batch", 0) if batch is None else batch)
+    feat = torch.empty(max(batch, 1), model.shape.embed_dim, dtype=torch.float32, device=model.device)
+    capi.check(model.lib.mudpt_image_features(model._h, batch, capi.ptr(feat), model._stream()), "image_features")  # batch 0: the library's "no forward yet"
+    return feat[:batch]
+
+
 class _Holder(nn.Module):
     """Namespace module so parameters get the reference's dotted state-dict keys."""
 
@@ -223,6 +238,7 @@ class CustomCLIP(nn.Module):
             self._cp_feat, self._cp_dfeat = (capi.device_view(q.value, n.value, self.device).view(self.n_cls, shape.embed_dim) for q in (f, df))
         self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._text_version = None  # flat_params._version the library's cached text features belong to
+        self._last_batch = 0       # images of the last eval forward, whose raw features the library still holds (image_features)
         self.loss_scale = 128.0    # the library's default (mudpt_set_loss_scale)
 
     # -- initialisation of the trainables, trainers/mudpt.py:57-81 and clip/model.py:512-519 ---------------------
@@ -306,16 +322,37 @@ class CustomCLIP(nn.Module):
         self._text_version = None
         return super().load_state_dict(*args, **kwargs)
 
+    def _text_reuse(self):
+        """(reuse, version) of an eval forward: the text features only depend on the parameters, so they are recomputed only when the flat
+        bucket's version counter moved (the reference re-runs the text tower for every test batch).  CoCoOp's depend on the image; VPT's on
+        no trainable: the library keeps them itself (until a frozen weight changes)."""
+        version = self.flat_params._version
+        return (not self.training) and self._text_version == version and self.variant not in ("cocoop", "vpt"), version
+
+    def forward_features(self, feat: torch.Tensor) -> torch.Tensor:
+        """``forward`` behind ``clip_model.visual(image)`` (trainers/coop.py:214-223, cocoop.py:182-198), for the CoOp and CoCoOp variants:
+        logits [B, n_cls] of the raw image features ``feat`` [B, embed_dim] -- what ``image_features()`` returns after a ``forward`` and what
+        lpclip/feat_extractor.py:125-137 saves.  Bit for bit the logits of the image forward the features came from.  Any other variant:
+        AssertionError (its trainable prompts run inside the vision tower)."""
+        check_features(feat, self.shape.embed_dim, self.max_batch)
+        feat = feat.to(self.device, torch.float32).contiguous()
+        B = feat.shape[0]
+        logits = torch.empty(B, self.n_cls, dtype=torch.float32, device=self.device)
+        reuse, version = self._text_reuse()
+        capi.check(self.lib.mudpt_forward_features(self._h, capi.ptr(feat), B, capi.ptr(logits), 1 if reuse else 0, self._stream()), "forward_features")
+        self._text_version, self._last_batch = version, B
+        return logits
+
+    def image_features(self) -> torch.Tensor:
+        """The raw ``clip_model.visual(image)`` features [B, embed_dim] of the last eval ``forward`` / ``forward_features`` (CoOp, CoCoOp)."""
+        return read_image_features(self)
+
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         self._check_images(image)
         image = image.to(self.device, torch.float32).contiguous()
         B = image.shape[0]
         logits = torch.empty(B, self.n_cls, dtype=torch.float32, device=self.device)
-        # eval mode: the text features only depend on the parameters; recompute them only when the flat bucket's version
-        # counter moved (the reference re-runs the text tower for every test batch)
-        version = self.flat_params._version
-        # CoCoOp's text features depend on the image; VPT's on no trainable: the library keeps them itself (until a frozen weight changes)
-        reuse = (not self.training) and self._text_version == version and self.variant not in ("cocoop", "vpt")
+        reuse, version = self._text_reuse()
         if self.class_shard is not None:
             capi.check(self.lib.mudpt_cp_forward(self._h, capi.ptr(image), B, 1 if reuse else 0, self._stream()), "cp_forward")
             if not reuse:
@@ -323,7 +360,7 @@ class CustomCLIP(nn.Module):
             capi.check(self.lib.mudpt_cp_head(self._h, None, B, 1.0, None, capi.ptr(logits), 1 if reuse else 0, self._stream()), "cp_head")
         else:
             capi.check(self.lib.mudpt_forward_ex(self._h, capi.ptr(image), B, capi.ptr(logits), 1 if reuse else 0, self._stream()), "forward")
-        self._text_version = version
+        self._text_version, self._last_batch = version, B
         return logits
 
     def _exchange(self, table: torch.Tensor, async_op: bool = False):
@@ -354,7 +391,7 @@ class CustomCLIP(nn.Module):
         if work is not None:
             work.wait()  # the current stream waits for the collective; the host does not
         capi.check(self.lib.mudpt_cp_backward(self._h, capi.CP_TEXT, self._stream()), "cp_backward(text)")
-        self._text_version = self.flat_params._version
+        self._text_version, self._last_batch = self.flat_params._version, 0
         return (self._loss[0], logits) if return_logits else self._loss[0]
 
     # -- trainers/mudpt.py:249-251 minus the optimizer step: loss (device scalar) + .grad of the 10 tensors ---------------
@@ -370,7 +407,7 @@ class CustomCLIP(nn.Module):
         logits = torch.empty(B, self.n_cls, dtype=torch.float32, device=self.device) if return_logits else None
         capi.check(self.lib.mudpt_forward_backward(self._h, capi.ptr(image), capi.ptr(label), B, grad_scale,
                                                    capi.ptr(self._loss), capi.ptr(logits), self._stream()), "forward_backward")
-        self._text_version = self.flat_params._version  # the step's forward left this version's text features in the library
+        self._text_version, self._last_batch = self.flat_params._version, 0  # the step's forward left this version's text features in the library
         return (self._loss[0], logits) if return_logits else self._loss[0]
 
     def set_loss_scale(self, scale: float):

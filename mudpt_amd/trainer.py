@@ -409,8 +409,10 @@ class PromptTrainer(TrainerX):
         self._local = local
 
     def test(self, split=None):
+        from . import featcache
         install_test_loader(self, self._local)  # the opt-in may be taken after construction (trainer.device_test_store)
-        return super().test(split=split)
+        # MUDPT_TEST_FEATURES=<dir> / trainer.test_features: CoOp and CoCoOp may run from cached image features; without it, the pass as it was
+        return featcache.run_test(self, split, super().test)
 
     def forward_backward(self, batch):
         return data_parallel_step(self, batch, with_acc=self.WITH_ACC)

@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from . import capi, synth
-from .model import ModelShape
+from .model import ModelShape, check_features, read_image_features
 from .trainer import TRAINER_REGISTRY, TrainerX, install_test_loader, load_clip_state_dict, precision_to_dtype, tokenize_prompts, warn_if_fp16_misses_the_bound
 
 # trainers/zsclip.py:32-48: the per-dataset prompt, keyed by cfg.DATASET.NAME
@@ -131,7 +131,23 @@ class FrozenCLIP(nn.Module):
         image = image.to(self.device, torch.float32).contiguous()
         logits = torch.empty(image.shape[0], self.n_cls, dtype=torch.float32, device=self.device)
         capi.check(self.lib.mudpt_forward(self._h, capi.ptr(image), image.shape[0], capi.ptr(logits), self._stream()), "forward")
+        self._last_batch = image.shape[0]
         return logits
+
+    def forward_features(self, feat: torch.Tensor) -> torch.Tensor:
+        """model_inference behind ``clip_model.visual(image)`` (zsclip.py:76-79): logits [B, n_cls] of the raw image features ``feat``
+        [B, embed_dim] -- ``encode_image`` / ``image_features()`` here, the rows lpclip/feat_extractor.py:125-137 saves.  Bit for bit the logits
+        of the image forward the features came from; needs no ``visual.*`` weight."""
+        check_features(feat, self.shape.embed_dim, self.max_batch)
+        feat = feat.to(self.device, torch.float32).contiguous()
+        logits = torch.empty(feat.shape[0], self.n_cls, dtype=torch.float32, device=self.device)
+        capi.check(self.lib.mudpt_forward_features(self._h, capi.ptr(feat), feat.shape[0], capi.ptr(logits), 0, self._stream()), "forward_features")
+        self._last_batch = feat.shape[0]
+        return logits
+
+    def image_features(self) -> torch.Tensor:
+        """The raw ``clip_model.visual(image)`` features [B, embed_dim] of the last ``forward`` / ``forward_features`` / ``encode_image``."""
+        return read_image_features(self)
 
     def encode_image(self, image: torch.Tensor) -> torch.Tensor:
         """clip/model.py:822: the raw (un-normalised) image features [B, embed_dim]."""
@@ -139,6 +155,7 @@ class FrozenCLIP(nn.Module):
         image = image.to(self.device, torch.float32).contiguous()
         feat = torch.empty(image.shape[0], self.shape.embed_dim, dtype=torch.float32, device=self.device)
         capi.check(self.lib.mudpt_encode_image(self._h, capi.ptr(image), image.shape[0], capi.ptr(feat), self._stream()), "encode_image")
+        self._last_batch = image.shape[0]
         return feat
 
     def text_features(self) -> torch.Tensor:
@@ -207,8 +224,9 @@ class ZeroshotCLIP(TrainerX):
         return self.model(image)
 
     def test(self, split=None):
+        from . import featcache
         install_test_loader(self, self.model.device.index or 0)  # the opt-in device-resident test pass (MUDPT_DEVICE_TEST=1 / device_test_store)
-        return super().test(split=split)
+        return featcache.run_test(self, split, super().test)  # MUDPT_TEST_FEATURES=<dir> / trainer.test_features: from cached image features
 
 
 @TRAINER_REGISTRY.register()
