@@ -84,19 +84,8 @@ class FeatureStore:
         return cls(features, labels, name=name, width=model.shape.embed_dim)
 
     def save(self, output_dir, dataset_name, split) -> str:
-        """``lpclip.save_features``' file, complete or absent: written under a temporary name in the same directory, then renamed."""
-        save_dir = os.path.join(output_dir, dataset_name)
-        os.makedirs(save_dir, exist_ok=True)
-        path = os.path.join(save_dir, f"{split}.npz")
-        tmp = os.path.join(save_dir, f".{split}.npz.{os.getpid()}.tmp")
-        try:
-            with open(tmp, "wb") as f:
-                np.savez(f, feature_list=np.asarray(self.features.cpu(), dtype=np.float32), label_list=np.asarray(self.labels.cpu(), dtype=np.int64))
-            os.replace(tmp, path)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        return path
+        """``lpclip.save_features``' file of this store."""
+        return lpclip.save_features(output_dir, dataset_name, split, self.features, self.labels)
 
 
 class FeatureLoader:

@@ -44,12 +44,20 @@ def extract_features(model, loader, on_device=False):
 
 
 def save_features(output_dir, dataset_name, split, features, labels) -> str:
-    """feat_extractor.py:130-137: ``{output_dir}/{dataset_name}/{split}.npz`` with the keys ``feature_list`` and ``label_list``."""
+    """feat_extractor.py:130-137: ``{output_dir}/{dataset_name}/{split}.npz`` with the keys ``feature_list`` (float32) and ``label_list``
+    (int64).  The file is complete or absent: written under a temporary name in the same directory, then renamed."""
     save_dir = os.path.join(output_dir, dataset_name)
     os.makedirs(save_dir, exist_ok=True)
     path = os.path.join(save_dir, f"{split}.npz")
-    np.savez(path, feature_list=np.asarray(torch.as_tensor(features).cpu(), dtype=np.float32),
-             label_list=np.asarray(torch.as_tensor(labels).cpu(), dtype=np.int64))
+    tmp = os.path.join(save_dir, f".{split}.npz.{os.getpid()}.tmp")
+    try:
+        with open(tmp, "wb") as f:
+            np.savez(f, feature_list=np.asarray(torch.as_tensor(features).cpu(), dtype=np.float32),
+                     label_list=np.asarray(torch.as_tensor(labels).cpu(), dtype=np.int64))
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
     return path
 
 

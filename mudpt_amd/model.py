@@ -110,31 +110,25 @@ def uumudpt_init_tensors(n_ctx: int, depth: int, d_t: int, d_v: int, embed_dim: 
     return out
 
 
-def check_features(feat: torch.Tensor, embed_dim: int, max_batch: int):
-    """The library is told only B: features of another width would make the copy read out of bounds."""
-    assert feat.dim() == 2 and feat.shape[1] == embed_dim, f"features must be [B, {embed_dim}], got {tuple(feat.shape)}"
-    assert 0 < feat.shape[0] <= max_batch, f"batch {feat.shape[0]} outside 1..max_batch={max_batch}"
+DTYPES = {"bf16": capi.BF16, "fp16": capi.F16, "fp32": capi.F32}  # F32: the parity mode
+VARIANTS = {"mudpt": capi.VARIANT_MUDPT, "cocoop": capi.VARIANT_COCOOP, "coop": capi.VARIANT_COOP, "coop_csc": capi.VARIANT_COOP_CSC,
+            "vpt": capi.VARIANT_VPT, "mpt": capi.VARIANT_MPT, "umudpt": capi.VARIANT_UMUDPT, "uumudpt": capi.VARIANT_UUMUDPT}
 
 
-def read_image_features(model, batch: Optional[int] = None) -> torch.Tensor:
-    """``mudpt_image_features`` of a CustomCLIP / FrozenCLIP: the raw features [B, embed_dim] of its last inference forward; B as the model's
-    last forward had it unless ``batch`` says which one the caller expects (bad state if the library's last one had another)."""
-    batch = int(getattr(model, "_last_batch", 0) if batch is None else batch)
-    feat = torch.empty(max(batch, 1), model.shape.embed_dim, dtype=torch.float32, device=model.device)
-    capi.check(model.lib.mudpt_image_features(model._h, batch, capi.ptr(feat), model._stream()), "image_features")  # batch 0: the library's "no forward yet"
-    return feat[:batch]
+def library_config(shape: ModelShape, n_cls: int, max_batch: int, dtype: str, variant: str = "mudpt", frozen: bool = False) -> capi.Config:
+    """The ``mudpt_config`` of a handle.  ``frozen``: a ``mudpt_create_frozen`` handle has no prompts and no variant (n_ctx 0, depth 1,
+    variant 0).  An unknown ``dtype`` or ``variant`` name is a KeyError."""
+    n_ctx, depth, code = (0, 1, 0) if frozen else (shape.n_ctx, shape.depth, VARIANTS[variant])
+    return capi.Config(shape.image_size, shape.patch, shape.v_width, shape.v_layers, shape.v_heads, shape.t_width, shape.t_layers,
+                       shape.t_heads, shape.ctx_len, shape.embed_dim, n_ctx, depth, int(n_cls), int(max_batch), DTYPES[dtype], code)
 
 
-class _Holder(nn.Module):
-    """Namespace module so parameters get the reference's dotted state-dict keys."""
+class LibraryModel(nn.Module):
+    """An ``nn.Module`` that owns one ``mudpt_model*``: everything about the handle that does not depend on what it computes.  ``create(lib,
+    cfg, h)`` is the subclass's create call (``mudpt_create`` / ``mudpt_create_ex`` / ``mudpt_create_frozen``) on byref(config) and
+    byref(handle); ``config`` are ``library_config``'s keywords.  The knobs are applied right behind it, before any weight or token."""
 
-
-class CustomCLIP(nn.Module):
-    def __init__(self, shape: ModelShape, clip_state: Dict[str, torch.Tensor], tokenized_prompts: torch.Tensor,
-                 ctx_token_ids: Optional[Sequence[int]] = None, max_batch: int = 256, dtype: str = "bf16",
-                 device: str = "cuda:0", seed: Optional[int] = None, variant: str = "mudpt", knobs: Optional[Dict[str, int]] = None,
-                 class_shard: Optional[Sequence[int]] = None, group=None, class_token_position: str = "end",
-                 name_lens: Optional[Sequence[int]] = None, prompt_shape: Optional[Sequence[int]] = None):
+    def __init__(self, shape: ModelShape, n_cls: int, max_batch: int, dtype: str, device: str, knobs: Optional[Dict[str, int]], create, **config):
         super().__init__()
         if not torch.cuda.is_available():
             raise capi.MudptError("mudpt_amd needs an MI355X (HIP device); there is no CPU path in the product")
@@ -142,9 +136,101 @@ class CustomCLIP(nn.Module):
         self.shape = shape
         self.device = torch.device(device)
         self.dtype_name = dtype
-        self.n_cls = int(tokenized_prompts.shape[0])
+        self.n_cls = int(n_cls)
         self.max_batch = int(max_batch)
-        self.tokenized_prompts = tokenized_prompts.clone()
+        cfg = library_config(shape, self.n_cls, self.max_batch, dtype, **config)
+        torch.cuda.set_device(self.device)
+        h = C.c_void_p()
+        create(self.lib, C.byref(cfg), C.byref(h))
+        self._h = h
+        self._last_batch = 0  # images of the last inference forward, whose raw features the library still holds (image_features)
+        for name, value in (knobs or {}).items():  # per-handle tuning knobs (mudpt_model_set): A/B runs and tests
+            self.set_knob(name, value)
+
+    def set_weight(self, key: str, value: torch.Tensor):
+        """One frozen weight, by OpenAI CLIP key (clip/model.py:919 load_state_dict)."""
+        t = value.detach().to("cpu", torch.float32).contiguous()
+        capi.check(self.lib.mudpt_set_weight(self._h, key.encode(), capi.ptr(t), t.numel()), f"set_weight({key})")
+
+    def set_knob(self, name: str, value: int):
+        """``mudpt_model_set``: "gemm_variant", "lp_grad" and the split-operand knobs ("vis_lo", "txt_lo", "vis_sites", "txt_sites",
+        "vis_exact_attn", "txt_exact_attn": include/mudpt.h MUDPT_F32, DESIGN.md 2) any time; "txt_trim" / "txt_buckets" only through
+        ``knobs=`` at construction (before the class prompts or tokens are ingested)."""
+        capi.check(self.lib.mudpt_model_set(self._h, name.encode(), int(value)), f"model_set({name})")
+
+    def text_layout(self):
+        """(token rows, length buckets, longest kept length) of one text-tower pass (``mudpt_text_layout``); a frozen handle: the rows summed
+        over its templates, the largest bucket count of a template."""
+        r, b, l = C.c_int32(), C.c_int32(), C.c_int32()
+        capi.check(self.lib.mudpt_text_layout(self._h, C.byref(r), C.byref(b), C.byref(l)), "text_layout")
+        return r.value, b.value, l.value
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check_images(self, image: torch.Tensor):
+        S = self.shape.image_size
+        # the library is told only B: a wrong-sized batch would make the patch gather read out of bounds (trainers/mudpt.py:55 asserts
+        # the configured size; this asserts the data)
+        assert image.dim() == 4 and tuple(image.shape[1:]) == (3, S, S), f"images must be [B, 3, {S}, {S}], got {tuple(image.shape)}"
+        assert 0 < image.shape[0] <= self.max_batch, f"batch {image.shape[0]} outside 1..max_batch={self.max_batch}"
+
+    def _check_features(self, feat: torch.Tensor):
+        """The library is told only B: features of another width would make the copy read out of bounds."""
+        E = self.shape.embed_dim
+        assert feat.dim() == 2 and feat.shape[1] == E, f"features must be [B, {E}], got {tuple(feat.shape)}"
+        assert 0 < feat.shape[0] <= self.max_batch, f"batch {feat.shape[0]} outside 1..max_batch={self.max_batch}"
+
+    def _infer(self, x: torch.Tensor, width: int, call) -> torch.Tensor:
+        """One inference call on a checked batch ``x``: moved to the device as fp32, ``call(x, B, out, stream)`` on the pointers, fp32
+        [B, width] back.  The library then holds the raw image features of these B rows."""
+        x = x.to(self.device, torch.float32).contiguous()
+        B = x.shape[0]
+        out = torch.empty(B, width, dtype=torch.float32, device=self.device)
+        call(capi.ptr(x), B, capi.ptr(out), self._stream())
+        self._last_batch = B
+        return out
+
+    def image_features(self) -> torch.Tensor:
+        """``mudpt_image_features``: the raw ``clip_model.visual(image)`` features [B, embed_dim] of the last inference forward (``forward``,
+        ``forward_features``, ``encode_image``), B as that forward had it.  Before any, B = 0 and the library answers with its bad state."""
+        B = self._last_batch
+        feat = torch.empty(max(B, 1), self.shape.embed_dim, dtype=torch.float32, device=self.device)
+        capi.check(self.lib.mudpt_image_features(self._h, B, capi.ptr(feat), self._stream()), "image_features")
+        return feat[:B]
+
+    def debug_read(self, name: str, batch: int = 1) -> torch.Tensor:
+        """Flat fp32 host copy of an internal activation of the last call, "image_features", "text_features" or "text_launches" (test
+        hook, see include/mudpt.h)."""
+        n = C.c_size_t()
+        capi.check(self.lib.mudpt_debug_read(self._h, name.encode(), batch, None, 0, C.byref(n)), "debug_read")
+        out = torch.empty(n.value, dtype=torch.float32)
+        capi.check(self.lib.mudpt_debug_read(self._h, name.encode(), batch, capi.ptr(out), n.value, C.byref(n)), "debug_read")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            torch.cuda.synchronize(self.device)
+            self.lib.mudpt_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Holder(nn.Module):
+    """Namespace module so parameters get the reference's dotted state-dict keys."""
+
+
+class CustomCLIP(LibraryModel):
+    def __init__(self, shape: ModelShape, clip_state: Dict[str, torch.Tensor], tokenized_prompts: torch.Tensor,
+                 ctx_token_ids: Optional[Sequence[int]] = None, max_batch: int = 256, dtype: str = "bf16",
+                 device: str = "cuda:0", seed: Optional[int] = None, variant: str = "mudpt", knobs: Optional[Dict[str, int]] = None,
+                 class_shard: Optional[Sequence[int]] = None, group=None, class_token_position: str = "end",
+                 name_lens: Optional[Sequence[int]] = None, prompt_shape: Optional[Sequence[int]] = None):
         # "cocoop": the same library runs trainers/cocoop.py's CustomCLIP (vanilla vision tower, meta_net, one text-tower pass
         # per (image, class) pair); the module then owns ctx + meta_net under the reference's names (prompt_learner.*)
         # "coop" / "coop_csc": trainers/coop.py's CustomCLIP (vanilla vision tower, forward only; one trainable, prompt_learner.ctx, shared
@@ -162,31 +248,22 @@ class CustomCLIP(nn.Module):
         # "image_encoder.visual_ctx*"; shape.n_ctx (1..16) / depth are TRAINER.UUMUDPT.N_CTX / DEEP_PROMPT_DEPTH
         if variant == "coop_csc" and ctx_token_ids is not None:
             variant = "coop"  # trainers/coop.py:52-61: the CTX_INIT path builds one shared context whatever CSC says
-        self.variant = variant
-        cfg = capi.Config(shape.image_size, shape.patch, shape.v_width, shape.v_layers, shape.v_heads, shape.t_width,
-                          shape.t_layers, shape.t_heads, shape.ctx_len, shape.embed_dim, shape.n_ctx, shape.depth,
-                          self.n_cls, self.max_batch, {"bf16": capi.BF16, "fp16": capi.F16, "fp32": capi.F32}[dtype],
-                          {"mudpt": capi.VARIANT_MUDPT, "cocoop": capi.VARIANT_COCOOP, "coop": capi.VARIANT_COOP,
-                           "coop_csc": capi.VARIANT_COOP_CSC, "vpt": capi.VARIANT_VPT, "mpt": capi.VARIANT_MPT,
-                           "umudpt": capi.VARIANT_UMUDPT, "uumudpt": capi.VARIANT_UUMUDPT}[variant])
         assert (prompt_shape is not None) == (variant in ("vpt", "mpt")), "prompt_shape is the VPT / MPT setting, and they need it"
-        self.prompt_shape = None if prompt_shape is None else tuple(int(v) for v in prompt_shape)
-        torch.cuda.set_device(self.device)
-        h = C.c_void_p()
-        if self.prompt_shape is not None:
-            ps = capi.PromptShape(*self.prompt_shape)
-            capi.check(self.lib.mudpt_create_ex(C.byref(cfg), C.byref(ps), C.byref(h)), "create_ex")
-        else:
-            capi.check(self.lib.mudpt_create(C.byref(cfg), C.byref(h)), "create")
-        self._h = h
-        for name, value in (knobs or {}).items():  # per-handle tuning knobs (mudpt_model_set): A/B runs and tests
-            self.set_knob(name, value)
-        # frozen weights, by OpenAI CLIP key (clip/model.py:919 load_state_dict)
-        for k, v in clip_state.items():
-            if k == "token_embedding.weight" or not isinstance(v, torch.Tensor):
-                continue
-            t = v.detach().to("cpu", torch.float32).contiguous()
-            capi.check(self.lib.mudpt_set_weight(h, k.encode(), capi.ptr(t), t.numel()), f"set_weight({k})")
+        prompt_shape = None if prompt_shape is None else tuple(int(v) for v in prompt_shape)
+
+        def create(lib, cfg, h):
+            if prompt_shape is not None:
+                capi.check(lib.mudpt_create_ex(cfg, C.byref(capi.PromptShape(*prompt_shape)), h), "create_ex")
+            else:
+                capi.check(lib.mudpt_create(cfg, h), "create")
+
+        super().__init__(shape, tokenized_prompts.shape[0], max_batch, dtype, device, knobs, create, variant=variant)
+        self.tokenized_prompts = tokenized_prompts.clone()
+        self.variant, self.prompt_shape = variant, prompt_shape
+        h = self._h
+        for k, v in clip_state.items():  # the frozen weights; of the token embedding only the class prompts' rows go up (below)
+            if k != "token_embedding.weight" and isinstance(v, torch.Tensor):
+                self.set_weight(k, v)
         # class-parallel text tower (include/mudpt.h): this rank encodes classes [c0, c1) of the n_cls; ``group`` is the process group
         # of the two exchanges (None = the default group)
         self.class_shard, self.group = None, group
@@ -238,7 +315,6 @@ class CustomCLIP(nn.Module):
             self._cp_feat, self._cp_dfeat = (capi.device_view(q.value, n.value, self.device).view(self.n_cls, shape.embed_dim) for q in (f, df))
         self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._text_version = None  # flat_params._version the library's cached text features belong to
-        self._last_batch = 0       # images of the last eval forward, whose raw features the library still holds (image_features)
         self.loss_scale = 128.0    # the library's default (mudpt_set_loss_scale)
 
     # -- initialisation of the trainables, trainers/mudpt.py:57-81 and clip/model.py:512-519 ---------------------
@@ -280,18 +356,6 @@ class CustomCLIP(nn.Module):
         return {"mudpt": "mudpt_prompt_learner.ctx", "mpt": "text_prompt_learner.visual_ctx",
                 "umudpt": "umudpt_prompt_learner.ctx", "uumudpt": "uumudpt_prompt_learner.ctx"}.get(self.variant, "prompt_learner.ctx")
 
-    def set_knob(self, name: str, value: int):
-        """``mudpt_model_set``: "gemm_variant", "lp_grad" and the split-operand knobs ("vis_lo", "txt_lo", "vis_sites", "txt_sites",
-        "vis_exact_attn", "txt_exact_attn": include/mudpt.h MUDPT_F32, DESIGN.md 2) any time; "txt_trim" / "txt_buckets" only through
-        ``knobs=`` at construction (before the class prompts are ingested)."""
-        capi.check(self.lib.mudpt_model_set(self._h, name.encode(), int(value)), f"model_set({name})")
-
-    def text_layout(self):
-        """(token rows, length buckets, longest kept length) of one text-tower pass (``mudpt_text_layout``)."""
-        r, b, l = C.c_int32(), C.c_int32(), C.c_int32()
-        capi.check(self.lib.mudpt_text_layout(self._h, C.byref(r), C.byref(b), C.byref(l)), "text_layout")
-        return r.value, b.value, l.value
-
     def set_params(self, tensors: Dict[str, torch.Tensor]):
         self._text_version = None
         with torch.no_grad():
@@ -301,17 +365,6 @@ class CustomCLIP(nn.Module):
 
     def grads(self) -> Dict[str, torch.Tensor]:
         return {k: p.grad for k, p in self.named_parameters()}
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    # -- trainers/mudpt.py:170-184 ---------------------------------------------------------------------------------
-    def _check_images(self, image: torch.Tensor):
-        S = self.shape.image_size
-        # the library is told only B: a wrong-sized batch would make the patch gather read out of bounds (trainers/mudpt.py:55 asserts
-        # the configured size; this asserts the data)
-        assert image.dim() == 4 and tuple(image.shape[1:]) == (3, S, S), f"images must be [B, 3, {S}, {S}], got {tuple(image.shape)}"
-        assert 0 < image.shape[0] <= self.max_batch, f"batch {image.shape[0]} outside 1..max_batch={self.max_batch}"
 
     def invalidate_text_cache(self):
         """Parameters changed behind the bucket's version counter (``p.data`` writes, optimizers, the library's SGD): the next eval
@@ -334,33 +387,29 @@ class CustomCLIP(nn.Module):
         logits [B, n_cls] of the raw image features ``feat`` [B, embed_dim] -- what ``image_features()`` returns after a ``forward`` and what
         lpclip/feat_extractor.py:125-137 saves.  Bit for bit the logits of the image forward the features came from.  Any other variant:
         AssertionError (its trainable prompts run inside the vision tower)."""
-        check_features(feat, self.shape.embed_dim, self.max_batch)
-        feat = feat.to(self.device, torch.float32).contiguous()
-        B = feat.shape[0]
-        logits = torch.empty(B, self.n_cls, dtype=torch.float32, device=self.device)
+        self._check_features(feat)
         reuse, version = self._text_reuse()
-        capi.check(self.lib.mudpt_forward_features(self._h, capi.ptr(feat), B, capi.ptr(logits), 1 if reuse else 0, self._stream()), "forward_features")
-        self._text_version, self._last_batch = version, B
+        logits = self._infer(feat, self.n_cls, lambda x, B, out, stream: capi.check(
+            self.lib.mudpt_forward_features(self._h, x, B, out, 1 if reuse else 0, stream), "forward_features"))
+        self._text_version = version
         return logits
 
-    def image_features(self) -> torch.Tensor:
-        """The raw ``clip_model.visual(image)`` features [B, embed_dim] of the last eval ``forward`` / ``forward_features`` (CoOp, CoCoOp)."""
-        return read_image_features(self)
-
+    # -- trainers/mudpt.py:170-184 ---------------------------------------------------------------------------------
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         self._check_images(image)
-        image = image.to(self.device, torch.float32).contiguous()
-        B = image.shape[0]
-        logits = torch.empty(B, self.n_cls, dtype=torch.float32, device=self.device)
         reuse, version = self._text_reuse()
-        if self.class_shard is not None:
-            capi.check(self.lib.mudpt_cp_forward(self._h, capi.ptr(image), B, 1 if reuse else 0, self._stream()), "cp_forward")
-            if not reuse:
-                self._exchange(self._cp_feat)
-            capi.check(self.lib.mudpt_cp_head(self._h, None, B, 1.0, None, capi.ptr(logits), 1 if reuse else 0, self._stream()), "cp_head")
-        else:
-            capi.check(self.lib.mudpt_forward_ex(self._h, capi.ptr(image), B, capi.ptr(logits), 1 if reuse else 0, self._stream()), "forward")
-        self._text_version, self._last_batch = version, B
+
+        def call(x, B, out, stream):
+            if self.class_shard is not None:
+                capi.check(self.lib.mudpt_cp_forward(self._h, x, B, 1 if reuse else 0, stream), "cp_forward")
+                if not reuse:
+                    self._exchange(self._cp_feat)
+                capi.check(self.lib.mudpt_cp_head(self._h, None, B, 1.0, None, out, 1 if reuse else 0, stream), "cp_head")
+            else:
+                capi.check(self.lib.mudpt_forward_ex(self._h, x, B, out, 1 if reuse else 0, stream), "forward")
+
+        logits = self._infer(image, self.n_cls, call)
+        self._text_version = version
         return logits
 
     def _exchange(self, table: torch.Tensor, async_op: bool = False):
@@ -438,23 +487,3 @@ class CustomCLIP(nn.Module):
         ms, work, n, ex = (C.c_double * 5)(), (C.c_double * 5)(), (C.c_int64 * 5)(), C.c_double()
         capi.check(self.lib.mudpt_profile_read_classes(self._h, C.byref(ms), C.byref(work), C.byref(n), C.byref(ex)), "profile_read_classes")
         return {k: (ms[i], work[i], n[i]) for i, k in enumerate(self.PROF_CLASSES)}, ex.value
-
-    def debug_read(self, name: str, batch: int) -> torch.Tensor:
-        """Flat fp32 host copy of an internal activation of the last call (test hook, see include/mudpt.h)."""
-        n = C.c_size_t()
-        capi.check(self.lib.mudpt_debug_read(self._h, name.encode(), batch, None, 0, C.byref(n)), "debug_read")
-        out = torch.empty(n.value, dtype=torch.float32)
-        capi.check(self.lib.mudpt_debug_read(self._h, name.encode(), batch, capi.ptr(out), n.value, C.byref(n)), "debug_read")
-        return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            torch.cuda.synchronize(self.device)
-            self.lib.mudpt_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -49,6 +49,16 @@ def load_clip_state_dict(cfg):
     return None
 
 
+def open_backbone(cfg):
+    """(ModelShape, CLIP state dict) of cfg.MODEL.BACKBONE: the checkpoint's, or the default ViT-B/16 shape with seeded random weights.  The
+    shape's n_ctx / depth are placeholders: every plugin sets its own (dataclasses.replace)."""
+    print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")
+    state = load_clip_state_dict(cfg)
+    if state is None:
+        return ModelShape(), synth.random_clip_state(ModelShape(), cfg.MODEL.BACKBONE.SYNTHETIC_SEED)
+    return ModelShape.from_state_dict(state, 4, 1), state
+
+
 def tokenize_prompts(prompts, ctx_len=77, near=None):
     """clip.tokenize (clip/clip.py:199-239) by the native BPE tokenizer (mudpt_amd/tokenizer.py); the merge table is looked for
     at $MUDPT_BPE_VOCAB, next to the checkpoint (``near``) and in an importable clip package.  Without a merge table only the
@@ -123,37 +133,49 @@ def data_parallel_step(trainer, batch, with_acc: bool = False):
 DEVICE_DATA_TRANSFORMS = {"random_resized_crop", "random_flip", "normalize"}  # INPUT.TRANSFORMS of every yaml the reference ships
 
 
+def _device_store(trainer, loader, local: int, attr: str, dm_method: str, noun: str, set_name: str, runs: str):
+    """The DeviceImageStore a device-resident loader runs on, announced and kept as ``trainer.<attr>``: the one handed over there, else the set
+    decoded once from the ``impath`` / ``label`` items of Dassl's data_source, else dassl_lite's synthetic uint8 set (``trainer.dm.<dm_method>``).
+    None, after a one-line note, when no image list is found or the store would take more than a quarter of the free device memory."""
+    from .augment import DeviceImageStore, StoreTooLarge
+    device = f"cuda:{local}"
+    budget = torch.cuda.mem_get_info(device)[0] // 4
+    store = getattr(trainer, attr, None)
+    if store is None:
+        source = getattr(getattr(loader, "dataset", None), "data_source", None)
+        try:
+            if source is not None and len(source) > 0 and all(hasattr(item, "impath") and hasattr(item, "label") for item in source):
+                store = DeviceImageStore.from_paths([item.impath for item in source], [item.label for item in source], device=device, max_bytes=budget)
+            elif hasattr(getattr(trainer, "dm", None), dm_method):
+                store = getattr(trainer.dm, dm_method)(device, max_bytes=budget)
+            else:
+                print(f"Device-resident {noun} refused: the {set_name} exposes no impath / label items; using the host loader")
+                return None
+        except StoreTooLarge as too_large:
+            print(f"Device-resident {noun} refused: {too_large}, a quarter of the free device memory; using the host loader")
+            return None
+    setattr(trainer, attr, store)
+    print(f"Device-resident {noun}: {len(store)} images, {store.nbytes / 2 ** 20:.1f} MiB of uint8 on {device}; {runs}")
+    return store
+
+
 def device_data_loader(trainer, loader, local: int):
     """The opt-in device-resident input path (mudpt_amd/augment.py; MUDPT_DEVICE_DATA=1 or trainer.device_store): a DeviceAugmentLoader over
     a DeviceImageStore -- trainer.device_store if one was handed over, else the training set decoded once from the ``impath`` / ``label``
     items of Dassl's data_source, else dassl_lite's synthetic uint8 set.  None, after a one-line note, when the configuration is not the one
     the kernel reproduces (exactly the three transforms above with INTERPOLATION "bicubic"), when no image list is found, or when the store
     would take more than a quarter of the free device memory: install_loader then goes on as without the opt-in."""
-    from .augment import CLIP_MEAN, CLIP_STD, DeviceAugmentLoader, DeviceImageStore, StoreTooLarge
+    from .augment import CLIP_MEAN, CLIP_STD, DeviceAugmentLoader
     inp = trainer.cfg.INPUT
     transforms, interpolation = set(getattr(inp, "TRANSFORMS", ()) or ()), getattr(inp, "INTERPOLATION", None)
     if transforms != DEVICE_DATA_TRANSFORMS or interpolation != "bicubic":
         print(f"Device-resident data refused: INPUT.TRANSFORMS {sorted(transforms)} / INTERPOLATION {interpolation!r} is not "
               f"{sorted(DEVICE_DATA_TRANSFORMS)} / 'bicubic'; using the host loader")
         return None
-    device = f"cuda:{local}"
-    budget = torch.cuda.mem_get_info(device)[0] // 4
-    store = getattr(trainer, "device_store", None)
+    store = _device_store(trainer, loader, local, "device_store", "uint8_store", "data", "training set",
+                          "crop, flip and normalize run in one HIP launch per step")
     if store is None:
-        source = getattr(getattr(loader, "dataset", None), "data_source", None)
-        try:
-            if source is not None and len(source) > 0 and all(hasattr(item, "impath") and hasattr(item, "label") for item in source):
-                store = DeviceImageStore.from_paths([item.impath for item in source], [item.label for item in source], device=device, max_bytes=budget)
-            elif hasattr(getattr(trainer, "dm", None), "uint8_store"):
-                store = trainer.dm.uint8_store(device, max_bytes=budget)
-            else:
-                print("Device-resident data refused: the training set exposes no impath / label items; using the host loader")
-                return None
-        except StoreTooLarge as too_large:
-            print(f"Device-resident data refused: {too_large}, a quarter of the free device memory; using the host loader")
-            return None
-    trainer.device_store = store
-    print(f"Device-resident data: {len(store)} images, {store.nbytes / 2 ** 20:.1f} MiB of uint8 on {device}; crop, flip and normalize run in one HIP launch per step")
+        return None
     return DeviceAugmentLoader(store, trainer.cfg.DATALOADER.TRAIN_X.BATCH_SIZE, inp.SIZE[0], getattr(inp, "PIXEL_MEAN", CLIP_MEAN), getattr(inp, "PIXEL_STD", CLIP_STD),
                                getattr(inp, "RRC_SCALE", (0.08, 1.0)), seed=trainer.cfg.SEED)
 
@@ -189,31 +211,17 @@ def device_test_loader(trainer, loader, local: int):
     Resize(max(INPUT.SIZE)) + CenterCrop(INPUT.SIZE) + ToTensor and, if INPUT.TRANSFORMS names it, normalize, with INTERPOLATION: the
     kernel reproduces it for a square size, "normalize" and "bicubic".  None, after a one-line note, under the conditions
     device_data_loader refuses: another transform, no image list, a store over a quarter of the free device memory."""
-    from .augment import CLIP_MEAN, CLIP_STD, DeviceEvalLoader, DeviceImageStore, StoreTooLarge
+    from .augment import CLIP_MEAN, CLIP_STD, DeviceEvalLoader
     inp = trainer.cfg.INPUT
     transforms, interpolation, size = set(getattr(inp, "TRANSFORMS", ()) or ()), getattr(inp, "INTERPOLATION", None), tuple(inp.SIZE)
     if "normalize" not in transforms or interpolation != "bicubic" or len(set(size)) != 1:
         print(f"Device-resident test data refused: INPUT.SIZE {size} / TRANSFORMS {sorted(transforms)} / INTERPOLATION {interpolation!r} is not "
               "a square size with 'normalize' / 'bicubic'; using the host loader")
         return None
-    device = f"cuda:{local}"
-    budget = torch.cuda.mem_get_info(device)[0] // 4
-    store = getattr(trainer, "device_test_store", None)
+    store = _device_store(trainer, loader, local, "device_test_store", "uint8_test_store", "test data", "test set",
+                          "resize, center crop and normalize run in one HIP launch per batch")
     if store is None:
-        source = getattr(getattr(loader, "dataset", None), "data_source", None)
-        try:
-            if source is not None and len(source) > 0 and all(hasattr(item, "impath") and hasattr(item, "label") for item in source):
-                store = DeviceImageStore.from_paths([item.impath for item in source], [item.label for item in source], device=device, max_bytes=budget)
-            elif hasattr(getattr(trainer, "dm", None), "uint8_test_store"):
-                store = trainer.dm.uint8_test_store(device, max_bytes=budget)
-            else:
-                print("Device-resident test data refused: the test set exposes no impath / label items; using the host loader")
-                return None
-        except StoreTooLarge as too_large:
-            print(f"Device-resident test data refused: {too_large}, a quarter of the free device memory; using the host loader")
-            return None
-    trainer.device_test_store = store
-    print(f"Device-resident test data: {len(store)} images, {store.nbytes / 2 ** 20:.1f} MiB of uint8 on {device}; resize, center crop and normalize run in one HIP launch per batch")
+        return None
     return DeviceEvalLoader(store, trainer.cfg.DATALOADER.TEST.BATCH_SIZE, size[0], getattr(inp, "PIXEL_MEAN", CLIP_MEAN), getattr(inp, "PIXEL_STD", CLIP_STD))
 
 
@@ -366,13 +374,7 @@ class PromptTrainer(TrainerX):
     def build_model(self):
         cfg = self.cfg
         node = getattr(cfg.TRAINER, self.CFG_NODE)
-        print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")
-        state = load_clip_state_dict(cfg)
-        if state is None:
-            backbone = ModelShape()
-            state = synth.random_clip_state(backbone, cfg.MODEL.BACKBONE.SYNTHETIC_SEED)
-        else:
-            backbone = ModelShape.from_state_dict(state, 4, 1)  # the prompt's n_ctx / depth come from prompt_setup
+        backbone, state = open_backbone(cfg)  # the prompt's n_ctx / depth come from prompt_setup
         cfg_imsize = cfg.INPUT.SIZE[0]
         assert cfg_imsize == backbone.image_size, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({backbone.image_size})"  # mudpt.py:55
         warn_if_fp16_misses_the_bound(node.PREC, state)

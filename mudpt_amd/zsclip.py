@@ -11,15 +11,14 @@ The two template tables below restate the reference's data (trainers/zsclip.py:3
 """
 from __future__ import annotations
 
-import ctypes as C
+import dataclasses
 from typing import Dict, List, Optional
 
 import torch
-from torch import nn
 
-from . import capi, synth
-from .model import ModelShape, check_features, read_image_features
-from .trainer import TRAINER_REGISTRY, TrainerX, install_test_loader, load_clip_state_dict, precision_to_dtype, tokenize_prompts, warn_if_fp16_misses_the_bound
+from . import capi
+from .model import LibraryModel, ModelShape
+from .trainer import TRAINER_REGISTRY, TrainerX, install_test_loader, open_backbone, precision_to_dtype, tokenize_prompts, warn_if_fp16_misses_the_bound
 
 # trainers/zsclip.py:32-48: the per-dataset prompt, keyed by cfg.DATASET.NAME
 CUSTOM_TEMPLATES = {
@@ -65,45 +64,27 @@ def ensemble_templates(dataset_name: str) -> List[str]:
     return templates
 
 
-class FrozenCLIP(nn.Module):
+class FrozenCLIP(LibraryModel):
     """Frozen CLIP over ``mudpt_create_frozen``: owns no parameter.  ``tokens`` [T, C, ctx_len] (or [C, ctx_len] for one template) are the
     tokenized prompts of every template and class; ``clip_state`` the OpenAI CLIP state dict ("token_embedding.weight" included: the
     library keeps it on the device)."""
 
     def __init__(self, shape: ModelShape, clip_state: Dict[str, torch.Tensor], tokens: torch.Tensor, max_batch: int = 100, dtype: str = "fp16",
                  device: str = "cuda:0", knobs: Optional[Dict[str, int]] = None):
-        super().__init__()
-        if not torch.cuda.is_available():
-            raise capi.MudptError("mudpt_amd needs an MI355X (HIP device); there is no CPU path in the product")
-        self.lib = capi.load()
-        self.shape = shape
-        self.device = torch.device(device)
-        self.dtype_name = dtype
         tokens = torch.as_tensor(tokens)
         if tokens.dim() == 2:
             tokens = tokens[None]
         assert tokens.dim() == 3 and tokens.shape[2] == shape.ctx_len, f"tokens must be [T, C, {shape.ctx_len}], got {tuple(tokens.shape)}"
+        # the knobs go in before the tokens: the layout knobs are read by mudpt_set_text_tokens
+        super().__init__(shape, tokens.shape[1], max_batch, dtype, device, knobs,
+                         lambda lib, cfg, h: capi.check(lib.mudpt_create_frozen(cfg, h), "create_frozen"), frozen=True)
         self.tokens = tokens.to("cpu", torch.int32).contiguous()
-        self.n_templates, self.n_cls = int(tokens.shape[0]), int(tokens.shape[1])
-        self.max_batch = int(max_batch)
-        cfg = capi.Config(shape.image_size, shape.patch, shape.v_width, shape.v_layers, shape.v_heads, shape.t_width, shape.t_layers,
-                          shape.t_heads, shape.ctx_len, shape.embed_dim, 0, 1, self.n_cls, self.max_batch,
-                          {"bf16": capi.BF16, "fp16": capi.F16, "fp32": capi.F32}[dtype], 0)
-        torch.cuda.set_device(self.device)
-        h = C.c_void_p()
-        capi.check(self.lib.mudpt_create_frozen(C.byref(cfg), C.byref(h)), "create_frozen")
-        self._h = h
-        for name, value in (knobs or {}).items():  # before the tokens: the layout knobs are read by mudpt_set_text_tokens
-            self.set_knob(name, value)
+        self.n_templates = int(tokens.shape[0])
         for k, v in clip_state.items():  # clip/model.py:919 load_state_dict
             if isinstance(v, torch.Tensor):
                 self.set_weight(k, v)
         if tokens.numel():  # no tokens: encode_image alone (the linear-probe extractor)
             self.set_tokens(self.tokens)
-
-    def set_weight(self, key: str, value: torch.Tensor):
-        t = value.detach().to("cpu", torch.float32).contiguous()
-        capi.check(self.lib.mudpt_set_weight(self._h, key.encode(), capi.ptr(t), t.numel()), f"set_weight({key})")
 
     def set_tokens(self, tokens: torch.Tensor):
         tokens = torch.as_tensor(tokens)
@@ -113,82 +94,30 @@ class FrozenCLIP(nn.Module):
         capi.check(self.lib.mudpt_set_text_tokens(self._h, capi.ptr(tokens), int(tokens.shape[0])), "set_text_tokens")
         self.tokens, self.n_templates = tokens, int(tokens.shape[0])
 
-    def set_knob(self, name: str, value: int):
-        capi.check(self.lib.mudpt_model_set(self._h, name.encode(), int(value)), f"model_set({name})")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _check_images(self, image: torch.Tensor):
-        S = self.shape.image_size
-        # the library is told only B: a wrong-sized batch would make the patch gather read out of bounds
-        assert image.dim() == 4 and tuple(image.shape[1:]) == (3, S, S), f"images must be [B, 3, {S}, {S}], got {tuple(image.shape)}"
-        assert 0 < image.shape[0] <= self.max_batch, f"batch {image.shape[0]} outside 1..max_batch={self.max_batch}"
-
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         """zsclip.py:74-79 model_inference: logits [B, n_cls]."""
         self._check_images(image)
-        image = image.to(self.device, torch.float32).contiguous()
-        logits = torch.empty(image.shape[0], self.n_cls, dtype=torch.float32, device=self.device)
-        capi.check(self.lib.mudpt_forward(self._h, capi.ptr(image), image.shape[0], capi.ptr(logits), self._stream()), "forward")
-        self._last_batch = image.shape[0]
-        return logits
+        return self._infer(image, self.n_cls, lambda x, B, out, stream: capi.check(self.lib.mudpt_forward(self._h, x, B, out, stream), "forward"))
 
     def forward_features(self, feat: torch.Tensor) -> torch.Tensor:
         """model_inference behind ``clip_model.visual(image)`` (zsclip.py:76-79): logits [B, n_cls] of the raw image features ``feat``
         [B, embed_dim] -- ``encode_image`` / ``image_features()`` here, the rows lpclip/feat_extractor.py:125-137 saves.  Bit for bit the logits
         of the image forward the features came from; needs no ``visual.*`` weight."""
-        check_features(feat, self.shape.embed_dim, self.max_batch)
-        feat = feat.to(self.device, torch.float32).contiguous()
-        logits = torch.empty(feat.shape[0], self.n_cls, dtype=torch.float32, device=self.device)
-        capi.check(self.lib.mudpt_forward_features(self._h, capi.ptr(feat), feat.shape[0], capi.ptr(logits), 0, self._stream()), "forward_features")
-        self._last_batch = feat.shape[0]
-        return logits
-
-    def image_features(self) -> torch.Tensor:
-        """The raw ``clip_model.visual(image)`` features [B, embed_dim] of the last ``forward`` / ``forward_features`` / ``encode_image``."""
-        return read_image_features(self)
+        self._check_features(feat)
+        return self._infer(feat, self.n_cls, lambda x, B, out, stream: capi.check(
+            self.lib.mudpt_forward_features(self._h, x, B, out, 0, stream), "forward_features"))
 
     def encode_image(self, image: torch.Tensor) -> torch.Tensor:
         """clip/model.py:822: the raw (un-normalised) image features [B, embed_dim]."""
         self._check_images(image)
-        image = image.to(self.device, torch.float32).contiguous()
-        feat = torch.empty(image.shape[0], self.shape.embed_dim, dtype=torch.float32, device=self.device)
-        capi.check(self.lib.mudpt_encode_image(self._h, capi.ptr(image), image.shape[0], capi.ptr(feat), self._stream()), "encode_image")
-        self._last_batch = image.shape[0]
-        return feat
+        return self._infer(image, self.shape.embed_dim, lambda x, B, out, stream: capi.check(
+            self.lib.mudpt_encode_image(self._h, x, B, out, stream), "encode_image"))
 
     def text_features(self) -> torch.Tensor:
         """The ensembled, normalised text features [n_cls, embed_dim] (zsclip.py:71,117)."""
         feat = torch.empty(self.n_cls, self.shape.embed_dim, dtype=torch.float32, device=self.device)
         capi.check(self.lib.mudpt_text_features(self._h, capi.ptr(feat), self._stream()), "text_features")
         return feat
-
-    def text_layout(self):
-        """(token rows summed over the templates, largest bucket count of a template, longest kept length) (``mudpt_text_layout``)."""
-        r, b, l = C.c_int32(), C.c_int32(), C.c_int32()
-        capi.check(self.lib.mudpt_text_layout(self._h, C.byref(r), C.byref(b), C.byref(l)), "text_layout")
-        return r.value, b.value, l.value
-
-    def debug_read(self, name: str, batch: int = 1) -> torch.Tensor:
-        """Flat fp32 host copy of "image_features", "text_features" or "text_launches" (test hook, see include/mudpt.h)."""
-        n = C.c_size_t()
-        capi.check(self.lib.mudpt_debug_read(self._h, name.encode(), batch, None, 0, C.byref(n)), "debug_read")
-        out = torch.empty(n.value, dtype=torch.float32)
-        capi.check(self.lib.mudpt_debug_read(self._h, name.encode(), batch, capi.ptr(out), n.value, C.byref(n)), "debug_read")
-        return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            torch.cuda.synchronize(self.device)
-            self.lib.mudpt_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 @TRAINER_REGISTRY.register()
@@ -201,13 +130,7 @@ class ZeroshotCLIP(TrainerX):
     def build_model(self):
         cfg = self.cfg
         classnames = self.dm.dataset.classnames
-        print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")
-        state = load_clip_state_dict(cfg)
-        if state is None:
-            backbone = ModelShape()
-            state = synth.random_clip_state(backbone, cfg.MODEL.BACKBONE.SYNTHETIC_SEED)
-        else:
-            backbone = ModelShape.from_state_dict(state, 0, 1)
+        backbone, state = open_backbone(cfg)
         templates = self.templates_for(cfg.DATASET.NAME)
         if len(templates) > 1:
             print(f"Prompt ensembling (n={len(templates)})")  # zsclip.py:104-105
@@ -218,7 +141,7 @@ class ZeroshotCLIP(TrainerX):
         tokens = torch.stack([tokenize_prompts(prompt_strings(t, classnames), backbone.ctx_len, near=near) for t in templates])
         device = f"cuda:{self.device.index or 0}" if self.device.type == "cuda" else "cuda:0"
         self.templates = templates
-        self.model = FrozenCLIP(backbone, state, tokens, max_batch=cfg.DATALOADER.TEST.BATCH_SIZE, dtype=precision_to_dtype(prec), device=device)
+        self.model = FrozenCLIP(dataclasses.replace(backbone, n_ctx=0, depth=1), state, tokens, max_batch=cfg.DATALOADER.TEST.BATCH_SIZE, dtype=precision_to_dtype(prec), device=device)
 
     def model_inference(self, image):
         return self.model(image)
