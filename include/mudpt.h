@@ -68,6 +68,11 @@
  *   mudpt_encode_image                   clip/model.py:822 encode_image, lpclip/feat_extractor.py:125  the raw visual(image) features
  *   mudpt_forward / _ex                  trainers/zsclip.py:74-79  model_inference: logit_scale * normalise(image features) @ text_features.t()
  *   (mudpt_param_count / _numel are 0; every training, class-prompt, class-shard and mudpt_cp_* entry point refuses the handle.)
+ * A handle made by mudpt_create_frozen_resnet is such a frozen handle with CLIP's ResNet image tower (RN50, RN101, RN50x16, RN50x64; the backbone
+ * of the zero-shot and linear-probe baselines, scripts/zsclip/run_zsclip.sh:15, lpclip/feat_extractor.py:113-116); the text side is the same:
+ *   mudpt_create_frozen_resnet / mudpt_set_weight   clip/model.py:686-694, 890-897  build_model's ResNet branch; the "visual.*" keys of ModifiedResNet
+ *   mudpt_encode_image / mudpt_forward / _ex         clip/model.py:17-161  ModifiedResNet.forward in eval mode: the stem, four stages of Bottleneck,
+ *                                        AttentionPool2d; BatchNorm folded into the convolutions, every convolution an im2col + MFMA GEMM
  * Frozen, CoOp and CoCoOp handles also run the test pass from cached image features:
  *   mudpt_forward_features               trainers/zsclip.py:74-79, coop.py:212-223, cocoop.py:178-188 behind their clip_model.visual(image)
  *   mudpt_image_features                 lpclip/feat_extractor.py:125-137  the features of the last inference forward, for {dir}/{dataset}/{split}.npz
@@ -172,6 +177,28 @@ int mudpt_create_ex(const mudpt_config* cfg, const mudpt_prompt_shape* prompts, 
  * mudpt_param_count / _numel return 0; mudpt_bind_params, mudpt_forward_backward, mudpt_sgd_step, mudpt_set_class_prompts,
  * mudpt_set_class_token_position, mudpt_set_class_shard, mudpt_cp_* and mudpt_allreduce_grads return MUDPT_ERR_ARG ("... frozen ..."). */
 int mudpt_create_frozen(const mudpt_config* cfg, mudpt_model** out);
+/* Frozen CLIP with the ResNet image tower ModifiedResNet(layers, embed_dim, heads, image_size, width) (clip/model.py:101-161, built by
+ * clip/model.py:686-694 whenever a checkpoint has no "visual.proj", :890-897).  A frozen handle in everything else: the text side
+ * (mudpt_set_text_tokens, mudpt_text_features, the ensembling), mudpt_encode_image, mudpt_forward / _ex, mudpt_forward_features,
+ * mudpt_image_features and mudpt_debug_read("image_features") are what they are for mudpt_create_frozen.  Read from cfg: image_size, embed_dim,
+ * n_cls, max_batch, dtype and the text shape; NOT read: patch, v_width, v_layers, v_heads, n_ctx, depth, variant.  embed_dim need not equal
+ * t_width (RN50: 1024 / 512).  Activations are NHWC in T, sized here for max_batch; BatchNorm (eval mode, eps 1e-5) is folded into the
+ * convolution weights on the host, in fp64, at the first forward after a "visual.*" upload (mudpt_conv_pack below is that function).
+ * MUDPT_ERR_ARG before any GPU call, the message naming the field: a null pointer; image_size % 32 != 0; a stage count < 1; width % 32 != 0
+ * (RN50x4, width 80: its 40-channel stem does not meet the GEMM's N % 16); heads < 1 or (32 width) % heads != 0; (32 width) / heads != 64, the
+ * head dimension of every released model (clip/model.py:687); dtype MUDPT_F32 ("ResNet towers run in bf16 / fp16; the parity mode is not built
+ * for them").
+ * mudpt_set_weight takes the reference's keys, shapes checked against this shape: visual.conv{1,2,3}.weight (conv1 is [width / 2, 3, 3, 3]),
+ * visual.bn{1,2,3}.{weight,bias,running_mean,running_var}, visual.layer{1..4}.{i}.{conv1,bn1,conv2,bn2,conv3,bn3}.*,
+ * visual.layer{1..4}.0.downsample.{0.weight,1.*}, visual.attnpool.positional_embedding, visual.attnpool.{q,k,v,c}_proj.{weight,bias};
+ * "*.num_batches_tracked" is accepted and ignored.  The entry points that run the tower return MUDPT_ERR_STATE naming the first missing key
+ * until all of them are there; mudpt_forward_features and mudpt_text_features need none of them. */
+typedef struct mudpt_resnet_shape {
+    int32_t layers1, layers2, layers3, layers4; /* Bottleneck blocks per stage: RN50 3, 4, 6, 3; RN101 3, 4, 23, 3 */
+    int32_t width;                              /* 64 (RN50, RN101), 96 (RN50x16), 128 (RN50x64); the tower's output has 32 width channels */
+    int32_t heads;                              /* of the attention pool: 32 width / 64 */
+} mudpt_resnet_shape;
+int mudpt_create_frozen_resnet(const mudpt_config* cfg, const mudpt_resnet_shape* rn, mudpt_model** out);
 int mudpt_destroy(mudpt_model* m);
 
 /* Frozen weight by OpenAI CLIP state-dict key ("visual.transformer.resblocks.0.attn.in_proj_weight", ...),
@@ -675,6 +702,33 @@ int mudpt_eval_reset(int32_t* state, int32_t n_cls, int32_t with_cmat, void* str
 int mudpt_eval_accumulate(const float* logits, int32_t ldz, const int64_t* labels, int32_t rows, int32_t n_cls, int32_t* state, int32_t with_cmat, int32_t* pred,
                           void* stream);
 int mudpt_eval_finalize(const int32_t* state, int32_t n_cls, double* results, void* stream);
+/* The ResNet tower's memory movers (mudpt_amd/csrc/resnet.hip) and its host-side weight packing.  Activations are NHWC in T (dtype 0 bf16 / 1 fp16),
+ * one pixel = one row of C channels (C % 8 == 0) at a row stride (elements) >= C that is a multiple of 8; every pointer 16-byte aligned.  Refused on
+ * the host (MUDPT_ERR_ARG): a null pointer, a size < 1, a stride or alignment outside that.
+ *   im2col           patch rows of a 3 x 3, pad 1 convolution of stride 1 | 2: dst [B * Ho * Wo, ldk] T, column (ky * 3 + kx) * C + c, Ho = (H - 1) / stride + 1,
+ *                    ldk >= 9 C and ldk % 8 == 0; border taps and the columns from 9 C on are WRITTEN as zeros on every call.  src_planar != 0: src is
+ *                    fp32 planar pixels [B, 3, H, W] (C must be 3, lds is not read), rounded to T
+ *   bias_act         out [M, N] T = act(acc + bias + residual): acc fp32 (row stride ldacc, % 4 == 0), bias [N] fp32 or NULL, residual T or NULL,
+ *                    relu != 0: max(., 0); both adds and the ReLU in fp32, ONE rounding.  N % 8 == 0
+ *   avgpool2d        AvgPool2d(k): [B, H, W, C] -> [B, H / k, W / k, C]; the fp32 sum in window order (rows, then columns) times 1 / k^2, one rounding
+ *   attnpool_tokens  AttentionPool2d's tokens (clip/model.py:76-78): [B, HW, C] -> [B, HW + 1, C]; row 0 = the fp32 mean over HW (sum in pixel order times
+ *                    1 / HW), every row + pos [HW + 1, C] fp32, one rounding
+ *   attnpool_attend  its attention for the pooled query (clip/model.py:79-97): q [B, H * 64] fp32 as q_proj left it (the kernel applies 64^-0.5), k / v rows
+ *                    b * L + l of H * 64 fp32 at row stride ldkv, out [B, H * 64] T = softmax(q k^T / 8) v per head; fp32 throughout, one rounding
+ *   conv_pack        HOST only, no device work: folds an eval-mode BatchNorm (eps 1e-5) into a bias-free convolution and packs it for the GEMM.  w
+ *                    [cout, cin, k, k] (k = 1 | 3), gamma / beta / mean / var [cout]; in fp64 scale = gamma / sqrt(var + 1e-5), w' = w scale,
+ *                    b' = beta - mean scale; w_out [cout, ldk] T (2-byte elements) = w' rounded ONCE from fp64, column (ky * k + kx) * cin + c, zeros from
+ *                    k k cin on (ldk >= k k cin); bias_out [cout] fp32 = b' */
+int mudpt_im2col(int32_t dtype, const void* src, int32_t src_planar, int32_t B, int32_t H, int32_t W, int32_t C, int32_t lds, int32_t stride, void* dst, int32_t ldk,
+                 void* stream);
+int mudpt_bias_act(int32_t dtype, const float* acc, int32_t ldacc, const float* bias, const void* residual, int32_t ldres, void* out, int32_t ldo, int32_t M, int32_t N,
+                   int32_t relu, void* stream);
+int mudpt_avgpool2d(int32_t dtype, const void* src, int32_t lds, void* dst, int32_t ldo, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k, void* stream);
+int mudpt_attnpool_tokens(int32_t dtype, const void* src, int32_t lds, const float* pos, void* dst, int32_t ldo, int32_t B, int32_t HW, int32_t C, void* stream);
+int mudpt_attnpool_attend(int32_t dtype, const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, void* out, int32_t ldo, int32_t B, int32_t L,
+                          int32_t H, void* stream);
+int mudpt_conv_pack(int32_t dtype, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, int32_t cout, int32_t cin, int32_t k,
+                    int32_t ldk, void* w_out, float* bias_out);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,11 @@ class PromptShape(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("t_n_ctx", "t_depth", "v_n_ctx", "v_depth")]
 
 
+class ResnetShape(C.Structure):
+    """mudpt_resnet_shape: the Bottleneck blocks of ModifiedResNet's four stages, its width and the heads of its attention pool."""
+    _fields_ = [(n, C.c_int32) for n in ("layers1", "layers2", "layers3", "layers4", "width", "heads")]
+
+
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "size_t": C.c_size_t}
 _RETURNS = {"int": C.c_int32, "size_t": C.c_size_t, "const char*": C.c_char_p}
 

@@ -268,6 +268,25 @@ int launch_augment(const uint8_t* pixels, const int64_t* images, int n_images, c
 int augment_form(int x_len, int x_out, int y_len, int y_out, int size);
 
 // ------------------------------------------------------------------------------------------------
+// CLIP's ModifiedResNet image tower (resnet.hip; clip/model.py:17-161): the memory movers around its GEMMs.  Activations are NHWC in T, one
+// pixel = one row of C channels (C % 8 == 0) at a row stride >= C that is a multiple of 8; every pointer 16-byte aligned
+// ------------------------------------------------------------------------------------------------
+// patch rows of a 3 x 3, pad 1 convolution of stride 1 | 2: dst [B * Ho * Wo, ldk] T, column (ky * 3 + kx) * C + c, Ho = (H - 1) / stride + 1;
+// border taps and columns 9 C .. ldk - 1 are WRITTEN as zeros.  planar: src is fp32 [B, 3, H, W] (C = 3, lds unused), rounded to T
+int launch_im2col(int dtype, const void* src, bool planar, int B, int H, int W, int C, int lds, int stride, void* dst, int ldk, hipStream_t s);
+// out [M, N] T = act(acc + bias + residual): acc fp32 (a GEMM's EPI_STORE_F32 output), bias [N] fp32 or null, residual T or null, the adds and
+// the ReLU in fp32, one rounding; N % 8 == 0, ldacc % 4 == 0
+int launch_bias_act(int dtype, const float* acc, int ldacc, const float* bias, const void* residual, int ldres, void* out, int ldo, int M, int N, bool relu, hipStream_t s);
+// AvgPool2d(k): [B, H, W, C] -> [B, H / k, W / k, C], fp32 sum in window order times 1 / k^2, one rounding
+int launch_avgpool2d(int dtype, const void* src, int lds, void* dst, int ldo, int B, int H, int W, int C, int k, hipStream_t s);
+// AttentionPool2d's tokens: [B, HW, C] -> [B, HW + 1, C]; row 0 = the fp32 mean over HW (sum in pixel order times 1 / HW), every row + pos
+// [HW + 1, C] fp32, one rounding
+int launch_attnpool_tokens(int dtype, const void* src, int lds, const float* pos, void* dst, int ldo, int B, int HW, int C, hipStream_t s);
+// AttentionPool2d's attention of the pooled query: q [B, H * 64] fp32 (unscaled; the kernel applies 1 / 8), k / v rows b * L + l of H * 64
+// fp32 at stride ldkv -> out [B, H * 64] T; one wave per (image, head), fp32 throughout
+int launch_attnpool_attend(int dtype, const float* q, int ldq, const float* k, const float* v, int ldkv, void* out, int ldo, int B, int L, int H, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // The linear probe (probe.hip; lpclip/linear_probe.py): one evaluation of the multinomial logistic objective in exact fp32 on the matrix cores
 // ------------------------------------------------------------------------------------------------
 // C [M, N] = A [M, K] . B [N, K]^T (+ bias[N]): both operands k-contiguous, any M, N, K and strides, 128 x 128 x 32 tiles through LDS

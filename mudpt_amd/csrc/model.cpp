@@ -157,6 +157,35 @@ struct Trainable {
     size_t off = 0, numel = 0;
 };
 
+// ---- CLIP's ResNet image tower (mudpt_create_frozen_resnet; clip/model.py:17-161; kernels: resnet.hip) ----
+// One bias-free convolution and the eval-mode BatchNorm behind it, folded into one GEMM B operand + fp32 bias (mudpt_conv_pack)
+struct RnConv {
+    std::string conv, bn;  // state-dict prefixes: conv + ".weight"; bn + ".weight" / ".bias" / ".running_mean" / ".running_var"
+    int cin = 0, cout = 0, k = 1;
+    int ldk = 0;  // the GEMM's K: k k cin rounded up to 64, zero-filled in the packed weights (and in the patch rows / the padded channels of A)
+    int np = 0;   // the GEMM's N and the output's channel stride: cout, rounded up to 64 where a 1 x 1 convolution reads the output as its A
+                  // operand as it lies (width 32: K = 32) -- the extra weight rows and biases are zero, so the extra channels are written as zeros
+    std::vector<float> w, bnp[4];  // fp32 host copies as uploaded: w [cout, cin, k, k]; gamma, beta, running_mean, running_var [cout]
+    void* w_dev = nullptr;         // T [np, ldk], column (ky * k + kx) * cin + c
+    float* b_dev = nullptr;        // [np]
+};
+struct RnBlock { int conv1 = 0, conv2 = 0, conv3 = 0, down = -1, stride = 1; };  // indices into Resnet::convs; down = -1: the identity is the input
+struct Resnet {
+    mudpt_resnet_shape shape;
+    int S = 0, C = 0, L = 0;  // image size; output channels 32 width; tokens of the attention pool (S / 32)^2 + 1
+    std::vector<RnConv> convs;  // 0, 1, 2: the stem
+    std::vector<RnBlock> blocks;
+    bool stale = true;  // a "visual.*" tensor arrived since the last fold
+    float *pos = nullptr, *b_q = nullptr, *b_kv = nullptr, *b_c = nullptr;  // attnpool: positional_embedding [L, C]; biases [C], [2 C] (k | v), [e]
+    void *w_q = nullptr, *w_kv = nullptr, *w_c = nullptr;                   // T [C, C], [2 C, C] (k_proj over v_proj), [e, C]
+    // activations, sized for max_batch at create (bytes for RN50 at B 100: DESIGN.md 4.9)
+    void* act[7] = {};     // T NHWC: block input, block output, conv1 / conv2 outputs, pooled conv2 output, downsample branch, pooled block input
+    void* rows = nullptr;  // T patch rows of the largest 3 x 3 convolution
+    float* acc = nullptr;  // fp32 output of the largest convolution GEMM
+    void *tok = nullptr, *ao = nullptr;  // T [B, L, C] pooled tokens, [B, C] attention output
+    float *q = nullptr, *kv = nullptr;   // fp32 [B, C], [B L, 2 C]
+};
+
 }  // namespace mudpt
 
 using namespace mudpt;
@@ -243,7 +272,8 @@ struct mudpt_model {
     // position) per token row, and the text tower runs once per template from the device-resident embedding table.  txt_n holds the ensembled,
     // normalised features (text_valid), the only thing a forward needs from the text side
     bool frozen = false;
-    float* tok_table = nullptr; int vocab = 0;  // "token_embedding.weight" fp32 [vocab, t_width]
+    Resnet* rn = nullptr;  // mudpt_create_frozen_resnet: the image tower is this instead of `vis`, which then has no block
+    float* tok_table = nullptr; int vocab = 0;// "token_embedding.weight" fp32 [vocab, t_width]
     struct Template {
         std::vector<Tower::Seg> segs;  // empty = one bucket of n_cls x L
         int rows = 0, L = 0;           // packed token rows, longest kept length
@@ -578,7 +608,7 @@ extern "C" int mudpt_abi_version(void) { return MUDPT_ABI_VERSION; }
 extern "C" const char* mudpt_last_error(void) { return get_error(); }
 
 // Fills a fresh model; on an error the caller (create_model) destroys it
-static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model* m, bool frozen) {
+static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model* m, bool frozen, bool resnet) {
     ARG_CHECK(c->dtype == MUDPT_BF16 || c->dtype == MUDPT_F16 || c->dtype == MUDPT_F32, "create: dtype must be MUDPT_BF16, MUDPT_F16 or MUDPT_F32");
     ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_UUMUDPT, "create: unknown variant %d", c->variant);
     m->cocoop = c->variant == MUDPT_VARIANT_COCOOP;
@@ -596,7 +626,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     ARG_CHECK(c->v_width % 64 == 0 && c->t_width % 64 == 0 && c->v_width <= 1024 && c->t_width <= 1024, "create: widths must be multiples of 64, <= 1024");
     ARG_CHECK(!m->uumudpt || c->embed_dim == c->t_width, "create (UUMuDPT): embed_dim %d must equal t_width %d (visual_ctx_text_proj's output is added to "
               "deep_prompts, trainers/uumudpt.py:224)", c->embed_dim, c->t_width);
-    ARG_CHECK(c->embed_dim == c->t_width, "create: embed_dim must equal t_width (visual_ctx_deep_projections output is added to text prompts)");
+    ARG_CHECK(resnet || c->embed_dim == c->t_width, "create: embed_dim must equal t_width (visual_ctx_deep_projections output is added to text prompts)");  // a ResNet handle has no prompt: RN50 is 1024 / 512
     ARG_CHECK(m->indep || 1 + c->n_ctx < c->ctx_len, "create: n_ctx too large for ctx_len");
     if (m->umudpt) { if (int r = pg_check_shape(m->uumudpt ? "create (UUMuDPT)" : "create (UMuDPT)", c->depth, c->n_ctx, c->t_width, c->v_width)) return r; }
     if (m->uumudpt && c->depth > 1) { if (int r = pg_check_shape("create (UUMuDPT, the vision tower's generator)", c->depth - 1, c->n_ctx, c->v_width, c->embed_dim)) return r; }
@@ -731,9 +761,14 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     return MUDPT_OK;
 }
 
-static int create_model(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out, bool frozen = false) {
+static int resnet_setup(mudpt_model* m, int image_size, const mudpt_resnet_shape& shape);
+// rn: a ResNet image tower is set up behind the (then block-less) ViT fields, for images of rn_image_size
+static int create_model(const mudpt_config* c, const mudpt_prompt_shape* ps, mudpt_model** out, bool frozen = false, const mudpt_resnet_shape* rn = nullptr,
+                        int rn_image_size = 0) {
     mudpt_model* m = new mudpt_model();
-    if (int rc = create_impl(c, ps, m, frozen)) { mudpt_destroy(m); return rc; }
+    int rc = create_impl(c, ps, m, frozen, rn != nullptr);
+    if (!rc && rn) rc = resnet_setup(m, rn_image_size, *rn);
+    if (rc) { mudpt_destroy(m); return rc; }
     *out = m;
     return MUDPT_OK;
 }
@@ -763,12 +798,127 @@ extern "C" int mudpt_create_frozen(const mudpt_config* c, mudpt_model** out) {
     return create_model(&f, nullptr, out, true);
 }
 
+// ---- frozen CLIP with the ResNet image tower (clip/model.py:17-161, 686-694, 890-897) ----
+static int round_up64(int v) { return (v + 63) / 64 * 64; }
+// fp64 -> T with ONE rounding (a detour over fp32 rounds twice): fp16 by the compiler's conversion, bf16 over an fp32 rounded to odd
+static inline uint16_t f64_to_lp(int dtype, double d) {
+    if (dtype == DT_F16) {
+        const _Float16 h = (_Float16)d;
+        uint16_t u;
+        memcpy(&u, &h, 2);
+        return u;
+    }
+    float f = (float)d;
+    if ((double)f != d && std::isfinite(f)) {  // inexact: keep the truncated magnitude and set the sticky bit
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        const bool above = std::fabs((double)f) > std::fabs(d);
+        if (!(u & 1u)) u = above ? u - 1 : u + 1;
+        memcpy(&f, &u, 4);
+    }
+    return f32_to_bf16(f);
+}
+// mudpt_conv_pack (include/mudpt.h): the one statement of the BatchNorm folding and of the packed weight layout
+static void conv_pack(int dtype, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, int cout, int cin, int k, int ldk,
+                      uint16_t* w_out, float* bias_out) {
+    for (int o = 0; o < cout; ++o) {
+        const double scale = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
+        bias_out[o] = (float)((double)beta[o] - (double)mean[o] * scale);
+        uint16_t* row = w_out + (size_t)o * ldk;
+        for (int t = 0; t < k * k; ++t)
+            for (int c = 0; c < cin; ++c) row[t * cin + c] = f64_to_lp(dtype, (double)w[((size_t)o * cin + c) * k * k + t] * scale);
+        for (int j = k * k * cin; j < ldk; ++j) row[j] = 0;
+    }
+}
+
+// The tower's convolutions in the reference's module order, its device weights and its activations for max_batch images
+static int resnet_setup(mudpt_model* m, int S, const mudpt_resnet_shape& shape) {
+    Resnet* r = new Resnet();
+    m->rn = r;
+    r->shape = shape; r->S = S; r->C = 32 * shape.width; r->L = (S / 32) * (S / 32) + 1;
+    m->cfg.image_size = S;
+    const int w = shape.width, B = m->cfg.max_batch, e = m->cfg.embed_dim, C = r->C, L = r->L;
+    size_t act = 0, rows = 0, acc = 0;  // elements per image
+    // a convolution on an H x H input whose output a 1 x 1 convolution (or nothing) reads next; returns its index
+    auto conv = [&](const std::string& cname, const std::string& bname, int cin, int cout, int k, bool feeds_1x1, int H, int stride) {
+        RnConv c;
+        c.conv = cname; c.bn = bname; c.cin = cin; c.cout = cout; c.k = k;
+        c.ldk = round_up64(k * k * cin);
+        c.np = feeds_1x1 ? round_up64(cout) : cout;
+        const size_t Ho = (size_t)((H - 1) / stride + 1), px = Ho * Ho;
+        act = std::max(act, px * c.np); acc = std::max(acc, px * c.np);
+        if (k == 3) rows = std::max(rows, px * c.ldk);
+        r->convs.push_back(c);
+        return (int)r->convs.size() - 1;
+    };
+    int H = S / 2;
+    conv("visual.conv1", "visual.bn1", 3, w / 2, 3, false, S, 2);
+    conv("visual.conv2", "visual.bn2", w / 2, w / 2, 3, false, H, 1);
+    conv("visual.conv3", "visual.bn3", w / 2, w, 3, true, H, 1);
+    H /= 2;  // AvgPool2d(2)
+    int inplanes = w;
+    const int counts[4] = {shape.layers1, shape.layers2, shape.layers3, shape.layers4};
+    for (int st = 0; st < 4; ++st) {
+        const int planes = w << st;
+        for (int i = 0; i < counts[st]; ++i) {
+            const std::string p = "visual.layer" + std::to_string(st + 1) + "." + std::to_string(i) + ".";
+            RnBlock b;
+            b.stride = (st > 0 && i == 0) ? 2 : 1;
+            const int Ho = H / b.stride;
+            b.conv1 = conv(p + "conv1", p + "bn1", inplanes, planes, 1, false, H, 1);
+            b.conv2 = conv(p + "conv2", p + "bn2", planes, planes, 3, true, H, 1);
+            b.conv3 = conv(p + "conv3", p + "bn3", planes, 4 * planes, 1, true, Ho, 1);
+            if (b.stride > 1 || inplanes != 4 * planes) b.down = conv(p + "downsample.0", p + "downsample.1", inplanes, 4 * planes, 1, true, Ho, 1);
+            r->blocks.push_back(b);
+            inplanes = 4 * planes;
+            H = Ho;
+        }
+    }
+    for (RnConv& c : r->convs) { ALLOC(c.w_dev, (size_t)c.np * c.ldk * 2); ALLOC(c.b_dev, (size_t)c.np * 4); }
+    ALLOC(r->pos, (size_t)L * C * 4); ALLOC(r->b_q, (size_t)C * 4); ALLOC(r->b_kv, (size_t)2 * C * 4); ALLOC(r->b_c, (size_t)e * 4);
+    ALLOC(r->w_q, (size_t)C * C * 2); ALLOC(r->w_kv, (size_t)2 * C * C * 2); ALLOC(r->w_c, (size_t)e * C * 2);
+    for (void*& a : r->act) ALLOC(a, (size_t)B * act * 2);
+    ALLOC(r->rows, (size_t)B * rows * 2); ALLOC(r->acc, (size_t)B * acc * 4);
+    ALLOC(r->tok, (size_t)B * L * C * 2); ALLOC(r->ao, (size_t)B * C * 2);
+    ALLOC(r->q, (size_t)B * C * 4); ALLOC(r->kv, (size_t)B * L * 2 * C * 4);
+    // the keys the tower needs before it may run, instead of the ViT's
+    m->missing.erase(std::remove_if(m->missing.begin(), m->missing.end(), [](const std::string& k) { return k.rfind("visual.", 0) == 0; }), m->missing.end());
+    for (const RnConv& c : r->convs) {
+        m->missing.push_back(c.conv + ".weight");
+        for (const char* n : {".weight", ".bias", ".running_mean", ".running_var"}) m->missing.push_back(c.bn + n);
+    }
+    m->missing.push_back("visual.attnpool.positional_embedding");
+    for (const char* n : {"q_proj", "k_proj", "v_proj", "c_proj"})
+        for (const char* x : {".weight", ".bias"}) m->missing.push_back(std::string("visual.attnpool.") + n + x);
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_create_frozen_resnet(const mudpt_config* c, const mudpt_resnet_shape* rn, mudpt_model** out) {
+    ARG_CHECK(c && rn && out, "create_frozen_resnet: null argument");
+    ARG_CHECK(c->dtype != MUDPT_F32, "create_frozen_resnet: dtype MUDPT_F32: ResNet towers run in bf16 / fp16; the parity mode is not built for them");
+    ARG_CHECK(c->image_size >= 32 && c->image_size % 32 == 0, "create_frozen_resnet: image_size %d must be a positive multiple of 32 (the tower divides it by 32)", c->image_size);
+    ARG_CHECK(rn->layers1 >= 1 && rn->layers2 >= 1 && rn->layers3 >= 1 && rn->layers4 >= 1, "create_frozen_resnet: layers (%d, %d, %d, %d): every stage needs at least one block",
+              rn->layers1, rn->layers2, rn->layers3, rn->layers4);
+    ARG_CHECK(rn->width >= 32 && rn->width % 32 == 0, "create_frozen_resnet: width %d must be a positive multiple of 32: the stem has width / 2 channels and the GEMM needs N %% 16 == 0 "
+              "(RN50x4, width 80, has a 40-channel stem and is not built)", rn->width);
+    ARG_CHECK(rn->heads >= 1 && (32 * rn->width) % rn->heads == 0, "create_frozen_resnet: heads %d must be >= 1 and divide 32 * width = %d", rn->heads, 32 * rn->width);
+    ARG_CHECK(32 * rn->width / rn->heads == 64, "create_frozen_resnet: heads %d gives a head dimension of %d; the attention pool runs 64 (heads = 32 * width / 64, clip/model.py:687)",
+              rn->heads, 32 * rn->width / rn->heads);
+    ARG_CHECK(c->embed_dim >= 16 && c->embed_dim % 16 == 0, "create_frozen_resnet: embed_dim %d must be a positive multiple of 16 (c_proj's GEMM N)", c->embed_dim);
+    // behind the tower the handle is mudpt_create_frozen's; its ViT fields describe one 32 x 32 patch and no block, and are never run
+    mudpt_config f = *c;
+    f.variant = MUDPT_VARIANT_MUDPT; f.n_ctx = 0; f.depth = 1;
+    f.image_size = 32; f.patch = 32; f.v_width = 64; f.v_layers = 0; f.v_heads = 1;
+    return create_model(&f, nullptr, out, true, rn, c->image_size);
+}
+
 // every entry point that trains, takes embedded class prompts or shards the classes
 #define NOT_FROZEN(m, what) ARG_CHECK(!((m) && (m)->frozen), "%s: a frozen handle (mudpt_create_frozen) has no parameters, class-prompt embeddings or class shards", what)
 
 extern "C" int mudpt_destroy(mudpt_model* m) {
     if (!m) return MUDPT_OK;
     if (m->tok_table) (void)hipFree(m->tok_table);
+    delete m->rn;  // its device buffers are in m->allocs
     if (m->tmpl_tables) (void)hipFree(m->tmpl_tables);
     for (void* p : m->allocs) (void)hipFree(p);
     for (Tower* t : {&m->vis, &m->txt})
@@ -845,6 +995,55 @@ static int set_block_weight(mudpt_model* m, Tower& t, int layer, const std::stri
     return MUDPT_ERR_ARG;
 }
 
+// A "visual.*" tensor of a ResNet handle.  Convolutions and BatchNorm statistics are kept on the host as they arrive and folded at the next
+// forward (resnet_fold); the attention pool's tensors go to the device at once, its Linear weights in T
+static int resnet_set_weight(mudpt_model* m, const std::string& k, const float* data, size_t numel) {
+    Resnet& r = *m->rn;
+    const size_t C = r.C, L = r.L, e = m->cfg.embed_dim;
+    const char* key = k.c_str();
+#define EXPECT(n) ARG_CHECK(numel == (size_t)(n), "set_weight: %s expects %zu elements, got %zu", key, (size_t)(n), numel)
+    static const char* tracked = ".num_batches_tracked";
+    if (k.size() > strlen(tracked) && k.compare(k.size() - strlen(tracked), strlen(tracked), tracked) == 0) return MUDPT_OK;  // BatchNorm's step counter: eval mode never reads it
+    r.stale = true;
+    static const char* bn_names[4] = {".weight", ".bias", ".running_mean", ".running_var"};
+    for (RnConv& c : r.convs) {
+        if (k == c.conv + ".weight") { EXPECT((size_t)c.cout * c.cin * c.k * c.k); c.w.assign(data, data + numel); return MUDPT_OK; }
+        for (int i = 0; i < 4; ++i)
+            if (k == c.bn + bn_names[i]) { EXPECT(c.cout); c.bnp[i].assign(data, data + numel); return MUDPT_OK; }
+    }
+    const std::string ap = "visual.attnpool.";
+    if (k == ap + "positional_embedding") { EXPECT(L * C); return upload_f32(r.pos, data, numel); }
+    if (k == ap + "q_proj.weight") { EXPECT(C * C); return upload_lp(m->dtype, r.w_q, nullptr, data, C, C); }
+    if (k == ap + "k_proj.weight") { EXPECT(C * C); return upload_lp(m->dtype, r.w_kv, nullptr, data, C, C); }
+    if (k == ap + "v_proj.weight") { EXPECT(C * C); return upload_lp(m->dtype, (char*)r.w_kv + C * C * 2, nullptr, data, C, C); }
+    if (k == ap + "c_proj.weight") { EXPECT(e * C); return upload_lp(m->dtype, r.w_c, nullptr, data, e, C); }
+    if (k == ap + "q_proj.bias") { EXPECT(C); return upload_f32(r.b_q, data, numel); }
+    if (k == ap + "k_proj.bias") { EXPECT(C); return upload_f32(r.b_kv, data, numel); }
+    if (k == ap + "v_proj.bias") { EXPECT(C); return upload_f32(r.b_kv + C, data, numel); }
+    if (k == ap + "c_proj.bias") { EXPECT(e); return upload_f32(r.b_c, data, numel); }
+#undef EXPECT
+    set_error("set_weight: unknown key '%s' for a ResNet image tower with stages (%d, %d, %d, %d)", key, r.shape.layers1, r.shape.layers2, r.shape.layers3, r.shape.layers4);
+    return MUDPT_ERR_ARG;
+}
+
+// BatchNorm folding + packing of every convolution, on the host in fp64, and the upload: at the first forward after a "visual.*" tensor
+// arrived.  The stream is drained first: a forward in flight may still read the weights this overwrites
+static int resnet_fold(mudpt_model* m, hipStream_t s) {
+    Resnet& r = *m->rn;
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<uint16_t> wp;
+    std::vector<float> bp;
+    for (const RnConv& c : r.convs) {
+        wp.assign((size_t)c.np * c.ldk, 0);
+        bp.assign(c.np, 0.f);
+        conv_pack(m->dtype, c.w.data(), c.bnp[0].data(), c.bnp[1].data(), c.bnp[2].data(), c.bnp[3].data(), c.cout, c.cin, c.k, c.ldk, wp.data(), bp.data());
+        HIP_TRY(hipMemcpy(c.w_dev, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.b_dev, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+    }
+    r.stale = false;
+    return MUDPT_OK;
+}
+
 extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* data, size_t numel) {
     ARG_CHECK(m && key && data, "set_weight: null argument");
     const mudpt_config& c = m->cfg;
@@ -859,7 +1058,8 @@ extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* da
         return set_block_weight(m, t, atoi(rest.substr(0, dot).c_str()), rest.substr(dot + 1), data, numel);
     };
 #define EXPECT(n) ARG_CHECK(numel == (size_t)(n), "set_weight: %s expects %zu elements, got %zu", key, (size_t)(n), numel)
-    if (k.rfind("visual.transformer.resblocks.", 0) == 0) rc = blk("visual.transformer.resblocks.", m->vis);
+    if (m->rn && k.rfind("visual.", 0) == 0) rc = resnet_set_weight(m, k, data, numel);
+    else if (k.rfind("visual.transformer.resblocks.", 0) == 0) rc = blk("visual.transformer.resblocks.", m->vis);
     else if (k.rfind("transformer.resblocks.", 0) == 0) rc = blk("transformer.resblocks.", m->txt);
     else if (k == "visual.conv1.weight") {
         EXPECT(dv * 3 * c.patch * c.patch);
@@ -1566,9 +1766,78 @@ static int zero_unused_rows(float* dprompt, int used, int R, int d, hipStream_t 
     return MUDPT_OK;
 }
 
+// ---- the ResNet image tower (clip/model.py:17-161), NHWC in T; the rounding sites: resnet.hip's header ----
+// One folded convolution: `in` is B images of H x H pixels with cin channels at channel stride ld_in (or, planar, the fp32 pixels); a 3 x 3 takes
+// its patch rows, a 1 x 1 the activation as it lies (its K = ldk may reach past cin into the producer's zero channels).  out [B Ho Ho, np] =
+// T(act(acc + bias + residual))
+static int resnet_conv(mudpt_model* m, const RnConv& c, const void* in, int ld_in, bool planar, int B, int H, int stride, const void* res, int ldres, bool relu,
+                       void* out, hipStream_t s) {
+    Resnet& r = *m->rn;
+    const int Ho = c.k == 3 ? (H - 1) / stride + 1 : H, M = B * Ho * Ho;
+    GemmArgs g;
+    if (c.k == 3) {
+        TRY(launch_im2col(m->dtype, in, planar, B, H, H, c.cin, ld_in, stride, r.rows, c.ldk, s));
+        g.A = r.rows; g.lda = c.ldk;
+    } else {
+        ARG_CHECK(ld_in >= c.ldk, "resnet: %s reads %d channels of an activation with %d", c.conv.c_str(), c.ldk, ld_in);
+        g.A = in; g.lda = ld_in;
+    }
+    g.B = c.w_dev; g.ldb = c.ldk; g.M = M; g.N = c.np; g.K = c.ldk; g.out0 = r.acc; g.ldo0 = c.np;
+    TRY(gemm_call(m, EPI_STORE_F32, g, s));
+    return launch_bias_act(m->dtype, r.acc, c.np, c.b_dev, res, ldres, out, c.np, M, c.np, relu, s);
+}
+
+// ModifiedResNet.forward (clip/model.py:145-161) in eval mode -> m->img_f [B, e]
+static int resnet_forward(mudpt_model* m, const float* images, int B, hipStream_t s) {
+    Resnet& r = *m->rn;
+    if (r.stale) TRY(resnet_fold(m, s));
+    const int dt = m->dtype, e = m->cfg.embed_dim, C = r.C, L = r.L;
+    void *X = r.act[0], *Y = r.act[1], *T1 = r.act[2], *T2 = r.act[3], *T3 = r.act[4], *ID = r.act[5], *XP = r.act[6];
+    // the stem (:146-151): three 3 x 3 convolutions, the first of stride 2 on the pixels, and AvgPool2d(2)
+    int H = r.S / 2;
+    TRY(resnet_conv(m, r.convs[0], images, 0, true, B, r.S, 2, nullptr, 0, true, T1, s));
+    TRY(resnet_conv(m, r.convs[1], T1, r.convs[0].np, false, B, H, 1, nullptr, 0, true, T2, s));
+    TRY(resnet_conv(m, r.convs[2], T2, r.convs[1].np, false, B, H, 1, nullptr, 0, true, T1, s));
+    int ldx = r.convs[2].np;
+    TRY(launch_avgpool2d(dt, T1, ldx, X, ldx, B, H, H, ldx, 2, s));
+    H /= 2;
+    // the four stages of Bottleneck (:49-62)
+    for (const RnBlock& b : r.blocks) {
+        const RnConv &c1 = r.convs[b.conv1], &c2 = r.convs[b.conv2], &c3 = r.convs[b.conv3];
+        const int Ho = H / b.stride;
+        TRY(resnet_conv(m, c1, X, ldx, false, B, H, 1, nullptr, 0, true, T1, s));
+        TRY(resnet_conv(m, c2, T1, c1.np, false, B, H, 1, nullptr, 0, true, T2, s));
+        const void* t = T2;
+        if (b.stride > 1) { TRY(launch_avgpool2d(dt, T2, c2.np, T3, c2.np, B, H, H, c2.np, b.stride, s)); t = T3; }
+        const void* id = X;
+        int ldid = ldx;
+        if (b.down >= 0) {
+            const RnConv& cd = r.convs[b.down];
+            const void* x = X;
+            if (b.stride > 1) { TRY(launch_avgpool2d(dt, X, ldx, XP, ldx, B, H, H, ldx, b.stride, s)); x = XP; }
+            TRY(resnet_conv(m, cd, x, ldx, false, B, Ho, 1, nullptr, 0, false, ID, s));
+            id = ID; ldid = cd.np;
+        }
+        TRY(resnet_conv(m, c3, t, c2.np, false, B, Ho, 1, id, ldid, true, Y, s));
+        std::swap(X, Y);
+        ldx = c3.np; H = Ho;
+    }
+    // AttentionPool2d (:75-98): the mean token in front, + positional_embedding; q from the mean token alone, k / v from all L tokens
+    ARG_CHECK(ldx == C && H * H + 1 == L, "resnet: the tower ends at %d x %d x %d, the attention pool expects %d tokens of %d", H, H, ldx, L, C);
+    TRY(launch_attnpool_tokens(dt, X, ldx, r.pos, r.tok, C, B, L - 1, C, s));
+    GemmArgs q; q.A = r.tok; q.lda = L * C; q.B = r.w_q; q.ldb = C; q.M = B; q.N = C; q.K = C; q.bias = r.b_q; q.out0 = r.q; q.ldo0 = C;
+    TRY(gemm_call(m, EPI_STORE_F32, q, s));
+    GemmArgs kv; kv.A = r.tok; kv.lda = C; kv.B = r.w_kv; kv.ldb = C; kv.M = B * L; kv.N = 2 * C; kv.K = C; kv.bias = r.b_kv; kv.out0 = r.kv; kv.ldo0 = 2 * C;
+    TRY(gemm_call(m, EPI_STORE_F32, kv, s));
+    TRY(launch_attnpool_attend(dt, r.q, C, r.kv, r.kv + C, 2 * C, r.ao, C, B, L, r.shape.heads, s));
+    GemmArgs cp; cp.A = r.ao; cp.lda = C; cp.B = r.w_c; cp.ldb = C; cp.M = B; cp.N = e; cp.K = C; cp.bias = r.b_c; cp.out0 = m->img_f; cp.ldo0 = e;
+    return gemm_call(m, EPI_STORE_F32, cp, s);
+}
+
 // Vision tower forward, clip/model.py:526-553 (MuDPT: prompt rows appended before ln_pre, deep prompts spliced per block) or
 // clip/model.py:478-496 (CoCoOp: the vanilla ViT, no prompt rows) -> m->img_f [B, e]
 static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_t s) {
+    if (m->rn) return resnet_forward(m, images, B, s);  // a frozen handle with the ResNet tower (mudpt_create_frozen_resnet)
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, n = m->vis.n, D1 = m->vis.D1, P = n_patches(c), Lv = m->vis.L, K0 = patch_k0(c);
     const PromptRoute pr = prompt_route(m, m->vis);
@@ -2829,3 +3098,31 @@ extern "C" int mudpt_augment_check(const int64_t* images_host, int32_t n_images,
     return MUDPT_OK;
 }
 extern "C" int mudpt_augment_form(int32_t x_len, int32_t x_out, int32_t y_len, int32_t y_out, int32_t size) { return augment_form(x_len, x_out, y_len, y_out, size); }
+
+// ---- the ResNet tower's memory movers (resnet.hip) and the host-only weight packing its fold runs (include/mudpt.h lists the operands) ----
+extern "C" int mudpt_im2col(int32_t dtype, const void* src, int32_t src_planar, int32_t B, int32_t H, int32_t W, int32_t C, int32_t lds, int32_t stride, void* dst,
+                            int32_t ldk, void* stream) {
+    return launch_im2col(dtype, src, src_planar != 0, B, H, W, C, lds, stride, dst, ldk, (hipStream_t)stream);
+}
+extern "C" int mudpt_bias_act(int32_t dtype, const float* acc, int32_t ldacc, const float* bias, const void* residual, int32_t ldres, void* out, int32_t ldo, int32_t M,
+                              int32_t N, int32_t relu, void* stream) {
+    return launch_bias_act(dtype, acc, ldacc, bias, residual, ldres, out, ldo, M, N, relu != 0, (hipStream_t)stream);
+}
+extern "C" int mudpt_avgpool2d(int32_t dtype, const void* src, int32_t lds, void* dst, int32_t ldo, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k, void* stream) {
+    return launch_avgpool2d(dtype, src, lds, dst, ldo, B, H, W, C, k, (hipStream_t)stream);
+}
+extern "C" int mudpt_attnpool_tokens(int32_t dtype, const void* src, int32_t lds, const float* pos, void* dst, int32_t ldo, int32_t B, int32_t HW, int32_t C, void* stream) {
+    return launch_attnpool_tokens(dtype, src, lds, pos, dst, ldo, B, HW, C, (hipStream_t)stream);
+}
+extern "C" int mudpt_attnpool_attend(int32_t dtype, const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, void* out, int32_t ldo, int32_t B, int32_t L,
+                                     int32_t H, void* stream) {
+    return launch_attnpool_attend(dtype, q, ldq, k, v, ldkv, out, ldo, B, L, H, (hipStream_t)stream);
+}
+extern "C" int mudpt_conv_pack(int32_t dtype, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, int32_t cout, int32_t cin, int32_t k,
+                               int32_t ldk, void* w_out, float* bias_out) {
+    ARG_CHECK(dtype == DT_BF16 || dtype == DT_F16, "conv_pack: unknown dtype %d", dtype);
+    ARG_CHECK(w && gamma && beta && mean && var && w_out && bias_out, "conv_pack: null argument");
+    ARG_CHECK(cout > 0 && cin > 0 && (k == 1 || k == 3) && ldk >= k * k * cin, "conv_pack: bad shape cout=%d cin=%d k=%d ldk=%d (k 1 | 3, ldk >= k k cin)", cout, cin, k, ldk);
+    conv_pack(dtype, w, gamma, beta, mean, var, cout, cin, k, ldk, (uint16_t*)w_out, bias_out);
+    return MUDPT_OK;
+}

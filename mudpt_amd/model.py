@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -34,10 +34,27 @@ class ModelShape:
     embed_dim: int = 512
     n_ctx: int = 4
     depth: int = 12
+    # CLIP's ResNet image tower (clip/model.py:101-161): the Bottleneck blocks of its four stages; () = a ViT.  Then v_width is the tower's
+    # `width` (64 for RN50), v_heads the attention pool's heads (32 width / 64), v_layers the blocks in all and patch its stride, 32
+    v_stages: Tuple[int, ...] = ()
+
+    @property
+    def resnet(self) -> bool:
+        return len(self.v_stages) > 0
 
     @staticmethod
     def from_state_dict(sd: Dict[str, torch.Tensor], n_ctx: int, depth: int) -> "ModelShape":
-        """Same inference rules as clip/model.py:881-904 build_model (ViT branch)."""
+        """Same inference rules as clip/model.py:881-904 build_model: the ViT branch, or -- without "visual.proj" -- the ResNet branch (:890-897)."""
+        if "visual.proj" not in sd:
+            stages = tuple(len(set(k.split(".")[2] for k in sd if k.startswith(f"visual.layer{b}."))) for b in (1, 2, 3, 4))
+            width = sd["visual.layer1.0.conv1.weight"].shape[0]
+            grid = round((sd["visual.attnpool.positional_embedding"].shape[0] - 1) ** 0.5)
+            assert grid ** 2 + 1 == sd["visual.attnpool.positional_embedding"].shape[0]
+            t_width = sd["ln_final.weight"].shape[0]
+            return ModelShape(image_size=32 * grid, patch=32, v_width=width, v_layers=sum(stages), v_heads=width * 32 // 64, t_width=t_width,
+                              t_layers=len(set(k.split(".")[2] for k in sd if k.startswith("transformer.resblocks"))), t_heads=t_width // 64,
+                              ctx_len=sd["positional_embedding"].shape[0], embed_dim=sd["text_projection"].shape[1], n_ctx=n_ctx, depth=depth,
+                              v_stages=stages)
         v_width = sd["visual.conv1.weight"].shape[0]
         v_layers = len([k for k in sd if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
         patch = sd["visual.conv1.weight"].shape[-1]
@@ -53,7 +70,8 @@ class ModelShape:
     def from_config(cfg, n_ctx: int, depth: int) -> "ModelShape":
         """The backbone dimensions of ``cfg`` -- any object with this class's backbone fields -- with the prompt config given here: a
         variant decides its own n_ctx / depth."""
-        return ModelShape(**{f: getattr(cfg, f) for f in ModelShape.__dataclass_fields__ if f not in ("n_ctx", "depth")}, n_ctx=n_ctx, depth=depth)
+        return ModelShape(**{f: getattr(cfg, f) for f in ModelShape.__dataclass_fields__ if f not in ("n_ctx", "depth", "v_stages")}, n_ctx=n_ctx, depth=depth,
+                          v_stages=tuple(getattr(cfg, "v_stages", ())))
 
 
 def umudpt_init_tensors(n_ctx: int, depth: int, d_t: int, d_v: int, ctx_rows: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -246,6 +264,7 @@ class CustomCLIP(LibraryModel):
         # "uumudpt": trainers/uumudpt.py's CustomCLIP (UMuDPT plus the vision tower's own visual_ctx, visual_ctx_deep_prompts and a second
         # generator that turns those into an addend of the text deep prompts): 40 trainables, "uumudpt_prompt_learner.*" then
         # "image_encoder.visual_ctx*"; shape.n_ctx (1..16) / depth are TRAINER.UUMUDPT.N_CTX / DEEP_PROMPT_DEPTH
+        assert not shape.resnet, "ResNet backbones run on the frozen handle only (ZeroshotCLIP, ZeroshotCLIP2, feature extraction)"
         if variant == "coop_csc" and ctx_token_ids is not None:
             variant = "coop"  # trainers/coop.py:52-61: the CTX_INIT path builds one shared context whatever CSC says
         assert (prompt_shape is not None) == (variant in ("vpt", "mpt")), "prompt_shape is the VPT / MPT setting, and they need it"

@@ -57,24 +57,66 @@ def synthetic_tokenized_prompts(n_cls: int, n_ctx: int = 4, ctx_len: int = 77, s
     return tok
 
 
+# the ResNet backbones of clip.load (clip/clip.py:32-36) the library runs, as ModelShape(**RESNET_SHAPES[name]); RN50x4 (width 80) is not built
+RESNET_SHAPES = {
+    "RN50": dict(image_size=224, patch=32, v_width=64, v_layers=16, v_heads=32, v_stages=(3, 4, 6, 3), embed_dim=1024),
+    "RN101": dict(image_size=224, patch=32, v_width=64, v_layers=33, v_heads=32, v_stages=(3, 4, 23, 3), embed_dim=512),
+    "RN50x16": dict(image_size=384, patch=32, v_width=96, v_layers=40, v_heads=48, v_stages=(6, 8, 18, 8), embed_dim=768, t_width=768, t_heads=12),
+    "RN50x64": dict(image_size=448, patch=32, v_width=128, v_layers=64, v_heads=64, v_stages=(3, 15, 36, 10), embed_dim=1024, t_width=1024, t_heads=16),
+}
+
+
+def resnet_state_table(shape: ModelShape):
+    """(key, tensor shape, init) of the "visual.*" entries of a CLIP ResNet state dict (clip/model.py:17-161) in the reference's module order.
+    Convolutions are N(0, 1 / fan_in): activations stay O(1) to O(10) through all stages (2 / fan_in reaches 1e5 at RN50, past fp16); BatchNorm is the identity it is before training
+    (weight and running_var ones, bias and running_mean zeros); the attention pool as clip/model.py:786-791."""
+    w, C = shape.v_width, 32 * shape.v_width
+    rows = []
+
+    def conv_bn(conv, bn, cin, cout, k):
+        rows.append((conv + ".weight", (cout, cin, k, k), (cin * k * k) ** -0.5))
+        rows.extend([(bn + ".weight", (cout,), "ones"), (bn + ".bias", (cout,), "zeros"), (bn + ".running_mean", (cout,), "zeros"),
+                     (bn + ".running_var", (cout,), "ones")])
+    conv_bn("visual.conv1", "visual.bn1", 3, w // 2, 3)
+    conv_bn("visual.conv2", "visual.bn2", w // 2, w // 2, 3)
+    conv_bn("visual.conv3", "visual.bn3", w // 2, w, 3)
+    inplanes = w
+    for s, blocks in enumerate(shape.v_stages):
+        planes = w << s
+        for i in range(blocks):
+            p = f"visual.layer{s + 1}.{i}."
+            conv_bn(p + "conv1", p + "bn1", inplanes, planes, 1)
+            conv_bn(p + "conv2", p + "bn2", planes, planes, 3)
+            conv_bn(p + "conv3", p + "bn3", planes, 4 * planes, 1)
+            if i == 0:  # stride > 1 or inplanes != 4 planes (clip/model.py:41): the first block of every stage
+                conv_bn(p + "downsample.0", p + "downsample.1", inplanes, 4 * planes, 1)
+            inplanes = 4 * planes
+    rows.append(("visual.attnpool.positional_embedding", ((shape.image_size // 32) ** 2 + 1, C), C ** -0.5))
+    for n, out in (("k_proj", C), ("q_proj", C), ("v_proj", C), ("c_proj", shape.embed_dim)):
+        rows += [(f"visual.attnpool.{n}.weight", (out, C), C ** -0.5), (f"visual.attnpool.{n}.bias", (out,), 0.02)]
+    return rows
+
+
 def clip_state_table(shape: ModelShape):
-    """(key, tensor shape, init) of every entry of a CLIP ViT state dict (clip/model.py:667-808): init is a std for N(0, std^2)
-    entries, "ones" / "zeros" for LayerNorm affine terms and attention biases."""
+    """(key, tensor shape, init) of every entry of a CLIP state dict (clip/model.py:667-808), ViT or -- ``shape.resnet`` -- ResNet image
+    tower: init is a std for N(0, std^2) entries, "ones" / "zeros" for LayerNorm / BatchNorm terms and attention biases."""
     dv, dt, e = shape.v_width, shape.t_width, shape.embed_dim
     P = (shape.image_size // shape.patch) ** 2
-    rows = [
+    rows = resnet_state_table(shape) if shape.resnet else [
         ("visual.conv1.weight", (dv, 3, shape.patch, shape.patch), (3 * shape.patch ** 2) ** -0.5),
         ("visual.class_embedding", (dv,), dv ** -0.5),
         ("visual.positional_embedding", (P + 1, dv), dv ** -0.5),
         ("visual.ln_pre.weight", (dv,), "ones"), ("visual.ln_pre.bias", (dv,), "zeros"),
         ("visual.ln_post.weight", (dv,), "ones"), ("visual.ln_post.bias", (dv,), "zeros"),
         ("visual.proj", (dv, e), dv ** -0.5),
+    ]
+    rows += [
         ("token_embedding.weight", (VOCAB, dt), 0.02),
         ("positional_embedding", (shape.ctx_len, dt), 0.01),
         ("ln_final.weight", (dt,), "ones"), ("ln_final.bias", (dt,), "zeros"),
         ("text_projection", (dt, e), dt ** -0.5),
     ]
-    for prefix, d, layers in (("visual.transformer", dv, shape.v_layers), ("transformer", dt, shape.t_layers)):
+    for prefix, d, layers in (("visual.transformer", dv, 0 if shape.resnet else shape.v_layers), ("transformer", dt, shape.t_layers)):
         for i in range(layers):
             p = f"{prefix}.resblocks.{i}."
             rows += [(p + "ln_1.weight", (d,), "ones"), (p + "ln_1.bias", (d,), "zeros"),

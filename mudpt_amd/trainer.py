@@ -54,8 +54,9 @@ def open_backbone(cfg):
     shape's n_ctx / depth are placeholders: every plugin sets its own (dataclasses.replace)."""
     print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")
     state = load_clip_state_dict(cfg)
-    if state is None:
-        return ModelShape(), synth.random_clip_state(ModelShape(), cfg.MODEL.BACKBONE.SYNTHETIC_SEED)
+    if state is None:  # a ResNet name of clip.load (clip/clip.py:32-36) selects that tower; every other name the default ViT-B/16, as before
+        shape = ModelShape(**synth.RESNET_SHAPES.get(cfg.MODEL.BACKBONE.NAME, {}))
+        return shape, synth.random_clip_state(shape, cfg.MODEL.BACKBONE.SYNTHETIC_SEED)
     return ModelShape.from_state_dict(state, 4, 1), state
 
 

@@ -1,5 +1,6 @@
 """Drop-in ``ZeroshotCLIP`` and ``ZeroshotCLIP2`` plugins -- the reference's ``trainers/zsclip.py:51-118`` -- and ``FrozenCLIP``, the module
-they run on: CLIP as it was trained, nothing to learn, over a frozen handle of libmudpt_hip.so (``mudpt_create_frozen``).
+they run on: CLIP as it was trained, nothing to learn, over a frozen handle of libmudpt_hip.so (``mudpt_create_frozen``; with a ResNet image
+tower -- RN50, RN101, RN50x16, RN50x64 -- ``mudpt_create_frozen_resnet``).
 
 The class prompts reach the library as token ids ``[T, C, ctx_len]``, one set per prompt template; the token embedding is looked up on the
 device, the text tower runs once per template, and the text features -- ``f / |f|`` for one template (zsclip.py:67-71),
@@ -11,6 +12,7 @@ The two template tables below restate the reference's data (trainers/zsclip.py:3
 """
 from __future__ import annotations
 
+import ctypes as C
 import dataclasses
 from typing import Dict, List, Optional
 
@@ -75,13 +77,19 @@ class FrozenCLIP(LibraryModel):
         if tokens.dim() == 2:
             tokens = tokens[None]
         assert tokens.dim() == 3 and tokens.shape[2] == shape.ctx_len, f"tokens must be [T, C, {shape.ctx_len}], got {tuple(tokens.shape)}"
+        def create(lib, cfg, h):
+            if shape.resnet:  # clip/model.py:686-694: a checkpoint without "visual.proj" carries the ResNet image tower
+                rn = capi.ResnetShape(*shape.v_stages, shape.v_width, shape.v_heads)
+                capi.check(lib.mudpt_create_frozen_resnet(cfg, C.byref(rn), h), "create_frozen_resnet")
+            else:
+                capi.check(lib.mudpt_create_frozen(cfg, h), "create_frozen")
+
         # the knobs go in before the tokens: the layout knobs are read by mudpt_set_text_tokens
-        super().__init__(shape, tokens.shape[1], max_batch, dtype, device, knobs,
-                         lambda lib, cfg, h: capi.check(lib.mudpt_create_frozen(cfg, h), "create_frozen"), frozen=True)
+        super().__init__(shape, tokens.shape[1], max_batch, dtype, device, knobs, create, frozen=True)
         self.tokens = tokens.to("cpu", torch.int32).contiguous()
         self.n_templates = int(tokens.shape[0])
         for k, v in clip_state.items():  # clip/model.py:919 load_state_dict
-            if isinstance(v, torch.Tensor):
+            if isinstance(v, torch.Tensor) and v.is_floating_point():  # not BatchNorm's num_batches_tracked, nor a JIT archive's integer attributes
                 self.set_weight(k, v)
         if tokens.numel():  # no tokens: encode_image alone (the linear-probe extractor)
             self.set_tokens(self.tokens)
