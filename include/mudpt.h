@@ -73,6 +73,10 @@
  *   mudpt_create_frozen_resnet / mudpt_set_weight   clip/model.py:686-694, 890-897  build_model's ResNet branch; the "visual.*" keys of ModifiedResNet
  *   mudpt_encode_image / mudpt_forward / _ex         clip/model.py:17-161  ModifiedResNet.forward in eval mode: the stem, four stages of Bottleneck,
  *                                        AttentionPool2d; BatchNorm folded into the convolutions, every convolution an im2col + MFMA GEMM
+ * A handle made by mudpt_create_resnet trains CoOp / CoCoOp on that tower (the backbone of CoOp's few-shot tables, scripts/coop/main.sh): the rows of
+ * MUDPT_VARIANT_COOP / _COOP_CSC / _COCOOP above with ModifiedResNet as the frozen image encoder:
+ *   mudpt_create_resnet / mudpt_set_weight           trainers/coop.py:20-37, cocoop.py:22-40  load_clip_to_cpu with an RN* backbone
+ *   mudpt_forward / _ex / mudpt_forward_backward     trainers/coop.py:212-226,281-296, cocoop.py:178-198  the tower forward only, no image gradient
  * Frozen, CoOp and CoCoOp handles also run the test pass from cached image features:
  *   mudpt_forward_features               trainers/zsclip.py:74-79, coop.py:212-223, cocoop.py:178-188 behind their clip_model.visual(image)
  *   mudpt_image_features                 lpclip/feat_extractor.py:125-137  the features of the last inference forward, for {dir}/{dataset}/{split}.npz
@@ -199,6 +203,17 @@ typedef struct mudpt_resnet_shape {
     int32_t heads;                              /* of the attention pool: 32 width / 64 */
 } mudpt_resnet_shape;
 int mudpt_create_frozen_resnet(const mudpt_config* cfg, const mudpt_resnet_shape* rn, mudpt_model** out);
+/* A TRAINABLE handle with that tower: what mudpt_create makes for MUDPT_VARIANT_COOP, _COOP_CSC and _COCOOP, the image tower set up as
+ * mudpt_create_frozen_resnet sets it up.  Both trainers keep the image encoder frozen and prompt-free (trainers/coop.py:212-226,
+ * cocoop.py:178-198), so the tower runs forward only where the vanilla ViT would; embed_dim need not equal t_width, CoCoOp's meta_net keeps
+ * its hidden width embed_dim / 16 (cocoop.py:104).  Read from cfg: image_size, embed_dim, n_ctx, n_cls, max_batch, dtype, variant and the text
+ * shape; NOT read: patch, v_width, v_layers, v_heads, depth.  Everything a ViT CoOp / CoCoOp handle takes, this one takes: mudpt_set_weight
+ * ("visual.*": the keys above, folded and refolded as above), mudpt_set_class_prompts, mudpt_set_class_token_position, mudpt_bind_params,
+ * mudpt_forward / _ex, mudpt_forward_backward, mudpt_forward_features, mudpt_image_features, mudpt_sgd_step.  The training head asks for no
+ * image gradient (mudpt_head_ex with dimg = NULL), and neither that buffer nor any ViT block activation is allocated.
+ * MUDPT_ERR_ARG before any GPU call: any other variant ("... its prompts live inside a ViT ..."), and everything
+ * mudpt_create_frozen_resnet refuses, in the same words. */
+int mudpt_create_resnet(const mudpt_config* cfg, const mudpt_resnet_shape* rn, mudpt_model** out);
 int mudpt_destroy(mudpt_model* m);
 
 /* Frozen weight by OpenAI CLIP state-dict key ("visual.transformer.resblocks.0.attn.in_proj_weight", ...),
@@ -583,7 +598,11 @@ int mudpt_attention_bwd_sel(int32_t dtype, const void* qkv, const void* out, con
 /* mudpt_head with the state the model keeps between calls in the caller's hands: txt_n [C, e] / txt_inv [C] (txt = NULL: reuse them as the
  * previous call left them -- the fused path only), B_total > 0 (this call is a chunk of a batch of B_total images: gradients are scaled by
  * 1 / B_total and `loss` is NOT written, the caller takes the mean of the row losses), row_loss [B] (may be NULL).  path 0: the dispatch of
- * mudpt_head; 1: force the unfused launchers.  *path_taken (HOST, may be NULL) = 0 if the fused kernels ran, 1 if the unfused ones. */
+ * mudpt_head; 1: force the unfused launchers.  *path_taken (HOST, may be NULL) = 0 if the fused kernels ran, 1 if the unfused ones.
+ * Training (labels given) needs `loss`; dimg may be NULL: no image gradient is computed (the head of a frozen, prompt-free image tower, as
+ * on a mudpt_create_resnet handle).  Every other output is then bit-identical to the call with dimg.  The fused training kernels take a
+ * shape if e % 16 == 0, e <= 1024 and ((dimg ? 32 : 16) e + 16 roundup(C, 16)) 4 + 256 <= 163840 bytes of LDS: without dimg that is the
+ * forward's rule plus e <= 1024 (e = 1024: C <= 1520 instead of 496; e = 512: C <= 2032 instead of 1520). */
 int mudpt_head_ex(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
                   int32_t e, float* txt_n, float* txt_inv, float* logits, float* loss, float* row_loss, float* dimg, float* dtxt, int32_t path,
                   int32_t* path_taken, void* stream);

@@ -482,17 +482,18 @@ int launch_head_fwd(const HeadArgs& a, hipStream_t s) {
 
 int launch_head_bwd(const HeadArgs& a, hipStream_t s) {
     if (int e = check_head(a)) return e;
-    ARG_CHECK(a.labels && a.loss && a.dlogits && a.row_loss && a.dimg, "head bwd: null operand");
+    ARG_CHECK(a.labels && a.loss && a.dlogits && a.row_loss, "head bwd: null operand");  // dimg null: no image gradient
     ARG_CHECK(a.B_total <= 0 || a.B_total >= a.B, "head bwd: B_total=%d is smaller than its chunk of B=%d rows", a.B_total, a.B);
     const int Bt = a.B_total > 0 ? a.B_total : a.B;  // chunked over the images, as in the fused head: the caller then takes the mean (launch_mean)
     hipLaunchKernelGGL(ce_rows_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.logits, a.labels, a.row_loss, a.dlogits, a.B, a.C, a.grad_scale / Bt);
     if (a.B_total <= 0) hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, a.row_loss, a.B, a.loss);
     HIP_TRY(hipGetLastError());
-    // d img_n = scale * dlogits . txt_n ; d txt_n = scale * dlogits^T . img_n  (dtxt null: the text side has nothing to learn, VPT)
-    if (int e = launch_sgemm(false, false, a.B, a.e, a.C, a.scale, a.dlogits, a.C, a.txt_n, a.e, 0.f, a.dimg, a.e, nullptr, s)) return e;
+    // d img_n = scale * dlogits . txt_n ; d txt_n = scale * dlogits^T . img_n  (dtxt null: the text side has nothing to learn, VPT; dimg null: neither has the image side)
+    if (a.dimg)
+        if (int e = launch_sgemm(false, false, a.B, a.e, a.C, a.scale, a.dlogits, a.C, a.txt_n, a.e, 0.f, a.dimg, a.e, nullptr, s)) return e;
     if (a.dtxt)
         if (int e = launch_sgemm(true, false, a.C, a.e, a.B, a.scale, a.dlogits, a.C, a.img_n, a.e, 0.f, a.dtxt, a.e, nullptr, s)) return e;
-    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.dimg, a.img_n, a.img_inv, a.B, a.e);
+    if (a.dimg) hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.dimg, a.img_n, a.img_inv, a.B, a.e);
     if (a.dtxt) hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((a.C + 3) / 4), dim3(256), 0, s, a.dtxt, a.txt_n, a.txt_inv, a.C, a.e);
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;

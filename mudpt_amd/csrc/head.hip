@@ -7,7 +7,8 @@
 // cross-entropy / dlogits never leave the workgroup that made the logit rows:
 //   head_rows_kernel  (one workgroup per 16 images): normalise the 16 image rows -> LDS; logit tile [16, C] by MFMA -> LDS + HBM;
 //       [training] per-row log-sum-exp, loss row, dlogits = (softmax - onehot) * gscale in place; d(normalised image features) =
-//       scale * dlogits . txt_n by MFMA; backward of the normalisation -> dimg.
+//       scale * dlogits . txt_n by MFMA; backward of the normalisation -> dimg.  [training, HeadArgs::dimg null: a frozen image tower
+//       with nothing trainable in front of it] the kernel ends behind dlogits: no gradient tile in LDS, no second contraction.
 //   head_dtxt_kernel  (one workgroup per 16 classes, training): d(normalised text features) = scale * dlogits^T . img_n by MFMA
 //       (images in ascending order: a fixed summation order), backward of the normalisation -> dtxt.
 // plus the existing row-normalisation of the C text features and the fixed-order mean of the loss rows: 4 launches instead of 9.
@@ -50,12 +51,14 @@ __device__ inline void l2norm_bwd_row(const float* d, const float* n, float inv,
     for (int k = lane; k < e; k += 64) out[k] = inv * (d[k] - n[k] * s);
 }
 
-template <bool TRAIN>
+// DIMG = false (training only): the image features need no gradient -- steps 4 and 5 and their [16][e] tile are left out, steps 1 to 3 are
+// the same instructions in the same order, so everything they write is bit-identical to the form with dimg
+template <bool TRAIN, bool DIMG = TRAIN>
 __global__ __launch_bounds__(HEAD_WAVES * 64) void head_rows_kernel(HeadArgs p, int Cpad) {
     extern __shared__ __attribute__((aligned(16))) float hsm[];
     float* In = hsm;                          // [16][e] normalised image rows
     float* Zt = In + HEAD_ROWS * p.e;         // [16][Cpad] logits, then dlogits
-    float* Dn = Zt + HEAD_ROWS * Cpad;        // [16][e] d(normalised image features)   (TRAIN only)
+    float* Dn = Zt + HEAD_ROWS * Cpad;        // [16][e] d(normalised image features)   (DIMG only)
     __shared__ float inv_s[HEAD_ROWS];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -138,6 +141,7 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_rows_kernel(HeadArgs p, 
             if (k < C && p.dlogits) p.dlogits[(size_t)r * C + k] = d;
         }
     }
+    if constexpr (!DIMG) return;
     __syncthreads();
 
     // ---- 4. d(normalised image features)[16, e] = scale * dlogits[16, C] . txt_n[C, e]: e tiles over the waves, 4 at a time -------
@@ -213,10 +217,11 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_dtxt_kernel(HeadArgs p) 
 
 static int head_lds_bytes(const HeadArgs& a, bool train) {
     const int Cpad = (a.C + 15) / 16 * 16;
-    return (HEAD_ROWS * a.e * (train ? 2 : 1) + HEAD_ROWS * Cpad) * 4;
+    return (HEAD_ROWS * a.e * (train && a.dimg ? 2 : 1) + HEAD_ROWS * Cpad) * 4;  // the gradient tile: only where dimg is asked for
 }
 // true if the fused kernels can hold a 16-row problem in LDS (otherwise the caller keeps the unfused fp32 path of elementwise.hip)
 // Training: head_dtxt_kernel keeps a [16][e] fp32 tile in its 64 KB LDS allowance, so e <= 1024 there (launch_head_fused_train refuses more).
+// Training without dimg needs the forward's LDS: e = 1024 fits up to Cpad 1520 (with dimg: 496), e = 512 up to 2032 (1520).
 bool head_fused_fits(const HeadArgs& a, bool train) {
     return a.e > 0 && a.e % 16 == 0 && (!train || a.e <= HEAD_MAX_E_TRAIN) && head_lds_bytes(a, train) + 256 <= 163840;
 }
@@ -236,8 +241,8 @@ int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s) {
 
 // forward + mean cross-entropy + backward to the RAW features in one pass over the logit rows (logits are written too)
 int launch_head_fused_train(const HeadArgs& a, hipStream_t s) {
-    ARG_CHECK(a.img && a.logits && a.txt_n && a.txt_inv && a.img_n && a.img_inv && a.labels && a.loss && a.dlogits && a.row_loss && a.dimg,
-              "head: null operand");
+    ARG_CHECK(a.img && a.logits && a.txt_n && a.txt_inv && a.img_n && a.img_inv && a.labels && a.loss && a.dlogits && a.row_loss,
+              "head: null operand");  // dimg may be null: no image gradient
     ARG_CHECK(a.B > 0 && a.C > 0 && a.e > 0 && a.e <= HEAD_MAX_E_TRAIN, "head: bad shape B=%d C=%d e=%d", a.B, a.C, a.e);
     ARG_CHECK(a.B_total <= 0 || a.B_total >= a.B, "head: B_total=%d is smaller than its chunk of B=%d rows", a.B_total, a.B);
     ARG_CHECK(head_fused_fits(a, true), "head: the fused training head does not take B=%d C=%d e=%d (e %% 16, LDS)", a.B, a.C, a.e);
@@ -245,9 +250,11 @@ int launch_head_fused_train(const HeadArgs& a, hipStream_t s) {
         if (int rc = launch_l2norm(a.txt, a.txt_n, a.txt_inv, a.C, a.e, s)) return rc;
     const int Cpad = (a.C + 15) / 16 * 16, lds = head_lds_bytes(a, true);
     const int dev = current_device();
-    if (int e = lds_limit_once<head_rows_kernel<true>>(dev, 163840 - 256)) return e;
+    if (int e = a.dimg ? lds_limit_once<head_rows_kernel<true>>(dev, 163840 - 256) : lds_limit_once<head_rows_kernel<true, false>>(dev, 163840 - 256)) return e;
     if (int e = lds_limit_once<head_dtxt_kernel>(dev, 65536)) return e;
-    hipLaunchKernelGGL(head_rows_kernel<true>, dim3((a.B + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), lds, s, a, Cpad);
+    const dim3 grid((a.B + HEAD_ROWS - 1) / HEAD_ROWS), block(HEAD_WAVES * 64);
+    if (a.dimg) hipLaunchKernelGGL(head_rows_kernel<true>, grid, block, lds, s, a, Cpad);
+    else hipLaunchKernelGGL((head_rows_kernel<true, false>), grid, block, lds, s, a, Cpad);
     HIP_TRY(hipGetLastError());
     if (a.B_total <= 0)
         if (int rc = launch_mean(a.row_loss, a.B, a.loss, s)) return rc;

@@ -216,7 +216,7 @@ struct HeadArgs {
     float* loss = nullptr;        // [1] mean CE over B (multiplied by loss_weight for the reported value? no: plain mean)
     float* dlogits = nullptr;     // [B, C] scratch
     float* row_loss = nullptr;    // [B] scratch
-    float* dimg = nullptr;        // [B, e] grad of raw image features
+    float* dimg = nullptr;        // [B, e] grad of raw image features; null in training: none is wanted (a frozen, prompt-free image tower)
     float* dtxt = nullptr;        // [C, e] grad of raw text features
     float* img_n = nullptr;       // [B, e] scratch: normalised features
     float* txt_n = nullptr;       // [C, e]
@@ -232,7 +232,7 @@ int launch_head_bwd(const HeadArgs& a, hipStream_t s);
 // in the workgroup that made the logit rows.  a.txt == null: keep the normalised text features of the previous call.
 bool head_fused_fits(const HeadArgs& a, bool train);
 int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s);
-int launch_head_fused_train(const HeadArgs& a, hipStream_t s);  // logits + loss + dimg + dtxt (gradients of the raw features; dtxt null: skipped)
+int launch_head_fused_train(const HeadArgs& a, hipStream_t s);  // logits + loss + dimg + dtxt (gradients of the raw features; dtxt null, dimg null: skipped)
 // CoCoOp (trainers/cocoop.py): per-image text features.  txt / txt_n / txt_inv / dtxt have B * C rows (row i * C + c).
 int launch_pair_head_fwd(const HeadArgs& a, hipStream_t s);
 int launch_pair_head_bwd(const HeadArgs& a, hipStream_t s);  // loss, dlogits, dtxt (gradient of the raw text features)

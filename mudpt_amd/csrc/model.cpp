@@ -157,7 +157,7 @@ struct Trainable {
     size_t off = 0, numel = 0;
 };
 
-// ---- CLIP's ResNet image tower (mudpt_create_frozen_resnet; clip/model.py:17-161; kernels: resnet.hip) ----
+// ---- CLIP's ResNet image tower (mudpt_create_frozen_resnet, mudpt_create_resnet; clip/model.py:17-161; kernels: resnet.hip) ----
 // One bias-free convolution and the eval-mode BatchNorm behind it, folded into one GEMM B operand + fp32 bias (mudpt_conv_pack)
 struct RnConv {
     std::string conv, bn;  // state-dict prefixes: conv + ".weight"; bn + ".weight" / ".bias" / ".running_mean" / ".running_var"
@@ -272,7 +272,7 @@ struct mudpt_model {
     // position) per token row, and the text tower runs once per template from the device-resident embedding table.  txt_n holds the ensembled,
     // normalised features (text_valid), the only thing a forward needs from the text side
     bool frozen = false;
-    Resnet* rn = nullptr;  // mudpt_create_frozen_resnet: the image tower is this instead of `vis`, which then has no block
+    Resnet* rn = nullptr;  // mudpt_create_frozen_resnet, mudpt_create_resnet: the image tower is this instead of `vis`, which then has no block
     float* tok_table = nullptr; int vocab = 0;// "token_embedding.weight" fp32 [vocab, t_width]
     struct Template {
         std::vector<Tower::Seg> segs;  // empty = one bucket of n_cls x L
@@ -709,7 +709,8 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     ALLOC(m->img_f, (size_t)B * e * 4); ALLOC(m->txt_f, (size_t)TS * e * 4); ALLOC(m->img_n, (size_t)B * e * 4); ALLOC(m->txt_n, (size_t)TS * e * 4);
     ALLOC(m->img_inv, B * 4); ALLOC(m->txt_inv, TS * 4);
     ALLOC(m->logits, (size_t)B * C * 4); ALLOC(m->dlogits, (size_t)B * C * 4); ALLOC(m->row_loss, B * 4);
-    ALLOC(m->dimg, (size_t)B * e * 4); ALLOC(m->dtxt, (size_t)TS * e * 4); ALLOC(m->loss, 16);
+    if (!resnet) ALLOC(m->dimg, (size_t)B * e * 4);  // a ResNet tower is frozen and prompt-free: head_train asks for no image gradient
+    ALLOC(m->dtxt, (size_t)TS * e * 4); ALLOC(m->loss, 16);
     if (m->cocoop) {
         m->hid = e / 16;
         ALLOC(m->mn_hid, (size_t)B * m->hid * 4); ALLOC(m->mn_dhid, (size_t)B * m->hid * 4);
@@ -893,23 +894,46 @@ static int resnet_setup(mudpt_model* m, int S, const mudpt_resnet_shape& shape) 
     return MUDPT_OK;
 }
 
+// What both ResNet entry points refuse, each before any device call (`fn` opens the message)
+static int resnet_check(const char* fn, const mudpt_config* c, const mudpt_resnet_shape* rn) {
+    ARG_CHECK(c->dtype != MUDPT_F32, "%s: dtype MUDPT_F32: ResNet towers run in bf16 / fp16; the parity mode is not built for them", fn);
+    ARG_CHECK(c->image_size >= 32 && c->image_size % 32 == 0, "%s: image_size %d must be a positive multiple of 32 (the tower divides it by 32)", fn, c->image_size);
+    ARG_CHECK(rn->layers1 >= 1 && rn->layers2 >= 1 && rn->layers3 >= 1 && rn->layers4 >= 1, "%s: layers (%d, %d, %d, %d): every stage needs at least one block", fn,
+              rn->layers1, rn->layers2, rn->layers3, rn->layers4);
+    ARG_CHECK(rn->width >= 32 && rn->width % 32 == 0, "%s: width %d must be a positive multiple of 32: the stem has width / 2 channels and the GEMM needs N %% 16 == 0 "
+              "(RN50x4, width 80, has a 40-channel stem and is not built)", fn, rn->width);
+    ARG_CHECK(rn->heads >= 1 && (32 * rn->width) % rn->heads == 0, "%s: heads %d must be >= 1 and divide 32 * width = %d", fn, rn->heads, 32 * rn->width);
+    ARG_CHECK(32 * rn->width / rn->heads == 64, "%s: heads %d gives a head dimension of %d; the attention pool runs 64 (heads = 32 * width / 64, clip/model.py:687)", fn,
+              rn->heads, 32 * rn->width / rn->heads);
+    ARG_CHECK(c->embed_dim >= 16 && c->embed_dim % 16 == 0, "%s: embed_dim %d must be a positive multiple of 16 (c_proj's GEMM N)", fn, c->embed_dim);
+    return MUDPT_OK;
+}
+// behind the tower the handle is a ViT handle's; its ViT fields describe one 32 x 32 patch and no block, and are never run
+static mudpt_config resnet_vit_stub(const mudpt_config& c) {
+    mudpt_config f = c;
+    f.image_size = 32; f.patch = 32; f.v_width = 64; f.v_layers = 0; f.v_heads = 1;
+    return f;
+}
+
 extern "C" int mudpt_create_frozen_resnet(const mudpt_config* c, const mudpt_resnet_shape* rn, mudpt_model** out) {
     ARG_CHECK(c && rn && out, "create_frozen_resnet: null argument");
-    ARG_CHECK(c->dtype != MUDPT_F32, "create_frozen_resnet: dtype MUDPT_F32: ResNet towers run in bf16 / fp16; the parity mode is not built for them");
-    ARG_CHECK(c->image_size >= 32 && c->image_size % 32 == 0, "create_frozen_resnet: image_size %d must be a positive multiple of 32 (the tower divides it by 32)", c->image_size);
-    ARG_CHECK(rn->layers1 >= 1 && rn->layers2 >= 1 && rn->layers3 >= 1 && rn->layers4 >= 1, "create_frozen_resnet: layers (%d, %d, %d, %d): every stage needs at least one block",
-              rn->layers1, rn->layers2, rn->layers3, rn->layers4);
-    ARG_CHECK(rn->width >= 32 && rn->width % 32 == 0, "create_frozen_resnet: width %d must be a positive multiple of 32: the stem has width / 2 channels and the GEMM needs N %% 16 == 0 "
-              "(RN50x4, width 80, has a 40-channel stem and is not built)", rn->width);
-    ARG_CHECK(rn->heads >= 1 && (32 * rn->width) % rn->heads == 0, "create_frozen_resnet: heads %d must be >= 1 and divide 32 * width = %d", rn->heads, 32 * rn->width);
-    ARG_CHECK(32 * rn->width / rn->heads == 64, "create_frozen_resnet: heads %d gives a head dimension of %d; the attention pool runs 64 (heads = 32 * width / 64, clip/model.py:687)",
-              rn->heads, 32 * rn->width / rn->heads);
-    ARG_CHECK(c->embed_dim >= 16 && c->embed_dim % 16 == 0, "create_frozen_resnet: embed_dim %d must be a positive multiple of 16 (c_proj's GEMM N)", c->embed_dim);
-    // behind the tower the handle is mudpt_create_frozen's; its ViT fields describe one 32 x 32 patch and no block, and are never run
-    mudpt_config f = *c;
+    if (int rc = resnet_check("create_frozen_resnet", c, rn)) return rc;
+    mudpt_config f = resnet_vit_stub(*c);  // ... mudpt_create_frozen's
     f.variant = MUDPT_VARIANT_MUDPT; f.n_ctx = 0; f.depth = 1;
-    f.image_size = 32; f.patch = 32; f.v_width = 64; f.v_layers = 0; f.v_heads = 1;
     return create_model(&f, nullptr, out, true, rn, c->image_size);
+}
+
+// CoOp / CoCoOp with the ResNet image tower (trainers/coop.py:212-226, cocoop.py:178-198: the image encoder is frozen and prompt-free, so the
+// tower runs forward only where the vanilla ViT would).  The other variants put trainable prompts into a ViT's token sequence
+extern "C" int mudpt_create_resnet(const mudpt_config* c, const mudpt_resnet_shape* rn, mudpt_model** out) {
+    ARG_CHECK(c && rn && out, "create_resnet: null argument");
+    static const char* names[] = {"MuDPT", "CoCoOp", "CoOp", "CoOp (CSC)", "VPT", "MPT", "UMuDPT", "UUMuDPT"};
+    ARG_CHECK(c->variant >= MUDPT_VARIANT_MUDPT && c->variant <= MUDPT_VARIANT_UUMUDPT, "create_resnet: unknown variant %d", c->variant);
+    ARG_CHECK(c->variant == MUDPT_VARIANT_COOP || c->variant == MUDPT_VARIANT_COOP_CSC || c->variant == MUDPT_VARIANT_COCOOP,
+              "create_resnet: variant %d (%s): its prompts live inside a ViT; a ResNet image tower serves CoOp, CoOp with CSC and CoCoOp", c->variant, names[c->variant]);
+    if (int rc = resnet_check("create_resnet", c, rn)) return rc;
+    const mudpt_config f = resnet_vit_stub(*c);
+    return create_model(&f, nullptr, out, false, rn, c->image_size);
 }
 
 // every entry point that trains, takes embedded class prompts or shards the classes
@@ -1837,7 +1861,7 @@ static int resnet_forward(mudpt_model* m, const float* images, int B, hipStream_
 // Vision tower forward, clip/model.py:526-553 (MuDPT: prompt rows appended before ln_pre, deep prompts spliced per block) or
 // clip/model.py:478-496 (CoCoOp: the vanilla ViT, no prompt rows) -> m->img_f [B, e]
 static int vision_forward(mudpt_model* m, const float* images, int B, hipStream_t s) {
-    if (m->rn) return resnet_forward(m, images, B, s);  // a frozen handle with the ResNet tower (mudpt_create_frozen_resnet)
+    if (m->rn) return resnet_forward(m, images, B, s);  // a handle with the ResNet tower (mudpt_create_frozen_resnet, mudpt_create_resnet)
     const mudpt_config& c = m->cfg;
     const int dv = c.v_width, n = m->vis.n, D1 = m->vis.D1, P = n_patches(c), Lv = m->vis.L, K0 = patch_k0(c);
     const PromptRoute pr = prompt_route(m, m->vis);
@@ -2237,12 +2261,14 @@ extern "C" int mudpt_image_features(mudpt_model* m, int32_t B, float* features, 
 
 // head of the training step: cross-entropy (mean) + cosine logits backward, trainers/mudpt.py:178-182,250 -> loss, dimg, dtxt (all classes)
 // reuse_text (VPT): m->txt_n / txt_inv still hold the normalised features of the cached text pass; text_grad = false (VPT): no dtxt
+// A ResNet handle (CoOp on mudpt_create_resnet) asks for no dimg: nothing in front of its image features trains, and without the gradient tile
+// the fused head takes embed_dim 1024 up to 1520 classes (with it: 496).  ViT handles keep passing m->dimg, CoOp's included
 static int head_train(mudpt_model* m, const int64_t* labels, int B, float grad_scale, float* loss, float* logits, hipStream_t s,
                       bool reuse_text = false, bool text_grad = true) {
     const mudpt_config& c = m->cfg;
     const int e = c.embed_dim, C = c.n_cls;
     HeadArgs h; h.img = m->img_f; h.txt = m->txt_f; h.labels = labels; h.scale = m->scale; h.logits = m->logits; h.loss = m->loss; h.dlogits = m->dlogits;
-    h.row_loss = m->row_loss; h.dimg = m->dimg; h.dtxt = text_grad ? m->dtxt : nullptr; h.img_n = m->img_n; h.txt_n = m->txt_n; h.img_inv = m->img_inv; h.txt_inv = m->txt_inv;
+    h.row_loss = m->row_loss; h.dimg = m->rn ? nullptr : m->dimg; h.dtxt = text_grad ? m->dtxt : nullptr; h.img_n = m->img_n; h.txt_n = m->txt_n; h.img_inv = m->img_inv; h.txt_inv = m->txt_inv;
     // Static loss scaling: the backward pass runs on per-sample gradients times loss_scale (dlogits = (softmax -
     // onehot) * loss_scale, independent of B and of the number of ranks), so the T copies of the token gradients
     // stay inside fp16's normal range (unscaled they are ~1e-7 at B = 256: flushed).  Every reduction that leaves a
@@ -2912,7 +2938,7 @@ extern "C" int mudpt_head_ex(const float* img, const float* txt, const int64_t* 
                              int32_t* path_taken, void* stream) {
     ARG_CHECK(img && txt_n && txt_inv && logits && B > 0 && B_total >= 0, "head_ex: bad arguments");  // C, e: the launchers' own checks
     ARG_CHECK(path == 0 || path == 1, "head_ex: path must be 0 (the dispatch of mudpt_head) or 1 (the unfused launchers)");
-    ARG_CHECK(!labels || (loss && dimg), "head_ex: training needs loss and dimg");
+    ARG_CHECK(!labels || loss, "head_ex: training needs loss (dimg may be NULL: no image gradient)");
     hipStream_t s = (hipStream_t)stream;
     float* scratch = nullptr;
     const size_t need = (size_t)B * e + B + (size_t)B * C + B;

@@ -6,6 +6,8 @@ constant, and the reference already names the file that holds it: lpclip/feat_ex
 whole split to ``{dir}/{dataset}/{split}.npz`` (``lpclip.save_features`` here).  With such a file a test pass is one
 ``model.forward_features`` launch chain per batch on rows of a table -- no decode, no transform, no vision tower -- and the file outlives
 the process: the ``base2new`` / ``xd_test`` / ``run_zsclip`` scripts re-run the same pass per checkpoint, seed, shot count and class split.
+On a ResNet backbone (RN50, RN101, RN50x16, RN50x64) the tower of a CoOp / CoCoOp handle is the frozen handle's bit for bit, so the file is the
+one ``lpclip``'s extractor writes for the zero-shot and linear-probe baselines of the same table.
 
 MuDPT, VPT, MPT, UMuDPT and UUMuDPT carry trainable prompts inside the vision tower: their features are no constants and are refused.
 

@@ -143,7 +143,7 @@ def library_config(shape: ModelShape, n_cls: int, max_batch: int, dtype: str, va
 
 class LibraryModel(nn.Module):
     """An ``nn.Module`` that owns one ``mudpt_model*``: everything about the handle that does not depend on what it computes.  ``create(lib,
-    cfg, h)`` is the subclass's create call (``mudpt_create`` / ``mudpt_create_ex`` / ``mudpt_create_frozen``) on byref(config) and
+    cfg, h)`` is the subclass's create call (``mudpt_create`` / ``mudpt_create_ex`` / ``mudpt_create_resnet`` / ``mudpt_create_frozen``) on byref(config) and
     byref(handle); ``config`` are ``library_config``'s keywords.  The knobs are applied right behind it, before any weight or token."""
 
     def __init__(self, shape: ModelShape, n_cls: int, max_batch: int, dtype: str, device: str, knobs: Optional[Dict[str, int]], create, **config):
@@ -264,14 +264,19 @@ class CustomCLIP(LibraryModel):
         # "uumudpt": trainers/uumudpt.py's CustomCLIP (UMuDPT plus the vision tower's own visual_ctx, visual_ctx_deep_prompts and a second
         # generator that turns those into an addend of the text deep prompts): 40 trainables, "uumudpt_prompt_learner.*" then
         # "image_encoder.visual_ctx*"; shape.n_ctx (1..16) / depth are TRAINER.UUMUDPT.N_CTX / DEEP_PROMPT_DEPTH
-        assert not shape.resnet, "ResNet backbones run on the frozen handle only (ZeroshotCLIP, ZeroshotCLIP2, feature extraction)"
+        # A ResNet ``shape`` (RN50, RN101, RN50x16, RN50x64): "coop" / "coop_csc" / "cocoop" only -- their image encoder is frozen and prompt-free
+        # (trainers/coop.py:212-226, cocoop.py:178-198), so the tower runs forward only where the vanilla ViT would (mudpt_create_resnet)
+        assert not shape.resnet or variant in ("coop", "coop_csc", "cocoop"), \
+            "ResNet backbones run on the frozen handle only (ZeroshotCLIP, ZeroshotCLIP2, feature extraction)"
         if variant == "coop_csc" and ctx_token_ids is not None:
             variant = "coop"  # trainers/coop.py:52-61: the CTX_INIT path builds one shared context whatever CSC says
         assert (prompt_shape is not None) == (variant in ("vpt", "mpt")), "prompt_shape is the VPT / MPT setting, and they need it"
         prompt_shape = None if prompt_shape is None else tuple(int(v) for v in prompt_shape)
 
         def create(lib, cfg, h):
-            if prompt_shape is not None:
+            if shape.resnet:
+                capi.check(lib.mudpt_create_resnet(cfg, C.byref(capi.ResnetShape(*shape.v_stages, shape.v_width, shape.v_heads)), h), "create_resnet")
+            elif prompt_shape is not None:
                 capi.check(lib.mudpt_create_ex(cfg, C.byref(capi.PromptShape(*prompt_shape)), h), "create_ex")
             else:
                 capi.check(lib.mudpt_create(cfg, h), "create")
@@ -281,7 +286,7 @@ class CustomCLIP(LibraryModel):
         self.variant, self.prompt_shape = variant, prompt_shape
         h = self._h
         for k, v in clip_state.items():  # the frozen weights; of the token embedding only the class prompts' rows go up (below)
-            if k != "token_embedding.weight" and isinstance(v, torch.Tensor):
+            if k != "token_embedding.weight" and isinstance(v, torch.Tensor) and v.is_floating_point():  # not BatchNorm's num_batches_tracked
                 self.set_weight(k, v)
         # class-parallel text tower (include/mudpt.h): this rank encodes classes [c0, c1) of the n_cls; ``group`` is the process group
         # of the two exchanges (None = the default group)

@@ -57,7 +57,8 @@ def synthetic_tokenized_prompts(n_cls: int, n_ctx: int = 4, ctx_len: int = 77, s
     return tok
 
 
-# the ResNet backbones of clip.load (clip/clip.py:32-36) the library runs, as ModelShape(**RESNET_SHAPES[name]); RN50x4 (width 80) is not built
+# the ResNet backbones of clip.load (clip/clip.py:32-36) the library runs -- frozen (zsclip.FrozenCLIP) and under CoOp / CoCoOp (model.CustomCLIP) --
+# as ModelShape(**RESNET_SHAPES[name]); RN50x4 (width 80) is not built
 RESNET_SHAPES = {
     "RN50": dict(image_size=224, patch=32, v_width=64, v_layers=16, v_heads=32, v_stages=(3, 4, 6, 3), embed_dim=1024),
     "RN101": dict(image_size=224, patch=32, v_width=64, v_layers=33, v_heads=32, v_stages=(3, 4, 23, 3), embed_dim=512),
