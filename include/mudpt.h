@@ -748,6 +748,20 @@ int mudpt_attnpool_attend(int32_t dtype, const float* q, int32_t ldq, const floa
                           int32_t H, void* stream);
 int mudpt_conv_pack(int32_t dtype, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, int32_t cout, int32_t cin, int32_t k,
                     int32_t ldk, void* w_out, float* bias_out);
+/* The text tower's sequence layout as mudpt_set_class_prompts / mudpt_set_text_tokens plan it, for eot [n_cls] (the EOT position of every class
+ * prompt, 0 <= eot < ctx_len) and n_prompt prompt rows per sequence (0 <= n_prompt, n_prompt + 2 <= ctx_len).  HOST arithmetic only: no handle,
+ * no device call; an addition, so MUDPT_ABI_VERSION stays.  txt_trim, txt_buckets, txt_bucket_cost: the knobs of mudpt_model_set; allow_buckets = 0
+ * is CoCoOp's setting (always one bucket); heads >= 1 only spaces the buckets' LSE buffers.  The rule: a sequence keeps len = max(eot + 1,
+ * n_prompt + 2) rows; untrimmed (txt_trim = 0) every sequence keeps ctx_len rows in one bucket.  One bucket runs every sequence to the longest
+ * len, in the caller's order.  With allow_buckets, txt_trim, txt_buckets > 1 and n_cls x (longest len) >= 2048 the sequences are sorted by len
+ * (a stable sort) and the sorted list is cut between distinct lengths into k <= txt_buckets buckets, each run to its longest member, so that
+ * rows + k txt_bucket_cost is smallest; among the k of equal cost the smallest wins, and k = 1 keeps the caller's order.
+ * Outputs, per packed sequence q (arrays of n_cls): cls[q] its class, first_row[q] its first packed row, bucket_len[q] the rows its bucket
+ * runs it to; *buckets = k, *rows = the packed rows, *max_len = the longest kept length (what mudpt_text_layout reports for such a handle).
+ * MUDPT_ERR_ARG with a message, nothing written: a null pointer, n_cls < 1, heads < 1, n_prompt or an eot outside the ranges above. */
+int mudpt_text_layout_plan(const int32_t* eot, int32_t n_cls, int32_t ctx_len, int32_t n_prompt, int32_t heads, int32_t txt_trim, int32_t txt_buckets,
+                           int32_t txt_bucket_cost, int32_t allow_buckets, int32_t* cls, int32_t* first_row, int32_t* bucket_len, int32_t* buckets, int32_t* rows,
+                           int32_t* max_len);
 
 #ifdef __cplusplus
 }

@@ -85,8 +85,20 @@ struct BlockAct {
     float* lse = nullptr;
 };
 
+// The text tower's sequence layout for one set of class prompts (plan_text_layout is the rule, fill_layout_tables makes the device tables,
+// bind_text_layout points the tower at one).  Length buckets (many classes): the sequences are sorted by length and packed bucket after bucket,
+// each bucket with its own row count per sequence, so the row-wise kernels (GEMMs, LayerNorm) run once over `rows` packed rows while the
+// kernels that know about sequences (attention, prompt splice, prompt-row reductions) run once per bucket.
+struct TextLayout {
+    struct Seg { int row0 = 0, seq0 = 0, nseq = 0, L = 0; size_t lse0 = 0; };  // first packed row / sequence, sequences, rows per sequence, offset into the LSE buffers
+    std::vector<Seg> segs;          // the buckets, at least one; one bucket keeps the caller's order
+    int rows = 0, L = 0, nseq = 0;  // packed rows, longest kept length, sequences per pass (CoCoOp: a chunk of images x n_cls)
+    int *eot_rows = nullptr, *eot_local = nullptr, *perm = nullptr;  // device: EOT row of every sequence, packed / relative to its bucket; packed position -> class
+    bool packed() const { return segs.size() > 1; }
+};
+
 struct Tower {
-    int d = 0, layers = 0, heads = 0, L = 0, max_seq = 0, Lp = 0;
+    int d = 0, layers = 0, heads = 0, L = 0, max_seq = 0, Lp = 0;  // L, Lp: rows per sequence (text: the bound layout's longest kept length), padded for attention
     bool causal = false;
     // Split operands (common.h LoMode).  The forward GEMMs' A operands -- both LayerNorm outputs, the attention output and QuickGELU(u) --
     // are stored as hi = T(v) plus the remainder lo in a second buffer, and the GEMM contracts lo in a second pass: against the same
@@ -132,22 +144,21 @@ struct Tower {
     int head_span = 0;               // rows prompt_row0 .. prompt_row0 + head_span - 1 hold every head row (0 = head_n; CoOp middle / front: wider)
     void *hd_dqkv = nullptr, *hd_h = nullptr;  // T [max_seq * n_ctx, 3 d], [max_seq * n_ctx, d]
     std::vector<void*> act_allocs;  // activation / scratch buffers (sized for max_seq sequences of L rows): re-made when L changes
-    // Length buckets (text tower with many classes): the sequences are sorted by length and packed bucket after bucket, each bucket with
-    // its own row count per sequence, so the row-wise kernels (GEMMs, LayerNorm) run once over `rows` packed rows while the kernels that
-    // know about sequences (attention, prompt splice, prompt-row reductions) run once per bucket.  Empty = one bucket of max_seq x L.
-    struct Seg { int row0 = 0, seq0 = 0, nseq = 0, L = 0; size_t lse0 = 0; };
-    std::vector<Seg> segs;
-    int rows = 0;                        // packed rows (segs non-empty)
-    const int* tail_local = nullptr;     // [nseq] tail row of a sequence relative to its bucket's first row (single-query attention)
+    typedef TextLayout::Seg Seg;
+    const TextLayout* lay = nullptr;  // text tower: the bound layout (bind_text_layout); the vision tower has none
+    bool packed() const { return lay && lay->packed(); }
 };
 
-// rows of a tower pass over nseq sequences; its buckets (one pseudo-bucket when the tower is not packed)
-static int tower_rows(const Tower& t, int nseq) { return t.segs.empty() ? nseq * t.L : t.rows; }
-static std::vector<Tower::Seg> tower_segs(const Tower& t, int nseq) {
-    if (!t.segs.empty()) return t.segs;
-    Tower::Seg one; one.nseq = nseq; one.L = t.L;
-    return {one};
-}
+// rows of a tower pass over nseq sequences; its buckets: the bound layout's as they lie when it is packed, else one pseudo-bucket of
+// nseq x L (the vision tower's batch, CoCoOp's chunk)
+static int tower_rows(const Tower& t, int nseq) { return t.packed() ? t.lay->rows : nseq * t.L; }
+struct TowerSegs {
+    Tower::Seg one;
+    const Tower::Seg *b = &one, *e = &one + 1;
+    TowerSegs(const Tower& t, int nseq) { one.nseq = nseq; one.L = t.L; if (t.packed()) { b = t.lay->segs.data(); e = b + t.lay->segs.size(); } }
+    TowerSegs(const TowerSegs&) = delete;
+    const Tower::Seg* begin() const { return b; } const Tower::Seg* end() const { return e; }
+};
 
 // One trainable tensor: the reference's state-dict key, its shape (ndim extents, the rest 0) and its place in the flat bucket (elements)
 struct Trainable {
@@ -214,8 +225,8 @@ struct mudpt_model {
     // text stem / head
     float *tpos = nullptr, *ln_fin_g = nullptr, *ln_fin_b = nullptr, *tproj = nullptr;
     float* emb_pos = nullptr;  // [C, Lt, dt] class token embeddings + positional embedding
-    int *eot_rows = nullptr, *tprompt_rows = nullptr;
-    int *eot_local = nullptr, *class_perm = nullptr;  // EOT row relative to the sequence's length bucket; packed position -> local class
+    int* tprompt_rows = nullptr;
+    TextLayout lay;  // of the class prompts (mudpt_set_class_prompts); its device tables are allocated at create.  Frozen handles: Template::lay
     float *txt_sorted = nullptr, *dtxt_sorted = nullptr;  // [C, e] text features / their gradient in packed (length-sorted) order
     float *t_ln = nullptr, *fin_mean = nullptr, *fin_rstd = nullptr, *dt_ln = nullptr;
     float scale = 1.f;
@@ -275,9 +286,8 @@ struct mudpt_model {
     Resnet* rn = nullptr;  // mudpt_create_frozen_resnet, mudpt_create_resnet: the image tower is this instead of `vis`, which then has no block
     float* tok_table = nullptr; int vocab = 0;// "token_embedding.weight" fp32 [vocab, t_width]
     struct Template {
-        std::vector<Tower::Seg> segs;  // empty = one bucket of n_cls x L
-        int rows = 0, L = 0;           // packed token rows, longest kept length
-        const int *tok = nullptr, *pos = nullptr, *eot_rows = nullptr, *eot_local = nullptr, *perm = nullptr;  // device, inside tmpl_tables
+        TextLayout lay;                            // its device tables inside tmpl_tables
+        const int *tok = nullptr, *pos = nullptr;  // device, inside tmpl_tables: token id and position of every packed token row
     };
     std::vector<Template> tmpl;
     int* tmpl_tables = nullptr;  // one allocation behind every Template's tables
@@ -562,7 +572,7 @@ static int alloc_tower_acts(mudpt_model* m, Tower& t, int L, int max_seq) {
         *(void**)&(ptr) = _p;                                                    \
     } while (0)
     const int d = t.d, heads = t.heads;
-    t.L = L; t.max_seq = max_seq;
+    t.L = L; t.max_seq = max_seq; t.lay = nullptr;  // text tower: bind_text_layout follows
     t.Lp = attn_padded_len(L);
     const size_t M = (size_t)max_seq * L;
     for (int i = 0; i < t.layers; ++i) {
@@ -684,7 +694,6 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     // the text tower's activations are sized by mudpt_set_class_prompts: its trimmed length (max(eot) + 1 of ctx_len positions) and, for
     // CoCoOp, the number of images whose B * C prompts fit the memory budget at once are only known there
     if (int r = alloc_tower_weights(m, m->txt, dt, c->t_layers, c->t_heads, true, 1, false)) return r;
-    m->txt.L = c->ctx_len; m->txt.Lp = attn_padded_len(c->ctx_len);
     const int K0 = patch_k0(*c);
     ALLOC(m->conv_w, (size_t)dv * K0 * 2);
     if (m->exact) { ALLOC(m->conv_w8, (size_t)dv * K0 * 2); ALLOC(m->patches_lo, (size_t)B * P * K0 * 2); }  // split pixels (vision tower's site 4)
@@ -698,7 +707,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     ALLOC(m->tpos, (size_t)c->ctx_len * dt * 4); ALLOC(m->ln_fin_g, dt * 4); ALLOC(m->ln_fin_b, dt * 4);
     ALLOC(m->tproj, (size_t)dt * e * 4);
     ALLOC(m->emb_pos, frozen ? 0 : (size_t)C * c->ctx_len * dt * 4);  // frozen: embedded on the device, template by template
-    ALLOC(m->eot_rows, TS * 4); ALLOC(m->eot_local, TS * 4); ALLOC(m->class_perm, C * 4);
+    ALLOC(m->lay.eot_rows, TS * 4); ALLOC(m->lay.eot_local, TS * 4); ALLOC(m->lay.perm, C * 4);
     ALLOC(m->txt_sorted, (size_t)C * e * 4); ALLOC(m->dtxt_sorted, (size_t)C * e * 4);
     ALLOC(m->t_ln, (size_t)TS * dt * 4); ALLOC(m->fin_mean, TS * 4); ALLOC(m->fin_rstd, TS * 4); ALLOC(m->dt_ln, (size_t)TS * dt * 4);
     const size_t dn = (size_t)(D1 > 0 ? D1 : 1) * n;
@@ -744,8 +753,7 @@ static int create_impl(const mudpt_config* c, const mudpt_prompt_shape* ps, mudp
     m->vis.tail_rows = m->cls_rows;
     m->vis.head_rows = nv > 0 ? m->vprompt_rows : nullptr;
     ALLOC(m->tprompt_rows, (size_t)TS * nt * 4);
-    m->txt.head_rows = nt > 0 ? m->tprompt_rows : nullptr;  // ctx rows of every prompt; this table and the next are filled by mudpt_set_class_prompts
-    m->txt.tail_rows = m->eot_rows;
+    m->txt.head_rows = nt > 0 ? m->tprompt_rows : nullptr;  // ctx rows of every prompt; filled by mudpt_set_class_prompts, which binds the EOT rows too
     HIP_TRY(hipMemcpy(m->vprompt_rows, pr.data(), pr.size() * 4, hipMemcpyHostToDevice));
 
     if (!frozen) build_trainables(m);  // a frozen handle has none: mudpt_param_count / _numel report 0
@@ -1161,23 +1169,31 @@ extern "C" int mudpt_set_class_token_position(mudpt_model* m, int32_t position, 
 // each run to its own longest member, removes most of the padding (C = 1000 synthetic names: 19 000 -> ~11 000 rows).  Sequences are
 // independent in every kernel of the tower, so the kept rows are bit-identical to the single-bucket run (tests).  A bucket costs a
 // handful of extra launches per block (attention, splice, reductions: ~1 000 rows' worth of time), which the cut search charges.
-// eot [C]: the EOT position of every prompt; Le: the trimmed length of the one-bucket run; n_prompt: prompt rows per sequence (a sequence keeps at
-// least n_prompt + 2 rows).  Returns packed position -> class; *segs stays empty (and *rows untouched) for one bucket in the caller's order.
-static std::vector<int> plan_length_buckets(const mudpt_model* m, const int32_t* eot, size_t C, size_t Le, int n_prompt, int heads, bool allow,
-                                            std::vector<Tower::Seg>* segs, int* rows) {
-    segs->clear();
-    std::vector<int> order(C);  // packed position -> local class
-    for (size_t cc = 0; cc < C; ++cc) order[cc] = (int)cc;
+// The whole layout rule, pure host arithmetic (exported as mudpt_text_layout_plan), into *lay's host half.  eot [C]: the EOT position of every prompt;
+// n_prompt: prompt rows per sequence; trim, max_buckets, bucket_cost: the knobs txt_trim, txt_buckets, txt_bucket_cost; allow_buckets: false for CoCoOp.
+// The text tower is causal (clip/model.py:407-413) and only the EOT row of a prompt is used (trainers/mudpt.py:154): positions behind it influence no
+// used output or gradient, so a sequence keeps max(eot + 1, n_prompt + 2) rows and a bucket runs to its longest member; trim = false: ctx_len rows, one bucket
+struct TextPlan { std::vector<int> order, first, seg; };  // per packed sequence: its class, its first packed row, the index of its bucket
+static TextPlan plan_text_layout(const int32_t* eot, int C, int ctx_len, int n_prompt, int heads, bool trim, int max_buckets, long bucket_cost, bool allow_buckets,
+                                 TextLayout* lay) {
+    TextPlan p;
+    p.order.resize(C); p.first.resize(C); p.seg.resize(C);
+    std::vector<int>& order = p.order;
+    std::vector<TextLayout::Seg>& segs = lay->segs;
+    segs.clear();
+    for (int cc = 0; cc < C; ++cc) order[cc] = cc;
     auto len_of = [&](int cc) { return std::max(eot[cc] + 1, n_prompt + 2); };
-    if (allow && m->txt_trim && m->txt_buckets > 1 && C * Le >= 2048) {
+    int Le = trim ? 0 : ctx_len;  // the kept length of the one-bucket run
+    if (trim) for (int cc = 0; cc < C; ++cc) Le = std::max(Le, len_of(cc));
+    if (allow_buckets && trim && max_buckets > 1 && (size_t)C * Le >= 2048) {
         std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return len_of(x) < len_of(y); });
         std::vector<int> dl, cnt;  // distinct lengths ascending, sequences per length
         for (int cc : order) {
             if (dl.empty() || dl.back() != len_of(cc)) { dl.push_back(len_of(cc)); cnt.push_back(0); }
             ++cnt.back();
         }
-        const int nd = (int)dl.size(), K = std::min(m->txt_buckets, nd);
-        const long PEN = m->txt_bucket_cost, INF = 1L << 60;
+        const int nd = (int)dl.size(), K = std::min(max_buckets, nd);
+        const long PEN = bucket_cost, INF = 1L << 60;
         std::vector<long> pre(nd + 1, 0);
         for (int j = 0; j < nd; ++j) pre[j + 1] = pre[j] + cnt[j];
         // best[b][j]: rows (+ penalties) of covering lengths 0..j-1 with b buckets, the last one ending at length j-1
@@ -1201,18 +1217,37 @@ static std::vector<int> plan_length_buckets(const mudpt_model* m, const int32_t*
             size_t lse0 = 0;
             for (int j1 : cuts) {
                 Tower::Seg g; g.row0 = row0; g.seq0 = (int)pre[j0]; g.nseq = (int)(pre[j1] - pre[j0]); g.L = dl[j1 - 1]; g.lse0 = lse0;
-                segs->push_back(g);
+                segs.push_back(g);
                 row0 += g.nseq * g.L;
                 lse0 += (size_t)g.nseq * heads * attn_padded_len(g.L);
                 j0 = j1;
             }
-            *rows = row0;
         } else {
-            for (size_t cc = 0; cc < C; ++cc) order[cc] = (int)cc;  // one bucket: keep the caller's order
+            for (int cc = 0; cc < C; ++cc) order[cc] = cc;  // one bucket: keep the caller's order
         }
     }
-    return order;
+    if (segs.empty()) { TextLayout::Seg one; one.nseq = C; one.L = Le; segs.push_back(one); }
+    lay->L = Le; lay->nseq = C; lay->rows = segs.back().row0 + segs.back().nseq * segs.back().L;
+    for (size_t b = 0; b < segs.size(); ++b)
+        for (int j = 0; j < segs[b].nseq; ++j) { p.first[segs[b].seq0 + j] = segs[b].row0 + j * segs[b].L; p.seg[segs[b].seq0 + j] = (int)b; }
+    return p;
 }
+// The device tables of a planned layout, sequence by sequence: perm, the EOT row of every sequence in the packed rows (rows) and relative to its
+// bucket's first row (local); own(sequence, class, first row, rows of its bucket) adds the caller's.  lay.nseq > C: CoCoOp's chunk, see there
+template <class F>
+static void fill_layout_tables(const TextLayout& lay, const TextPlan& p, const int32_t* eot, int* perm, int* rows, int* local, F own) {
+    const int C = (int)p.order.size(), per = lay.rows / (lay.nseq / C);  // packed rows of one image's class set
+    for (int sq = 0; sq < lay.nseq; ++sq) {
+        const TextLayout::Seg& g = lay.segs[p.seg[sq % C]];
+        const int cc = p.order[sq % C], r0 = sq / C * per + p.first[sq % C];
+        if (sq < C) perm[sq] = cc;
+        rows[sq] = r0 + eot[cc]; local[sq] = rows[sq] - g.row0;
+        own(sq, cc, (size_t)r0, g.L);
+    }
+}
+
+// Points the text tower at a layout: what its block functions, tower_rows and TowerSegs read of it
+static void bind_text_layout(Tower& t, const TextLayout& lay) { t.lay = &lay; t.L = lay.L; t.Lp = attn_padded_len(lay.L); t.tail_rows = lay.eot_rows; }
 
 extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const int32_t* eot) {
     ARG_CHECK(m && emb && eot, "set_class_prompts: null argument");
@@ -1232,14 +1267,9 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
             ARG_CHECK(name_len(cc) >= 0 && 1 + n + name_len(cc) <= eot[cc], "set_class_prompts: class %zu: name_lens %d with n_ctx %d does not fit before its EOT row %d",
                       cc, name_len(cc), n, eot[cc]);
     }
-    // The text tower is causal (clip/model.py:407-413 build_attention_mask) and only the EOT row of each prompt is used
-    // (trainers/mudpt.py:154): positions behind the last EOT of the class set influence neither a used output nor a gradient,
-    // so the tower runs on the first Le = max(eot) + 1 positions of every prompt ("a photo of a <name>." ends at position 7-9
-    // of 77).  Row-wise operators and causal attention make the kept rows bit-identical to the full-length run;
-    // mudpt_model_set("txt_trim", 0) keeps all ctx_len positions (A/B runs, tests).
-    int max_eot = 0;
-    for (size_t cc = 0; cc < C; ++cc) max_eot = std::max(max_eot, (int)eot[cc]);
-    const size_t Le = m->txt_trim ? (size_t)std::max(max_eot + 1, m->txt.n + 2) : L;
+    Tower& X = m->txt; TextLayout& lay = m->lay;
+    const TextPlan plan = plan_text_layout(eot, (int)C, c.ctx_len, X.n, X.heads, m->txt_trim, m->txt_buckets, m->txt_bucket_cost, !m->cocoop, &lay);
+    const size_t Le = (size_t)lay.L, class_rows = (size_t)lay.rows;  // kept length; packed rows of the C class prompts
     // Sequences per text-tower pass.  MuDPT: the C class prompts.  CoCoOp: every image has its own C prompts (trainers/cocoop.py:187-194
     // loops over the images, C sequences at a time); here a CHUNK of images goes through the tower at once -- as many as fit a
     // memory budget (activations for the backward are ~150 KB per token at width 512) and the kernels' 32-bit offsets -- and
@@ -1267,53 +1297,42 @@ extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const i
         }
     }
     m->txt_chunk = (int)chunk;
-    if (int rc = alloc_tower_acts(m, m->txt, (int)Le, (int)(m->cocoop ? chunk * C : C))) return rc;
-    Tower& X = m->txt;
-    const std::vector<int> order = plan_length_buckets(m, eot, C, Le, X.n, X.heads, !m->cocoop, &X.segs, &X.rows);  // packed position -> local class
+    lay.segs[0].nseq *= (int)chunk; lay.nseq *= (int)chunk; lay.rows *= (int)chunk;  // CoCoOp: sequence i * C + c for image i of a chunk, one bucket
+    if (int rc = alloc_tower_acts(m, X, lay.L, lay.nseq)) return rc;
+    bind_text_layout(X, lay);
     std::vector<float> pos(L * d);
     HIP_TRY(hipMemcpy(pos.data(), m->tpos, pos.size() * 4, hipMemcpyDeviceToHost));
-    const size_t reps = chunk;  // CoCoOp: sequence i * C + c for every image i of a chunk (the tables are chunk-local, reused per chunk)
-    const std::vector<Tower::Seg> segs = tower_segs(X, (int)C);
-    const size_t packed_rows = X.segs.empty() ? C * Le : (size_t)X.rows;
-    std::vector<float> ep(packed_rows * d);
-    std::vector<int> rows(C * reps), rows_local(C * reps), tr(C * reps * X.n), perm(C), cpos(m->coop ? C * n : 0);
+    std::vector<float> ep(class_rows * d);
+    std::vector<int> rows(lay.nseq), rows_local(lay.nseq), tr((size_t)lay.nseq * X.n), perm(C), cpos(m->coop ? C * n : 0);
     int span = X.n;
-    for (const Tower::Seg& g : segs)
-        for (int j = 0; j < g.nseq; ++j) {
-            const int sq = g.seq0 + j, cc = order[sq];
-            const size_t r0 = (size_t)g.row0 + (size_t)j * g.L;
-            perm[sq] = cc;
-            for (size_t i = 0; i < reps; ++i) {  // reps > 1 (CoCoOp) only with one bucket: image i's prompts follow image i - 1's
-                rows[i * C + sq] = (int)(i * C * Le + r0) + eot[cc];
-                rows_local[i * C + sq] = (int)(i * C * Le + r0 - g.row0) + eot[cc];
-                if (!m->coop)
-                    for (int k = 0; k < X.n; ++k) tr[(i * C + sq) * X.n + k] = (int)(i * C * Le + r0) + 1 + k;  // ctx rows 1..n (trainers/mudpt.py:97-115)
+    fill_layout_tables(lay, plan, eot, perm.data(), rows.data(), rows_local.data(), [&](int sq, int cc, size_t r0, int Lg) {
+        if (!m->coop)
+            for (int k = 0; k < X.n; ++k) tr[(size_t)sq * X.n + k] = (int)r0 + 1 + k;  // ctx rows 1..n (trainers/mudpt.py:97-115)
+        if ((size_t)sq >= C) return;  // CoCoOp's further images: launch_cocoop_prompts builds their rows from these
+        if (m->coop) {
+            // CoOp: the prompt rows in construct_prompts' order, THEN the positional embedding (trainers/coop.py:187-188); the context
+            // rows' table in the caller's class order, token rows of the packed layout (coop.hip)
+            const int nl = name_len(cc);
+            for (int k = 0; k < n; ++k) {
+                cpos[(size_t)cc * n + k] = coop_ctx_row(ctp, n, nl, k);
+                tr[(size_t)cc * n + k] = (int)r0 + cpos[(size_t)cc * n + k];
             }
-            if (m->coop) {
-                // CoOp: the prompt rows in construct_prompts' order, THEN the positional embedding (trainers/coop.py:187-188); the context
-                // rows' table in the caller's class order, token rows of the packed layout (coop.hip)
-                const int nl = name_len(cc);
-                for (int k = 0; k < n; ++k) {
-                    cpos[(size_t)cc * n + k] = coop_ctx_row(ctp, n, nl, k);
-                    tr[(size_t)cc * n + k] = (int)r0 + cpos[(size_t)cc * n + k];
-                }
-                span = std::max(span, coop_ctx_row(ctp, n, nl, n - 1));
-                for (int t = 0; t < g.L; ++t) {
-                    const float* src = emb + ((size_t)cc * L + coop_src_row(ctp, n, nl, t)) * d;
-                    for (size_t k = 0; k < d; ++k) ep[(r0 + t) * d + k] = src[k] + pos[(size_t)t * d + k];
-                }
-                continue;
+            span = std::max(span, coop_ctx_row(ctp, n, nl, n - 1));
+            for (int t = 0; t < Lg; ++t) {
+                const float* src = emb + ((size_t)cc * L + coop_src_row(ctp, n, nl, t)) * d;
+                for (size_t k = 0; k < d; ++k) ep[(r0 + t) * d + k] = src[k] + pos[(size_t)t * d + k];
             }
-            for (size_t i = 0; i < (size_t)g.L * d; ++i) ep[r0 * d + i] = emb[(size_t)cc * L * d + i] + pos[i];  // trainers/mudpt.py:143
+            return;
         }
+        for (size_t i = 0; i < (size_t)Lg * d; ++i) ep[r0 * d + i] = emb[(size_t)cc * L * d + i] + pos[i];  // trainers/mudpt.py:143
+    });
     HIP_TRY(hipMemcpy(m->emb_pos, ep.data(), ep.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->eot_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->eot_local, rows_local.data(), rows_local.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(lay.eot_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(lay.eot_local, rows_local.data(), rows_local.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->tprompt_rows, tr.data(), tr.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->class_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(lay.perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
     if (m->coop) HIP_TRY(hipMemcpy(m->coop_pos, cpos.data(), cpos.size() * 4, hipMemcpyHostToDevice));
     X.head_span = span;  // block 0's backward computes the attention rows 1 .. span, which hold every context row (CoOp middle / front: > n)
-    X.tail_local = m->eot_local;
     m->prompts_set = true;
     m->text_valid = false;
     return MUDPT_OK;
@@ -1342,47 +1361,33 @@ extern "C" int mudpt_set_text_tokens(mudpt_model* m, const int32_t* tokens, int3
     for (size_t t = 0; t < T; ++t) {
         const int32_t* tk = tokens + t * C * L;
         std::vector<int32_t> eot(C);
-        int max_eot = 0;
         for (size_t cc = 0; cc < C; ++cc) {
             const int32_t* row = tk + cc * L;
             eot[cc] = (int32_t)(std::max_element(row, row + L) - row);  // the first of equal maxima
-            max_eot = std::max(max_eot, (int)eot[cc]);
         }
-        mudpt_model::Template& P = tm[t];
-        const size_t Le = m->txt_trim ? (size_t)std::max(max_eot + 1, 2) : L;
-        int packed = 0;
-        const std::vector<int> order = plan_length_buckets(m, eot.data(), C, Le, 0, X.heads, true, &P.segs, &packed);
-        P.L = (int)Le;
-        P.rows = P.segs.empty() ? (int)(C * Le) : packed;
-        Tower::Seg one; one.nseq = (int)C; one.L = (int)Le;
-        const std::vector<Tower::Seg> segs = P.segs.empty() ? std::vector<Tower::Seg>{one} : P.segs;
+        TextLayout& P = tm[t].lay;
+        const TextPlan plan = plan_text_layout(eot.data(), (int)C, c.ctx_len, 0, X.heads, m->txt_trim, m->txt_buckets, m->txt_bucket_cost, true, &P);
         base[t] = host.size();
         host.resize(base[t] + 2 * (size_t)P.rows + 3 * C);
         int *tok = host.data() + base[t], *pos = tok + P.rows, *rows = pos + P.rows, *local = rows + C, *perm = local + C;
-        for (const Tower::Seg& g : segs)
-            for (int j = 0; j < g.nseq; ++j) {
-                const int sq = g.seq0 + j, cc = order[sq], r0 = g.row0 + j * g.L;
-                perm[sq] = cc;
-                rows[sq] = r0 + eot[cc];
-                local[sq] = r0 - g.row0 + eot[cc];
-                for (int l = 0; l < g.L; ++l) { tok[r0 + l] = tk[(size_t)cc * L + l]; pos[r0 + l] = l; }
-            }
+        fill_layout_tables(P, plan, eot.data(), perm, rows, local, [&](int, int cc, size_t r0, int Lg) {
+            for (int l = 0; l < Lg; ++l) { tok[r0 + l] = tk[(size_t)cc * L + l]; pos[r0 + l] = l; }
+        });
         Lmax = std::max(Lmax, P.L);
     }
+    m->prompts_set = false;
+    m->text_valid = false;
+    // one set of activations for every template: n_cls sequences of the longest kept length hold any template's packed rows (the tower lets go of its layout here)
+    if (int rc = alloc_tower_acts(m, X, Lmax, (int)C)) return rc;
     if (m->tmpl_tables) (void)hipFree(m->tmpl_tables);
     m->tmpl_tables = nullptr;
     m->tmpl.clear();
-    m->prompts_set = false;
-    m->text_valid = false;
     HIP_TRY(hipMalloc((void**)&m->tmpl_tables, host.size() * 4));
     HIP_TRY(hipMemcpy(m->tmpl_tables, host.data(), host.size() * 4, hipMemcpyHostToDevice));
     for (size_t t = 0; t < T; ++t) {
-        mudpt_model::Template& P = tm[t];
-        P.tok = m->tmpl_tables + base[t]; P.pos = P.tok + P.rows; P.eot_rows = P.pos + P.rows; P.eot_local = P.eot_rows + C; P.perm = P.eot_local + C;
+        mudpt_model::Template& P = tm[t]; int* tables = m->tmpl_tables + base[t];
+        P.tok = tables; P.pos = tables + P.lay.rows; P.lay.eot_rows = tables + 2 * P.lay.rows; P.lay.eot_local = P.lay.eot_rows + C; P.lay.perm = P.lay.eot_local + C;
     }
-    // one set of activations for every template: n_cls sequences of the longest kept length hold any template's packed rows
-    X.segs.clear();
-    if (int rc = alloc_tower_acts(m, X, Lmax, (int)C)) return rc;
     m->tmpl = tm;
     m->prompts_set = true;
     return MUDPT_OK;
@@ -1390,18 +1395,12 @@ extern "C" int mudpt_set_text_tokens(mudpt_model* m, const int32_t* tokens, int3
 
 extern "C" int mudpt_text_layout(const mudpt_model* m, int32_t* rows, int32_t* buckets, int32_t* max_len) {
     ARG_CHECK(m && m->prompts_set, "text_layout: call mudpt_set_class_prompts (a frozen handle: mudpt_set_text_tokens) first");
-    if (m->frozen) {  // over the templates: token rows summed, the largest bucket count, the longest kept length
-        int r = 0, b = 0, l = 0;
-        for (const mudpt_model::Template& t : m->tmpl) { r += t.rows; b = std::max(b, t.segs.empty() ? 1 : (int)t.segs.size()); l = std::max(l, t.L); }
-        if (rows) *rows = r;
-        if (buckets) *buckets = b;
-        if (max_len) *max_len = l;
-        return MUDPT_OK;
-    }
-    const int nseq = m->cocoop ? m->txt_chunk * m->cfg.n_cls : m->ct;
-    if (rows) *rows = tower_rows(m->txt, nseq);
-    if (buckets) *buckets = m->txt.segs.empty() ? 1 : (int)m->txt.segs.size();
-    if (max_len) *max_len = m->txt.L;
+    // over the handle's layouts (a frozen handle: one per template): token rows summed, the largest bucket count, the longest kept length
+    int r = 0, b = 0, l = 0;
+    auto add = [&](const TextLayout& t) { r += t.rows; b = std::max(b, (int)t.segs.size()); l = std::max(l, t.L); };
+    if (!m->frozen) add(m->lay);
+    for (const mudpt_model::Template& t : m->tmpl) add(t.lay);
+    if (rows) *rows = r; if (buckets) *buckets = b; if (max_len) *max_len = l;
     return MUDPT_OK;
 }
 
@@ -1538,7 +1537,7 @@ static AttnArgs seg_attn(const Tower& t, const BlockAct& a, const Tower::Seg& g,
     if (saved) { at.out = lp_at(a.attn, (size_t)g.row0 * t.d); at.lse = a.lse + g.lse0; }
     return at;
 }
-static const int* seg_tail_rows(const Tower& t, const Tower::Seg& g) { return t.segs.size() > 1 ? t.tail_local + g.seq0 : t.tail_rows; }  // packed: relative to the bucket
+static const int* seg_tail_rows(const Tower& t, const Tower::Seg& g) { return t.packed() ? t.lay->eot_local + g.seq0 : t.tail_rows; }  // packed: relative to the bucket
 
 // Forward of the last block after its attention, on the one used row of every sequence (Tower::tail_rows): gathers the
 // rows, then out_proj (+ residual in the small GEMM's epilogue), ln_2, c_fc + QuickGELU, c_proj (+ residual) -> t.xout_sel.
@@ -1568,7 +1567,7 @@ static int block_fwd_tail(mudpt_model* m, Tower& t, int nseq, hipStream_t s, boo
 static int block_fwd(mudpt_model* m, Tower& t, int i, int nseq, const float* splice, hipStream_t s) {
     const BlockRows r = rows_all(t, i, nseq);
     const int M = r.rows, d = t.d, dt = m->dtype, n = t.n;
-    const std::vector<Tower::Seg> segs = tower_segs(t, nseq);
+    const TowerSegs segs(t, nseq);
     // bf16 mode: the update stream (out_proj / c_proj results) is kept in T like the gradient stream -- half the store time
     // of those GEMMs and 2 bytes less per element in the LayerNorm that adds it.  The last block's c_proj stays fp32 (launch_add).
     const bool lp = m->lp_upd;
@@ -1582,7 +1581,7 @@ static int block_fwd(mudpt_model* m, Tower& t, int i, int nseq, const float* spl
         if (lp) l1.add_lp = t.upd; else l1.add = t.upd;
         if (splice) { l1.ov_rows = splice; l1.ov_row0 = t.prompt_row0; l1.ov_n = n; l1.ov_L = t.L; }
     }
-    if (splice && i > 0 && segs.size() > 1) {
+    if (splice && i > 0 && t.packed()) {
         // the splice replaces rows by their position inside a sequence: one launch per length bucket
         for (const Tower::Seg& g : segs) {
             LnFwdArgs b = l1;
@@ -1653,7 +1652,7 @@ static int mlp_bwd(mudpt_model* m, Tower& t, int i, const BlockRows& r, hipStrea
 // the tower output; out: t.dx / t.dx_lp = gradient w.r.t. the last block's input, all rows.
 static int block_bwd_tail(mudpt_model* m, Tower& t, int nseq, hipStream_t s) {
     const int i = t.layers - 1, M = tower_rows(t, nseq), S = nseq, d = t.d, dt = m->dtype;
-    const std::vector<Tower::Seg> segs = tower_segs(t, nseq);
+    const TowerSegs segs(t, nseq);
     const BlockW& w = t.w[i]; const BlockAct& a = t.a[i];
     TRY(mlp_bwd(m, t, i, rows_tail(t, nseq), s));  // t.dsel(_lp) = gradient w.r.t. x_mid on the selected rows
     if (m->last_single && !t.exact_attn) {
@@ -1693,7 +1692,8 @@ static int block_bwd(mudpt_model* m, Tower& t, int i, int nseq, hipStream_t s, f
     const int M = tower_rows(t, nseq), d = t.d;
     const BlockW& w = t.w[i]; const BlockAct& a = t.a[i];
     TRY(mlp_bwd(m, t, i, rows_all(t, i, nseq), s));
-    for (const Tower::Seg& g : tower_segs(t, nseq)) {
+    const TowerSegs segs(t, nseq);
+    for (const Tower::Seg& g : segs) {
         AttnArgs at = seg_attn(t, a, g);
         at.dout = lp_at(t.dattn, (size_t)g.row0 * d); at.dqkv = lp_at(t.dqkv, (size_t)g.row0 * 3 * d); at.delta = t.delta + g.lse0;
         // block 0: only the prompt rows of dqkv are read below (Tower::head_rows)
@@ -1895,16 +1895,25 @@ static int image_side_forward(mudpt_model* m, const ImageSide& in, int B, hipStr
     return MUDPT_OK;
 }
 
+// One pass of the text tower over nseq sequences of the bound layout, block 0's input in place: the blocks (deep != null: its [D1][n][d] rows spliced
+// into blocks 1 .. D1), the head on the EOT rows (statistics rows r0 ..) and, packed, the scatter back to the caller's class order -> feat [nseq, e]
+static int text_tower_pass(mudpt_model* m, int nseq, size_t r0, const float* deep, float* feat, hipStream_t s) {
+    Tower& X = m->txt;
+    for (int i = 0; i < X.layers; ++i) TRY(block_fwd(m, X, i, nseq, (deep && i >= 1 && i - 1 < X.D1) ? deep + (size_t)(i - 1) * X.n * X.d : nullptr, s));
+    TRY(tower_head_fwd(m, X, text_head(m), X.packed() ? m->txt_sorted : feat, nseq, r0, s));
+    if (X.packed()) TRY(scatter(m->txt_sorted, X.lay->perm, feat, nseq, m->cfg.embed_dim, 4, s));
+    return MUDPT_OK;
+}
+
 // ---- CoCoOp (trainers/cocoop.py) ------------------------------------------------------------------------------------
 // text tower over the prompts of images [i0, i0 + nb): prompts (:148-165) + positional embedding (:52), 12 causal blocks, ln_final on
 // the EOT rows, text_projection -> rows i0 * C .. of m->txt_f
 static int cocoop_text_chunk(mudpt_model* m, int i0, int nb, hipStream_t s) {
     const mudpt_config& c = m->cfg;
-    const int dt = c.t_width, e = c.embed_dim, n = c.n_ctx, C = c.n_cls, Lt = m->txt.L, TS = nb * C;
+    const int dt = c.t_width, e = c.embed_dim, n = c.n_ctx, C = c.n_cls, Lt = m->txt.L;
     const size_t r0 = (size_t)i0 * C;
     TRY(launch_cocoop_prompts(m->txt.a[0].x_in, m->emb_pos, m->params + m->off(Q_CTX), m->mn_bias + (size_t)i0 * dt, m->tpos, nb, C, Lt, dt, n, s));
-    for (int i = 0; i < m->txt.layers; ++i) TRY(block_fwd(m, m->txt, i, TS, nullptr, s));
-    return tower_head_fwd(m, m->txt, text_head(m), m->txt_f + r0 * e, TS, r0, s);
+    return text_tower_pass(m, nb * C, r0, nullptr, m->txt_f + r0 * e, s);
 }
 
 static HeadArgs cocoop_head_args(mudpt_model* m, int i0, int nb, int B) {
@@ -2037,10 +2046,9 @@ static int uumudpt_forward_text(mudpt_model* m, hipStream_t s2) {
 // text tower, trainers/mudpt.py:142-156, over this handle's classes [c0, c0 + ct): rows c0.. of the [n_cls, e] feature table
 static int text_forward(mudpt_model* m, hipStream_t s2) {
     const mudpt_config& c = m->cfg;
-    const int dt = c.t_width, e = c.embed_dim, n = m->txt.n, D1 = m->txt.D1, Ct = m->ct;
+    const int dt = c.t_width, e = c.embed_dim, n = m->txt.n, Ct = m->ct;
     float* Pm = m->params;
-    const std::vector<Tower::Seg> segs = tower_segs(m->txt, Ct);
-    const bool packed = segs.size() > 1;
+    const TowerSegs segs(m->txt, Ct);
     const PromptRoute pr = prompt_route(m, m->txt);
     ++m->text_launches;
     HIP_TRY(hipMemcpyAsync(m->txt.a[0].x_in, m->emb_pos, (size_t)tower_rows(m->txt, Ct) * dt * 4, hipMemcpyDeviceToDevice, s2));
@@ -2049,11 +2057,8 @@ static int text_forward(mudpt_model* m, hipStream_t s2) {
     else if (n > 0)  // MuDPT ctx / MPT text_prompt_learner.visual_ctx at rows 1..n
         for (const Tower::Seg& g : segs)
             TRY(launch_set_rows(m->txt.a[0].x_in + (size_t)g.row0 * dt, g.nseq, g.L, dt, 1, n, pr.in0, pr.in0_add, s2));
-    for (int i = 0; i < m->txt.layers; ++i) TRY(block_fwd(m, m->txt, i, Ct, (i >= 1 && i - 1 < D1) ? pr.deep + (size_t)(i - 1) * n * dt : nullptr, s2));
     if (m->sharded) HIP_TRY(hipMemsetAsync(m->txt_f, 0, (size_t)c.n_cls * e * 4, s2));  // other ranks' rows: zero, so a sum completes the table
-    float* feat = m->txt_f + (size_t)m->c0 * e;
-    TRY(tower_head_fwd(m, m->txt, text_head(m), packed ? m->txt_sorted : feat, Ct, 0, s2));
-    if (packed) TRY(scatter(m->txt_sorted, m->class_perm, feat, Ct, e, 4, s2));  // back to the caller's class order
+    TRY(text_tower_pass(m, Ct, 0, pr.deep, m->txt_f + (size_t)m->c0 * e, s2));
     m->text_valid = true;
     return MUDPT_OK;
 }
@@ -2135,13 +2140,10 @@ static int frozen_text_features(mudpt_model* m, hipStream_t s) {
     Tower& X = m->txt;
     for (int t = 0; t < T; ++t) {
         const mudpt_model::Template& P = m->tmpl[t];
-        X.segs = P.segs; X.rows = P.rows; X.L = P.L; X.Lp = attn_padded_len(P.L); X.tail_rows = P.eot_rows; X.tail_local = P.eot_local;
+        bind_text_layout(X, P.lay);
         ++m->text_launches;
-        TRY(launch_embed_tokens(m->tok_table, m->vocab, P.tok, P.pos, m->tpos, X.a[0].x_in, P.rows, dt, s));
-        for (int i = 0; i < X.layers; ++i) TRY(block_fwd(m, X, i, C, nullptr, s));
-        const bool packed = P.segs.size() > 1;
-        TRY(tower_head_fwd(m, X, text_head(m), packed ? m->txt_sorted : m->txt_f, C, 0, s));
-        if (packed) TRY(scatter(m->txt_sorted, P.perm, m->txt_f, C, e, 4, s));
+        TRY(launch_embed_tokens(m->tok_table, m->vocab, P.tok, P.pos, m->tpos, X.a[0].x_in, P.lay.rows, dt, s));
+        TRY(text_tower_pass(m, C, 0, nullptr, m->txt_f, s));
         TRY(launch_feature_ensemble(m->txt_f, m->ens_acc, m->txt_n, C, e, t == 0, t == T - 1, T, s));
     }
     m->text_valid = true;
@@ -2304,10 +2306,10 @@ static int text_backward(mudpt_model* m, float unscale, hipStream_t s2) {
     Tower& X = m->txt;
     const PromptRoute pr = prompt_route(m, X);
     ++m->text_launches;
-    const std::vector<Tower::Seg> segs = tower_segs(X, Ct);
+    const TowerSegs segs(X, Ct);
     const float* dfeat = m->dtxt + (size_t)m->c0 * e;
-    if (segs.size() > 1) {  // length buckets: the tower's sequences are in length-sorted order
-        TRY(gather(dfeat, m->class_perm, m->dtxt_sorted, Ct, e, 4, s2));
+    if (X.packed()) {  // length buckets: the tower's sequences are in length-sorted order
+        TRY(gather(dfeat, m->lay.perm, m->dtxt_sorted, Ct, e, 4, s2));
         dfeat = m->dtxt_sorted;
     }
     TRY(tower_head_bwd(m, X, text_head(m), dfeat, Ct, 0, s2));
@@ -2699,7 +2701,7 @@ extern "C" int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch,
     const float* src = nullptr;
     size_t n = 0;
     auto tower = [&](Tower& t, const std::string& rest, int nseq) {
-        if (!t.segs.empty() && rest != "x_out") return;  // packed in length buckets: no [seq, L, d] view (set txt_buckets = 1 to tap)
+        if (t.packed() && rest != "x_out") return;  // packed in length buckets: no [seq, L, d] view (set txt_buckets = 1 to tap)
         n = (size_t)nseq * t.L * t.d;
         if (rest == "x_out") { src = t.xout_sel; n = (size_t)nseq * t.d; }  // the used row (CLS / EOT) of every sequence only
         else if (rest.rfind("x_in.", 0) == 0) {
@@ -3150,5 +3152,20 @@ extern "C" int mudpt_conv_pack(int32_t dtype, const float* w, const float* gamma
     ARG_CHECK(w && gamma && beta && mean && var && w_out && bias_out, "conv_pack: null argument");
     ARG_CHECK(cout > 0 && cin > 0 && (k == 1 || k == 3) && ldk >= k * k * cin, "conv_pack: bad shape cout=%d cin=%d k=%d ldk=%d (k 1 | 3, ldk >= k k cin)", cout, cin, k, ldk);
     conv_pack(dtype, w, gamma, beta, mean, var, cout, cin, k, ldk, (uint16_t*)w_out, bias_out);
+    return MUDPT_OK;
+}
+
+// ---- the text tower's sequence layout (plan_text_layout), host only ----
+extern "C" int mudpt_text_layout_plan(const int32_t* eot, int32_t n_cls, int32_t ctx_len, int32_t n_prompt, int32_t heads, int32_t txt_trim, int32_t txt_buckets,
+                                      int32_t txt_bucket_cost, int32_t allow_buckets, int32_t* cls, int32_t* first_row, int32_t* bucket_len, int32_t* buckets,
+                                      int32_t* rows, int32_t* max_len) {
+    ARG_CHECK(eot && cls && first_row && bucket_len && buckets && rows && max_len, "text_layout_plan: null argument");
+    ARG_CHECK(n_cls >= 1 && heads >= 1, "text_layout_plan: n_cls %d and heads %d must be >= 1", n_cls, heads);
+    ARG_CHECK(n_prompt >= 0 && n_prompt + 2 <= ctx_len, "text_layout_plan: n_prompt %d needs 0 <= n_prompt and n_prompt + 2 <= ctx_len (%d)", n_prompt, ctx_len);
+    for (int32_t cc = 0; cc < n_cls; ++cc) ARG_CHECK(eot[cc] >= 0 && eot[cc] < ctx_len, "text_layout_plan: eot[%d] = %d outside [0, %d)", cc, eot[cc], ctx_len);
+    TextLayout lay;
+    const TextPlan p = plan_text_layout(eot, n_cls, ctx_len, n_prompt, heads, txt_trim != 0, txt_buckets, txt_bucket_cost, allow_buckets != 0, &lay);
+    for (int32_t q = 0; q < n_cls; ++q) { cls[q] = p.order[q]; first_row[q] = p.first[q]; bucket_len[q] = lay.segs[p.seg[q]].L; }
+    *buckets = (int32_t)lay.segs.size(); *rows = lay.rows; *max_len = lay.L;
     return MUDPT_OK;
 }
