@@ -11,6 +11,7 @@
  *   mudpt_forward                        trainers/mudpt.py:170-184 CustomCLIP.forward == model_inference()
  *   mudpt_forward_backward               trainers/mudpt.py:249-251 forward, F.cross_entropy, backward
  *   mudpt_sgd_step                       trainers/mudpt.py:251     model_backward_and_update's optimizer step
+ *   mudpt_optim_step                     trainers/mudpt.py:225,251 the same step under any other OPTIM.NAME build_optimizer takes (adam, amsgrad, adamw, rmsprop)
  *   mudpt_allreduce_grads                trainers/mudpt.py:230-233 nn.DataParallel's gradient reduce (here: one RCCL all-reduce)
  *   mudpt_set_class_shard / mudpt_cp_*   trainers/mudpt.py:142-156,178-182 the same step with the class prompts divided over the ranks
  *   mudpt_gemm / _layernorm_* / _attention_*   the ATen ops under clip/model.py:164-175,257-301 (unit parity)
@@ -100,7 +101,7 @@
 extern "C" {
 #endif
 
-/* 7 still with mudpt_create_frozen, mudpt_set_text_tokens, mudpt_text_features, mudpt_encode_image and the mudpt_augment* three: they are additions, no existing
+/* 7 still with mudpt_create_frozen, mudpt_set_text_tokens, mudpt_text_features, mudpt_encode_image, the mudpt_augment* three and mudpt_optim_step: they are additions, no existing
  * declaration, struct or constant changed, so every caller built against 7 runs unchanged -- the number moves when one would not.
  * mudpt_amd/capi.py binds from this file: it parses every declaration (int / int32_t / int64_t / float / size_t, const char*, any other pointer
  * or array; a type outside that raises at import) and every integer #define MUDPT_*, so names, types and order are stated here only. */
@@ -342,6 +343,37 @@ int mudpt_sgd_step(mudpt_model* m, float lr, float momentum, float weight_decay,
                    int32_t nesterov, void* stream);
 int mudpt_sgd_reset(mudpt_model* m);
 
+/* The optimizer step for every OPTIM.NAME of Dassl's build_optimizer but "radam" (additions: MUDPT_ABI_VERSION stays): torch.optim.SGD, Adam
+ * (amsgrad), AdamW and RMSprop (centered, momentum) by torch 2.10's single-tensor rules (torch/optim/adam.py::_single_tensor_adam, the
+ * non-capturable branch; torch/optim/rmsprop.py::_single_tensor_rmsprop; the statements: mudpt_amd/csrc/optim.hip), ONE launch over the flat bucket.
+ * The hyper-parameters are doubles, as torch's Python floats are: 1 - beta2, lr / (1 - beta1^step) and sqrt(1 - beta2^step) are formed in
+ * double and rounded to fp32 once (1 - 0.999f would be 1.3e-5 off).  `step` is the 1-based count of THIS update, kept by the caller.
+ * The state is CALLER-owned fp32 device memory of mudpt_param_numel elements per slot, zero before step 1 (a checkpoint is a copy of it):
+ *   algo                  state[0]          state[1]                          state[2]
+ *   MUDPT_OPTIM_SGD       momentum_buffer (momentum != 0; written, not read, at step 1)
+ *   MUDPT_OPTIM_ADAM      exp_avg           exp_avg_sq                        max_exp_avg_sq (amsgrad)      L2 decay: grad + weight_decay param
+ *   MUDPT_OPTIM_ADAMW     exp_avg           exp_avg_sq                        max_exp_avg_sq (amsgrad)      decoupled: param (1 - lr weight_decay)
+ *   MUDPT_OPTIM_RMSPROP   square_avg        momentum_buffer (momentum > 0)    grad_avg (centered)
+ * A slot the configuration does not use is not read and may be NULL.  Fields an algorithm does not use are not read either (SGD: lr, momentum,
+ * weight_decay, dampening, nesterov; Adam / AdamW: lr, beta1, beta2, eps, weight_decay, amsgrad; RMSprop: lr, alpha, eps, weight_decay,
+ * momentum, centered).  MUDPT_ERR_ARG before any GPU call: a null pointer, step < 1, eps <= 0, beta1 or beta2 outside [0, 1), a negative or
+ * non-finite lr / weight_decay / alpha / momentum, a needed state slot that is NULL or (but for SGD) not 16-byte aligned, two buffers that
+ * overlap, an unknown algo. */
+#define MUDPT_OPTIM_SGD 0
+#define MUDPT_OPTIM_ADAM 1
+#define MUDPT_OPTIM_ADAMW 2
+#define MUDPT_OPTIM_RMSPROP 3
+typedef struct mudpt_optim {
+    int32_t algo; /* MUDPT_OPTIM_* */
+    double lr, beta1, beta2, eps, weight_decay, momentum, alpha, dampening;
+    int32_t nesterov, amsgrad, centered;
+    int64_t step; /* the 1-based count of this update */
+    float* state[3];
+} mudpt_optim;
+/* Updates the bound parameters from the bound gradients (mudpt_bind_params); asynchronous on `stream`.  A frozen handle: MUDPT_ERR_ARG
+ * ("... frozen ...").  It neither reads nor moves what mudpt_sgd_step keeps (its momentum buffer, its first-step flag). */
+int mudpt_optim_step(mudpt_model* m, const mudpt_optim* optim, void* stream);
+
 /* ======================================================================================================================================
  * Everything below this line is TEST / MEASUREMENT / DEBUG surface, not part of the drop-in boundary: a trainer plugin needs none of it.
  * ====================================================================================================================================== */
@@ -567,6 +599,9 @@ int mudpt_coop_dctx(int32_t dtype, const float* dx_f32, const void* dx_lp, const
 /* fp32 C[M,N] = alpha * op(A) . op(B) (+ bias[N]) (+ beta * C): the prompt projections (trainers/mudpt.py:127-128, clip/model.py:539). */
 int mudpt_sgemm(int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda,
                 const float* B, int32_t ldb, float beta, float* C, int32_t ldc, const float* bias, void* stream);
+/* mudpt_optim_step without a handle: one update of p [n] from g [n] with the state slots of `optim`, every check of mudpt_optim_step's launcher
+ * (they read no device memory, so they answer without a GPU). */
+int mudpt_optim_apply(const mudpt_optim* optim, float* p, const float* g, int64_t n, void* stream);
 
 /* ---- the launchers' production forms (test surface like the rest of this section: additions here leave MUDPT_ABI_VERSION alone, it
  * numbers the drop-in boundary above the line) ---- */

@@ -33,6 +33,13 @@ class ResnetShape(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("layers1", "layers2", "layers3", "layers4", "width", "heads")]
 
 
+class Optim(C.Structure):
+    """mudpt_optim: one optimizer update.  The hyper-parameters are doubles (torch's Python floats), ``step`` the 1-based count of this update,
+    ``state`` the caller-owned fp32 device buffers of the algorithm (include/mudpt.h names the slots)."""
+    _fields_ = ([("algo", C.c_int32)] + [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "momentum", "alpha", "dampening")] +
+                [(n, C.c_int32) for n in ("nesterov", "amsgrad", "centered")] + [("step", C.c_int64), ("state", C.c_void_p * 3)])
+
+
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "size_t": C.c_size_t}
 _RETURNS = {"int": C.c_int32, "size_t": C.c_size_t, "const char*": C.c_char_p}
 
@@ -81,6 +88,7 @@ VARIANT_MUDPT, VARIANT_COCOOP, VARIANT_COOP, VARIANT_COOP_CSC, VARIANT_VPT, VARI
     "VARIANT_MUDPT", "VARIANT_COCOOP", "VARIANT_COOP", "VARIANT_COOP_CSC", "VARIANT_VPT", "VARIANT_MPT", "VARIANT_UMUDPT", "VARIANT_UUMUDPT")(_DEFINES)
 CLASS_TOKEN_END, CLASS_TOKEN_MIDDLE, CLASS_TOKEN_FRONT = itemgetter("CLASS_TOKEN_END", "CLASS_TOKEN_MIDDLE", "CLASS_TOKEN_FRONT")(_DEFINES)  # TRAINER.COOP.CLASS_TOKEN_POSITION
 CP_VISION, CP_TEXT = itemgetter("CP_VISION", "CP_TEXT")(_DEFINES)  # mudpt_cp_backward parts
+OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW, OPTIM_RMSPROP = itemgetter("OPTIM_SGD", "OPTIM_ADAM", "OPTIM_ADAMW", "OPTIM_RMSPROP")(_DEFINES)  # mudpt_optim.algo
 FWD_REUSE_TEXT, FWD_TRAINING = itemgetter("FWD_REUSE_TEXT", "FWD_TRAINING")(_DEFINES)  # mudpt_forward_ex / mudpt_cp_forward flags
 # the codes of mudpt_attention_form / mudpt_gemm_form (MUDPT_ATTN_* / MUDPT_GEMM_*): the names after the prefix, ordered by value
 ATTN_FORMS, GEMM_FORMS = (tuple(n[len(pre):] for n in sorted(_DEFINES, key=_DEFINES.get) if n.startswith(pre)) for pre in ("ATTN_", "GEMM_"))

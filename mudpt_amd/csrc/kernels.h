@@ -260,6 +260,22 @@ int launch_relu_bwd(float* dy, const float* y, size_t n, hipStream_t s);
 // Fused SGD (torch.optim.SGD semantics) over the flat bucket.
 int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay,
                float dampening, bool nesterov, bool first_step, hipStream_t s);
+// The fused optimizer step (optim.hip): torch 2.10's single-tensor Adam / AdamW (amsgrad) and RMSprop (centered, momentum) rules over a flat
+// fp32 bucket in ONE launch; MUDPT_OPTIM_SGD goes through launch_sgd with first_step = (step == 1).  The fields are mudpt_optim's
+// (include/mudpt.h), hyper-parameters in double: the host derives 1 - beta, lr / (1 - beta1^step), sqrt(1 - beta2^step) in double, as torch's
+// Python does, and rounds each to fp32 once.  state[k]: Adam exp_avg, exp_avg_sq, max_exp_avg_sq (amsgrad); RMSprop square_avg,
+// momentum_buffer (momentum > 0), grad_avg (centered); SGD momentum_buffer (momentum != 0); a slot the configuration does not use is not read.
+// Refused on the host: a null or (but for SGD) misaligned buffer, n < 1, step < 1, eps <= 0, a beta outside [0, 1), a needed state slot that
+// is null, any two of the buffers overlapping.
+struct OptimArgs {
+    int algo = MUDPT_OPTIM_SGD;
+    double lr = 0, beta1 = 0.9, beta2 = 0.999, eps = 1e-8, weight_decay = 0, momentum = 0, alpha = 0.99, dampening = 0;
+    bool nesterov = false, amsgrad = false, centered = false;
+    int64_t step = 0;  // the 1-based count of this update
+    float* p = nullptr; const float* g = nullptr; float* state[3] = {nullptr, nullptr, nullptr};
+    int64_t n = 0;
+};
+int launch_optim(const OptimArgs& a, hipStream_t s);
 // The input pipeline on the device (augment.hip; the arguments and the operation: include/mudpt.h at mudpt_augment).  images / params are
 // DEVICE tables the launcher cannot read (mudpt_augment_check validates a host copy); mean_std_host is read before the launch returns.
 int launch_augment(const uint8_t* pixels, const int64_t* images, int n_images, const int32_t* params, int batch, int size, const float* mean_std_host,

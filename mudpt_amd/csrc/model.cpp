@@ -2570,6 +2570,22 @@ extern "C" int mudpt_sgd_reset(mudpt_model* m) {
     return MUDPT_OK;
 }
 
+// mudpt_optim -> the launcher's arguments; the buffers are the caller's
+static OptimArgs optim_args(const mudpt_optim& o, float* p, const float* g, int64_t n) {
+    OptimArgs a;
+    a.algo = o.algo; a.lr = o.lr; a.beta1 = o.beta1; a.beta2 = o.beta2; a.eps = o.eps; a.weight_decay = o.weight_decay; a.momentum = o.momentum;
+    a.alpha = o.alpha; a.dampening = o.dampening; a.nesterov = o.nesterov != 0; a.amsgrad = o.amsgrad != 0; a.centered = o.centered != 0; a.step = o.step;
+    a.p = p; a.g = g; a.n = n;
+    for (int k = 0; k < 3; ++k) a.state[k] = o.state[k];
+    return a;
+}
+extern "C" int mudpt_optim_step(mudpt_model* m, const mudpt_optim* optim, void* stream) {
+    NOT_FROZEN(m, "optim_step");
+    ARG_CHECK(m && optim, "optim_step: null argument");
+    ARG_CHECK(m->params && m->grads, "optim_step: parameters / gradients not bound");
+    return launch_optim(optim_args(*optim, m->params, m->grads, (int64_t)m->total), (hipStream_t)stream);
+}
+
 // ---- data-parallel exchange for hosts without torch.distributed ---------------------------------------------------------------
 // The ONE collective of a step: sum of the flat gradient bucket over the ranks of an RCCL communicator the caller
 // created (ncclCommInitRank; one process per GPU).  RCCL is resolved at first use from the process (librccl.so.1, the SONAME torch
@@ -2768,6 +2784,10 @@ extern "C" int mudpt_gemm_split(int32_t dtype, int32_t epi, int32_t M, int32_t N
     GemmArgs a; a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.bias = bias; a.out0 = out0; a.ldo0 = ldo0; a.out1 = out1; a.ldo1 = ldo1;
     a.aux = aux; a.ldaux = ldaux; a.A_lo = A_lo; a.lo_mode = lo_mode; a.B8 = B8; a.b8_scale = b8_scale; a.out1_lo = out1_lo; a.out1_lo_mode = out1_lo ? out1_lo_mode : (int)LO_F16;
     return launch_gemm(dtype, epi, a, (hipStream_t)stream, o);
+}
+extern "C" int mudpt_optim_apply(const mudpt_optim* optim, float* p, const float* g, int64_t n, void* stream) {
+    ARG_CHECK(optim, "optim_apply: null argument");
+    return launch_optim(optim_args(*optim, p, g, n), (hipStream_t)stream);
 }
 extern "C" int mudpt_e4m3_from_f32(const float* in_host, uint8_t* out_host, size_t n, int32_t shift) {
     ARG_CHECK(in_host && out_host, "e4m3_from_f32: null argument");

@@ -39,7 +39,8 @@ def default_cfg() -> CfgNode:
         DATASET=C(NAME="Synthetic", NUM_CLASSES=11, NUM_TRAIN=64, NUM_TEST=32),
         DATALOADER=C(TRAIN_X=C(BATCH_SIZE=4), TEST=C(BATCH_SIZE=100)),
         OPTIM=C(NAME="sgd", LR=0.0025, MAX_EPOCH=10, LR_SCHEDULER="cosine", WARMUP_EPOCH=1, WARMUP_TYPE="constant",
-                WARMUP_CONS_LR=1e-5, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, SGD_DAMPNING=0.0, SGD_NESTEROV=False),
+                WARMUP_CONS_LR=1e-5, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, SGD_DAMPNING=0.0, SGD_NESTEROV=False,
+                ADAM_BETA1=0.9, ADAM_BETA2=0.999, RMSPROP_ALPHA=0.99),  # Dassl's defaults (dassl/config/defaults.py)
         TRAIN=C(PRINT_FREQ=5),
         TEST=C(EVALUATOR="Classification", PER_CLASS_RESULT=False, COMPUTE_CMAT=False),  # Dassl's defaults (dassl/config/defaults.py)
         TRAINER=C(NAME="MuDPT", MUDPT=C(N_CTX=2, CTX_INIT="a photo of a", DEEP_PROMPT_DEPTH=8, PREC="fp16"),
@@ -79,11 +80,31 @@ def build_trainer(cfg):
     return TRAINER_REGISTRY.get(cfg.TRAINER.NAME)(cfg)
 
 
+AVAI_OPTIMS = ("adam", "amsgrad", "sgd", "rmsprop", "adamw")  # Dassl's list without "radam"
+
+
 def build_optimizer(model, optim_cfg):
-    """Dassl's build_optimizer for NAME == "sgd": torch SGD over the module's parameters."""
-    assert optim_cfg.NAME == "sgd", "dassl_lite only provides SGD"
-    return torch.optim.SGD([p for p in model.parameters() if p.requires_grad], lr=optim_cfg.LR, momentum=optim_cfg.MOMENTUM,
-                           weight_decay=optim_cfg.WEIGHT_DECAY, dampening=optim_cfg.SGD_DAMPNING, nesterov=optim_cfg.SGD_NESTEROV)
+    """Dassl's build_optimizer over the module's trainable parameters in one group (no STAGED_LR): the torch class of OPTIM.NAME with LR,
+    WEIGHT_DECAY, MOMENTUM, SGD_DAMPNING, SGD_NESTEROV, ADAM_BETA1 / ADAM_BETA2 and RMSPROP_ALPHA.  "radam" is refused by name: Dassl steps
+    its own RAdam class, which is not here to restate."""
+    name = optim_cfg.NAME
+    params = [p for p in model.parameters() if p.requires_grad]
+    lr, wd = optim_cfg.LR, optim_cfg.WEIGHT_DECAY
+    if name == "sgd":
+        return torch.optim.SGD(params, lr=lr, momentum=optim_cfg.MOMENTUM,
+                               weight_decay=wd, dampening=optim_cfg.SGD_DAMPNING, nesterov=optim_cfg.SGD_NESTEROV)
+    if name == "radam":
+        raise NotImplementedError('OPTIM.NAME "radam": Dassl steps its own RAdam class, which dassl_lite does not provide; use one of ' + ", ".join(AVAI_OPTIMS))
+    if name not in AVAI_OPTIMS:
+        raise ValueError(f"optim must be one of {list(AVAI_OPTIMS)}, but got {name}")
+    betas = (optim_cfg.ADAM_BETA1, optim_cfg.ADAM_BETA2)
+    if name == "adam":
+        return torch.optim.Adam(params, lr=lr, weight_decay=wd, betas=betas)
+    if name == "amsgrad":
+        return torch.optim.Adam(params, lr=lr, weight_decay=wd, betas=betas, amsgrad=True)
+    if name == "adamw":
+        return torch.optim.AdamW(params, lr=lr, weight_decay=wd, betas=betas)
+    return torch.optim.RMSprop(params, lr=lr, momentum=optim_cfg.MOMENTUM, weight_decay=wd, alpha=optim_cfg.RMSPROP_ALPHA)
 
 
 class _ConstantWarmupCosine(torch.optim.lr_scheduler._LRScheduler):

@@ -4,6 +4,7 @@
     python -m mudpt_amd.harness --trainer CoOp --epochs 2 [--csc] [--class-token-position end|middle|front]
     python -m mudpt_amd.harness --trainer VPT|MPT --epochs 2 [--deep-text-n-ctx N --text-prompt-depth D --deep-visual-n-ctx N --visual-prompt-depth D]
     python -m mudpt_amd.harness --trainer UMuDPT|UUMuDPT --epochs 2 [--n-ctx N --depth D]
+    [MUDPT_FUSED_OPTIM=1] python -m mudpt_amd.harness --optim adam|amsgrad|adamw|rmsprop|sgd [--lr 0.0025]
 
 Mirrors what ``train.py`` (reference :153-173) does after config assembly: build_trainer(cfg) -> train() / test()."""
 from __future__ import annotations
@@ -31,6 +32,8 @@ def run(argv=None):
     # VPT / MPT: TRAINER.<NAME>.DEEP_TEXT_N_CTX / TEXT_PROMPT_DEPTH / DEEP_VISUAL_N_CTX / VISUAL_PROMPT_DEPTH; default: the shipped yaml's
     for flag in ("--deep-text-n-ctx", "--text-prompt-depth", "--deep-visual-n-ctx", "--visual-prompt-depth"):
         ap.add_argument(flag, type=int, default=None, help="VPT / MPT prompt shape (default: configs/trainers/<NAME>/vit_b16_c2_ep5_batch4.yaml)")
+    ap.add_argument("--optim", default="sgd", choices=list(dassl_lite.AVAI_OPTIMS), help="OPTIM.NAME (MUDPT_FUSED_OPTIM=1: its step as one HIP launch)")
+    ap.add_argument("--lr", type=float, default=None, help="OPTIM.LR (default: the shipped MuDPT yaml's 0.0025)")
     ap.add_argument("--output-dir", default="output/mudpt_amd")
     ap.add_argument("--backbone-path", default="")
     ap.add_argument("--eval-only", action="store_true")
@@ -42,6 +45,9 @@ def run(argv=None):
     cfg = dassl_lite.default_cfg()
     cfg.OUTPUT_DIR = a.output_dir
     cfg.OPTIM.MAX_EPOCH = a.epochs
+    cfg.OPTIM.NAME = a.optim
+    if a.lr is not None:
+        cfg.OPTIM.LR = a.lr
     cfg.DATALOADER.TRAIN_X.BATCH_SIZE = a.batch
     cfg.DATALOADER.TEST.BATCH_SIZE = max(a.batch, 8)
     cfg.DATASET.NUM_CLASSES, cfg.DATASET.NUM_TRAIN, cfg.DATASET.NUM_TEST = a.classes, a.train_images, 16

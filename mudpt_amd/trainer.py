@@ -238,6 +238,21 @@ def install_test_loader(trainer, local: int):
             trainer.test_loader = device_loader
 
 
+def fused_optimizer(model, optim):
+    """The opt-in fused optimizer step (mudpt_amd/optim.py; MUDPT_FUSED_OPTIM=1): a torch.optim.SGD / Adam / AdamW / RMSprop over exactly the
+    tensors of the model's bucket becomes the BucketOptimizer of the same hyper-parameters, whose step is ONE HIP launch; its state_dict is
+    torch's, so checkpoints move between the two.  Anything else -- another class, parameter groups that differ, maximize, only a part of
+    the bucket -- is refused with a one-line note and ``optim`` is returned as it came."""
+    from .optim import BucketOptimizer
+    try:
+        fused = BucketOptimizer.from_torch(optim, model=model, backend="hip")
+    except ValueError as why:
+        print(f"Fused optimizer step refused: {why}; stepping through torch.optim.{type(optim).__name__}")
+        return optim
+    print(f"Fused optimizer step: {fused.algo_name} over the bucket's {model.flat_params.numel()} elements in one HIP launch per step")
+    return fused
+
+
 def parse_batch(trainer, batch):
     """parse_batch_train of both plugins (trainers/mudpt.py:263-268, trainers/cocoop.py:278-283).  N > 1: this rank's share of the global
     batch -- already the whole batch when the loader is rank-aware or the batch came through the DevicePrefetcher (sliced, on the
@@ -402,6 +417,8 @@ class PromptTrainer(TrainerX):
         if cfg.MODEL.INIT_WEIGHTS:
             load_pretrained_weights(trained, cfg.MODEL.INIT_WEIGHTS)
         self.optim = build_optimizer(trained, cfg.OPTIM)
+        if os.environ.get("MUDPT_FUSED_OPTIM") == "1":
+            self.optim = fused_optimizer(self.model, self.optim)
         self.sched = build_lr_scheduler(self.optim, cfg.OPTIM)
         self.register_model(self.MODEL_NAME, trained, self.optim, self.sched)
         self.scaler = None  # loss scaling lives inside the library (mudpt_set_loss_scale)
