@@ -756,6 +756,33 @@ int mudpt_eval_reset(int32_t* state, int32_t n_cls, int32_t with_cmat, void* str
 int mudpt_eval_accumulate(const float* logits, int32_t ldz, const int64_t* labels, int32_t rows, int32_t n_cls, int32_t* state, int32_t with_cmat, int32_t* pred,
                           void* stream);
 int mudpt_eval_finalize(const int32_t* state, int32_t n_cls, double* results, void* stream);
+/* Top-k on the device (mudpt_amd/csrc/topk.hip): ranked predictions, their softmax, and the rank of every label.  Stateless additions without a
+ * model handle, so MUDPT_ABI_VERSION stays.  logits [rows, n_cls] fp32 at row stride ldz >= n_cls, DEVICE data; 16-byte loads when the base is
+ * 16-byte aligned and ldz % 4 == 0, the same results either way.
+ * THE ORDER.  Column a precedes column b of a row z iff, on the key (isnan(z), z, -index): z[a] is NaN and (z[b] is not NaN or a < b); or neither
+ * is NaN and (z[a] > z[b] or (z[a] == z[b] and a < b)).  +0 == -0.  It is mudpt_eval_accumulate's prediction rule carried to every place and
+ * equals torch.sort(z, 1, descending=True, stable=True) on the CPU (NOT torch.topk, which returns ties in no defined order).
+ *   topk             index (int32 [rows, k]) = the first k columns of every row in that order; index[:, 0] is mudpt_eval_accumulate's pred.
+ *                    value (fp32 [rows, k], may be NULL) = their logits bit for bit (a NaN's payload excepted).  prob (fp32 [rows, k], may be
+ *                    NULL) = the softmax of the WHOLE row at those columns: m = the logit of the first column (the row maximum, or a NaN);
+ *                    terms expf(z - m), the accurate expf; lane l of a 64-lane wave adds, in ascending column order, the terms of columns
+ *                    4 l .. 4 l + 3 (+ 256, + 512, ..) below n_cls & ~3 and then of column (n_cls & ~3) + l; the 64 sums are added by an xor
+ *                    tree (32, 16, .. 1); prob = expf(z - m) / sum, one division per output.  The chain is fixed: a row gives the same bits in
+ *                    every run, at every position of every batch, at every ldz and alignment.  A row that holds a NaN, a +inf, or only -inf
+ *                    gives NaN probabilities, as torch.softmax does.  No LDS, no sort: k rounds over the row, which a lane keeps in
+ *                    registers up to n_cls = 1027; above that the first round reads memory and the others the cache.
+ *   rank_accumulate  labels int64 [rows], DEVICE data.  The rank of a row's label y = the number of columns that precede y (0: y is
+ *                    mudpt_eval_accumulate's prediction; it is the inverse permutation of the stable sort).  state: int32 [2 + kmax] =
+ *                    [total, invalid, hist[0 .. kmax)], caller-owned and zeroed by the caller: a valid row adds one to total and, if its rank
+ *                    is below kmax, to hist[rank]; a label outside [0, n_cls) adds one to invalid and nothing else (it never indexes
+ *                    anything).  Top-k accuracy for any k <= kmax = sum(hist[:k]) / total.  Integer atomics only: two runs give the same
+ *                    bits; nothing is reset: launches add up.  rank (int32 [rows], may be NULL) receives the full rank 0 .. n_cls - 1, -1 for
+ *                    an invalid label.
+ * MUDPT_ERR_ARG with a message that names the argument, before any GPU call, no output touched: a null logits, index, labels or state;
+ * rows < 1; n_cls < 1; ldz < n_cls; k or kmax outside 1 .. 64; k > n_cls. */
+int mudpt_topk(const float* logits, int32_t ldz, int32_t rows, int32_t n_cls, int32_t k, int32_t* index, float* value, float* prob, void* stream);
+int mudpt_rank_accumulate(const float* logits, int32_t ldz, const int64_t* labels, int32_t rows, int32_t n_cls, int32_t kmax, int32_t* state, int32_t* rank,
+                          void* stream);
 /* The ResNet tower's memory movers (mudpt_amd/csrc/resnet.hip) and its host-side weight packing.  Activations are NHWC in T (dtype 0 bf16 / 1 fp16),
  * one pixel = one row of C channels (C % 8 == 0) at a row stride (elements) >= C that is a multiple of 8; every pointer 16-byte aligned.  Refused on
  * the host (MUDPT_ERR_ARG): a null pointer, a size < 1, a stride or alignment outside that.

@@ -11,8 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "lib", "libmudpt_hip.so")
-SOURCES = ["gemm.hip", "gemm_pp.hip", "attention.hip", "attention_single.hip", "attention_exact.hip", "attention_resident.hip", "layernorm.hip", "elementwise.hip", "head.hip", "coop.hip", "promptgen.hip", "zeroshot.hip", "augment.hip", "probe.hip", "evaluate.hip", "resnet.hip", "optim.hip", "model.cpp"]
-HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "mudpt.h")]
+SOURCES = ["gemm.hip", "gemm_pp.hip", "attention.hip", "attention_single.hip", "attention_exact.hip", "attention_resident.hip", "layernorm.hip", "elementwise.hip", "head.hip", "coop.hip", "promptgen.hip", "zeroshot.hip", "augment.hip", "probe.hip", "evaluate.hip", "topk.hip", "resnet.hip", "optim.hip", "model.cpp"]
+HEADERS = ["common.h", "kernels.h", "eval_order.h", os.path.join("..", "..", "include", "mudpt.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 EXTRA_FLAGS = {"attention_resident.hip": ["-fno-slp-vectorize"], "augment.hip": ["-ffp-contract=off"]}  # why: the header of each file
 
@@ -36,7 +36,7 @@ def source_hash() -> str:
     tools/profile_round.sh, compared by bench.py -- a traffic figure measured on other kernels than the ones loaded is reported as null."""
     import hashlib
     h = hashlib.sha256()
-    for f in sorted(SOURCES + ["common.h", "kernels.h"]):
+    for f in sorted(SOURCES + ["common.h", "kernels.h", "eval_order.h"]):
         h.update(f.encode())
         h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()[:16]

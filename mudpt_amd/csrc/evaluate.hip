@@ -6,20 +6,12 @@
 // Only integers are added atomically, so the order of the adds does not change the state: two runs give the same bits.
 #include <climits>
 
+#include "eval_order.h"  // eval_take: the first NaN wins, otherwise the lowest index of the largest value; shared with topk.hip
 #include "kernels.h"
 
 namespace mudpt {
 
 constexpr int EV_HEAD = 4;  // total, correct, invalid, reserved
-
-// Does (ov, oi) beat (v, i)?  torch's CPU max walks the row with `if (!(value <= max)) { max = value; index = i; if (isnan(value)) break; }`:
-// the first NaN wins, otherwise the lowest index of the largest value (+0 == -0, so the earlier of the two).  Stated as an order on
-// (is NaN, value, -index) it is associative, so lanes and the wave tree may combine their candidates in any grouping.
-__device__ __forceinline__ void eval_take(float& v, int& i, float ov, int oi) {
-    const bool vn = v != v, on = ov != ov;
-    const bool other = on ? (!vn || oi < i) : (!vn && (ov > v || (ov == v && oi < i)));
-    if (other) { v = ov; i = oi; }
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void eval_accumulate_kernel(const float* __restrict__ Z, int ldz, const int64_t* __restrict__ labels, int rows, int C,

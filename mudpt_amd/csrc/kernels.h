@@ -333,6 +333,17 @@ int launch_eval_accumulate(const float* logits, int ldz, const int64_t* labels, 
 int launch_eval_finalize(const int* state, int n_cls, double* results, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Top-k in the evaluator's order (topk.hip; eval_order.h states the order): ranked predictions with their logits and softmax probabilities, and
+// the rank of every label.  1 <= k, kmax <= 64, k <= n_cls
+// ------------------------------------------------------------------------------------------------
+// index [rows, k] = the first k columns of every row in that order; value (may be null) their logits; prob (may be null) the fp32 softmax of
+// the WHOLE row at them, summed in a fixed chain: the same bits for a row wherever it lies
+int launch_topk(const float* logits, int ldz, int rows, int n_cls, int k, int* index, float* value, float* prob, hipStream_t s);
+// state [2 + kmax] int32 = [total, invalid, hist[kmax]]: hist[r] += rows whose label has rank r = the number of columns that precede it; a
+// label outside [0, n_cls) only counts as invalid; nothing is reset, launches add up.  rank [rows] (may be null): the full rank, -1 for such a label
+int launch_rank_accumulate(const float* logits, int ldz, const int64_t* labels, int rows, int n_cls, int kmax, int* state, int* rank, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // UMuDPT's prompt generator (promptgen.hip; trainers/umudpt.py:56-76,161-178): fp32 end to end, TRAINABLE weights
 // ------------------------------------------------------------------------------------------------
 // LayerNorm backward that also produces the affine gradients: dx = (dres +) LN'(dy), dgamma[j] (+)= sum_r dy[r][j] xhat[r][j],

@@ -3068,6 +3068,14 @@ extern "C" int mudpt_eval_accumulate(const float* logits, int32_t ldz, const int
 extern "C" int mudpt_eval_finalize(const int32_t* state, int32_t n_cls, double* results, void* stream) {
     return launch_eval_finalize(state, n_cls, results, (hipStream_t)stream);
 }
+// top-k in the evaluator's order (topk.hip): stateless, no model handle
+extern "C" int mudpt_topk(const float* logits, int32_t ldz, int32_t rows, int32_t n_cls, int32_t k, int32_t* index, float* value, float* prob, void* stream) {
+    return launch_topk(logits, ldz, rows, n_cls, k, index, value, prob, (hipStream_t)stream);
+}
+extern "C" int mudpt_rank_accumulate(const float* logits, int32_t ldz, const int64_t* labels, int32_t rows, int32_t n_cls, int32_t kmax, int32_t* state,
+                                     int32_t* rank, void* stream) {
+    return launch_rank_accumulate(logits, ldz, labels, rows, n_cls, kmax, state, rank, (hipStream_t)stream);
+}
 // UMuDPT's prompt generator (promptgen.hip): its three kernels, and the whole block as the model path runs it
 extern "C" int mudpt_layernorm_bwd_affine(const float* x, int32_t ldx, const float* mean, const float* rstd, const float* gamma, const float* dy, int32_t lddy,
                                           const float* dres, int32_t lddres, float* dx, int32_t lddx, float* dgamma, float* dbeta, int32_t accumulate,

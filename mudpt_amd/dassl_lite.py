@@ -197,8 +197,14 @@ class SyntheticDataManager:
 def build_evaluator(cfg, **kwargs):
     """Dassl's build_evaluator for its one classification evaluator: TEST.EVALUATOR "Classification" (Dassl's default) and
     "DeviceClassification" (the name registered with real Dassl) both give mudpt_amd.evaluator.DeviceClassification, which computes
-    Classification's numbers."""
+    Classification's numbers.  MUDPT_TEST_TOPK=5 or =3,5 (opt-in) adds top-k accuracy for those k to the test pass."""
     from .evaluator import DeviceClassification
+    wish = os.environ.get("MUDPT_TEST_TOPK", "").strip()
+    if wish and "topk" not in kwargs:
+        try:
+            kwargs["topk"] = tuple(int(k) for k in wish.split(","))
+        except ValueError:
+            raise ValueError(f"MUDPT_TEST_TOPK = {wish!r} is not a list of integers such as 5 or 3,5") from None
     test = getattr(cfg, "TEST", None)
     name = getattr(test, "EVALUATOR", "Classification")
     if name not in ("Classification", "DeviceClassification"):

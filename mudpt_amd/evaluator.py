@@ -11,6 +11,11 @@ labels=np.unique(y_true)) and confusion_matrix(normalize="true") give, called th
 ``evaluator`` = None (by the tensors: CUDA -> "hip", CPU -> "torch"), "hip" (needs the GPU; no fallback) or "torch" (the same counts
 restated with torch.bincount on the host: the reference the tests hold the kernels to).  Merging ranks is not built: the state is integers,
 so an all-reduce of it before finalize would be exact.
+
+``topk`` = (3, 5) (opt-in; dassl_lite.build_evaluator fills it from MUDPT_TEST_TOPK=3,5) adds top-k accuracy, the second number of CLIP's
+ImageNet tables: ``process`` makes one more launch, mudpt_rank_accumulate (csrc/topk.hip), into a second small state [total, invalid,
+hist[max k]] of the labels' ranks, and ``evaluate`` adds ``top{k}_accuracy`` = 100 x sum(hist[:k]) / total.  The two kernels rank by one order, so
+hist[0] is ``correct``: ``evaluate`` raises if they differ.  Without it nothing changes: the same launches, keys and printed text.
 """
 from __future__ import annotations
 
@@ -19,19 +24,25 @@ from collections import OrderedDict
 
 import torch
 
-from . import capi
+from . import capi, metrics
 
 MAX_ROWS = 2 ** 31 - 1  # the counts are int32
 HEAD = 4                # total, correct, invalid, reserved
+RANK_HEAD = 2           # the rank state: total, invalid, then hist[max k]
 
 
 class DeviceClassification:
     """Dassl's EvaluatorBase protocol: ``reset()``, ``process(mo, gt)`` per batch, ``evaluate() -> OrderedDict``.  The class count is
     len(lab2cname) when given, else the width of the first logits; the state is allocated by the first ``process``."""
 
-    def __init__(self, cfg, lab2cname=None, evaluator=None, **kwargs):
+    def __init__(self, cfg, lab2cname=None, evaluator=None, topk=(), **kwargs):
         if evaluator not in (None, "hip", "torch"):
             raise ValueError(f"unknown evaluator {evaluator!r}")
+        self._topk = tuple(int(k) for k in topk)
+        if any(not 1 <= k <= metrics.MAX_K for k in self._topk):
+            raise ValueError(f"topk = {self._topk}: every k must lie in 1 .. {metrics.MAX_K}")
+        if lab2cname is not None:
+            self._check_topk(len(lab2cname))
         self.cfg, self._lab2cname, self.evaluator = cfg, lab2cname, evaluator
         test = getattr(cfg, "TEST", None)
         self._per_class = bool(getattr(test, "PER_CLASS_RESULT", False))
@@ -39,9 +50,13 @@ class DeviceClassification:
         if self._per_class:
             assert lab2cname is not None  # dassl/evaluation/evaluator.py: the table prints class names
         self._n_cls = len(lab2cname) if lab2cname is not None else None
-        self._state = self._kind = None
+        self._state = self._kind = self._rank_state = None
         self._rows = 0
         self.last = None  # after evaluate(): the six numbers of mudpt_eval_finalize by name
+
+    def _check_topk(self, n_cls):
+        if self._topk and max(self._topk) > n_cls:
+            raise ValueError(f"topk = {self._topk}: k = {max(self._topk)} is more than the {n_cls} classes")
 
     # -- the state ---------------------------------------------------------------------------------------------------
     def state_numel(self, n_cls: int) -> int:
@@ -59,6 +74,8 @@ class DeviceClassification:
                                      stream=torch.cuda.current_stream(self._state.device).cuda_stream), "eval_reset")
         else:
             self._state.zero_()
+        if self._rank_state is not None:
+            self._rank_state.zero_()
 
     def _prepare(self, mo, gt):
         if mo.dim() != 2 or gt.dim() != 1 or gt.shape[0] != mo.shape[0] or mo.shape[0] < 1 or mo.shape[1] < 1:
@@ -67,6 +84,7 @@ class DeviceClassification:
         if kind == "hip" and not (mo.is_cuda and gt.is_cuda):
             raise capi.MudptError('the "hip" evaluator counts on the GPU: logits and labels must be CUDA tensors (there is no fallback)')
         if self._n_cls is None:
+            self._check_topk(mo.shape[1])
             self._n_cls = mo.shape[1]
         if mo.shape[1] != self._n_cls:
             raise ValueError(f"process: logits of {mo.shape[1]} classes, the evaluator counts {self._n_cls}")
@@ -82,6 +100,8 @@ class DeviceClassification:
                 self.reset()
             else:
                 self._state = torch.zeros(numel, dtype=torch.int64)
+            if self._topk:
+                self._rank_state = torch.zeros(RANK_HEAD + max(self._topk), dtype=self._state.dtype, device=self._state.device)
         return kind
 
     # -- the protocol ------------------------------------------------------------------------------------------------
@@ -98,8 +118,14 @@ class DeviceClassification:
             with torch.cuda.device(z.device):
                 capi.check(capi.call("mudpt_eval_accumulate", logits=z, ldz=z.stride(0), labels=y, rows=B, n_cls=C, state=self._state,
                                      with_cmat=int(self._with_cmat), stream=torch.cuda.current_stream(z.device).cuda_stream), "eval_accumulate")
+                if self._topk:
+                    capi.check(capi.call("mudpt_rank_accumulate", logits=z, ldz=z.stride(0), labels=y, rows=B, n_cls=C, kmax=max(self._topk),
+                                         state=self._rank_state, stream=torch.cuda.current_stream(z.device).cuda_stream), "rank_accumulate")
         else:
-            self._accumulate_torch(mo.detach().float().cpu(), gt.detach().to(torch.int64).cpu())
+            z, y = mo.detach().float().cpu(), gt.detach().to(torch.int64).cpu()
+            self._accumulate_torch(z, y)
+            if self._topk:
+                self._accumulate_ranks_torch(z, y)
         self._rows += B
 
     def _accumulate_torch(self, z, y):
@@ -116,6 +142,14 @@ class DeviceClassification:
         s[HEAD + 2 * C:HEAD + 3 * C] += torch.bincount(y[p == y], minlength=C)
         if self._with_cmat:
             s[HEAD + 3 * C:] += torch.bincount(y * C + p, minlength=C * C)
+
+    def _accumulate_ranks_torch(self, z, y):
+        """mudpt_rank_accumulate restated: the labels' ranks by the stable sort, the same cells as int64 on the host."""
+        s, kmax = self._rank_state, max(self._topk)
+        rank = metrics.label_ranks(z, y)
+        s[0] += int((rank >= 0).sum())
+        s[1] += int((rank < 0).sum())
+        s[RANK_HEAD:] += torch.bincount(rank[(rank >= 0) & (rank < kmax)], minlength=kmax)
 
     def _finalize_torch(self):
         """mudpt_eval_finalize restated in float64."""
@@ -161,12 +195,21 @@ class DeviceClassification:
         macro_f1 = six[4]
         self.last = {"total": total, "correct": correct, "invalid": invalid, "n_supported": int(six[3]), "macro_f1": macro_f1, "perclass_accuracy": six[5]}
         results["accuracy"], results["error_rate"], results["macro_f1"] = acc, err, macro_f1
+        topk_lines = ""
+        if self._topk:
+            ranks = self._rank_state.cpu().tolist() if self._rank_state is not None else [0] * (RANK_HEAD + max(self._topk))
+            if ranks[0] != total or ranks[1] != invalid or ranks[RANK_HEAD] != correct:  # one order in both kernels: a difference is a bug
+                raise RuntimeError(f"evaluate: the rank state counts total {ranks[0]}, invalid {ranks[1]}, rank 0 {ranks[RANK_HEAD]}; "
+                                   f"the evaluator's state counts total {total}, invalid {invalid}, correct {correct}")
+            for k in self._topk:
+                results[f"top{k}_accuracy"] = 100.0 * sum(ranks[RANK_HEAD:RANK_HEAD + k]) / total if total else 0.0
+                topk_lines += f"\n* top{k}_accuracy: {results[f'top{k}_accuracy']:.1f}%"
         print("=> result\n"
               f"* total: {total:,}\n"
               f"* correct: {correct:,}\n"
               f"* accuracy: {acc:.1f}%\n"
               f"* error: {err:.1f}%\n"
-              f"* macro_f1: {macro_f1:.1f}%")
+              f"* macro_f1: {macro_f1:.1f}%" + topk_lines)
         if self._per_class:
             print("=> per-class result")
             if per_class is not None:

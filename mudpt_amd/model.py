@@ -217,6 +217,14 @@ class LibraryModel(nn.Module):
         capi.check(self.lib.mudpt_image_features(self._h, B, capi.ptr(feat), self._stream()), "image_features")
         return feat[:B]
 
+    @torch.no_grad()
+    def predict(self, image: torch.Tensor, k: int = 5):
+        """CLIP's zero-shot recipe ``logits.softmax(-1).topk(k)`` on ``forward``'s logits: ``(prob [B, k] fp32, index [B, k] int64)`` from one
+        more launch (``metrics.topk``).  Ties are ranked by the evaluator's order (lower index first), so two runs agree."""
+        from . import metrics
+        index, prob = metrics.topk(self.forward(image), k, probabilities=True)
+        return prob, index
+
     def debug_read(self, name: str, batch: int = 1) -> torch.Tensor:
         """Flat fp32 host copy of an internal activation of the last call, "image_features", "text_features" or "text_launches" (test
         hook, see include/mudpt.h)."""
