@@ -215,6 +215,15 @@ int mudpt_create_frozen_resnet(const mudpt_config* cfg, const mudpt_resnet_shape
  * MUDPT_ERR_ARG before any GPU call: any other variant ("... its prompts live inside a ViT ..."), and everything
  * mudpt_create_frozen_resnet refuses, in the same words. */
 int mudpt_create_resnet(const mudpt_config* cfg, const mudpt_resnet_shape* rn, mudpt_model** out);
+/* How a ResNet handle (either of the two above) runs the convolutions of its tower.  path 0, the default: every convolution is patch rows
+ * (mudpt_im2col; a 1 x 1 reads the activation as it lies) + the GEMM with an fp32 output + mudpt_bias_act.  path 1: every convolution of the
+ * stem, the Bottlenecks and the downsample branches is ONE mudpt_conv2d launch, the residual of conv3 in its epilogue; the stem's first
+ * convolution (fp32 planar pixels, 3 channels) keeps its patch rows and runs mudpt_conv2d over them as a 1 x 1.  The poolings and the
+ * attention pool are the same launches.  Both paths round at the same places (mudpt_amd/csrc/resnet.hip lists them), so both are held to the
+ * same bounds; their bits differ where the fp32 sums run in another order.  May be called between any two forwards; an addition, so
+ * MUDPT_ABI_VERSION stays.  The buffers of path 0 stay allocated on path 1.
+ * MUDPT_ERR_ARG with a message: a null handle; a handle without a ResNet tower ("... has no ResNet image tower ..."); a path outside {0, 1}. */
+int mudpt_resnet_conv_path(mudpt_model* m, int32_t path);
 int mudpt_destroy(mudpt_model* m);
 
 /* Frozen weight by OpenAI CLIP state-dict key ("visual.transformer.resblocks.0.attn.in_proj_weight", ...),
@@ -385,7 +394,8 @@ int mudpt_optim_step(mudpt_model* m, const mudpt_optim* optim, void* stream);
  * launches -- normalisation of the text features, their gradient -- since the handle was created); UMuDPT: "umudpt.G" (the generator's output)
  * and "umudpt.dG" (its gradient as the vision tower's backward left it), each [depth, n_ctx, v_width]; UUMuDPT: "uumudpt.G" / "uumudpt.dG"
  * likewise and, at depth > 1, "uumudpt.T" (the second generator's output) / "uumudpt.dT" (its gradient as the text tower's backward left it),
- * each [depth - 1, n_ctx, embed_dim].  host_out may be NULL to query *numel. */
+ * each [depth - 1, n_ctx, embed_dim]; a ResNet handle: "conv2d_launches" (1 value: the mudpt_conv2d launches of its tower since the handle was
+ * created -- mudpt_resnet_conv_path 0 adds none, path 1 one per convolution).  host_out may be NULL to query *numel. */
 int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch, float* host_out, size_t capacity, size_t* numel);
 
 /* Debug knobs of ONE handle, for A/B measurements in one process and for tests (tools/gemm_bench.py, bench.py flags, tests/).  Nothing is
@@ -810,6 +820,28 @@ int mudpt_attnpool_attend(int32_t dtype, const float* q, int32_t ldq, const floa
                           int32_t H, void* stream);
 int mudpt_conv_pack(int32_t dtype, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, int32_t cout, int32_t cin, int32_t k,
                     int32_t ldk, void* w_out, float* bias_out);
+/* The convolution as one kernel (mudpt_amd/csrc/conv.hip): an implicit GEMM that gathers the taps while it stages its operand, with bias, residual
+ * and ReLU in its epilogue -- no patch rows and no fp32 accumulator go through memory.  An addition, so MUDPT_ABI_VERSION stays.
+ *   out[b, oy, ox, n] = T(act(sum_{ky, kx, c} src[b, oy stride + ky - p, ox stride + kx - p, c] w[n, (ky k + kx) C + c] + bias[n] + residual[b, oy, ox, n]))
+ *   k = 3: p = 1, stride 1 | 2;  k = 1: p = 0, stride 1.  Ho = (H - 1) / stride + 1, Wo likewise; a tap outside the image contributes zero.
+ *   src       [B, H, W, C] T NHWC at channel stride lds: C % 8 == 0, lds >= C, lds % 8 == 0; channels C .. lds - 1 are never read
+ *   w         [N, ldk] T as mudpt_conv_pack writes it: ldk >= k k C, ldk % 8 == 0; columns k k C .. ldk - 1 are never read.  N % 16 == 0
+ *   bias      [N] fp32 or NULL;  residual [B Ho Wo, N] T at row stride ldres (>= N, % 4 == 0) or NULL (ldres is then not read)
+ *   out       [B Ho Wo, N] T at row stride ldo (>= N, % 4 == 0); columns N .. ldo - 1 are not written
+ *   The products are summed in fp32 on the 16-bit MFMA in column order, 32 columns per instruction; then + bias, + residual, ReLU (relu != 0)
+ *   in fp32, in that order, and ONE rounding to T.  No split of K, no atomics, no workspace: a pixel's bits are the same in every run, at every
+ *   position of every batch and in every tile form.
+ * MUDPT_ERR_ARG before any launch, the message naming the argument: an unknown dtype; a null src, w or out; B, H, W, C or N < 1; k outside
+ * {1, 3}; stride outside the above; C % 8; a bad lds, ldk, N, ldo or ldres; a pointer that is not 16-byte aligned; B H W beyond 31 bits.
+ * mudpt_conv2d_form: HOST arithmetic only, the tile that runs M = B Ho Wo pixels x N channels (-1 for M or N < 1).  The first rule that matches,
+ * counted in tiles against the MI355X's 256 compute units whatever the device: N > 64 and at least 256 tiles of 128 x 128: T128x128; at least
+ * 256 tiles of 128 x 64: T128x64; T64x64. */
+#define MUDPT_CONV_T128x128 0 /* conv2d_kernel, 128 pixels x 128 channels x 64, 4 waves */
+#define MUDPT_CONV_T128x64 1  /* conv2d_kernel, 128 pixels x 64 channels x 64, 4 waves */
+#define MUDPT_CONV_T64x64 2   /* conv2d_kernel, 64 pixels x 64 channels x 64, 4 waves */
+int mudpt_conv2d(int32_t dtype, const void* src, int32_t B, int32_t H, int32_t W, int32_t C, int32_t lds, int32_t k, int32_t stride, const void* w, int32_t ldk,
+                 const float* bias, const void* residual, int32_t ldres, void* out, int32_t ldo, int32_t N, int32_t relu, void* stream);
+int mudpt_conv2d_form(int32_t M, int32_t N);
 /* The text tower's sequence layout as mudpt_set_class_prompts / mudpt_set_text_tokens plan it, for eot [n_cls] (the EOT position of every class
  * prompt, 0 <= eot < ctx_len) and n_prompt prompt rows per sequence (0 <= n_prompt, n_prompt + 2 <= ctx_len).  HOST arithmetic only: no handle,
  * no device call; an addition, so MUDPT_ABI_VERSION stays.  txt_trim, txt_buckets, txt_bucket_cost: the knobs of mudpt_model_set; allow_buckets = 0

@@ -301,6 +301,13 @@ int launch_attnpool_tokens(int dtype, const void* src, int lds, const float* pos
 // AttentionPool2d's attention of the pooled query: q [B, H * 64] fp32 (unscaled; the kernel applies 1 / 8), k / v rows b * L + l of H * 64
 // fp32 at stride ldkv -> out [B, H * 64] T; one wave per (image, head), fp32 throughout
 int launch_attnpool_attend(int dtype, const float* q, int ldq, const float* k, const float* v, int ldkv, void* out, int ldo, int B, int L, int H, hipStream_t s);
+// The convolution as one kernel (conv.hip): out [B Ho Wo, N] T = act(conv_k(src, w) + bias + residual), k = 3 (pad 1, stride 1 | 2) or 1 (stride 1);
+// src NHWC T (C % 8 == 0, channel stride lds), w [N, ldk] as mudpt_conv_pack writes it (N % 16 == 0), bias fp32 or null, residual T or null; fp32
+// accumulate on the MFMA, the adds and the ReLU in fp32, one rounding.  Reads no channel >= C, no weight column >= k k C, nothing outside the image
+int launch_conv2d(int dtype, const void* src, int B, int H, int W, int C, int lds, int k, int stride, const void* w, int ldk, const float* bias, const void* residual,
+                  int ldres, void* out, int ldo, int N, bool relu, hipStream_t s);
+// host arithmetic: the MUDPT_CONV_* tile launch_conv2d runs M pixels x N channels on, -1 for M or N < 1
+int conv2d_form(int M, int N);
 
 // ------------------------------------------------------------------------------------------------
 // The linear probe (probe.hip; lpclip/linear_probe.py): one evaluation of the multinomial logistic objective in exact fp32 on the matrix cores

@@ -187,6 +187,8 @@ struct Resnet {
     std::vector<RnConv> convs;  // 0, 1, 2: the stem
     std::vector<RnBlock> blocks;
     bool stale = true;  // a "visual.*" tensor arrived since the last fold
+    int conv_path = 0;  // mudpt_resnet_conv_path: 0 = im2col + GEMM + bias_act per convolution, 1 = one launch_conv2d (conv.hip)
+    long conv2d_launches = 0;  // launch_conv2d calls of the tower since create (mudpt_debug_read "conv2d_launches"): path 0 adds none
     float *pos = nullptr, *b_q = nullptr, *b_kv = nullptr, *b_c = nullptr;  // attnpool: positional_embedding [L, C]; biases [C], [2 C] (k | v), [e]
     void *w_q = nullptr, *w_kv = nullptr, *w_c = nullptr;                   // T [C, C], [2 C, C] (k_proj over v_proj), [e, C]
     // activations, sized for max_batch at create (bytes for RN50 at B 100: DESIGN.md 4.9)
@@ -942,6 +944,15 @@ extern "C" int mudpt_create_resnet(const mudpt_config* c, const mudpt_resnet_sha
     if (int rc = resnet_check("create_resnet", c, rn)) return rc;
     const mudpt_config f = resnet_vit_stub(*c);
     return create_model(&f, nullptr, out, false, rn, c->image_size);
+}
+
+// include/mudpt.h: which launches resnet_conv makes from the next forward on
+extern "C" int mudpt_resnet_conv_path(mudpt_model* m, int32_t path) {
+    ARG_CHECK(m, "resnet_conv_path: null model");
+    ARG_CHECK(m->rn, "resnet_conv_path: this handle has no ResNet image tower (mudpt_create_frozen_resnet, mudpt_create_resnet make one)");
+    ARG_CHECK(path == 0 || path == 1, "resnet_conv_path: path %d (0: im2col + GEMM + bias_act, 1: mudpt_conv2d)", path);
+    m->rn->conv_path = path;
+    return MUDPT_OK;
 }
 
 // every entry point that trains, takes embedded class prompts or shards the classes
@@ -1798,6 +1809,15 @@ static int resnet_conv(mudpt_model* m, const RnConv& c, const void* in, int ld_i
                        void* out, hipStream_t s) {
     Resnet& r = *m->rn;
     const int Ho = c.k == 3 ? (H - 1) / stride + 1 : H, M = B * Ho * Ho;
+    if (r.conv_path == 1) {
+        ++r.conv2d_launches;
+        // the planar pixels (3 channels) keep their patch rows; the kernel then runs over them as a 1 x 1 whose channels are the ldk columns
+        if (planar) {
+            TRY(launch_im2col(m->dtype, in, true, B, H, H, c.cin, ld_in, stride, r.rows, c.ldk, s));
+            return launch_conv2d(m->dtype, r.rows, B, Ho, Ho, c.ldk, c.ldk, 1, 1, c.w_dev, c.ldk, c.b_dev, res, ldres, out, c.np, c.np, relu, s);
+        }
+        return launch_conv2d(m->dtype, in, B, H, H, c.cin, ld_in, c.k, c.k == 3 ? stride : 1, c.w_dev, c.ldk, c.b_dev, res, ldres, out, c.np, c.np, relu, s);
+    }
     GemmArgs g;
     if (c.k == 3) {
         TRY(launch_im2col(m->dtype, in, planar, B, H, H, c.cin, ld_in, stride, r.rows, c.ldk, s));
@@ -2733,9 +2753,9 @@ extern "C" int mudpt_debug_read(mudpt_model* m, const char* name, int32_t batch,
     else if (m->umudpt && !m->uumudpt && (k == "umudpt.G" || k == "umudpt.dG")) { src = k == "umudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
     else if (m->uumudpt && (k == "uumudpt.G" || k == "uumudpt.dG")) { src = k == "uumudpt.G" ? m->pg_G : m->pg_dG; n = (size_t)c.depth * c.n_ctx * c.v_width; }
     else if (m->uumudpt && c.depth > 1 && (k == "uumudpt.T" || k == "uumudpt.dT")) { src = k == "uumudpt.T" ? m->pg2_T : m->d_txt_deep; n = (size_t)(c.depth - 1) * c.n_ctx * c.embed_dim; }
-    else if (k == "text_launches") {  // a host counter, not a device tensor
+    else if (k == "text_launches" || (m->rn && k == "conv2d_launches")) {  // host counters, not device tensors
         *numel = 1;
-        if (host_out) { ARG_CHECK(capacity >= 1, "debug_read: capacity 0"); host_out[0] = (float)m->text_launches; }
+        if (host_out) { ARG_CHECK(capacity >= 1, "debug_read: capacity 0"); host_out[0] = (float)(k == "text_launches" ? m->text_launches : m->rn->conv2d_launches); }
         return MUDPT_OK;
     }
     ARG_CHECK(src, "debug_read: unknown tensor '%s'", name);
@@ -3160,6 +3180,11 @@ extern "C" int mudpt_im2col(int32_t dtype, const void* src, int32_t src_planar, 
                             int32_t ldk, void* stream) {
     return launch_im2col(dtype, src, src_planar != 0, B, H, W, C, lds, stride, dst, ldk, (hipStream_t)stream);
 }
+extern "C" int mudpt_conv2d(int32_t dtype, const void* src, int32_t B, int32_t H, int32_t W, int32_t C, int32_t lds, int32_t k, int32_t stride, const void* w,
+                            int32_t ldk, const float* bias, const void* residual, int32_t ldres, void* out, int32_t ldo, int32_t N, int32_t relu, void* stream) {
+    return launch_conv2d(dtype, src, B, H, W, C, lds, k, stride, w, ldk, bias, residual, ldres, out, ldo, N, relu != 0, (hipStream_t)stream);
+}
+extern "C" int mudpt_conv2d_form(int32_t M, int32_t N) { return conv2d_form(M, N); }
 extern "C" int mudpt_bias_act(int32_t dtype, const float* acc, int32_t ldacc, const float* bias, const void* residual, int32_t ldres, void* out, int32_t ldo, int32_t M,
                               int32_t N, int32_t relu, void* stream) {
     return launch_bias_act(dtype, acc, ldacc, bias, residual, ldres, out, ldo, M, N, relu != 0, (hipStream_t)stream);

@@ -13,6 +13,9 @@
 //   3. the residual is read in T; acc + bias, + residual and ReLU are fp32, then one rounding (launch_bias_act);
 //   4. q / k / v (fp32 GEMM outputs) and the attention are fp32 (launch_attnpool_attend); its output is rounded to T for c_proj;
 //   5. the features c_proj writes are fp32.
+// The fused convolution (conv.hip, mudpt_resnet_conv_path 1) rounds at these five sites and nowhere else: it reads the same T operands (1, 2),
+// accumulates in fp32 on the same matrix instruction, adds bias and residual and applies the ReLU in fp32 in the order of launch_bias_act and
+// rounds once (3).  The emulation and every emulated_rel of the fixtures therefore hold for it as they stand.
 // Sums are written with __fadd_rn / __fmul_rn: hipcc contracts a * b + c into one fma by default, and the tests hold these kernels to the
 // bits of the same fp32 operations done one after the other.
 #include "kernels.h"

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -146,7 +147,8 @@ class LibraryModel(nn.Module):
     cfg, h)`` is the subclass's create call (``mudpt_create`` / ``mudpt_create_ex`` / ``mudpt_create_resnet`` / ``mudpt_create_frozen``) on byref(config) and
     byref(handle); ``config`` are ``library_config``'s keywords.  The knobs are applied right behind it, before any weight or token."""
 
-    def __init__(self, shape: ModelShape, n_cls: int, max_batch: int, dtype: str, device: str, knobs: Optional[Dict[str, int]], create, **config):
+    def __init__(self, shape: ModelShape, n_cls: int, max_batch: int, dtype: str, device: str, knobs: Optional[Dict[str, int]], create,
+                 rn_fused_conv: Optional[bool] = None, **config):
         super().__init__()
         if not torch.cuda.is_available():
             raise capi.MudptError("mudpt_amd needs an MI355X (HIP device); there is no CPU path in the product")
@@ -164,11 +166,21 @@ class LibraryModel(nn.Module):
         self._last_batch = 0  # images of the last inference forward, whose raw features the library still holds (image_features)
         for name, value in (knobs or {}).items():  # per-handle tuning knobs (mudpt_model_set): A/B runs and tests
             self.set_knob(name, value)
+        # opt-in: a ResNet tower's convolutions as one launch each (set_resnet_conv_path); None: MUDPT_RN_FUSED_CONV=1 on a ResNet shape
+        if rn_fused_conv is None:
+            rn_fused_conv = shape.resnet and os.environ.get("MUDPT_RN_FUSED_CONV") == "1"
+        if rn_fused_conv:
+            self.set_resnet_conv_path(1)
 
     def set_weight(self, key: str, value: torch.Tensor):
         """One frozen weight, by OpenAI CLIP key (clip/model.py:919 load_state_dict)."""
         t = value.detach().to("cpu", torch.float32).contiguous()
         capi.check(self.lib.mudpt_set_weight(self._h, key.encode(), capi.ptr(t), t.numel()), f"set_weight({key})")
+
+    def set_resnet_conv_path(self, path: int):
+        """``mudpt_resnet_conv_path``: 0 = every convolution of the ResNet tower as im2col + GEMM + bias_act (the default), 1 = as one
+        ``mudpt_conv2d`` launch.  Between any two forwards; a handle without that tower is refused by the library."""
+        capi.check(self.lib.mudpt_resnet_conv_path(self._h, int(path)), "resnet_conv_path")
 
     def set_knob(self, name: str, value: int):
         """``mudpt_model_set``: "gemm_variant", "lp_grad" and the split-operand knobs ("vis_lo", "txt_lo", "vis_sites", "txt_sites",
@@ -273,7 +285,8 @@ class CustomCLIP(LibraryModel):
         # generator that turns those into an addend of the text deep prompts): 40 trainables, "uumudpt_prompt_learner.*" then
         # "image_encoder.visual_ctx*"; shape.n_ctx (1..16) / depth are TRAINER.UUMUDPT.N_CTX / DEEP_PROMPT_DEPTH
         # A ResNet ``shape`` (RN50, RN101, RN50x16, RN50x64): "coop" / "coop_csc" / "cocoop" only -- their image encoder is frozen and prompt-free
-        # (trainers/coop.py:212-226, cocoop.py:178-198), so the tower runs forward only where the vanilla ViT would (mudpt_create_resnet)
+        # (trainers/coop.py:212-226, cocoop.py:178-198), so the tower runs forward only where the vanilla ViT would (mudpt_create_resnet).  Its
+        # convolutions run fused (set_resnet_conv_path(1)) from construction on under MUDPT_RN_FUSED_CONV=1, or after that call at any time
         assert not shape.resnet or variant in ("coop", "coop_csc", "cocoop"), \
             "ResNet backbones run on the frozen handle only (ZeroshotCLIP, ZeroshotCLIP2, feature extraction)"
         if variant == "coop_csc" and ctx_token_ids is not None:

@@ -72,7 +72,7 @@ class FrozenCLIP(LibraryModel):
     library keeps it on the device)."""
 
     def __init__(self, shape: ModelShape, clip_state: Dict[str, torch.Tensor], tokens: torch.Tensor, max_batch: int = 100, dtype: str = "fp16",
-                 device: str = "cuda:0", knobs: Optional[Dict[str, int]] = None):
+                 device: str = "cuda:0", knobs: Optional[Dict[str, int]] = None, rn_fused_conv: Optional[bool] = None):
         tokens = torch.as_tensor(tokens)
         if tokens.dim() == 2:
             tokens = tokens[None]
@@ -85,7 +85,7 @@ class FrozenCLIP(LibraryModel):
                 capi.check(lib.mudpt_create_frozen(cfg, h), "create_frozen")
 
         # the knobs go in before the tokens: the layout knobs are read by mudpt_set_text_tokens
-        super().__init__(shape, tokens.shape[1], max_batch, dtype, device, knobs, create, frozen=True)
+        super().__init__(shape, tokens.shape[1], max_batch, dtype, device, knobs, create, rn_fused_conv=rn_fused_conv, frozen=True)
         self.tokens = tokens.to("cpu", torch.int32).contiguous()
         self.n_templates = int(tokens.shape[0])
         for k, v in clip_state.items():  # clip/model.py:919 load_state_dict

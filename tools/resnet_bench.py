@@ -1,18 +1,20 @@
 """Timing of CLIP's ResNet image tower on the frozen handle (mudpt_create_frozen_resnet) on one MI355X: random-init RN50 / RN101, synthetic
 images.  A measurement, not a test: nothing here is a bound.
 
-    python tools/resnet_bench.py [--models RN50,RN101] [--batches 100,256] [--dtypes fp16,bf16] [--iters 5] [--rounds 5] [--no-split]
+    python tools/resnet_bench.py [--models RN50,RN101] [--batches 100,256] [--dtypes fp16,bf16] [--iters 5] [--rounds 5] [--no-split] [--ours-only]
 
-Per (model, batch, dtype), in ONE process and in alternating rounds (ours, yardstick, ViT, ours, ...): median and min-max of `rounds` rounds
-of `iters` encode_image calls, device-synchronised, for
+Per (model, batch, dtype), in ONE process and in alternating rounds (ours, fused, yardstick, ViT, ours, ...): median and min-max of `rounds`
+rounds of `iters` encode_image calls, device-synchronised, for
   ours       FrozenCLIP.encode_image on the ResNet handle (im2col + MFMA GEMM per convolution, mudpt_amd/csrc/resnet.hip);
+  fused      the same on a second handle with rn_fused_conv=True (one mudpt_conv2d launch per convolution, mudpt_amd/csrc/conv.hip);
   yardstick  the same tower written below as plain torch.nn modules (eval-mode BatchNorm, AvgPool2d, F.scaled_dot_product_attention for the
              pool) in T and channels_last on torch-ROCm: what a user gets without this library;
   vit        the ViT-B/16 frozen handle's encode_image of the same process, batch and dtype (the project's flagship tower, as a scale).
 Then the time split of ours by kernel class -- patch rows / GEMM / epilogue / pool -- from HIP events around every launch of a replay of the
 tower's launch list through the single-kernel exports (mudpt_im2col, mudpt_gemm epilogue 5, mudpt_bias_act, mudpt_avgpool2d; the attention
 pool's four small launches are not replayed).  An event pair adds queue time per launch, so the split's sum is above the forward's time: read
-the shares, not the sum."""
+the shares, not the sum.  The same replay for the fused path: the stem's patch rows, one mudpt_conv2d per convolution ("conv"), the pools.
+--ours-only leaves the yardstick and the ViT out (the two paths against each other, in less time)."""
 import argparse
 import os
 import statistics
@@ -103,8 +105,8 @@ def launch_list(shape):
     return out
 
 
-def class_split(shape, B, dtype, passes=3):
-    """ms per kernel class of one forward's convolution / pooling launches, the median over `passes` replays."""
+def class_split(shape, B, dtype, passes=3, fused=False):
+    """ms per kernel class of one forward's convolution / pooling launches, the median over `passes` replays; fused: of the mudpt_conv2d path."""
     code, T = {"fp16": capi.F16, "bf16": capi.BF16}[dtype], TORCH_DTYPE[dtype]
     launches = launch_list(shape)
     px = lambda H, stride=1: ((H - 1) // stride + 1) ** 2  # noqa: E731
@@ -132,6 +134,15 @@ def class_split(shape, B, dtype, passes=3):
                 continue
             _, cin, cout, k, H, stride, ld_in, np_ = a
             ldk, M = up64(k * k * cin), B * px(H, stride)
+            if fused:
+                if cin == 3:  # the planar pixels keep their patch rows; the kernel runs over them as a 1 x 1
+                    run("patch rows", "mudpt_im2col", dtype=code, src=pixels, src_planar=1, B=B, H=H, W=H, C=3, lds=0, stride=stride, dst=patch, ldk=ldk)
+                    run("conv", "mudpt_conv2d", dtype=code, src=patch, B=B, H=(H - 1) // stride + 1, W=(H - 1) // stride + 1, C=ldk, lds=ldk, k=1, stride=1, w=weight, ldk=ldk,
+                        bias=bias, out=dst, ldo=np_, N=np_, relu=1)
+                else:
+                    run("conv", "mudpt_conv2d", dtype=code, src=src, B=B, H=H, W=H, C=cin, lds=ld_in, k=k, stride=stride, w=weight, ldk=ldk, bias=bias, residual=src, ldres=np_,
+                        out=dst, ldo=np_, N=np_, relu=1)
+                continue
             if k == 3:
                 run("patch rows", "mudpt_im2col", dtype=code, src=pixels if cin == 3 else src, src_planar=int(cin == 3), B=B, H=H, W=H, C=cin, lds=ld_in, stride=stride,
                     dst=patch, ldk=ldk)
@@ -147,6 +158,12 @@ def class_split(shape, B, dtype, passes=3):
     return {c: statistics.median(o[c] for o in out) for c in out[0]}, flop, sum(1 for a in launches if a[0] == "conv")
 
 
+def print_split(tag, split, flop, convs, gemm_class):
+    total = sum(split.values())
+    print(f"{tag} split over {convs} convolutions: " + ", ".join(f"{c} {v:6.2f} ms ({v / total * 100:2.0f} %)" for c, v in split.items())
+          + f"; sum {total:.2f} ms; GEMM {flop / 1e12:.2f} TFLOP -> {flop / split[gemm_class] / 1e9:.0f} TFLOP/s", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="RN50,RN101")
@@ -155,6 +172,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-split", action="store_true")
+    ap.add_argument("--ours-only", action="store_true")
     a = ap.parse_args()
     tok = synth.bench_tokenized_prompts()
     vit_shape = ModelShape(n_ctx=0, depth=1)
@@ -167,13 +185,19 @@ def main():
             images = torch.randn(B, 3, shape.image_size, shape.image_size, generator=torch.Generator().manual_seed(0)).cuda()
             vit_images = images if shape.image_size == 224 else torch.randn(B, 3, 224, 224, device="cuda")
             for dtype in a.dtypes.split(","):
-                ours = FrozenCLIP(shape, state, tok, max_batch=B, dtype=dtype)
-                vit = FrozenCLIP(vit_shape, vit_state, tok, max_batch=B, dtype=dtype)
-                yard = TorchTower(shape, state).cuda().to(TORCH_DTYPE[dtype]).eval()
-                fns = {"ours": lambda: ours.encode_image(images), "yardstick": lambda: yard(images), "vit_b16": lambda: vit.encode_image(vit_images)}
+                ours = FrozenCLIP(shape, state, tok, max_batch=B, dtype=dtype, rn_fused_conv=False)
+                fused = FrozenCLIP(shape, state, tok, max_batch=B, dtype=dtype, rn_fused_conv=True)
+                fns = {"ours": lambda: ours.encode_image(images), "fused": lambda: fused.encode_image(images)}
+                vit = yard = None
+                if not a.ours_only:
+                    vit = FrozenCLIP(vit_shape, vit_state, tok, max_batch=B, dtype=dtype)
+                    yard = TorchTower(shape, state).cuda().to(TORCH_DTYPE[dtype]).eval()
+                    fns.update({"yardstick": lambda: yard(images), "vit_b16": lambda: vit.encode_image(vit_images)})
                 with torch.no_grad():
-                    got, want = ours.encode_image(images).double(), yard(images).double()
+                    got, got1 = ours.encode_image(images).double(), fused.encode_image(images).double()
+                    want = yard(images).double() if yard is not None else got
                     rel = ((got - want).norm(dim=1) / want.norm(dim=1)).max().item()
+                    rel1 = ((got1 - got).norm(dim=1) / got.norm(dim=1)).max().item()
                     for fn in fns.values():  # warm up (the yardstick's convolution algorithm search included)
                         fn(); fn()
                     ms = {k: [] for k in fns}
@@ -181,16 +205,18 @@ def main():
                         for k, fn in fns.items():
                             ms[k].append(timed(fn, a.iters))
                 line = "; ".join(f"{k} {statistics.median(v):7.2f} ms ({min(v):.2f}-{max(v):.2f})" for k, v in ms.items())
-                print(f"{name} B={B:3d} {dtype}: {line}; ours / yardstick {statistics.median(ms['ours']) / statistics.median(ms['yardstick']):.2f}; "
-                      f"{B / statistics.median(ms['ours']) * 1e3:6.0f} images/s; ours vs yardstick features {rel:.1e}", flush=True)
-                ours.close(); vit.close()
-                del ours, vit, yard
+                med = {k: statistics.median(v) for k, v in ms.items()}
+                print(f"{name} B={B:3d} {dtype}: {line}; fused / ours {med['fused'] / med['ours']:.3f}; "
+                      + (f"ours / yardstick {med['ours'] / med['yardstick']:.2f}; ours vs yardstick features {rel:.1e}; " if yard is not None else "")
+                      + f"{B / med['ours'] * 1e3:6.0f} images/s, fused {B / med['fused'] * 1e3:6.0f}; fused vs ours features {rel1:.1e}", flush=True)
+                ours.close(); fused.close()
+                if vit is not None:
+                    vit.close()
+                del ours, fused, vit, yard
                 torch.cuda.empty_cache()
                 if not a.no_split:
-                    split, flop, convs = class_split(shape, B, dtype)
-                    total = sum(split.values())
-                    print(f"{name} B={B:3d} {dtype} split over {convs} convolutions: " + ", ".join(f"{c} {v:6.2f} ms ({v / total * 100:2.0f} %)" for c, v in split.items())
-                          + f"; GEMM {flop / 1e12:.2f} TFLOP -> {flop / split['gemm'] / 1e9:.0f} TFLOP/s", flush=True)
+                    print_split(f"{name} B={B:3d} {dtype}", *class_split(shape, B, dtype), "gemm")
+                    print_split(f"{name} B={B:3d} {dtype} fused", *class_split(shape, B, dtype, fused=True), "conv")
 
 
 if __name__ == "__main__":

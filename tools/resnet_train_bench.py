@@ -4,8 +4,9 @@ gradient, on one MI355X: random-init weights, synthetic images.  A measurement, 
     python tools/resnet_train_bench.py [--dtype fp16] [--iters 5] [--rounds 5] [--skip-steps] [--skip-heads]
 
 One process, alternating rounds (a, b, c, a, b, c, ...): median and min-max of `rounds` rounds of `iters` device-synchronised calls.
-  steps  CoOp forward_backward at B 32, N_CTX 16, with 1000 and with 100 classes, on RN50 and on the ViT-B/16 handle; CoCoOp on RN50 at B 1 with
-         100 classes (the reference script's batch)
+  steps  CoOp forward_backward at B 32, N_CTX 16, with 1000 and with 100 classes, on RN50, on RN50 with the fused convolutions
+         (set_resnet_conv_path(1): one mudpt_conv2d launch per convolution) and on the ViT-B/16 handle; CoCoOp on RN50 at B 1 with 100 classes (the
+         reference script's batch)
   heads  mudpt_head_ex in training, e = 1024: at (B, C) = (32, 1000) and (256, 1000) the fused head without dimg against the unfused launchers,
          without dimg and with it (where a training call with dimg lands at these shapes); at (32, 496), where both fused forms fit, the
          fused head with and without dimg.  A call includes the export's own scratch allocation and stream synchronisation, the same for
@@ -58,6 +59,9 @@ def steps(dtype, iters, rounds):
         tok = synth.synthetic_tokenized_prompts(n_cls, 16)  # "X .. X <name>." with name lengths mixed like ImageNet's; class token at the end
         labels = torch.randint(0, n_cls, (32,), generator=g).cuda()
         models = {k: CustomCLIP(s, sd, tok, max_batch=32, dtype=dtype, seed=1, variant="coop") for k, (s, sd) in states.items()}
+        models["RN50 fused conv"] = CustomCLIP(*states["RN50"], tok, max_batch=32, dtype=dtype, seed=1, variant="coop")
+        models["RN50"].set_resnet_conv_path(0)  # whatever MUDPT_RN_FUSED_CONV says
+        models["RN50 fused conv"].set_resnet_conv_path(1)
         for m in models.values():
             m.train()
         ms = alternate({k: (lambda m=m: m.forward_backward(images, labels)) for k, m in models.items()}, iters, rounds)
