@@ -171,6 +171,23 @@ struct Attn {
             *(vec4*)(dst_row + 16 * dt + 4 * g) = v;
         }
     }
+    // the backward's register operands: the Q, dO and forward-output pieces of this lane's query, the K and V pieces of this lane's key (both k-steps)
+    struct QFrags { vec8 q0, q1, g0, g1, o0, o1; };
+    struct KFrags { vec8 k0, k1, v0, v1; };
+    // lq = L, or 0 where Q is not wanted (grow() then returns zeros without touching memory and q0 / q1 are dead): a block outside the window, or
+    // the sweep kernel, which takes dO and O for delta only
+    __device__ static inline QFrags fetch_q(const elem* Q, size_t ld, const elem* dO, size_t ldg, const elem* Of, size_t ldof, int q, int lq, int L, int lane) {
+        return QFrags{grow(Q, ld, q, lq, 0, lane), grow(Q, ld, q, lq, 1, lane), grow(dO, ldg, q, L, 0, lane),
+                      grow(dO, ldg, q, L, 1, lane), grow(Of, ldof, q, L, 0, lane), grow(Of, ldof, q, L, 1, lane)};
+    }
+    __device__ static inline KFrags fetch_kv(const elem* K, const elem* V, size_t ld, int key, int lk, int lane) {
+        return KFrags{grow(K, ld, key, lk, 0, lane), grow(K, ld, key, lk, 1, lane), grow(V, ld, key, lk, 0, lane), grow(V, ld, key, lk, 1, lane)};
+    }
+    // dK (with the 1 / sqrt(d) the steps leave out) and dV of this lane's key: ok = the key's dK row in dqkv, its dV row lies HD further
+    __device__ static inline void store_dkv(elem* ok, int HD, const f32x4 (&dK)[4], const f32x4 (&dV)[4], int lane) {
+        store_t(ok, dK, 0.125f, lane);
+        store_t(ok + HD, dV, 1.f, lane);
+    }
 };
 
 __device__ inline float group_max(float v) {  // over the 4 lanes that share lane & 15
@@ -180,6 +197,10 @@ __device__ inline float group_max(float v) {  // over the 4 lanes that share lan
 __device__ inline float group_sum(float v) {
     v += __shfl_xor(v, 16, 64);
     return v + __shfl_xor(v, 32, 64);
+}
+__device__ inline void zero4(f32x4 (&x)[4]) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) x[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -383,13 +404,137 @@ __global__ __launch_bounds__(NC * 128) void attn_fwd_kernel(AttnArgs p, int npai
 }
 
 // ------------------------------------------------------------------------------------------------
+// backward: the two tile steps and the small pieces that every backward kernel of this file shares
+// ------------------------------------------------------------------------------------------------
+// The kernels below differ in what they keep resident, how they stage and where their barriers sit -- their schedules.  The arithmetic of a
+// tile is bwd_dq_step ("query on the lane") and bwd_dkv_step ("key on the lane") for all of them.
+
+// delta = rowsum(dO * O) of this lane's query (each of the row's 4 lanes holds 16 of the 64 columns)
+template <typename T>
+__device__ inline float bwd_delta(const typename Attn<T>::QFrags& f) {
+    float delta = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) delta += (float)f.g0[i] * (float)f.o0[i] + (float)f.g1[i] * (float)f.o1[i];
+    return group_sum(delta);
+}
+
+// window form (AttnArgs::win_n): do rows row0 .. row0 + n - 1 hold a wanted row?
+__device__ inline bool in_win(const AttnArgs& p, int row0, int n) { return p.win_n <= 0 || (row0 < p.win_row0 + p.win_n && row0 + n > p.win_row0); }
+
+// a query block outside the sel_rows block: dO = 0 on every row of it, so delta = 0 and dQ = 0 (q = this lane's query)
+template <typename T>
+__device__ inline void bwd_zero_qblock(const AttnArgs& p, int b, int hd, int Lp, int q, int lane) {
+    using elem = typename T::elem;
+    if ((lane >> 4) == 0 && q < Lp) p.delta[((size_t)b * p.H + hd) * Lp + q] = 0.f;
+    const f32x4 z[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    if (q < p.L) Attn<T>::store_t((elem*)p.dqkv + ((size_t)b * p.L + q) * ((size_t)3 * p.H * 64) + hd * 64, z, 0.f, lane);
+}
+
+// amdgpu_waves_per_eu's lower bound for a workgroup of `waves` waves: what the launch bound implies anyway (4 SIMDs per CU); an upper bound of 8 is
+// the hardware's, so (wg_waves_per_simd(w), 8) leaves a kernel as the compiler builds it by default
+constexpr int wg_waves_per_simd(int waves) { return (waves + 3) / 4; }
+
+// which keys of a dQ step get P = 0 on top of what S starts from: those after the query, those at or beyond L
+enum : int { MASK_NONE = 0, MASK_CAUSAL = 1, MASK_END = 2 };
+
+// The dQ step: the 32 keys in rows 32 kc .. 32 kc + 31 of the K and V images (image row i = key key0 + i of the sequence) against this lane's
+// query q; accumulates dQ^T of the 16-query block.  S^T = K Q^T starts from the kmask vector (0 for real keys, -inf for padding: p = 0 without a
+// per-element mask) or, KMASK = false, from zero; dP starts from -delta.  ds = p dP is dS^T up to the 1 / sqrt(d) applied at the store.
+template <typename T, bool KMASK, int MASK>
+__device__ __forceinline__ void bwd_dq_step(const typename T::elem* Ks, const typename T::elem* Vs, const float* kmask, int kc, int key0, int L, int q,
+                                            const typename Attn<T>::QFrags& f, float nlse, float delta, int lane, f32x4 (&dQ)[4]) {
+    using A = Attn<T>;
+    const int g = lane >> 4;
+    f32x4 ds[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int kt = 2 * kc + t;
+        f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = {-delta, -delta, -delta, -delta};
+        if constexpr (KMASK) S = *(const f32x4*)(kmask + kt * 16 + 4 * g);
+        S = T::mfma16(A::rows(Ks, kt * 16, 0, lane), f.q0, S);
+        S = T::mfma16(A::rows(Ks, kt * 16, 1, lane), f.q1, S);
+        dP = T::mfma16(A::rows(Vs, kt * 16, 0, lane), f.g0, dP);
+        dP = T::mfma16(A::rows(Vs, kt * 16, 1, lane), f.g1, dP);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int key = key0 + kt * 16 + 4 * g + r;
+            float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nlse));  // padding queries (q >= L) are never stored
+            if (((MASK & MASK_END) && key >= L) || ((MASK & MASK_CAUSAL) && key > q)) pr = 0.f;
+            ds[t][r] = pr * dP[r];
+        }
+    }
+    const typename T::vec8 db = A::pack2(ds[0], ds[1]);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dQ[dt] = T::mfma16(A::cols(Ks, kc * 32, dt * 16, lane), db, dQ[dt]);
+}
+
+// The dK/dV step: the 32 queries in rows 32 qc .. 32 qc + 31 of the Q and dO images (image row i = query q0 + i of the sequence) against this
+// lane's key; accumulates dV^T += dO^T P and dK^T += Q^T dS of the 16-key block.  nlse = -lse log2(e) (-inf for padding queries: p = 0 without
+// a per-element mask) and delta are the per-query vectors in LDS, indexed by image row.  Padding keys (key >= L) are whole lanes that are never
+// stored.  sink(db) receives the packed dS (rounded to T, 1 / sqrt(d) still to come) before it feeds dK: the sweep kernel keeps it for its dQ.
+struct NoSink {
+    template <typename V>
+    __device__ inline void operator()(const V&) const {}
+};
+template <typename T, bool CAUSAL, typename Sink = NoSink>
+__device__ __forceinline__ void bwd_dkv_step(const typename T::elem* Qs, const typename T::elem* Gs, const float* nlse, const float* delta, int qc,
+                                                         int q0, int key, const typename Attn<T>::KFrags& f, int lane, f32x4 (&dK)[4], f32x4 (&dV)[4], Sink&& sink = Sink{}) {
+    using A = Attn<T>;
+    const int g = lane >> 4;
+    f32x4 P[2], dS[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int qt = 2 * qc + t;
+        const f32x4 nl = *(const f32x4*)(nlse + qt * 16 + 4 * g);
+        const f32x4 d4 = *(const f32x4*)(delta + qt * 16 + 4 * g);
+        f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = -d4;
+        S = T::mfma16(A::rows(Qs, qt * 16, 0, lane), f.k0, S);
+        S = T::mfma16(A::rows(Qs, qt * 16, 1, lane), f.k1, S);
+        dP = T::mfma16(A::rows(Gs, qt * 16, 0, lane), f.v0, dP);
+        dP = T::mfma16(A::rows(Gs, qt * 16, 1, lane), f.v1, dP);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nl[r]));
+            if (CAUSAL && key > q0 + qt * 16 + 4 * g + r) pr = 0.f;
+            P[t][r] = pr;
+            dS[t][r] = pr * dP[r];
+        }
+    }
+    const typename T::vec8 pb = A::pack2(P[0], P[1]), db = A::pack2(dS[0], dS[1]);
+    sink(db);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        dV[dt] = T::mfma16(A::cols(Gs, qc * 32, dt * 16, lane), pb, dV[dt]);
+        dK[dt] = T::mfma16(A::cols(Qs, qc * 32, dt * 16, lane), db, dK[dt]);
+    }
+}
+
+// LDS-DMA of a [rows][ld] global matrix of T into the swizzled images (buffer_load ... lds: no VGPR round trip): one instruction moves the 64
+// columns of an 8-row group, 1 KiB, for the whole wave.  Rows past the end of the buffer read as zero through the descriptor.
+struct RowDma {
+    __amdgpu_buffer_rsrc_t rs;
+    unsigned lane_off, ld2;  // lane part of the source offset, row stride in bytes
+    __device__ inline RowDma(const void* buf, size_t bytes, size_t ld, int lane)
+        : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(buf), 0, (int)bytes, 0x00020000)),
+          // row (lane >> 3) of the group, 16-byte chunk (lane & 7) ^ (row & 7) (the LDS slot is lane-linear)
+          lane_off((unsigned)(((size_t)(lane >> 3) * ld + (size_t)(((lane & 7) ^ (lane >> 3)) << 3)) * 2)), ld2((unsigned)(ld * 2)) {}
+    // row group rg of the matrix whose row 0, column 0 lies `base` bytes into the buffer -> row group rg of the image img
+    __device__ inline void issue(char* img, unsigned base, int rg) const {
+        // the whole address goes through the bounds-checked vector offset (soffset is not range-checked)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(img + rg * 1024), 16, (int)(base + lane_off + (unsigned)(rg * 8) * ld2), 0, 0, 0);
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // backward, pass 1: dQ (and delta = rowsum(dO * O)); query on the lane
 // ------------------------------------------------------------------------------------------------
+// Waves per SIMD: NC = 1 without the mask runs its key loop once, and the step's LDS reads then rise above its MFMAs at the price of a wave: that
+// instantiation is held to at least five waves.  The others keep the compiler's default range.
 template <typename T, int NC, bool CAUSAL>
-__global__ __launch_bounds__(NC * 64) void attn_bwd_dq_kernel(AttnArgs p, const void* fwd_out) {
+__global__ __launch_bounds__(NC * 64) __attribute__((amdgpu_waves_per_eu(NC == 1 && !CAUSAL ? 5 : wg_waves_per_simd(NC), 8)))
+void attn_bwd_dq_kernel(AttnArgs p, const void* fwd_out) {
     using A = Attn<T>;
     using elem = typename T::elem;
-    using vec8 = typename T::vec8;
     constexpr int Lp = NC * 32, NT = NC * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     elem* Ks = (elem*)smem;
@@ -406,14 +551,9 @@ __global__ __launch_bounds__(NC * 64) void attn_bwd_dq_kernel(AttnArgs p, const 
     const size_t ldof = p.ld_out ? (size_t)p.ld_out : (size_t)HD;  // (a caller may keep the forward output in rows wider than H * 64)
     const elem* Of = (const elem*)fwd_out + (size_t)b * L * ldof + hd * 64;
 
-    struct Frags { vec8 q0, q1, g0, g1, o0, o1; };
-    // window form (AttnArgs::win_n): a block without a wanted row only contributes delta -- its Q fragments are not fetched
-    auto in_win = [&](int blk) { return p.win_n <= 0 || (blk * 16 < p.win_row0 + p.win_n && blk * 16 + 16 > p.win_row0); };
-    auto fetch = [&](int qb) {
-        const int q = qb * 16 + c, lq = in_win(qb) ? L : 0;  // lq = 0: grow() returns zeros without touching memory (wave-uniform)
-        return Frags{A::grow(base, ld, q, lq, 0, lane), A::grow(base, ld, q, lq, 1, lane), A::grow(dO, HD, q, L, 0, lane),
-                     A::grow(dO, HD, q, L, 1, lane), A::grow(Of, ldof, q, L, 0, lane), A::grow(Of, ldof, q, L, 1, lane)};
-    };
+    using Frags = typename A::QFrags;
+    // window form: a block without a wanted row only contributes delta -- its Q fragments are not fetched (wave-uniform)
+    auto fetch = [&](int qb) { return A::fetch_q(base, ld, dO, HD, Of, ldof, qb * 16 + c, in_win(p, qb * 16, 16) ? L : 0, L, lane); };
     // the first block's Q / dO / O fragments travel during the K / V staging, the second block's during the first block's compute
     const int nqb = (L + 15) >> 4, qbA = wave, qbB = wave + NC;
     const Frags fa = fetch(qbA);
@@ -428,50 +568,18 @@ __global__ __launch_bounds__(NC * 64) void attn_bwd_dq_kernel(AttnArgs p, const 
     const int qb_sel = p.sel_rows ? (p.sel_rows[b] - b * L) >> 4 : -1;
     auto block = [&](int qb, const Frags& f, float lse_q) {
         const int q = qb * 16 + c;
-        if (qb_sel >= 0 && qb != qb_sel) {  // dO = 0 on every row of this block: delta = 0, dQ = 0
-            if (g == 0) p.delta[((size_t)b * p.H + hd) * Lp + q] = 0.f;
-            const f32x4 z[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            if (q < L) A::store_t((elem*)p.dqkv + ((size_t)b * L + q) * ld + hd * 64, z, 0.f, lane);
-            return;
-        }
-        const vec8 q0 = f.q0, q1 = f.q1, g0 = f.g0, g1 = f.g1, o0 = f.o0, o1 = f.o1;
-        float delta = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) delta += (float)g0[i] * (float)o0[i] + (float)g1[i] * (float)o1[i];
-        delta = group_sum(delta);
-        const size_t stat = ((size_t)b * p.H + hd) * Lp + q;
-        if (g == 0) p.delta[stat] = delta;
+        if (qb_sel >= 0 && qb != qb_sel) return bwd_zero_qblock<T>(p, b, hd, Lp, q, lane);
+        const float delta = bwd_delta<T>(f);
+        if (g == 0) p.delta[((size_t)b * p.H + hd) * Lp + q] = delta;
         // window form: delta of EVERY query (the dK / dV pass sums over all of them), dQ only for the blocks that hold a wanted row
-        if (!in_win(qb)) return;
+        if (!in_win(p, qb * 16, 16)) return;
         const float nlse = -lse_q * LOG2E;
         const int nkc = CAUSAL ? (qb >> 1) + 1 : NC;
 
         f32x4 dQ[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dQ[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero4(dQ);
 #pragma unroll 1
-        for (int kc = 0; kc < nkc; ++kc) {
-            f32x4 ds[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int kt = 2 * kc + t;
-                f32x4 S = *(const f32x4*)(kmask + kt * 16 + 4 * g), dP = {-delta, -delta, -delta, -delta};
-                S = T::mfma16(A::rows(Ks, kt * 16, 0, lane), q0, S);
-                S = T::mfma16(A::rows(Ks, kt * 16, 1, lane), q1, S);
-                dP = T::mfma16(A::rows(Vs, kt * 16, 0, lane), g0, dP);
-                dP = T::mfma16(A::rows(Vs, kt * 16, 1, lane), g1, dP);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    // padding keys: S = -inf -> p = 0; padding queries (q >= L) are never stored
-                    float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nlse));
-                    if (CAUSAL && kt * 16 + 4 * g + r > q) pr = 0.f;
-                    ds[t][r] = pr * dP[r];  // dS^T up to the 1 / sqrt(d) applied at the store; delta entered through dP's initial value
-                }
-            }
-            const vec8 db = A::pack2(ds[0], ds[1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) dQ[dt] = T::mfma16(A::cols(Ks, kc * 32, dt * 16, lane), db, dQ[dt]);
-        }
+        for (int kc = 0; kc < nkc; ++kc) bwd_dq_step<T, true, CAUSAL ? MASK_CAUSAL : MASK_NONE>(Ks, Vs, kmask, kc, 0, L, q, f, nlse, delta, lane, dQ);
         if (q < L) A::store_t((elem*)p.dqkv + ((size_t)b * L + q) * ld + hd * 64, dQ, 0.125f, lane);
     };
     if (qbA < nqb) block(qbA, fa, lseA);
@@ -485,7 +593,6 @@ template <typename T, int NC, bool CAUSAL>
 __global__ __launch_bounds__(NC * 64) void attn_bwd_dkv_kernel(AttnArgs p) {
     using A = Attn<T>;
     using elem = typename T::elem;
-    using vec8 = typename T::vec8;
     constexpr int Lp = NC * 32, NT = NC * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     elem* Qs = (elem*)smem;            // [Lp][RS]
@@ -493,7 +600,7 @@ __global__ __launch_bounds__(NC * 64) void attn_bwd_dkv_kernel(AttnArgs p) {
     float* lse_s = (float*)(Gs + Lp * RS);  // [Lp]  -lse * log2(e)
     float* del_s = lse_s + Lp;              // [Lp]
 
-    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x / p.H, hd = blockIdx.x % p.H;
     const int HD = p.H * 64, L = p.L;
@@ -503,13 +610,9 @@ __global__ __launch_bounds__(NC * 64) void attn_bwd_dkv_kernel(AttnArgs p) {
 
     // this wave's (at most two) key blocks: K / V fragments requested before the Q / dO staging
     const int nkb = (L + 15) >> 4, kbA = wave, kbB = wave + NC;
-    struct Frags { vec8 k0, k1, v0, v1; };
-    auto in_win = [&](int blk) { return p.win_n <= 0 || (blk * 16 < p.win_row0 + p.win_n && blk * 16 + 16 > p.win_row0); };
-    auto fetch = [&](int kb) {
-        const int key = kb * 16 + c, lk = in_win(kb) ? L : 0;  // window form: blocks without a wanted key row fetch nothing
-        return Frags{A::grow(base + HD, ld, key, lk, 0, lane), A::grow(base + HD, ld, key, lk, 1, lane),
-                     A::grow(base + 2 * HD, ld, key, lk, 0, lane), A::grow(base + 2 * HD, ld, key, lk, 1, lane)};
-    };
+    using Frags = typename A::KFrags;
+    // window form: blocks without a wanted key row fetch nothing
+    auto fetch = [&](int kb) { return A::fetch_kv(base + HD, base + 2 * HD, ld, kb * 16 + c, in_win(p, kb * 16, 16) ? L : 0, lane); };
     const Frags fa = fetch(kbA), fb = fetch(kbB);
     // the row statistics (Lp = NT / 2 values: one per thread) are requested with the fragments, BEFORE the staging waits for
     // its loads: one HBM round trip per workgroup instead of two (a workgroup is a latency chain: 2 per CU)
@@ -526,47 +629,15 @@ __global__ __launch_bounds__(NC * 64) void attn_bwd_dkv_kernel(AttnArgs p) {
     const int qc_sel = p.sel_rows ? (p.sel_rows[b] - b * L) >> 5 : -1;  // dO is zero outside this 32-query chunk
     auto block = [&](int kb, const Frags& f) {
         const int key = kb * 16 + c;
-        if (!in_win(kb)) return;  // window form: no wanted key row in this block
-        const vec8 k0 = f.k0, k1 = f.k1, v0 = f.v0, v1 = f.v1;
+        if (!in_win(p, kb * 16, 16)) return;  // window form: no wanted key row in this block
         f32x4 dK[4], dV[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) { dK[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dV[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        zero4(dK);
+        zero4(dV);
         const int qc_lo = CAUSAL ? (kb >> 1) : 0;  // query chunks that hold a query >= this block's first key
         const int qc0 = qc_sel >= 0 ? (qc_sel > qc_lo ? qc_sel : qc_lo) : qc_lo, qc1 = qc_sel >= 0 ? qc_sel + 1 : NC;
 #pragma unroll 1
-        for (int qc = qc0; qc < qc1; ++qc) {
-            f32x4 P[2], dS[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int qt = 2 * qc + t;
-                const f32x4 nl = *(const f32x4*)(lse_s + qt * 16 + 4 * g);
-                const f32x4 d4 = *(const f32x4*)(del_s + qt * 16 + 4 * g);
-                f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = -d4;
-                S = T::mfma16(A::rows(Qs, qt * 16, 0, lane), k0, S);
-                S = T::mfma16(A::rows(Qs, qt * 16, 1, lane), k1, S);
-                dP = T::mfma16(A::rows(Gs, qt * 16, 0, lane), v0, dP);
-                dP = T::mfma16(A::rows(Gs, qt * 16, 1, lane), v1, dP);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    // padding queries have nl = -inf -> p = 0; padding keys (key >= L) are whole lanes that are never stored
-                    float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nl[r]));
-                    if (CAUSAL && key > qt * 16 + 4 * g + r) pr = 0.f;
-                    P[t][r] = pr;
-                    dS[t][r] = pr * dP[r];  // 1 / sqrt(d) applied at the store
-                }
-            }
-            const vec8 pb = A::pack2(P[0], P[1]), db = A::pack2(dS[0], dS[1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                dV[dt] = T::mfma16(A::cols(Gs, qc * 32, dt * 16, lane), pb, dV[dt]);
-                dK[dt] = T::mfma16(A::cols(Qs, qc * 32, dt * 16, lane), db, dK[dt]);
-            }
-        }
-        if (key < L) {
-            elem* ok = (elem*)p.dqkv + ((size_t)b * L + key) * ld + HD + hd * 64;
-            A::store_t(ok, dK, 0.125f, lane);
-            A::store_t(ok + HD, dV, 1.f, lane);
-        }
+        for (int qc = qc0; qc < qc1; ++qc) bwd_dkv_step<T, CAUSAL>(Qs, Gs, lse_s, del_s, qc, 0, key, f, lane, dK, dV);
+        if (key < L) A::store_dkv((elem*)p.dqkv + ((size_t)b * L + key) * ld + HD + hd * 64, HD, dK, dV, lane);
     };
     if (kbA < nkb) block(kbA, fa);
     if (kbB < nkb) block(kbB, fb);
@@ -579,9 +650,9 @@ __global__ __launch_bounds__(NC * 64) void attn_bwd_dkv_kernel(AttnArgs p) {
 // 632 MB) and round-trips delta through HBM.  Here one persistent workgroup per CU keeps all four [Lp][64] images of a pair in LDS
 // (4 x 28 KB at Lp = 224) and runs both sweeps on them -- still two independent sweeps (no dS image, no atomics, bitwise
 // reproducible), recomputing S and dP once as before:
-//   phase A (query on the lane, = attn_bwd_dq_kernel's block): dQ from the K / V images and this wave's Q / dO / O fragments; delta and
+//   phase A (query on the lane, bwd_dq_step as in attn_bwd_dq_kernel): dQ from the K / V images and this wave's Q / dO / O fragments; delta and
 //     -lse log2(e) go to LDS for phase B.  Meanwhile the pair's Q / dO images arrive by LDS-DMA.
-//   phase B (key on the lane, = attn_bwd_dkv_kernel's block): dK, dV from the Q / dO images; the wave's K / V fragments were read from
+//   phase B (key on the lane, bwd_dkv_step as in attn_bwd_dkv_kernel): dK, dV from the Q / dO images; the wave's K / V fragments were read from
 //     the K / V images at the end of phase A, so those images are free: the NEXT pair's K / V stream into them, and the next pair's
 //     Q / dO / O fragments travel to registers.
 // One barrier between the phases and one per pair; the only exposed memory latency is the first pair's.  The fragments of the
@@ -596,11 +667,13 @@ __global__ __launch_bounds__(NC * 64) void attn_bwd_dkv_kernel(AttnArgs p) {
 // kernels at two workgroups per CU: the kernels are bound by instruction issue (VALU ~ MFMA ~ LDS issue, ~20 us per pair per CU against
 // 4.4 us of matrix-pipe time), not by the 948 -> 632 MB of HBM traffic the single pass saves, and one workgroup per CU hides less
 // latency.  So the dispatcher uses this kernel for NC <= 3 and the two-kernel form above it.
+// Waves per SIMD: the causal NC = 3 / 4 instantiations of W2 = 2 -- the text tower -- are held to at most two waves.  Allowed a third, the scheduler
+// keeps every region under 168 registers and the dK / dV loop waits for each of its LDS reads.  The others keep the default range.
 template <typename T, int NC, bool CAUSAL, int W2>
-__global__ __launch_bounds__(NC * 64 * W2) void attn_bwd_fused_kernel(AttnArgs p, const void* fwd_out, int npairs) {
+__global__ __launch_bounds__(NC * 64 * W2) __attribute__((amdgpu_waves_per_eu(wg_waves_per_simd(NC * W2), CAUSAL && W2 == 2 && (NC == 3 || NC == 4) ? 2 : 8)))
+void attn_bwd_fused_kernel(AttnArgs p, const void* fwd_out, int npairs) {
     using A = Attn<T>;
     using elem = typename T::elem;
-    using vec8 = typename T::vec8;
     constexpr int Lp = NC * 32, NW = NC * W2, NT = NW * 64, IMG = Lp * 128, NBLK = 2 / W2, RGW = 8 / W2;  // RGW: 8-row groups per wave per image pair
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const elem* Ks = (const elem*)smem;
@@ -616,12 +689,7 @@ __global__ __launch_bounds__(NC * 64 * W2) void attn_bwd_fused_kernel(AttnArgs p
     const int HD = p.H * 64, L = p.L;
     const size_t ld = (size_t)3 * HD;
     const size_t ldof = p.ld_out ? (size_t)p.ld_out : (size_t)HD;  // (a caller may keep the forward output in rows wider than H * 64)
-    const auto rsQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.qkv), 0, (int)((size_t)p.B * L * ld * 2), 0x00020000);
-    const auto rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.dout), 0, (int)((size_t)p.B * L * HD * 2), 0x00020000);
-    // lane part of a DMA source: row (lane >> 3) of an 8-row group, 16-byte chunk (lane & 7) ^ (row & 7) (the LDS slot is lane-linear)
-    const unsigned lane_q = (unsigned)(((size_t)(lane >> 3) * ld + (size_t)(((lane & 7) ^ (lane >> 3)) << 3)) * 2);
-    const unsigned lane_g = (unsigned)(((size_t)(lane >> 3) * HD + (size_t)(((lane & 7) ^ (lane >> 3)) << 3)) * 2);
-    using lds_ptr = __attribute__((address_space(3))) void*;
+    const RowDma dmaQ(p.qkv, (size_t)p.B * L * ld * 2, ld, lane), dmaG(p.dout, (size_t)p.B * L * HD * 2, (size_t)HD, lane);
     // K and V images of a pair -> smem[0, 2 IMG)
     auto issue_kv = [&](int pair) {
         const int b = pair / p.H, hd = pair - b * p.H;
@@ -629,8 +697,7 @@ __global__ __launch_bounds__(NC * 64 * W2) void attn_bwd_fused_kernel(AttnArgs p
 #pragma unroll
         for (int k = 0; k < RGW; ++k) {
             const int j = wave * RGW + k, img = j / (Lp / 8), rg = j - img * (Lp / 8);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lds_ptr)(smem + img * IMG + rg * 1024), 16,
-                                                     (int)(base + (unsigned)((1 + img) * HD * 2) + lane_q + (unsigned)(rg * 8) * (unsigned)(ld * 2)), 0, 0, 0);
+            dmaQ.issue(smem + img * IMG, base + (unsigned)((1 + img) * HD * 2), rg);
         }
     };
     // Q and dO images of a pair -> smem[2 IMG, 4 IMG)
@@ -640,33 +707,25 @@ __global__ __launch_bounds__(NC * 64 * W2) void attn_bwd_fused_kernel(AttnArgs p
 #pragma unroll
         for (int k = 0; k < RGW; ++k) {
             const int j = wave * RGW + k, img = j / (Lp / 8), rg = j - img * (Lp / 8);
-            if (img == 0)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lds_ptr)(smem + 2 * IMG + rg * 1024), 16, (int)(baseq + lane_q + (unsigned)(rg * 8) * (unsigned)(ld * 2)), 0, 0, 0);
-            else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr)(smem + 3 * IMG + rg * 1024), 16, (int)(baseg + lane_g + (unsigned)(rg * 8) * (unsigned)(HD * 2)), 0, 0, 0);
+            if (img == 0) dmaQ.issue(smem + 2 * IMG, baseq, rg);
+            else dmaG.issue(smem + 3 * IMG, baseg, rg);
         }
     };
-    struct QFrags { vec8 q0, q1, g0, g1, o0, o1; float lse; };
+    struct QFrags { typename A::QFrags f; float lse; };
     auto fetch_q = [&](int pair, int qb) {
         const int b = pair / p.H, hd = pair - b * p.H, q = qb * 16 + c;
         const elem* base = (const elem*)p.qkv + (size_t)b * L * ld + hd * 64;
         const elem* dO = (const elem*)p.dout + (size_t)b * L * HD + hd * 64;
         const elem* Of = (const elem*)fwd_out + (size_t)b * L * ldof + hd * 64;
-        QFrags f{A::grow(base, ld, q, L, 0, lane), A::grow(base, ld, q, L, 1, lane), A::grow(dO, HD, q, L, 0, lane), A::grow(dO, HD, q, L, 1, lane),
-                 A::grow(Of, ldof, q, L, 0, lane), A::grow(Of, ldof, q, L, 1, lane), 0.f};
-        f.lse = q < Lp ? p.lse[(size_t)pair * Lp + q] : 0.f;
-        return f;
+        return QFrags{A::fetch_q(base, ld, dO, HD, Of, ldof, q, L, L, lane), q < Lp ? p.lse[(size_t)pair * Lp + q] : 0.f};
     };
-    struct KFrags { vec8 k0, k1, v0, v1; };
+    using KFrags = typename A::KFrags;
 
     const int nb16 = (L + 15) >> 4;  // 16-row blocks that hold a real row (queries and keys alike)
     // ---- phase A block: dQ of query block qb; leaves delta / lse of its queries in LDS ------------------------------------
     auto phase_a = [&](int pair, int qb, const QFrags& f) {
         const int b = pair / p.H, hd = pair - b * p.H, q = qb * 16 + c;
-        float delta = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) delta += (float)f.g0[i] * (float)f.o0[i] + (float)f.g1[i] * (float)f.o1[i];
-        delta = group_sum(delta);
+        const float delta = bwd_delta<T>(f.f);
         const float nlse = -f.lse * LOG2E;
         if (g == 0) {
             del_s[q] = delta;
@@ -674,72 +733,20 @@ __global__ __launch_bounds__(NC * 64 * W2) void attn_bwd_fused_kernel(AttnArgs p
         }
         const int nkc = CAUSAL ? (qb >> 1) + 1 : NC;
         f32x4 dQ[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dQ[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero4(dQ);
 #pragma unroll 1
-        for (int kc = 0; kc < nkc; ++kc) {
-            f32x4 ds[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int kt = 2 * kc + t;
-                f32x4 S = *(const f32x4*)(kmask + kt * 16 + 4 * g), dP = {-delta, -delta, -delta, -delta};
-                S = T::mfma16(A::rows(Ks, kt * 16, 0, lane), f.q0, S);
-                S = T::mfma16(A::rows(Ks, kt * 16, 1, lane), f.q1, S);
-                dP = T::mfma16(A::rows(Vs, kt * 16, 0, lane), f.g0, dP);
-                dP = T::mfma16(A::rows(Vs, kt * 16, 1, lane), f.g1, dP);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nlse));
-                    if (CAUSAL && kt * 16 + 4 * g + r > q) pr = 0.f;
-                    ds[t][r] = pr * dP[r];
-                }
-            }
-            const vec8 db = A::pack2(ds[0], ds[1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) dQ[dt] = T::mfma16(A::cols(Ks, kc * 32, dt * 16, lane), db, dQ[dt]);
-        }
+        for (int kc = 0; kc < nkc; ++kc) bwd_dq_step<T, true, CAUSAL ? MASK_CAUSAL : MASK_NONE>(Ks, Vs, kmask, kc, 0, L, q, f.f, nlse, delta, lane, dQ);
         if (q < L) A::store_t((elem*)p.dqkv + ((size_t)b * L + q) * ld + hd * 64, dQ, 0.125f, lane);
     };
     // ---- phase B block: dK, dV of key block kb --------------------------------------------------------------------------------
     auto phase_b = [&](int pair, int kb, const KFrags& f) {
         const int b = pair / p.H, hd = pair - b * p.H, key = kb * 16 + c;
         f32x4 dK[4], dV[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) { dK[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dV[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        const int qc0 = CAUSAL ? (kb >> 1) : 0;
+        zero4(dK);
+        zero4(dV);
 #pragma unroll 1
-        for (int qc = qc0; qc < NC; ++qc) {
-            f32x4 P[2], dS[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int qt = 2 * qc + t;
-                const f32x4 nl = *(const f32x4*)(lse_s + qt * 16 + 4 * g);
-                const f32x4 d4 = *(const f32x4*)(del_s + qt * 16 + 4 * g);
-                f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = -d4;
-                S = T::mfma16(A::rows(Qs, qt * 16, 0, lane), f.k0, S);
-                S = T::mfma16(A::rows(Qs, qt * 16, 1, lane), f.k1, S);
-                dP = T::mfma16(A::rows(Gs, qt * 16, 0, lane), f.v0, dP);
-                dP = T::mfma16(A::rows(Gs, qt * 16, 1, lane), f.v1, dP);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nl[r]));
-                    if (CAUSAL && key > qt * 16 + 4 * g + r) pr = 0.f;
-                    P[t][r] = pr;
-                    dS[t][r] = pr * dP[r];
-                }
-            }
-            const vec8 pb = A::pack2(P[0], P[1]), db = A::pack2(dS[0], dS[1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                dV[dt] = T::mfma16(A::cols(Gs, qc * 32, dt * 16, lane), pb, dV[dt]);
-                dK[dt] = T::mfma16(A::cols(Qs, qc * 32, dt * 16, lane), db, dK[dt]);
-            }
-        }
-        if (key < L) {
-            elem* ok = (elem*)p.dqkv + ((size_t)b * L + key) * ld + HD + hd * 64;
-            A::store_t(ok, dK, 0.125f, lane);
-            A::store_t(ok + HD, dV, 1.f, lane);
-        }
+        for (int qc = CAUSAL ? (kb >> 1) : 0; qc < NC; ++qc) bwd_dkv_step<T, CAUSAL>(Qs, Gs, lse_s, del_s, qc, 0, key, f, lane, dK, dV);
+        if (key < L) A::store_dkv((elem*)p.dqkv + ((size_t)b * L + key) * ld + HD + hd * 64, HD, dK, dV, lane);
     };
 
     for (int i = tid; i < Lp; i += NT) { kmask[i] = i < L ? 0.f : -INFINITY; lse_s[i] = -INFINITY; del_s[i] = 0.f; }
@@ -809,8 +816,11 @@ __device__ inline int ds_off(int key, int q) {  // byte offset of element (key, 
     return (q >> 5) * (LP * 64) + key * 64 + ((((q >> 4) & 1) ^ ((key >> 2) & 1)) << 5) + ((((q & 15) >> 2) ^ (((key >> 3) & 1) << 1)) << 3) + (q & 3) * 2;
 }
 
+// Waves per SIMD: at NC = 7 the LDS admits one workgroup of 14 waves per CU, 3.5 per SIMD, so the compiler is told not to save registers for a
+// fifth; NC = 1 is held to at least five waves (ten small workgroups per CU).  The others keep the compiler's default range.
 template <typename T, int NC>
-__global__ __launch_bounds__(NC * 128) void attn_bwd_sweep_kernel(AttnArgs p, const void* fwd_out) {
+__global__ __launch_bounds__(NC * 128) __attribute__((amdgpu_waves_per_eu(NC == 1 ? 5 : wg_waves_per_simd(NC * 2), NC == 7 ? 4 : 8)))
+void attn_bwd_sweep_kernel(AttnArgs p, const void* fwd_out) {
     using A = Attn<T>;
     using elem = typename T::elem;
     using vec8 = typename T::vec8;
@@ -832,40 +842,29 @@ __global__ __launch_bounds__(NC * 128) void attn_bwd_sweep_kernel(AttnArgs p, co
     const elem* base = (const elem*)p.qkv + (size_t)b * L * ld + hd * 64;
     const elem* dO = (const elem*)p.dout + (size_t)b * L * HD + hd * 64;
     const elem* Of = (const elem*)fwd_out + (size_t)b * L * ldof + hd * 64;
-    const auto rsQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.qkv), 0, (int)((size_t)p.B * L * ld * 2), 0x00020000);
-    const auto rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.dout), 0, (int)((size_t)p.B * L * HD * 2), 0x00020000);
-    const unsigned lane_q = (unsigned)(((size_t)(lane >> 3) * ld + (size_t)(((lane & 7) ^ (lane >> 3)) << 3)) * 2);
-    const unsigned lane_g = (unsigned)(((size_t)(lane >> 3) * HD + (size_t)(((lane & 7) ^ (lane >> 3)) << 3)) * 2);
+    const RowDma dmaQ(p.qkv, (size_t)p.B * L * ld * 2, ld, lane), dmaG(p.dout, (size_t)p.B * L * HD * 2, (size_t)HD, lane);
     const unsigned baseq = (unsigned)(((size_t)b * L * ld + (size_t)hd * 64) * 2), baseg = (unsigned)(((size_t)b * L * HD + (size_t)hd * 64) * 2);
-    using lds_ptr = __attribute__((address_space(3))) void*;
 
     // ---- loads: Q and dO images by LDS-DMA (4 row groups of 8 rows per wave), this wave's K / V fragments, and the O / dO fragments
     // of its query block for delta
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int j = wave * 4 + k, img = j / (Lp / 8), rg = j - img * (Lp / 8);
-        if (img == 0)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lds_ptr)(smem + rg * 1024), 16, (int)(baseq + lane_q + (unsigned)(rg * 8) * (unsigned)(ld * 2)), 0, 0, 0);
-        else
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr)(smem + IMG + rg * 1024), 16, (int)(baseg + lane_g + (unsigned)(rg * 8) * (unsigned)(HD * 2)), 0, 0, 0);
+        if (img == 0) dmaQ.issue(smem, baseq, rg);
+        else dmaG.issue(smem + IMG, baseg, rg);
     }
     const int nb16 = (L + 15) >> 4;
     const int row = wave * 16 + c;  // this lane's key (sweep) and query (delta, final phase)
-    const vec8 k0 = A::grow(base + HD, ld, row, L, 0, lane), k1 = A::grow(base + HD, ld, row, L, 1, lane);
-    const vec8 v0 = A::grow(base + 2 * HD, ld, row, L, 0, lane), v1 = A::grow(base + 2 * HD, ld, row, L, 1, lane);
+    const typename A::KFrags kf = A::fetch_kv(base + HD, base + 2 * HD, ld, row, L, lane);
     {
-        const vec8 g0 = A::grow(dO, HD, row, L, 0, lane), g1 = A::grow(dO, HD, row, L, 1, lane);
-        const vec8 o0 = A::grow(Of, ldof, row, L, 0, lane), o1 = A::grow(Of, ldof, row, L, 1, lane);
+        const typename A::QFrags qf = A::fetch_q(base, ld, dO, HD, Of, ldof, row, 0, L, lane);  // dO and O only: Q comes as an image
         const float lse_q = row < L ? p.lse[(size_t)pair * Lp + row] : 0.f;
         // DS rows of the key blocks that hold no real key are never written by a sweep: they must read as zero
         for (int i = tid; i < (Lp - nb16 * 16) * NC * 4; i += NT) {  // (Lp - 16 nb16) keys x NC panels x 64 bytes, 16 bytes per thread
             const int chunk = i & 3, rp = i >> 2, key = nb16 * 16 + rp % (Lp - nb16 * 16), panel = rp / (Lp - nb16 * 16);
             *(f32x4*)(DS + panel * (Lp * 64) + key * 64 + chunk * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        float delta = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) delta += (float)g0[i] * (float)o0[i] + (float)g1[i] * (float)o1[i];
-        delta = group_sum(delta);
+        const float delta = bwd_delta<T>(qf);
         if (g == 0) {
             del_s[row] = delta;
             lse_s[row] = row < L ? -lse_q * LOG2E : -INFINITY;
@@ -878,33 +877,14 @@ __global__ __launch_bounds__(NC * 128) void attn_bwd_sweep_kernel(AttnArgs p, co
     if (wave < nb16) {
         const bool kvalid = row < L;
         f32x4 dK[4], dV[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) { dK[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dV[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        zero4(dK);
+        zero4(dV);
 #pragma unroll
         // (round 4: skipping the last query tile when it lies wholly beyond L -- tile 13 of 14 at L = 201 -- behind a uniform branch: 215.5 vs 212.0 us)
         for (int qc = 0; qc < NC; ++qc) {  // fully unrolled: every LDS address becomes a loop-invariant lane base + an immediate offset
-            f32x4 P[2], dS[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int qt = 2 * qc + t;
-                const f32x4 nl = *(const f32x4*)(lse_s + qt * 16 + 4 * g);
-                const f32x4 d4 = *(const f32x4*)(del_s + qt * 16 + 4 * g);
-                f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = -d4;
-                S = T::mfma16(A::rows(Qs, qt * 16, 0, lane), k0, S);
-                S = T::mfma16(A::rows(Qs, qt * 16, 1, lane), k1, S);
-                dP = T::mfma16(A::rows(Gs, qt * 16, 0, lane), v0, dP);
-                dP = T::mfma16(A::rows(Gs, qt * 16, 1, lane), v1, dP);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    // padded queries have nl = -inf -> p = 0; padded keys (whole lanes) are zeroed below
-                    const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nl[r]));
-                    P[t][r] = pr;
-                    dS[t][r] = pr * dP[r];  // 1 / sqrt(d) applied at the stores
-                }
-            }
-            const vec8 pb = A::pack2(P[0], P[1]), db = A::pack2(dS[0], dS[1]);
-            // dS of this lane's key for queries 32 qc + 4 g .. + 3 (tile 2 qc) and 32 qc + 16 + 4 g .. (tile 2 qc + 1): 8 bytes each
-            {
+            // dS of this lane's key for queries 32 qc + 4 g .. + 3 (tile 2 qc) and 32 qc + 16 + 4 g .. (tile 2 qc + 1): 8 bytes each; zero for
+            // padded keys (whole lanes)
+            auto store_ds = [&](const vec8& db) {
                 vec4 lo = {db[0], db[1], db[2], db[3]}, hi = {db[4], db[5], db[6], db[7]};
                 if (!kvalid) {
 #pragma unroll
@@ -912,27 +892,16 @@ __global__ __launch_bounds__(NC * 128) void attn_bwd_sweep_kernel(AttnArgs p, co
                 }
                 *(vec4*)(DS + ds_off<Lp>(row, 32 * qc + 4 * g)) = lo;
                 *(vec4*)(DS + ds_off<Lp>(row, 32 * qc + 16 + 4 * g)) = hi;
-            }
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                dV[dt] = T::mfma16(A::cols(Gs, qc * 32, dt * 16, lane), pb, dV[dt]);
-                dK[dt] = T::mfma16(A::cols(Qs, qc * 32, dt * 16, lane), db, dK[dt]);
-            }
+            };
+            bwd_dkv_step<T, false>(Qs, Gs, lse_s, del_s, qc, 0, row, kf, lane, dK, dV, store_ds);
         }
-        if (kvalid) {
-            elem* ok = (elem*)p.dqkv + ((size_t)b * L + row) * ld + HD + hd * 64;
-            A::store_t(ok, dK, 0.125f, lane);
-            A::store_t(ok + HD, dV, 1.f, lane);
-        }
+        if (kvalid) A::store_dkv((elem*)p.dqkv + ((size_t)b * L + row) * ld + HD + hd * 64, HD, dK, dV, lane);
     }
     __syncthreads();  // DS is complete and nobody reads the Q image any more
 
     // ---- the K image takes the Q image's place (2 row groups per wave) -------------------------------------------------------
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int rg = wave * 2 + k;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lds_ptr)(smem + rg * 1024), 16, (int)(baseq + (unsigned)(HD * 2) + lane_q + (unsigned)(rg * 8) * (unsigned)(ld * 2)), 0, 0, 0);
-    }
+    for (int k = 0; k < 2; ++k) dmaQ.issue(smem, baseq + (unsigned)(HD * 2), wave * 2 + k);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -1073,7 +1042,6 @@ template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(TW * 64) void attn_bwd_dq_tiled_kernel(AttnArgs p, const void* fwd_out, int nsb) {
     using A = Attn<T>;
     using elem = typename T::elem;
-    using vec8 = typename T::vec8;
     __shared__ __attribute__((aligned(16))) elem Ks[2][64 * RS];
     __shared__ __attribute__((aligned(16))) elem Vs[2][64 * RS];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
@@ -1085,29 +1053,18 @@ __global__ __launch_bounds__(TW * 64) void attn_bwd_dq_tiled_kernel(AttnArgs p, 
     const elem* dO = (const elem*)p.dout + (size_t)b * L * HD + hd * 64;
     const elem* Of = (const elem*)fwd_out + (size_t)b * L * ldof + hd * 64;
     const int q = sb * TROWS + wave * 16 + c;
-    if (p.sel_rows && (p.sel_rows[b] - b * L) / TROWS != sb) {  // dO = 0 on this workgroup's queries (uniform branch)
-        if (g == 0 && q < Lp) p.delta[(size_t)pair * Lp + q] = 0.f;
-        const f32x4 z[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        if (q < L) A::store_t((elem*)p.dqkv + ((size_t)b * L + q) * ld + hd * 64, z, 0.f, lane);
-        return;
-    }
-    const vec8 q0 = A::grow(base, ld, q, L, 0, lane), q1 = A::grow(base, ld, q, L, 1, lane);
-    const vec8 g0 = A::grow(dO, HD, q, L, 0, lane), g1 = A::grow(dO, HD, q, L, 1, lane);
-    const vec8 o0 = A::grow(Of, ldof, q, L, 0, lane), o1 = A::grow(Of, ldof, q, L, 1, lane);
-    float delta = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) delta += (float)g0[i] * (float)o0[i] + (float)g1[i] * (float)o1[i];
-    delta = group_sum(delta);
+    if (p.sel_rows && (p.sel_rows[b] - b * L) / TROWS != sb) return bwd_zero_qblock<T>(p, b, hd, Lp, q, lane);  // dO = 0 on this workgroup's queries (uniform branch)
+    const typename A::QFrags f = A::fetch_q(base, ld, dO, HD, Of, ldof, q, L, L, lane);
+    const float delta = bwd_delta<T>(f);
     const size_t stat = (size_t)pair * Lp + (q < Lp ? q : 0);
     if (g == 0 && q < Lp) p.delta[stat] = delta;
     // window form: delta of every query, dQ only for the workgroups that hold a wanted row; a wave that leaves skips the barriers
     // below, so the decision is made per WORKGROUP (its TROWS queries)
-    if (p.win_n > 0 && (sb * TROWS >= p.win_row0 + p.win_n || sb * TROWS + TROWS <= p.win_row0)) return;
+    if (!in_win(p, sb * TROWS, TROWS)) return;
     const bool live = sb * TROWS + wave * 16 < L;
     const float nlse = q < L ? -p.lse[stat] * LOG2E : 0.f;
     f32x4 dQ[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) dQ[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero4(dQ);
     const int nall = (L + 63) / 64, last_q = sb * TROWS + TROWS - 1;
     const int nst = CAUSAL ? (last_q / 64 + 1 < nall ? last_q / 64 + 1 : nall) : nall;
     Stage64<T> sg;
@@ -1120,34 +1077,12 @@ __global__ __launch_bounds__(TW * 64) void attn_bwd_dq_tiled_kernel(AttnArgs p, 
         if (live && (!CAUSAL || st * 64 <= sb * TROWS + wave * 16 + 15)) {
             // only the stage that holds the end of the sequence (and causal stages) pays for the per-key mask (8 compare / select pairs per
             // 16 x 64 block: a sixth of the stage's vector issue)
-            auto block = [&](auto masked_c) {
-                constexpr bool MASKED = decltype(masked_c)::value;
+            auto block = [&](auto mask_c) {
 #pragma unroll
-                for (int kc = 0; kc < 2; ++kc) {
-                    f32x4 ds[2];
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const int kt = 2 * kc + t;
-                        f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = {-delta, -delta, -delta, -delta};
-                        S = T::mfma16(A::rows(Ks[cur], kt * 16, 0, lane), q0, S);
-                        S = T::mfma16(A::rows(Ks[cur], kt * 16, 1, lane), q1, S);
-                        dP = T::mfma16(A::rows(Vs[cur], kt * 16, 0, lane), g0, dP);
-                        dP = T::mfma16(A::rows(Vs[cur], kt * 16, 1, lane), g1, dP);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int key = st * 64 + kt * 16 + 4 * g + r;
-                            float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nlse));
-                            if (MASKED && (key >= L || (CAUSAL && key > q))) pr = 0.f;
-                            ds[t][r] = pr * dP[r];
-                        }
-                    }
-                    const vec8 db = A::pack2(ds[0], ds[1]);
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) dQ[dt] = T::mfma16(A::cols(Ks[cur], kc * 32, dt * 16, lane), db, dQ[dt]);
-                }
+                for (int kc = 0; kc < 2; ++kc) bwd_dq_step<T, false, decltype(mask_c)::value>(Ks[cur], Vs[cur], nullptr, kc, st * 64, L, q, f, nlse, delta, lane, dQ);
             };
-            if (CAUSAL || st * 64 + 64 > L) block(std::true_type{});
-            else block(std::false_type{});
+            if (CAUSAL || st * 64 + 64 > L) block(std::integral_constant<int, MASK_END | (CAUSAL ? MASK_CAUSAL : MASK_NONE)>{});
+            else block(std::integral_constant<int, MASK_NONE>{});
         }
         if (st + 1 < nst) sg.write(Ks[cur ^ 1], Vs[cur ^ 1], tid);
         __syncthreads();
@@ -1159,11 +1094,10 @@ template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(TW * 64) void attn_bwd_dkv_tiled_kernel(AttnArgs p, int nsb) {
     using A = Attn<T>;
     using elem = typename T::elem;
-    using vec8 = typename T::vec8;
     __shared__ __attribute__((aligned(16))) elem Qs[2][64 * RS];
     __shared__ __attribute__((aligned(16))) elem Gs[2][64 * RS];
     __shared__ float lse_s[2][64], del_s[2][64];
-    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pair = blockIdx.x / nsb, sb = blockIdx.x - pair * nsb, b = pair / p.H, hd = pair - b * p.H;
     const int HD = p.H * 64, L = p.L, Lp = attn_padded_len_dev(L);
@@ -1171,13 +1105,12 @@ __global__ __launch_bounds__(TW * 64) void attn_bwd_dkv_tiled_kernel(AttnArgs p,
     const elem* base = (const elem*)p.qkv + (size_t)b * L * ld + hd * 64;
     const elem* dO = (const elem*)p.dout + (size_t)b * L * HD + hd * 64;
     const int key = sb * TROWS + wave * 16 + c;
-    if (p.win_n > 0 && (sb * TROWS >= p.win_row0 + p.win_n || sb * TROWS + TROWS <= p.win_row0)) return;  // window form: no wanted key in this workgroup
+    if (!in_win(p, sb * TROWS, TROWS)) return;  // window form: no wanted key in this workgroup
     const bool live = sb * TROWS + wave * 16 < L;
-    const vec8 k0 = A::grow(base + HD, ld, key, L, 0, lane), k1 = A::grow(base + HD, ld, key, L, 1, lane);
-    const vec8 v0 = A::grow(base + 2 * HD, ld, key, L, 0, lane), v1 = A::grow(base + 2 * HD, ld, key, L, 1, lane);
+    const typename A::KFrags f = A::fetch_kv(base + HD, base + 2 * HD, ld, key, L, lane);
     f32x4 dK[4], dV[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) { dK[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dV[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    zero4(dK);
+    zero4(dV);
     const int st_sel = p.sel_rows ? (p.sel_rows[b] - b * L) >> 6 : -1;  // dO is zero outside this 64-query stage
     const int st_lo = CAUSAL ? (sb * TROWS) >> 6 : 0;  // causal: query stages that hold a query >= this workgroup's first key
     const int st0 = st_sel >= 0 ? (st_sel > st_lo ? st_sel : st_lo) : st_lo, nst = st_sel >= 0 ? st_sel + 1 : (L + 63) / 64;
@@ -1202,33 +1135,7 @@ __global__ __launch_bounds__(TW * 64) void attn_bwd_dkv_tiled_kernel(AttnArgs p,
         if (st + 1 < nst) { sg.load(base, ld, dO, (size_t)HD, (st + 1) * 64, L, tid); load_stats(st + 1); }
         if (live && (!CAUSAL || st * 64 + 63 >= sb * TROWS + wave * 16)) {
 #pragma unroll
-            for (int qc = 0; qc < 2; ++qc) {
-                f32x4 P[2], dS[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int qt = 2 * qc + t;
-                    const f32x4 nl = *(const f32x4*)(lse_s[cur] + qt * 16 + 4 * g);
-                    const f32x4 d4 = *(const f32x4*)(del_s[cur] + qt * 16 + 4 * g);
-                    f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = -d4;
-                    S = T::mfma16(A::rows(Qs[cur], qt * 16, 0, lane), k0, S);
-                    S = T::mfma16(A::rows(Qs[cur], qt * 16, 1, lane), k1, S);
-                    dP = T::mfma16(A::rows(Gs[cur], qt * 16, 0, lane), v0, dP);
-                    dP = T::mfma16(A::rows(Gs[cur], qt * 16, 1, lane), v1, dP);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], SC, nl[r]));
-                        if (CAUSAL && key > st * 64 + qt * 16 + 4 * g + r) pr = 0.f;
-                        P[t][r] = pr;
-                        dS[t][r] = pr * dP[r];
-                    }
-                }
-                const vec8 pb = A::pack2(P[0], P[1]), db = A::pack2(dS[0], dS[1]);
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    dV[dt] = T::mfma16(A::cols(Gs[cur], qc * 32, dt * 16, lane), pb, dV[dt]);
-                    dK[dt] = T::mfma16(A::cols(Qs[cur], qc * 32, dt * 16, lane), db, dK[dt]);
-                }
-            }
+            for (int qc = 0; qc < 2; ++qc) bwd_dkv_step<T, CAUSAL>(Qs[cur], Gs[cur], lse_s[cur], del_s[cur], qc, st * 64, key, f, lane, dK, dV);
         }
         if (st + 1 < nst) {
             sg.write(Qs[cur ^ 1], Gs[cur ^ 1], tid);
@@ -1236,11 +1143,7 @@ __global__ __launch_bounds__(TW * 64) void attn_bwd_dkv_tiled_kernel(AttnArgs p,
         }
         __syncthreads();
     }
-    if (key < L) {
-        elem* ok = (elem*)p.dqkv + ((size_t)b * L + key) * ld + HD + hd * 64;
-        A::store_t(ok, dK, 0.125f, lane);
-        A::store_t(ok + HD, dV, 1.f, lane);
-    }
+    if (key < L) A::store_dkv((elem*)p.dqkv + ((size_t)b * L + key) * ld + HD + hd * 64, HD, dK, dV, lane);
 }
 
 // the staged forms (FWD_STAGED / BWD_STAGED): one workgroup per TROWS-query (backward dK/dV: TROWS-key) group of a pair
