@@ -309,6 +309,34 @@ int mudpt_image_features(mudpt_model* m, int32_t batch, float* features_dev, voi
 int mudpt_forward_backward(mudpt_model* m, const float* images_dev, const int64_t* labels_dev, int32_t batch,
                            float grad_scale, float* loss_dev, float* logits_dev, void* stream);
 
+/* The step split at the head, for a loss of the caller's (additions: MUDPT_ABI_VERSION stays).  The reference's CustomCLIP.forward returns
+ * logits (trainers/mudpt.py:170-184) and the loss is one line of forward_backward (:249-251) that anyone can change; here
+ *   mudpt_forward_train(images)        the first half of mudpt_forward_backward: both towers as a TRAINING forward, the logits-only head;
+ *                                      logits_dev [batch, n_cls] fp32
+ *   mudpt_train_features(...)          the RAW (un-normalised) features of that forward, device to device: image_features_dev [batch, embed_dim],
+ *                                      text_features_dev [n_cls, embed_dim]; either may be NULL
+ *   <the caller's loss L and its gradients with respect to the three tensors>
+ *   mudpt_backward_logits(dL/dlogits, dL/dimage_features, dL/dtext_features)   the second half: the bucket is zeroed and receives the gradient of
+ *                                      (grad_scale * L).  Any of the three may be NULL (not all).  The head's backward from the given gradients
+ *                                      (mudpt_head_grad with gmul = loss_scale * batch, so for L = mean cross-entropy the towers see the logit gradients
+ *                                      mudpt_forward_backward forms itself), then that call's tail: VPT runs the vision side only, a vanilla vision
+ *                                      tower the text side only; a ResNet handle accepts and ignores dimg_dev (nothing in front of its features trains).
+ * All three are asynchronous on `stream`.  ONE forward feeds ONE backward: MUDPT_ERR_STATE from mudpt_train_features / mudpt_backward_logits if no
+ * mudpt_forward_train with the same batch precedes, or if any other forward, step or a second backward came in between.  MUDPT_ERR_ARG before any
+ * launch: a null model, a frozen handle, a class-sharded handle, CoCoOp (its step is chunked over the images and frees each chunk's text
+ * activations before the next: all logits exist only after every backward would have had to start), a null images / logits pointer. */
+int mudpt_forward_train(mudpt_model* m, const float* images_dev, int32_t batch, float* logits_dev, void* stream);
+int mudpt_train_features(mudpt_model* m, int32_t batch, float* image_features_dev, float* text_features_dev, void* stream);
+int mudpt_backward_logits(mudpt_model* m, const float* dlogits_dev, const float* dimg_dev, const float* dtxt_dev, int32_t batch, float grad_scale,
+                          void* stream);
+/* Which forward is in flight, for a host that keeps several results of mudpt_forward_train around (an autograd graph per call): every
+ * mudpt_forward_train of a handle has a number, 1, 2, ...  mudpt_train_token writes the number of the one in flight to *token (may be NULL);
+ * expect != 0: MUDPT_ERR_STATE unless that is the one in flight -- a later forward of the same batch size would otherwise take an earlier
+ * forward's gradients.  MUDPT_ERR_STATE also when none is in flight.  mudpt_train_release ends the forward in flight without a backward (a
+ * forward whose outputs are only read); none in flight: nothing happens.  mudpt_set_weight, mudpt_set_class_prompts and mudpt_bind_params end it too. */
+int mudpt_train_token(mudpt_model* m, int64_t expect, int64_t* token);
+int mudpt_train_release(mudpt_model* m);
+
 /* Data parallelism (replaces nn.DataParallel, trainers/mudpt.py:230-233): one process per GPU, each computing the gradient of
  * (1/world) * local-mean loss (grad_scale above); the ONE exchange of a step is the sum of the flat gradient bucket over the ranks.
  * A host with torch.distributed does that itself (mudpt_amd/parallel.py: dist.all_reduce on the bound bucket); any other host
@@ -651,6 +679,20 @@ int mudpt_attention_bwd_sel(int32_t dtype, const void* qkv, const void* out, con
 int mudpt_head_ex(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
                   int32_t e, float* txt_n, float* txt_inv, float* logits, float* loss, float* row_loss, float* dimg, float* dtxt, int32_t path,
                   int32_t* path_taken, void* stream);
+/* The head's backward from a GIVEN logit gradient, on the state a head forward left (img_n [B, e] / img_inv [B] / txt_n [C, e] / txt_inv [C]; the
+ * caller owns every buffer; asynchronous on `stream`):
+ *   dimg = gmul * (l2norm_bwd(scale * G   . txt_n, img_n, img_inv) + Eimg)   [B, e]     l2norm_bwd(d, n, inv) = inv * (d - n <d, n>) per row
+ *   dtxt = gmul * (l2norm_bwd(scale * G^T . img_n, txt_n, txt_inv) + Etxt)   [C, e]
+ * G [B, C] fp32 at row stride ldg >= C (the padding columns are never read), Eimg, Etxt: each may be NULL, not all three; dimg / dtxt: either may
+ * be NULL (not computed), not both.  G NULL: no contraction, the outputs are gmul * E bit for bit (zeros where that E is NULL).  The contraction
+ * runs in exact fp32 on the matrix cores in a fixed order; gmul is folded into its scale.  path 0, the dispatch: fused (one workgroup per 16
+ * images resp. 16 classes, a [16][e] tile in LDS) if e % 16 == 0, e <= 1024, B <= 16 and C <= 16 (one workgroup per kernel: where it is the faster form), else unfused; 1: force
+ * the unfused form (mudpt_sgemm twice + a row-wise kernel); 2: force the fused form (MUDPT_ERR_ARG where e does not fit).  *path_taken (HOST, may
+ * be NULL) = 0 fused, 1 unfused; a refused call does not write it.  MUDPT_ERR_ARG before any launch, naming the field: a null state pointer, B, C or e < 1,
+ * ldg < C, dimg and dtxt both NULL, G, Eimg and Etxt all NULL. */
+int mudpt_head_grad(const float* img_n, const float* img_inv, const float* txt_n, const float* txt_inv, const float* G, int64_t ldg, const float* Eimg,
+                    const float* Etxt, float scale, float gmul, int32_t B, int32_t C, int32_t e, float* dimg, float* dtxt, int32_t path,
+                    int32_t* path_taken, void* stream);
 /* CoCoOp's head (trainers/cocoop.py:187-197): every image has its own text features txt [B * C, e] (row i * C + c); logits[i, c] = scale *
  * <normalise(img_i), normalise(txt_{i,c})>, row_loss [B], dtxt [B * C, e] = gradient of (grad_scale * mean CE) w.r.t. the raw text features.
  * B_total > 0: a chunk of a batch of B_total images (gradients scaled by 1 / B_total, `loss` not written); 0: loss[0] = mean(row_loss).

@@ -18,6 +18,10 @@ class CoCoOp(PromptTrainer):
     DROP_KEYS = ("token_prefix", "token_suffix")  # trainers/cocoop.py:314-318
     SKIPPED_NOTE = "Note that load_model() is skipped as no Pretrained model is given"  # :292
 
+    def check_compute_loss(self):
+        assert self.compute_loss is None, ("CoCoOp takes no compute_loss: its step is chunked over the images, so all logits exist only after "
+                                           "every backward would have had to start")
+
     def prompt_setup(self, cc, names, ctx_len, near):
         n_ctx, ctx_init, ctx_ids = cc.N_CTX, cc.CTX_INIT, None
         if ctx_init:  # trainers/cocoop.py:79-87: n_ctx follows the init words

@@ -23,16 +23,18 @@ constexpr int HEAD_ROWS = 16, HEAD_WAVES = 8, HEAD_RPW = HEAD_ROWS / HEAD_WAVES;
 
 // acc[t] += A[16, K] . B[K, 16 tile t]: A from `a_row` (this lane's row, k contiguous: LDS or global), B rows from `b_base + k * ldb`
 // (k-major operand: element (k, col) at b[k * ldb + col]); K a multiple of 16; rows of B beyond k_valid read as zero.
-template <int NT>
+// GUARD_A (A straight from memory, not from a padded LDS tile): A is read only where a_ok and k < k_valid, zero elsewhere.
+template <int NT, bool GUARD_A = false>
 __device__ inline void mfma_kmajor(f32x4 (&acc)[NT], const float* a_row, int a_stride_k, const float* b_base, size_t ldb, const int (&col)[NT],
-                                   const bool (&col_ok)[NT], int K, int k_valid, int g) {
+                                   const bool (&col_ok)[NT], int K, int k_valid, int g, bool a_ok = true) {
     // 4 steps' operands are requested before the first MFMA (the loop is otherwise one dependent memory round trip per step); K % 16 == 0
     for (int k0 = 0; k0 < K; k0 += 16) {
         float av[4], bv[4][NT];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int k = k0 + 4 * u + g;
-            av[u] = a_row[(size_t)k * a_stride_k];
+            if constexpr (GUARD_A) av[u] = (a_ok && k < k_valid) ? a_row[(size_t)k * a_stride_k] : 0.f;
+            else av[u] = a_row[(size_t)k * a_stride_k];
 #pragma unroll
             for (int t = 0; t < NT; ++t) bv[u][t] = (col_ok[t] && k < k_valid) ? b_base[(size_t)k * ldb + col[t]] : 0.f;
         }
@@ -49,6 +51,15 @@ __device__ inline void l2norm_bwd_row(const float* d, const float* n, float inv,
     for (int k = lane; k < e; k += 64) s += d[k] * n[k];
     s = wave_sum(s);
     for (int k = lane; k < e; k += 64) out[k] = inv * (d[k] - n[k] * s);
+}
+// l2norm_bwd_row + gmul * extra in the one store; extra null: l2norm_bwd_row itself.  out may be d (every lane reads its d[k] before it writes out[k],
+// and the sum is complete before the first store)
+__device__ inline void l2norm_bwd_row_add(const float* d, const float* n, float inv, float* out, const float* extra, float gmul, int e, int lane) {
+    if (!extra) { l2norm_bwd_row(d, n, inv, out, e, lane); return; }
+    float s = 0.f;
+    for (int k = lane; k < e; k += 64) s += d[k] * n[k];
+    s = wave_sum(s);
+    for (int k = lane; k < e; k += 64) out[k] = inv * (d[k] - n[k] * s) + gmul * extra[k];
 }
 
 // DIMG = false (training only): the image features need no gradient -- steps 4 and 5 and their [16][e] tile are left out, steps 1 to 3 are
@@ -169,8 +180,9 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_rows_kernel(HeadArgs p, 
     }
 }
 
-// d(raw text features) of 16 classes: scale * dlogits^T[16, B] . img_n[B, e], then the backward of the normalisation
-__global__ __launch_bounds__(HEAD_WAVES * 64) void head_dtxt_kernel(HeadArgs p) {
+// d(raw text features) of 16 classes: scale * G^T[16, B] . img_n[B, e], then the backward of the normalisation, + gmul * Etxt.
+// p.scale is the product the launcher folded (head scale * gmul).  The training head passes G = dlogits, ldg = C, gmul = 1, Etxt = null.
+__global__ __launch_bounds__(HEAD_WAVES * 64) void head_dtxt_kernel(HeadGradArgs p) {
     extern __shared__ __attribute__((aligned(16))) float hsm[];
     float* Dn = hsm;  // [16][e]
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
@@ -178,8 +190,9 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_dtxt_kernel(HeadArgs p) 
     const int c0 = blockIdx.x * HEAD_ROWS, e = p.e, C = p.C, B = p.B;
     const int Bpad = (B + 3) & ~3, ne = e / 16;
     const int cls = c0 + c;
-    // A[class c][k = image] = dlogits[image][class]: this lane's "row" is a column of dlogits, stride C between consecutive k
-    const float* a_row = p.dlogits + (cls < C ? cls : 0);
+    const size_t ldg = (size_t)p.ldg;
+    // A[class c][k = image] = G[image][class]: this lane's "row" is a column of G, stride ldg between consecutive k
+    const float* a_row = p.G + (cls < C ? cls : 0);
     for (int et0 = wave * 4; et0 < ne; et0 += 4 * HEAD_WAVES) {
         f32x4 acc[4];
         int col[4];
@@ -193,7 +206,7 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_dtxt_kernel(HeadArgs p) 
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = k0 + 4 * u + g;
-                av[u] = (k < B && cls < C) ? a_row[(size_t)k * C] : 0.f;
+                av[u] = (k < B && cls < C) ? a_row[(size_t)k * ldg] : 0.f;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) bv[u][t] = (ok[t] && k < B) ? p.img_n[(size_t)k * e + col[t]] : 0.f;
             }
@@ -211,8 +224,55 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_dtxt_kernel(HeadArgs p) 
     __syncthreads();
     for (int i = 0; i < HEAD_RPW; ++i) {
         const int rl = wave * HEAD_RPW + i, r = c0 + rl;
-        if (r < C) l2norm_bwd_row(Dn + rl * e, p.txt_n + (size_t)r * e, p.txt_inv[r], p.dtxt + (size_t)r * e, e, lane);
+        if (r >= C) continue;
+        l2norm_bwd_row_add(Dn + rl * e, p.txt_n + (size_t)r * e, p.txt_inv[r], p.dtxt + (size_t)r * e, p.Etxt ? p.Etxt + (size_t)r * e : nullptr, p.gmul, e, lane);
     }
+}
+
+// d(raw image features) of 16 images: scale * G[16, C] . txt_n[C, e] (G's rows are the A operand straight from memory, classes ascending: a
+// fixed summation order, and a row's result does not depend on the rows beside it), then steps 5 of head_rows_kernel<true> on img_n / img_inv
+// from memory, + gmul * Eimg.  A row >= B or a class >= C is never read (the padding columns of ldg > C may hold anything).
+__global__ __launch_bounds__(HEAD_WAVES * 64) void head_dimg_kernel(HeadGradArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float hsm[];
+    float* Dn = hsm;  // [16][e]
+    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r0 = blockIdx.x * HEAD_ROWS, e = p.e, C = p.C, B = p.B;
+    const int Cpad = (C + 15) / 16 * 16, ne = e / 16;
+    const bool row_ok = r0 + c < B;
+    const float* a_row = p.G + (size_t)(row_ok ? r0 + c : 0) * (size_t)p.ldg;
+    for (int et0 = wave * 4; et0 < ne; et0 += 4 * HEAD_WAVES) {
+        f32x4 acc[4];
+        int col[4];
+        bool ok[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; col[t] = (et0 + t) * 16 + c; ok[t] = et0 + t < ne; }
+        mfma_kmajor<4, true>(acc, a_row, 1, p.txt_n, (size_t)e, col, ok, Cpad, C, g, row_ok);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (ok[t])
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Dn[(4 * g + r) * e + col[t]] = p.scale * acc[t][r];
+    }
+    __syncthreads();
+    for (int i = 0; i < HEAD_RPW; ++i) {
+        const int rl = wave * HEAD_RPW + i, r = r0 + rl;
+        if (r >= B) continue;
+        l2norm_bwd_row_add(Dn + rl * e, p.img_n + (size_t)r * e, p.img_inv[r], p.dimg + (size_t)r * e, p.Eimg ? p.Eimg + (size_t)r * e : nullptr, p.gmul, e, lane);
+    }
+}
+
+// unfused form, behind launch_sgemm: the same row step in place on d, one wave per row
+__global__ __launch_bounds__(256) void head_grad_rows_kernel(float* d, const float* n, const float* inv, const float* extra, float gmul, int rows, int e) {
+    const int lane = threadIdx.x & 63;
+    const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= (size_t)rows) return;
+    float* dr = d + r * e;
+    l2norm_bwd_row_add(dr, n + r * e, inv[r], dr, extra ? extra + r * e : nullptr, gmul, e, lane);
+}
+// y = gmul * x: the gradient of a loss that reads the features only (no logit gradient, no contraction)
+__global__ __launch_bounds__(256) void head_grad_scale_kernel(const float* x, float gmul, float* y, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = gmul * x[i];
 }
 
 static int head_lds_bytes(const HeadArgs& a, bool train) {
@@ -259,7 +319,73 @@ int launch_head_fused_train(const HeadArgs& a, hipStream_t s) {
     if (a.B_total <= 0)
         if (int rc = launch_mean(a.row_loss, a.B, a.loss, s)) return rc;
     if (!a.dtxt) return MUDPT_OK;  // the text features have nothing to learn (VPT): no text half
-    hipLaunchKernelGGL(head_dtxt_kernel, dim3((a.C + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), HEAD_ROWS * a.e * 4, s, a);
+    HeadGradArgs t; t.img_n = a.img_n; t.txt_n = a.txt_n; t.txt_inv = a.txt_inv; t.G = a.dlogits; t.ldg = a.C; t.dtxt = a.dtxt; t.scale = a.scale;
+    t.B = a.B; t.C = a.C; t.e = a.e;
+    hipLaunchKernelGGL(head_dtxt_kernel, dim3((a.C + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), HEAD_ROWS * a.e * 4, s, t);
+    HIP_TRY(hipGetLastError());
+    return MUDPT_OK;
+}
+
+bool head_grad_fused_fits(const HeadGradArgs& a) { return a.e > 0 && a.e % 16 == 0 && a.e <= HEAD_MAX_E_TRAIN; }
+// head_dimg_kernel has one workgroup per 16 images and each walks ALL classes, 16 per step of a dependent load chain (head_dtxt_kernel: the
+// same over the images); the unfused form spreads each contraction over an sgemm grid.  Measured (tools/custom_loss_bench.py):
+// the fused pair is the faster one only while each kernel is ONE workgroup (13.7 against 16.6 us at B 4, 11 classes); from 50 classes or 32
+// images on it loses, 2.3 x at 256 x 1000, e 512 and 4.4 x at 32 x 1000, e 1024.  The dispatch follows that
+constexpr int HEAD_GRAD_FUSED_MAX_ROWS = HEAD_ROWS;
+bool head_grad_fused(const HeadGradArgs& a) { return head_grad_fused_fits(a) && a.B <= HEAD_GRAD_FUSED_MAX_ROWS && a.C <= HEAD_GRAD_FUSED_MAX_ROWS; }
+
+// one output of a feature-only loss: gmul * E, or zeros where that output has no gradient input at all
+static int head_grad_scaled(const float* E, float gmul, float* out, size_t n, hipStream_t s) {
+    if (!E) { HIP_TRY(hipMemsetAsync(out, 0, n * 4, s)); return MUDPT_OK; }
+    const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(head_grad_scale_kernel, dim3(grid), dim3(256), 0, s, E, gmul, out, n);
+    HIP_TRY(hipGetLastError());
+    return MUDPT_OK;
+}
+
+int launch_head_grad(const HeadGradArgs& a, hipStream_t s, int form) {
+    ARG_CHECK(form >= 0 && form <= 2, "head_grad: form %d is none of 0 (dispatch), 1 (unfused), 2 (fused)", form);
+    ARG_CHECK(form != 2 || head_grad_fused_fits(a), "head_grad: the fused form does not take e=%d (e %% 16 == 0, e <= %d)", a.e, HEAD_MAX_E_TRAIN);
+    ARG_CHECK(a.img_n, "head_grad: img_n is null");
+    ARG_CHECK(a.img_inv, "head_grad: img_inv is null");
+    ARG_CHECK(a.txt_n, "head_grad: txt_n is null");
+    ARG_CHECK(a.txt_inv, "head_grad: txt_inv is null");
+    ARG_CHECK(a.B >= 1, "head_grad: B=%d must be at least 1", a.B);
+    ARG_CHECK(a.C >= 1, "head_grad: C=%d must be at least 1", a.C);
+    ARG_CHECK(a.e >= 1, "head_grad: e=%d must be at least 1", a.e);
+    ARG_CHECK(!a.G || a.ldg >= a.C, "head_grad: ldg=%lld is smaller than C=%d", (long long)a.ldg, a.C);
+    ARG_CHECK(a.dimg || a.dtxt, "head_grad: dimg and dtxt are both null: nothing to compute");
+    ARG_CHECK(a.G || a.Eimg || a.Etxt, "head_grad: G, Eimg and Etxt are all null: no gradient to start from");
+    const size_t ne_img = (size_t)a.B * a.e, ne_txt = (size_t)a.C * a.e;
+    if (!a.G) {
+        if (a.dimg) if (int rc = head_grad_scaled(a.Eimg, a.gmul, a.dimg, ne_img, s)) return rc;
+        if (a.dtxt) if (int rc = head_grad_scaled(a.Etxt, a.gmul, a.dtxt, ne_txt, s)) return rc;
+        return MUDPT_OK;
+    }
+    HeadGradArgs p = a;
+    p.scale = a.scale * a.gmul;  // l2norm_bwd is linear: gmul goes through the contraction's scale
+    if (form == 2 || (form == 0 && head_grad_fused(a))) {
+        const int dev = current_device(), lds = HEAD_ROWS * a.e * 4;
+        if (a.dimg) {
+            if (int e = lds_limit_once<head_dimg_kernel>(dev, 65536)) return e;
+            hipLaunchKernelGGL(head_dimg_kernel, dim3((a.B + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), lds, s, p);
+        }
+        if (a.dtxt) {
+            if (int e = lds_limit_once<head_dtxt_kernel>(dev, 65536)) return e;
+            hipLaunchKernelGGL(head_dtxt_kernel, dim3((a.C + HEAD_ROWS - 1) / HEAD_ROWS), dim3(HEAD_WAVES * 64), lds, s, p);
+        }
+        HIP_TRY(hipGetLastError());
+        return MUDPT_OK;
+    }
+    ARG_CHECK(a.ldg <= 0x7fffffff, "head_grad: ldg=%lld is beyond the unfused form's 32-bit stride", (long long)a.ldg);
+    if (a.dimg) {
+        if (int rc = launch_sgemm(false, false, a.B, a.e, a.C, p.scale, a.G, (int)a.ldg, a.txt_n, a.e, 0.f, a.dimg, a.e, nullptr, s)) return rc;
+        hipLaunchKernelGGL(head_grad_rows_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.dimg, a.img_n, a.img_inv, a.Eimg, a.gmul, a.B, a.e);
+    }
+    if (a.dtxt) {
+        if (int rc = launch_sgemm(true, false, a.C, a.e, a.B, p.scale, a.G, (int)a.ldg, a.img_n, a.e, 0.f, a.dtxt, a.e, nullptr, s)) return rc;
+        hipLaunchKernelGGL(head_grad_rows_kernel, dim3((a.C + 3) / 4), dim3(256), 0, s, a.dtxt, a.txt_n, a.txt_inv, a.Etxt, a.gmul, a.C, a.e);
+    }
     HIP_TRY(hipGetLastError());
     return MUDPT_OK;
 }

@@ -233,6 +233,30 @@ int launch_head_bwd(const HeadArgs& a, hipStream_t s);
 bool head_fused_fits(const HeadArgs& a, bool train);
 int launch_head_fused_fwd(const HeadArgs& a, hipStream_t s);
 int launch_head_fused_train(const HeadArgs& a, hipStream_t s);  // logits + loss + dimg + dtxt (gradients of the raw features; dtxt null, dimg null: skipped)
+// The head's backward from a GIVEN logit gradient (the custom-loss step): with the state a head forward left (img_n / img_inv / txt_n / txt_inv),
+//   dimg = gmul * (l2norm_bwd(scale * G   . txt_n, img_n, img_inv) + Eimg)   [B, e]      l2norm_bwd(d, n, inv) = inv * (d - n <d, n>) per row
+//   dtxt = gmul * (l2norm_bwd(scale * G^T . img_n, txt_n, txt_inv) + Etxt)   [C, e]
+// G [B, C] fp32 at row stride ldg >= C, Eimg [B, e], Etxt [C, e]: each may be null (not all three); dimg / dtxt: either may be null (not computed).
+// gmul is folded into the scale of the contraction: no pass over G.  G null: no contraction, the outputs are gmul * E (zeros where E is null too).
+struct HeadGradArgs {
+    const float* img_n = nullptr;    // [B, e]
+    const float* img_inv = nullptr;  // [B]
+    const float* txt_n = nullptr;    // [C, e]
+    const float* txt_inv = nullptr;  // [C]
+    const float* G = nullptr;        // [B, ldg]
+    const float* Eimg = nullptr;     // [B, e]
+    const float* Etxt = nullptr;     // [C, e]
+    float* dimg = nullptr;           // [B, e]
+    float* dtxt = nullptr;           // [C, e]
+    int64_t ldg = 0;
+    float scale = 1.f, gmul = 1.f;
+    int B = 0, C = 0, e = 0;
+};
+bool head_grad_fused_fits(const HeadGradArgs& a);  // e % 16 == 0 and e <= 1024: the [16][e] fp32 tile in 64 KB of LDS
+bool head_grad_fused(const HeadGradArgs& a);       // the dispatch: it fits, B <= 16 and C <= 16 (head.hip: where the fused form is the faster one)
+// form 0: the dispatch; 1: unfused -- launch_sgemm twice + the row-wise normalisation backward (what launch_head_bwd runs behind its
+// cross-entropy rows); 2: fused, refused where it does not fit
+int launch_head_grad(const HeadGradArgs& a, hipStream_t s, int form = 0);
 // CoCoOp (trainers/cocoop.py): per-image text features.  txt / txt_n / txt_inv / dtxt have B * C rows (row i * C + c).
 int launch_pair_head_fwd(const HeadArgs& a, hipStream_t s);
 int launch_pair_head_bwd(const HeadArgs& a, hipStream_t s);  // loss, dlogits, dtxt (gradient of the raw text features)

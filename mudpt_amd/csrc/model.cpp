@@ -255,6 +255,8 @@ struct mudpt_model {
     bool sharded = false;
     float cp_unscale = 0.f;  // of the step in flight between mudpt_cp_head and mudpt_cp_backward
     int cp_B = 0, cp_stage = 0;  // 1 = towers forward done, 2 = head (training) done
+    int cl_B = 0;  // images of the mudpt_forward_train whose activations and head state are still in place (mudpt_backward_logits); 0: of none
+    int64_t cl_serial = 0;  // number of that forward (mudpt_train_token): 1, 2, ... over the handle's life
     int hid = 0;  // meta_net hidden width = embed_dim / 16 (trainers/cocoop.py:104)
     // CoOp variant (trainers/coop.py): 1 trainable (ctx, shared or one per class with CSC), vanilla vision tower (forward only), C text
     // sequences as MuDPT.  The context rows of class c sit at prompt positions coop_pos[c * n ..] (CLASS_TOKEN_POSITION); tprompt_rows
@@ -1089,6 +1091,7 @@ static int resnet_fold(mudpt_model* m, hipStream_t s) {
 
 extern "C" int mudpt_set_weight(mudpt_model* m, const char* key, const float* data, size_t numel) {
     ARG_CHECK(m && key && data, "set_weight: null argument");
+    m->cl_B = 0;  // a new weight ends a mudpt_forward_train in flight
     const mudpt_config& c = m->cfg;
     const std::string k(key);
     const size_t dv = c.v_width, dt = c.t_width, e = c.embed_dim;
@@ -1263,6 +1266,7 @@ static void bind_text_layout(Tower& t, const TextLayout& lay) { t.lay = &lay; t.
 extern "C" int mudpt_set_class_prompts(mudpt_model* m, const float* emb, const int32_t* eot) {
     ARG_CHECK(m && emb && eot, "set_class_prompts: null argument");
     NOT_FROZEN(m, "set_class_prompts (a frozen handle takes token ids: mudpt_set_text_tokens)");
+    m->cl_B = 0;  // the text tower's tables and activations may be rebuilt below: a mudpt_forward_train in flight ends here
     for (const std::string& k : m->missing)
         if (k == "positional_embedding") { set_error("set_class_prompts: set 'positional_embedding' first"); return MUDPT_ERR_STATE; }
     const mudpt_config& c = m->cfg;
@@ -1431,6 +1435,7 @@ extern "C" int mudpt_bind_params(mudpt_model* m, float* p, float* g) {
     NOT_FROZEN(m, "bind_params");
     ARG_CHECK(m && p, "bind_params: null argument");
     ARG_CHECK((uintptr_t)p % 16 == 0 && (uintptr_t)g % 16 == 0, "bind_params: buckets must be 16-byte aligned");
+    m->cl_B = 0;  // the forward in flight ran on the old bucket's parameters
     m->params = p;
     m->grads = g;
     return MUDPT_OK;
@@ -2103,6 +2108,7 @@ static Learner learner(const mudpt_model* m);
 // features of the previous call are kept.
 static int towers_forward(mudpt_model* m, const ImageSide& in, int B, hipStream_t s, bool reuse_text) {
     const Learner L = learner(m);
+    m->cl_B = 0;  // every forward overwrites what a mudpt_forward_train left for its backward
     if (L.fwd) TRY(L.fwd(m, s));
     if (!reuse_text) {
         HIP_TRY(hipEventRecord(m->ev_fork, s));
@@ -2120,6 +2126,7 @@ static int towers_forward(mudpt_model* m, const ImageSide& in, int B, hipStream_
 // cosine logits, trainers/mudpt.py:178-182 (needs both towers' features; txt_f must hold all n_cls rows)
 static int head_forward(mudpt_model* m, int B, bool reuse_text, hipStream_t s) {
     const mudpt_config& c = m->cfg;
+    m->cl_B = 0;
     HeadArgs h; h.img = m->img_f; h.txt = m->txt_f; h.scale = m->scale; h.logits = m->logits; h.img_n = m->img_n; h.txt_n = m->txt_n;
     h.img_inv = m->img_inv; h.txt_inv = m->txt_inv; h.B = B; h.C = c.n_cls; h.e = c.embed_dim;
     if (!reuse_text || !head_fused_fits(h, false)) ++m->text_launches;  // the normalisation of the text features
@@ -2289,6 +2296,7 @@ static int head_train(mudpt_model* m, const int64_t* labels, int B, float grad_s
                       bool reuse_text = false, bool text_grad = true) {
     const mudpt_config& c = m->cfg;
     const int e = c.embed_dim, C = c.n_cls;
+    m->cl_B = 0;
     HeadArgs h; h.img = m->img_f; h.txt = m->txt_f; h.labels = labels; h.scale = m->scale; h.logits = m->logits; h.loss = m->loss; h.dlogits = m->dlogits;
     h.row_loss = m->row_loss; h.dimg = m->rn ? nullptr : m->dimg; h.dtxt = text_grad ? m->dtxt : nullptr; h.img_n = m->img_n; h.txt_n = m->txt_n; h.img_inv = m->img_inv; h.txt_inv = m->txt_inv;
     // Static loss scaling: the backward pass runs on per-sample gradients times loss_scale (dlogits = (softmax -
@@ -2486,6 +2494,99 @@ extern "C" int mudpt_forward_backward(mudpt_model* m, const float* images, const
     if (m->vpt) return vision_backward(m, B, m->cp_unscale, s);
     if (!m->vis.head_rows) return text_backward(m, m->cp_unscale, s);
     // text tower backward on the side stream (enqueued first; joins before the learner's backward)
+    HIP_TRY(hipEventRecord(m->ev_fork_b, s));
+    HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork_b, 0));
+    TRY(text_backward(m, m->cp_unscale, m->s2));
+    if (L.bwd_text) TRY(L.bwd_text(m, m->s2));
+    HIP_TRY(hipEventRecord(m->ev_join_b, m->s2));
+    TRY(vision_backward(m, B, m->cp_unscale, s));
+    HIP_TRY(hipStreamWaitEvent(s, m->ev_join_b, 0));
+    return L.bwd ? L.bwd(m, s) : MUDPT_OK;
+}
+
+// ---- the step split at the head: a loss of the caller's (mudpt_forward_train -> the caller's loss -> mudpt_backward_logits) ----
+// One training forward leaves the towers' activations and the head's state (img_n, img_inv, txt_n, txt_inv) in place; the backward starts from
+// the caller's dL/dlogits, dL/d(image features), dL/d(text features) instead of from labels and then runs the tail of mudpt_forward_backward.
+static int custom_loss_ok(const mudpt_model* m, const char* what) {
+    ARG_CHECK(m, "%s: null model", what);
+    ARG_CHECK(!m->frozen, "%s: a frozen handle (mudpt_create_frozen) has no parameters: nothing to train with a custom loss", what);
+    ARG_CHECK(!m->sharded, "%s: a class-sharded handle (mudpt_set_class_shard) has no custom-loss step: its logits exist only behind the mudpt_cp_* exchanges", what);
+    ARG_CHECK(!m->cocoop, "%s: CoCoOp has no custom-loss step: its step is chunked over the images and frees each chunk's text activations before "
+              "the next, so all logits exist only after every backward would have had to start", what);
+    return MUDPT_OK;
+}
+static int custom_loss_armed(const mudpt_model* m, int B, const char* what) {
+    if (m->cl_B == 0) { set_error("%s: no mudpt_forward_train is in flight: one forward feeds one backward, and any other forward, step or a second backward ends it", what); return MUDPT_ERR_STATE; }
+    if (m->cl_B != B) { set_error("%s: the mudpt_forward_train in flight ran on %d images, not %d: one forward feeds one backward of the same batch", what, m->cl_B, B); return MUDPT_ERR_STATE; }
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_forward_train(mudpt_model* m, const float* images, int32_t B, float* logits, void* stream) {
+    TRY(custom_loss_ok(m, "forward_train"));
+    TRY(ready(m, B, true));
+    ARG_CHECK(images && logits, "forward_train: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    m->train_fwd = true;
+    m->feat_B = 0;  // as mudpt_forward_backward: a training forward may split K
+    m->cp_stage = 0;
+    const bool reuse = m->vpt && m->text_valid;
+    TRY(towers_forward(m, images, B, s, reuse));
+    TRY(head_forward(m, B, reuse, s));
+    HIP_TRY(hipMemcpyAsync(logits, m->logits, (size_t)B * m->cfg.n_cls * 4, hipMemcpyDeviceToDevice, s));
+    m->cl_B = B;
+    ++m->cl_serial;
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_train_token(mudpt_model* m, int64_t expect, int64_t* token) {
+    TRY(custom_loss_ok(m, "train_token"));
+    if (m->cl_B == 0) { set_error("train_token: no mudpt_forward_train is in flight: one forward feeds one backward, and any other forward, step or a second backward ends it"); return MUDPT_ERR_STATE; }
+    if (expect != 0 && expect != m->cl_serial) {
+        set_error("train_token: the mudpt_forward_train in flight is number %lld of this handle, not %lld: a later forward has overwritten what that one left: "
+                  "one forward feeds one backward, and any other forward ends it", (long long)m->cl_serial, (long long)expect);
+        return MUDPT_ERR_STATE;
+    }
+    if (token) *token = m->cl_serial;
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_train_release(mudpt_model* m) {
+    ARG_CHECK(m, "train_release: null model");
+    m->cl_B = 0;
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_train_features(mudpt_model* m, int32_t B, float* image_features, float* text_features, void* stream) {
+    TRY(custom_loss_ok(m, "train_features"));
+    TRY(custom_loss_armed(m, B, "train_features"));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t e = (size_t)m->cfg.embed_dim;
+    if (image_features) HIP_TRY(hipMemcpyAsync(image_features, m->img_f, (size_t)B * e * 4, hipMemcpyDeviceToDevice, s));
+    if (text_features) HIP_TRY(hipMemcpyAsync(text_features, m->txt_f, (size_t)m->cfg.n_cls * e * 4, hipMemcpyDeviceToDevice, s));
+    return MUDPT_OK;
+}
+
+extern "C" int mudpt_backward_logits(mudpt_model* m, const float* dlogits, const float* dimg, const float* dtxt, int32_t B, float grad_scale, void* stream) {
+    TRY(custom_loss_ok(m, "backward_logits"));
+    TRY(ready(m, B, true));
+    ARG_CHECK(dlogits || dimg || dtxt, "backward_logits: dlogits, dimg and dtxt are all null: no gradient to start from");
+    TRY(custom_loss_armed(m, B, "backward_logits"));
+    m->cl_B = 0;  // consumed, whatever happens below
+    hipStream_t s = (hipStream_t)stream;
+    const mudpt_config& c = m->cfg;
+    const Learner L = learner(m);
+    HIP_TRY(hipMemsetAsync(m->grads, 0, m->total * 4, s));
+    const bool img_grad = !m->rn && m->vis.head_rows, txt_grad = !m->vpt;  // the towers with a trainable ancestor, as mudpt_forward_backward's shortcuts
+    const float gmul = m->loss_scale * (float)B;  // the convention of head_train: per-sample gradients times loss_scale inside the towers
+    m->cp_unscale = grad_scale / gmul;
+    HeadGradArgs h; h.img_n = m->img_n; h.img_inv = m->img_inv; h.txt_n = m->txt_n; h.txt_inv = m->txt_inv; h.G = dlogits; h.ldg = c.n_cls;
+    h.Eimg = img_grad ? dimg : nullptr; h.Etxt = txt_grad ? dtxt : nullptr; h.dimg = img_grad ? m->dimg : nullptr; h.dtxt = txt_grad ? m->dtxt : nullptr;
+    h.scale = m->scale; h.gmul = gmul; h.B = B; h.C = c.n_cls; h.e = c.embed_dim;
+    if (!h.G && !h.Eimg && !h.Etxt) return MUDPT_OK;  // only gradients of features nothing trainable stands in front of: the bucket stays zero
+    if (txt_grad) ++m->text_launches;  // the text half of the head's backward, as head_train counts it
+    TRY(launch_head_grad(h, s));
+    if (m->vpt) return vision_backward(m, B, m->cp_unscale, s);
+    if (!m->vis.head_rows) return text_backward(m, m->cp_unscale, s);
     HIP_TRY(hipEventRecord(m->ev_fork_b, s));
     HIP_TRY(hipStreamWaitEvent(m->s2, m->ev_fork_b, 0));
     TRY(text_backward(m, m->cp_unscale, m->s2));
@@ -2999,6 +3100,16 @@ extern "C" int mudpt_head_ex(const float* img, const float* txt, const int64_t* 
     (void)hipStreamSynchronize(s);
     (void)hipFree(scratch);
     return rc;
+}
+extern "C" int mudpt_head_grad(const float* img_n, const float* img_inv, const float* txt_n, const float* txt_inv, const float* G, int64_t ldg, const float* Eimg,
+                               const float* Etxt, float scale, float gmul, int32_t B, int32_t C, int32_t e, float* dimg, float* dtxt, int32_t path,
+                               int32_t* path_taken, void* stream) {
+    ARG_CHECK(path >= 0 && path <= 2, "head_grad: path must be 0 (the dispatch), 1 (the unfused launchers) or 2 (the fused kernels)");
+    HeadGradArgs h; h.img_n = img_n; h.img_inv = img_inv; h.txt_n = txt_n; h.txt_inv = txt_inv; h.G = G; h.ldg = ldg; h.Eimg = Eimg; h.Etxt = Etxt;
+    h.scale = scale; h.gmul = gmul; h.B = B; h.C = C; h.e = e; h.dimg = dimg; h.dtxt = dtxt;
+    TRY(launch_head_grad(h, (hipStream_t)stream, path));
+    if (path_taken) *path_taken = path == 2 || (path == 0 && head_grad_fused(h)) ? 0 : 1;  // a refused call writes nothing
+    return MUDPT_OK;
 }
 extern "C" int mudpt_pair_head(const float* img, const float* txt, const int64_t* labels, float scale, float grad_scale, int32_t B, int32_t B_total, int32_t C,
                                int32_t e, float* logits, float* loss, float* row_loss, float* dtxt, void* stream) {

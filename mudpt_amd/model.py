@@ -12,7 +12,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -259,6 +259,61 @@ class LibraryModel(nn.Module):
             pass
 
 
+class ClipOutputs(NamedTuple):
+    """What ``CustomCLIP.differentiable`` returns: the logits and the RAW (un-normalised) features of both towers, fp32 on the device."""
+    logits: torch.Tensor
+    image_features: torch.Tensor
+    text_features: torch.Tensor
+
+
+def _forward_train(model, image, keep: bool):
+    """``mudpt_forward_train`` + ``mudpt_train_features`` on a checked device batch: (logits, image features, text features, token).  keep:
+    the forward stays in flight for a backward and ``token`` is its number (``mudpt_train_token``); else it is released and the token is 0."""
+    B, E = image.shape[0], model.shape.embed_dim
+    logits = torch.empty(B, model.n_cls, dtype=torch.float32, device=model.device)
+    img_f = torch.empty(B, E, dtype=torch.float32, device=model.device)
+    txt_f = torch.empty(model.n_cls, E, dtype=torch.float32, device=model.device)
+    capi.check(model.lib.mudpt_forward_train(model._h, capi.ptr(image), B, capi.ptr(logits), model._stream()), "forward_train")
+    capi.check(model.lib.mudpt_train_features(model._h, B, capi.ptr(img_f), capi.ptr(txt_f), model._stream()), "train_features")
+    model._text_version, model._last_batch = model.flat_params._version, 0  # as forward_backward: this version's text features are in the library
+    token = C.c_int64(0)
+    if keep:
+        capi.check(model.lib.mudpt_train_token(model._h, 0, C.byref(token)), "train_token")
+    else:
+        capi.check(model.lib.mudpt_train_release(model._h), "train_release")
+    return logits, img_f, txt_f, token.value
+
+
+class _DifferentiableStep(torch.autograd.Function):
+    """The library's training step as one autograd node.  The trainables are no inputs of it: autograd's accumulator may REPLACE a
+    parameter's ``.grad``, and every ``.grad`` here must stay its view of the flat bucket (the optimizer, the all-reduce and the step
+    consensus read that bucket).  The backward therefore accumulates into the bucket as a side effect and returns None for the anchor."""
+
+    @staticmethod
+    def forward(ctx, model, image, grad_scale, anchor):
+        ctx.model, ctx.batch, ctx.grad_scale = model, image.shape[0], grad_scale
+        ctx.set_materialize_grads(False)  # an output the loss does not read arrives as None, and goes to the library as null
+        *out, ctx.token = _forward_train(model, image, keep=True)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, d_logits, d_img, d_txt):
+        model = ctx.model
+        given = [None if g is None else g.to(model.device, torch.float32).contiguous() for g in (d_logits, d_img, d_txt)]
+        if all(g is None for g in given):
+            return None, None, None, None
+        # THIS node's forward must be the one in flight: a later forward of the same batch size would otherwise take these gradients
+        capi.check(model.lib.mudpt_train_token(model._h, ctx.token, None), "backward_logits")
+        before = model.flat_grads.clone()  # the library zeroes the bucket and writes this step's gradient; torch accumulates, so add it back
+        try:
+            capi.check(model.lib.mudpt_backward_logits(model._h, *(capi.ptr(g) for g in given), ctx.batch, ctx.grad_scale, model._stream()), "backward_logits")
+        except BaseException:
+            model.flat_grads.copy_(before)  # zeroed or not: the bucket is what it was
+            raise
+        model.flat_grads.add_(before)
+        return None, None, None, None
+
+
 class _Holder(nn.Module):
     """Namespace module so parameters get the reference's dotted state-dict keys."""
 
@@ -503,6 +558,23 @@ class CustomCLIP(LibraryModel):
                                                    capi.ptr(self._loss), capi.ptr(logits), self._stream()), "forward_backward")
         self._text_version, self._last_batch = self.flat_params._version, 0  # the step's forward left this version's text features in the library
         return (self._loss[0], logits) if return_logits else self._loss[0]
+
+    # -- a loss of the caller's: the step split at the head (include/mudpt.h mudpt_forward_train / mudpt_backward_logits) -------------
+    def differentiable(self, image: torch.Tensor, grad_scale: float = 1.0) -> "ClipOutputs":
+        """The training forward as torch sees it: ``ClipOutputs(logits [B, n_cls], image_features [B, embed_dim], text_features [n_cls,
+        embed_dim])`` -- the features RAW, as the towers leave them -- fp32 on the device, behind one ``torch.autograd.Function``.  Any torch
+        loss of the three can be backpropagated with ``loss.backward()``: the library's backward then ADDS the gradient of ``grad_scale *
+        loss`` to every trainable's ``.grad``, which stays the view of ``flat_grads`` it was.  One forward feeds one backward: a second
+        ``backward`` through the same outputs, or one after another forward or step of this model, raises the library's bad-state error.
+        Under ``torch.no_grad()`` the three tensors come back and nothing is armed for a backward.  CoCoOp, a class-sharded and a frozen
+        handle are refused with the library's line."""
+        self._check_images(image)
+        image = image.to(self.device, torch.float32).contiguous()
+        if not torch.is_grad_enabled():
+            return ClipOutputs(*_forward_train(self, image, keep=False)[:3])
+        if not hasattr(self, "_autograd_anchor"):  # what makes the outputs require grad; it never receives one (backward returns None for it)
+            self._autograd_anchor = torch.zeros((), dtype=torch.float32, device=self.device, requires_grad=True)
+        return ClipOutputs(*_DifferentiableStep.apply(self, image, float(grad_scale), self._autograd_anchor))
 
     def set_loss_scale(self, scale: float):
         """Static scale of the backward pass (include/mudpt.h mudpt_set_loss_scale; default 128 per sample); the trainer plugins move it

@@ -94,17 +94,29 @@ def data_parallel_step(trainer, batch, with_acc: bool = False):
     double it again, up to the initial value.  A non-finite LOSS is an error, as in Dassl's model_backward_and_update.
 
     with_acc (the CoOp plugin, trainers/coop.py:297-300): the summary also has "acc", the top-1 accuracy of the GLOBAL batch in percent
-    (dassl.metrics.compute_accuracy of the gathered logits): correct and total counts are summed over the ranks."""
+    (dassl.metrics.compute_accuracy of the gathered logits): correct and total counts are summed over the ranks.
+
+    A plugin that defines ``compute_loss(out, label)`` (PromptTrainer: None = not defined) replaces the ONE library call by
+    ``model.differentiable`` (the training forward as a ``ClipOutputs`` of torch tensors), its own loss and ``loss.backward()`` into the
+    zeroed bucket; everything behind the bucket -- all-reduce, consensus, loss-scale state machine, optimizer step -- is the same."""
     image, label = trainer.parse_batch_train(batch)
     model = trainer.model
-    if with_acc:
+    compute_loss = getattr(trainer, "compute_loss", None)
+    if compute_loss is not None:  # a plugin with a loss of its own: the step split at the head, autograd in between
+        model.flat_grads.zero_()  # differentiable() accumulates, as torch does
+        out = model.differentiable(image, grad_scale=parallel.grad_scale())
+        loss = compute_loss(out, label.to(out.logits.device))
+        loss.backward()
+        loss, logits = loss.detach(), out.logits
+    elif with_acc:
         loss, logits = model.forward_backward(image, label, grad_scale=parallel.grad_scale(), return_logits=True)
+    else:
+        loss = model.forward_backward(image, label, grad_scale=parallel.grad_scale())
+    if with_acc:
         counts = torch.stack([(logits.argmax(dim=1) == label.to(logits.device)).sum().float(),
                               torch.tensor(float(label.shape[0]), device=logits.device)])
         if parallel.world_size() > 1:
             torch.distributed.all_reduce(counts, op=torch.distributed.ReduceOp.SUM)
-    else:
-        loss = model.forward_backward(image, label, grad_scale=parallel.grad_scale())
     parallel.allreduce_grads(model.flat_grads)
     loss_ok, grads_ok, global_loss = parallel.step_consensus(loss, model.flat_grads)
     if not loss_ok:
@@ -378,6 +390,10 @@ class PromptTrainer(TrainerX):
     WITH_ACC = False               # the step's summary also has "acc" (compute_accuracy of the logits)
     PROMPT_LEARNER_ONLY = False    # optimise, register and initialise model.prompt_learner, not the whole model
     FREEZE_NOTE = True             # print the reference's "Turning off gradients ..." line
+    # compute_loss(self, out, label) -> scalar loss tensor; out: model.ClipOutputs(logits, image_features, text_features), label [B] on the
+    # device.  None: not defined -- the step is the library's fused forward + cross-entropy + backward.  A subclass that defines it trains
+    # on that loss instead (data_parallel_step; INTEGRATION.md has worked examples)
+    compute_loss = None
 
     def check_cfg(self, cfg):
         assert getattr(cfg.TRAINER, self.CFG_NODE).PREC in ["fp16", "fp32", "amp"]  # trainers/mudpt.py:190, cocoop.py:204, coop.py:236, ...
@@ -390,6 +406,7 @@ class PromptTrainer(TrainerX):
     def build_model(self):
         cfg = self.cfg
         node = getattr(cfg.TRAINER, self.CFG_NODE)
+        self.check_compute_loss()
         backbone, state = open_backbone(cfg)  # the prompt's n_ctx / depth come from prompt_setup
         cfg_imsize = cfg.INPUT.SIZE[0]
         assert cfg_imsize == backbone.image_size, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({backbone.image_size})"  # mudpt.py:55
@@ -427,6 +444,9 @@ class PromptTrainer(TrainerX):
             parallel.broadcast_params(self.model.flat_params)
         install_loader(self, local)  # rank-aware (world > 1) and prefetched training loader
         self._local = local
+
+    def check_compute_loss(self):
+        """A plugin whose step cannot be split at the head refuses a defined ``compute_loss`` here, before anything is built."""
 
     def test(self, split=None):
         from . import featcache
